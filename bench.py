@@ -9,8 +9,14 @@ host.  Per GPU: 1e6 candidates (config #3).  With N GPUs every rank scores its o
 shard (global indices rank*1e6 + i) and the local winners meet in one RCCL all_gather
 (weak scaling; config #4's 1e7 candidates at N=8 is `--candidates 1250000`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line (the roofline figures in it come
+from the timed steps' own events).  --full adds every side measurement (the CPU baselines, config #2 /
+#4 / #5, the ln-pdf contract and its oracle check, the drop-in lines), each a run of its own after the
+timed steps; --no-cpu and --no-config5 leave parts of those out again.  --dump-outputs DIR writes the
+last timed step's winner record (what pair.acquire returned to its caller) as DIR/<name>.npy.
 
 Rank 0 prints ONE JSON line.  value = all ranks' (candidate, observation) pairs / max-over-ranks
 time.  roofline: the scoring kernel (kde_logpdf: l and g in one pair launch per step), timed with HIP events on
@@ -101,9 +107,15 @@ def parse(argv=None):
     ap.add_argument("--dc", type=int, default=24)
     ap.add_argument("--du", type=int, default=8)
     ap.add_argument("--levels", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements (CPU baselines, configs #2/#4/#5, "
+                         "the ln-pdf contract, the drop-in lines); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's winner record as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-config5", action="store_true", help="skip the secondary SH-promotion line")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-config5", action="store_true",
+                    help="with --full: skip the secondary SH-promotion line and the other GPU side lines")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="winner exchange: nccl (= RCCL over xGMI) or gloo (CPU, multi-process rehearsal)")
     ap.add_argument("--share-gpu", action="store_true", help="ranks share the visible GPUs (rehearsal only)")
@@ -1111,6 +1123,19 @@ def load_clock(workload):
     return None
 
 
+def dump_outputs(path, rec, world):
+    """--dump-outputs: what the last timed step handed its caller -- the winner's global index, its
+    score max(1e-8, g)/max(l, 1e-8) and, on one GPU, the two pdfs of the acquisition's record -- one
+    float64 array of one element per file (the index is exact in a double).  The inputs are seeded, so
+    two builds given the same arguments must write the same bytes."""
+    os.makedirs(path, exist_ok=True)
+    fields = {"index": rec.index, "score": rec.score}
+    if world == 1:  # the exchange's reduction is on (score, index): the pdfs are one rank's record only
+        fields.update(pdf_l=rec.pdf_l, pdf_g=rec.pdf_g)
+    for name, v in fields.items():
+        np.save(os.path.join(path, name + ".npy"), np.array([v], dtype=np.float64))
+
+
 def main():
     a = parse()
     # before anything touches the GPU: N ranks however bench.py was started
@@ -1189,14 +1214,12 @@ def main():
 
     def step(ev):
         if xchg is None:  # one rank: the acquisition's record reaches the host in the same native call
-            r = pair.acquire(c_dev, index_base=base, workspace=ws, events=ev)
-            return r.index, r.score
+            return pair.acquire(c_dev, index_base=base, workspace=ws, events=ev)
         rv = pair.acquire(c_dev, index_base=base, workspace=ws, sync=False, events=ev)
         rv = xchg.exchange(rv)
         # the winner reaches the host (what BOHB needs); the exact scores are the pinned reference's
         # float64 values bit for bit, so the (score, index) reduction is the reference's pick
-        r = kde.AcqResult.from_bytes(kde.fetch_bytes(rv))
-        return r.index, r.score
+        return kde.AcqResult.from_bytes(kde.fetch_bytes(rv))
 
     for _ in range(a.warmup):
         step(ev)
@@ -1208,14 +1231,17 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    winner = None
+    rec = None
     for s in range(a.steps):
-        winner = step(evs[s])
+        rec = step(evs[s])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    winner = (rec.index, rec.score)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, rec, world)
     t_l = t_g = 0.0
     launch_ms = []  # the scoring launch of every timed step (HIP events on its stream)
     for e in evs:
@@ -1313,17 +1339,18 @@ def main():
     chk = winner_check(pinned_prefix(pairs_step // (Ng + Nb), a.dc, a.du, a.levels, a.obs), winner[0], winner[1],
                        last.pdf_l if world == 1 else None, last.pdf_g if world == 1 else None)
     out["config"].update(chk or {"winner_ok": None, "pinned_by": "no pinned winner for this workload"})
-    if world > 1 and a.strong_total and not a.total_candidates:
+    side = a.full and not a.no_config5  # the GPU side lines
+    if a.full and world > 1 and a.strong_total and not a.total_candidates:
         try:  # config #4 beside the weak line: the same total at every N (strong scaling)
             out["strong_config4"] = strong_line(pair, device, a, rank, world, dist, xchg)
         except Exception as e:
             out["strong_config4"] = {"error": repr(e)}
-    if not a.no_config5:  # every rank promotes its share of the brackets
+    if side:  # every rank promotes its share of the brackets
         try:
             out["config5"] = config5(device, rank=rank, world=world, dist=dist if world > 1 else None)
         except Exception as e:  # a side measurement; report why it is missing
             out["config5"] = {"error": repr(e)}
-    if rank == 0 and not a.no_config5:
+    if rank == 0 and side:
         try:
             out["promote_dropin"] = promote_dropin(device)
             out["promote_dropin_n81"] = promote_dropin(device, n=81)
@@ -1379,7 +1406,7 @@ def main():
             out["cv_objective"] = cv_line(device)
         except Exception as e:
             out["cv_objective"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu:
         try:
             out["cpu_baseline"] = cpu_baseline(X, pair.good.rows_dev.cpu().numpy(), pair.bad.rows_dev.cpu().numpy(),
                                                pair, var_type,

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of an engine environment switch on ONE box, alternating runs of the default bench line:
+# A/B of an engine environment switch on ONE box, alternating runs of the full bench line (--full --no-cpu):
 #   bash tools/ab_env.sh <outdir> <VAR> <value>... [-- <bench args>]   (via gpurun)
 # prints the main launch statistics and config #5's promotion / refit times per run
 set -o pipefail
@@ -14,7 +14,7 @@ mkdir -p $OUT
 cd $R
 for i in 1 2; do
   for v in "${vals[@]}"; do
-    env $VAR=$v timeout -k 10 200 python -u bench.py --no-cpu "$@" > $OUT/${VAR}_${v}_$i.json 2>> $OUT/err.log || exit 1
+    env $VAR=$v timeout -k 10 200 python -u bench.py --full --no-cpu "$@" > $OUT/${VAR}_${v}_$i.json 2>> $OUT/err.log || exit 1
   done
 done
 python3 - $OUT <<'PY'

@@ -3,7 +3,7 @@
 # chained so that the first failure ends the session:
 #   bash tools/gpu_session.sh TAG tests [PYTEST_ARGS...]   -> the -m gpu suite (or a selection)
 #   bash tools/gpu_session.sh TAG bench [BENCH_ARGS...]    -> one bench.py line
-#   bash tools/gpu_session.sh TAG both                     -> the suite, then the default bench line
+#   bash tools/gpu_session.sh TAG both                     -> the suite, then the full bench line (--full)
 #   bash tools/gpu_session.sh TAG py SCRIPT [ARGS...]      -> a tools/ measurement script
 #   bash tools/gpu_session.sh TAG prof SCRIPT [ARGS...]    -> the same under rocprofv3 --kernel-trace --stats
 # Output under gpurun_out/TAG/ (merged back by gpurun); copy what is judged into profiles/.
@@ -32,7 +32,7 @@ run_bench() {
 case $MODE in
   tests) run_tests "$@" ;;
   bench) run_bench "$@" ;;
-  both) run_tests && run_bench ;;
+  both) run_tests && run_bench --full ;;
   py) S=$1; shift; timeout -k 10 900 python -u $S "$@" > $OUT/$(basename $S .py).txt 2>&1; rc=$?; tail -40 $OUT/$(basename $S .py).txt; exit $rc ;;
   prof) S=$1; shift; cd /tmp && export TMPDIR=/tmp && cd $R
     timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 -u $S "$@" \

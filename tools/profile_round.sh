@@ -1,6 +1,6 @@
 #!/bin/bash
 # One round's measurement set on ONE GPU box (run via gpurun), every file from the same session:
-#   1. the default bench line (what the driver runs),
+#   1. the full bench line (bench.py --full: the headline figure and every side line),
 #   2. the same bench under rocprofv3 --kernel-trace --stats: its JSON line and the kernel trace come from
 #      ONE process, so the line's per-launch HIP-event times and rocprof's durations describe the same
 #      launches (tools/ksteady.py reads the trace; tools/trace_vs_line.py checks the two agree),
@@ -12,11 +12,11 @@ TAG=$1
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-  python3 $R/bench.py --no-cpu --profile-tag profiles/$TAG > $OUT/bench_traced.json 2> $OUT/trace.log || { echo "trace failed"; tail -5 $OUT/trace.log; exit 2; }
+  python3 $R/bench.py --full --no-cpu --profile-tag profiles/$TAG > $OUT/bench_traced.json 2> $OUT/trace.log || { echo "trace failed"; tail -5 $OUT/trace.log; exit 2; }
 B="$R/bench.py --steps 5 --warmup 1 --no-cpu --no-config5"
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE GRBM_GUI_ACTIVE" \
