@@ -546,6 +546,46 @@ class BOHB(base_config_generator):
                 res = pair.acquire_pick(cands, err, ws, row)
         return res, (row.copy() if res.index >= 0 else None)
 
+    # -- the k best candidates of one pool --------------------------------------------------------
+    def get_config_topk(self, budget, k):
+        """The k best of ONE pool of num_samples candidates (KDEPair.acquire_topk) instead of get_config's single
+        best: ``[(config_dict, {'model_based_pick': True, 'score': s}), ...]`` in ascending (score, candidate
+        index) order -- entry 0 is what a model-based get_config returns from the same RNG state.  Fewer than k
+        entries when the pool holds fewer candidates with a score; an empty list when there is no model yet or
+        the sampling fails (the caller then draws random configurations, as get_config does).
+
+        The candidates are drawn as get_config draws them (sampler 'host': the global numpy RNG; 'gpu': the
+        Philox counter), and the RNG is consumed exactly as by one get_config call that goes model-based: its
+        random_fraction draw is taken (and ignored: this call is model-based by definition), then the pool."""
+        k = int(k)
+        if k < 1 or k > 1024:
+            raise ValueError("k must be in [1, 1024], got %d" % k)
+        if len(self.kde_models.keys()) == 0:
+            return []
+        np.random.rand()  # get_config's random_fraction draw
+        try:
+            pair = self.kde_models[max(self.kde_models.keys())]  # bohb.py:124
+            if self.sampler == "gpu":
+                cands, _, err = pair['good'].sample(self.vartypes, self.bw_factor, self.num_samples,
+                                                    self.sampler_seed, self._sample_counter)
+                self._sample_counter += self.num_samples
+                if bool(err.any().item()):
+                    raise ValueError("truncnorm domain error: a sampled datum has no valid bounds")
+                top = pair.acquire_topk(cands, k)
+                rows = cands.cpu().numpy()[top.index]
+            else:
+                cands = self.sample_candidates(pair['good'], self.num_samples)
+                top = pair.acquire_topk(cands, k)
+                rows = cands[top.index]
+        except _native.HbxError:
+            raise  # the engine failed: never hide it
+        except Exception:
+            self.logger.warning("Sampling based optimization with %i samples failed\n %s \nNo model-based "
+                                "configurations" % (self.num_samples, traceback.format_exc()))
+            return []
+        return [(ConfigSpace.Configuration(self.configspace, vector=rows[j]).get_dictionary(),
+                 {'model_based_pick': True, 'score': float(top.score[j])}) for j in range(top.count)]
+
     # -- several get_config calls in one GPU pass (SURVEY 8f row 1) ----------------------------
     def speculation_enabled(self):
         return self.speculative == "always" or (self.speculative == "auto" and self.sampler == "gpu")

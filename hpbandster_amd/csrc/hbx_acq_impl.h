@@ -1,0 +1,119 @@
+// hbx_acq_impl.h -- device arithmetic shared by the acquisition's selection steps: the argmin's
+// (hbx_kde.hip: combine, final) and the top-k's (hbx_topk.hip: bounds, final).  One definition of the
+// score interval, the score and its error bound, so both paths screen and rank by the same numbers.
+#pragma once
+#include "hbx_kde_impl.h"
+
+// ln-pdf interval [lo, hi] and point estimate from (ln S+, ln S-, relative bound); -inf means pdf <= 0
+__device__ __forceinline__ void est_interval(const KdeEst e, float* lo, float* hi, float* pt) {
+  const float m = fmaxf(e.lpos, e.lneg);
+  if (m == -INFINITY) {
+    *lo = *hi = *pt = -INFINITY;
+    return;
+  }
+  const float a = __expf(e.lpos - m), b = __expf(e.lneg - m);
+  const float S = a - b, E = e.err * (a + b) + 1e-6f * (a + b);
+  *pt = S > 0.f ? m + __logf(S) : -INFINITY;
+  *hi = (S + E) > 0.f ? m + __logf(S + E) + 1e-6f * fabsf(m) + 1e-5f : -INFINITY;
+  *lo = (S - E) > 0.f ? m + __logf(S - E) - 1e-6f * fabsf(m) - 1e-5f : -INFINITY;
+}
+
+// Interval [slo, shi] of ln(max(1e-8, g) / max(l, 1e-8)) (bohb.py:129) of one candidate from its two
+// estimates a (l) and b (g), with the ln-pdf point estimates.
+//   lnan: l is NaN -> max(l, 1e-8) is NaN -> the score is NaN (never selected); slo = shi = NaN
+//   of:   a pdf's upper bound is past fp64's exp range: the intervals of this call cannot be trusted
+//   one:  both factors are certainly clamped: the score is exactly 1e-8 / 1e-8 = 1, slo = shi = 0
+struct ScoreIv {
+  float slo, shi, lpt, gpt;
+  bool lnan, of, one;
+};
+__device__ __forceinline__ ScoreIv score_interval(const KdeEst a, const KdeEst b) {
+  const float C = (float)HBX_LN_CLAMP;
+  ScoreIv v;
+  v.of = false;
+  v.one = false;
+  v.lnan = a.lpos != a.lpos;
+  float llo, lhi, glo, ghi;
+  if (v.lnan) {
+    v.slo = v.shi = NAN;
+    v.lpt = NAN;
+    est_interval(b, &glo, &ghi, &v.gpt);
+    if (b.lpos != b.lpos) v.gpt = NAN;
+    return v;
+  }
+  est_interval(a, &llo, &lhi, &v.lpt);
+  float Glo, Ghi;
+  if (b.lpos != b.lpos) {  // g NaN -> max(1e-8, g) == 1e-8
+    Glo = Ghi = C;
+    v.gpt = NAN;
+  } else {
+    est_interval(b, &glo, &ghi, &v.gpt);
+    Glo = fmaxf(glo, C);
+    Ghi = fmaxf(ghi, C);
+    v.of = ghi > 700.f;
+  }
+  v.of = v.of || lhi > 700.f;
+  v.slo = Glo - fmaxf(lhi, C);
+  v.shi = Ghi - fmaxf(llo, C);
+  const float C1 = C - 1e-4f;  // margin for the rounding of ln(1e-8) to float
+  if (lhi < C1 && (b.lpos != b.lpos || ghi < C1)) {  // both clamped: score exactly 1 (ln 0)
+    v.one = true;
+    v.slo = v.shi = 0.f;
+  }
+  return v;
+}
+
+// bohb.py:129 with Python max(): max(1e-8, g) keeps 1e-8 unless g > 1e-8 (NaN -> 1e-8); max(l, 1e-8)
+// keeps l unless 1e-8 > l (NaN -> NaN).  Scores are > 0 or NaN (both factors are clamped to >= 1e-8), so
+// the bits of a non-NaN score order like the score.
+__device__ __forceinline__ double bohb_score(double g, double l) {
+  return ((g > 1e-8) ? g : 1e-8) / ((1e-8 > l) ? 1e-8 : l);
+}
+
+// Bound of |exact pdf here - pdf in numpy's arithmetic| / pdf for one KDE at one candidate.  Both run
+// the same IEEE operations in the same order (SM:_kernel_base.py:509-516: per-dim kernels, dim-ordered
+// product, / prod(bw_c), numpy's pairwise sum, / n) except exp, where ocml's and numpy's results may
+// differ by ulps: per term <= (6 D + 4) u, plus 2 u per level of the summation tree (<= 40 levels up
+// to 1e5 observations) -- (8 D + 160) 2^-52 leaves a margin over both.  Sums with negative terms
+// (categorical bandwidth > 1) scale by their condition number sum|t| / |sum t|, taken pessimistically
+// from the fp32 estimate (inf when its sign is not certain).
+__device__ __forceinline__ double exact_rel(const KdeParams* __restrict__ P, const KdeEst e) {
+  const double base = (8.0 * (double)P->D + 160.0) * 0x1p-52;
+  if (!P->has_neg) return base;
+  if (e.err < -1.5f) return INFINITY;  // exact-only acquisition: no fp32 estimate of the condition
+  const float m = fmaxf(e.lpos, e.lneg);
+  if (!(m > -INFINITY)) return base;
+  const float a = __expf(e.lpos - m), b = __expf(e.lneg - m);
+  const float den = fabsf(a - b) - (e.err + 1e-6f) * (a + b);
+  if (!(den > 0.f)) return INFINITY;
+  return base * (double)((a + b) / den) * 1.01;
+}
+
+// relative bound of one candidate's score (bohb.py:129: g clamped, / l clamped): both pdfs' bounds
+// plus the division's rounding
+__device__ __forceinline__ double score_rel(const KdeParams* __restrict__ Pg, const KdeParams* __restrict__ Pb,
+                                            const KdeEst* __restrict__ el, const KdeEst* __restrict__ eg,
+                                            int64_t i) {
+  return exact_rel(Pg, el[i]) + exact_rel(Pb, eg[i]) + 0x1p-51;
+}
+
+// p may beat the winner in numpy's arithmetic only if s_p (1 - R_p) <= s_best (1 + R_best)
+__device__ __forceinline__ bool near_best(double s, double rp, double best, double rb) {
+  return s < INFINITY && s <= best * (1.0 + 1.0001 * (rp + rb));
+}
+
+// hbx_topk.hip: the top-k selection steps hbx_kde_acquire_topk launches around the exact re-score.
+// Workspace of the k-th bound's radix select: 4 histograms of 256 bins.
+#define TOPK_HIST_WORDS (4 * 256)
+// score intervals from the (merged, rescued) estimates: lo[i] as the shortlist predicate reads it, the
+// ordered key of hi into hik[i]; the overflow rule into flags[0]; zeroes the select's histograms
+int hbx_topk_bounds(const KdeEst* el, const KdeEst* eg, int64_t Nc, float* lo, uint32_t* hik, int32_t* flags,
+                    uint32_t* hist, hipStream_t s);
+// U[0] = the k-th smallest finite hi (+inf with fewer than k), then the shortlist {i: lo[i] == lo[i] &&
+// (flags[0] & 1 || lo[i] <= U[0])} into list / count; zeroes the scoring launch's marker count
+int hbx_topk_shortlist(const float* lo, const uint32_t* hik, int64_t Nc, int32_t k, uint32_t* hist, uint32_t* U,
+                       const int32_t* flags, int32_t* list, int32_t* count, int32_t* rescue_cnt, hipStream_t s);
+// the k smallest (score, index) of the re-scored shortlist, ranked, into the result block
+int hbx_topk_final(const int32_t* list, const int32_t* count, const double* exact_l, const double* exact_g,
+                   const int32_t* flags, int64_t index_base, int32_t k, const KdeParams* Pg, const KdeParams* Pb,
+                   const KdeEst* el, const KdeEst* eg, void* results, hipStream_t s);

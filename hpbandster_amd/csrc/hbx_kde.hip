@@ -13,6 +13,8 @@
 //   kde_shortlist    every candidate with lo <= U (the only ones that can be the argmin)
 //   kde_exact        fp64 re-score of the shortlist in the reference's arithmetic/operation order
 //   kde_final        strict-'<', first-index argmin over the exact scores
+// hbx_kde_acquire_topk (the k best of one pool) runs the same scoring and exact re-score around its own
+// bounds / k-th bound / shortlist / ranking steps: hbx_topk.hip.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,6 +28,7 @@
 #include "hbx_common.h"
 #include <hip/hip_ext.h>
 #include "hbx_kde_impl.h"
+#include "hbx_acq_impl.h"
 #include "hbx_npsort.h"
 #include "hbx_sort.h"
 #include <type_traits>
@@ -1110,20 +1113,6 @@ __global__ void acq_init_batch_kernel(int64_t B, uint32_t* __restrict__ U, int32
   }
 }
 
-// ln-pdf interval [lo, hi] and point estimate from (ln S+, ln S-, relative bound); -inf means pdf <= 0
-__device__ __forceinline__ void est_interval(const KdeEst e, float* lo, float* hi, float* pt) {
-  const float m = fmaxf(e.lpos, e.lneg);
-  if (m == -INFINITY) {
-    *lo = *hi = *pt = -INFINITY;
-    return;
-  }
-  const float a = __expf(e.lpos - m), b = __expf(e.lneg - m);
-  const float S = a - b, E = e.err * (a + b) + 1e-6f * (a + b);
-  *pt = S > 0.f ? m + __logf(S) : -INFINITY;
-  *hi = (S + E) > 0.f ? m + __logf(S + E) + 1e-6f * fabsf(m) + 1e-5f : -INFINITY;
-  *lo = (S - E) > 0.f ? m + __logf(S - E) - 1e-6f * fabsf(m) - 1e-5f : -INFINITY;
-}
-
 // Candidates [b*seg, (b+1)*seg) form acquisition b (seg = Nc: one acquisition).  U[b] = min over the
 // segment of the upper score bound, flags[b] bit 0 = overflow risk (re-score the whole segment).
 // Candidates whose l and g are both certainly below 1e-8 score exactly 1e-8/1e-8 = 1 (bohb.py:129):
@@ -1241,39 +1230,14 @@ __global__ __launch_bounds__(256) void kde_combine_kernel(KdeEst* __restrict__ e
     bool one = false;
     const uint32_t sg = (uint32_t)(i < Nc ? i : Nc - 1) / seg;
     if (i < Nc) {
-      const KdeEst a = ea[r], b = eb[r];
-      const float C = (float)HBX_LN_CLAMP;
-      float slo, shi;
-      bool of = false;
-      float llo, lhi, lpt, glo, ghi, gpt;
-      if (a.lpos != a.lpos) {  // l NaN -> max(l, 1e-8) is NaN -> score NaN (never selected)
-        slo = shi = NAN;
-        lpt = NAN;
-        est_interval(b, &glo, &ghi, &gpt);
-        if (b.lpos != b.lpos) gpt = NAN;
-      } else {
-        est_interval(a, &llo, &lhi, &lpt);
-        float Glo, Ghi;
-        if (b.lpos != b.lpos) {  // g NaN -> max(1e-8, g) == 1e-8
-          Glo = Ghi = C;
-          gpt = NAN;
-        } else {
-          est_interval(b, &glo, &ghi, &gpt);
-          Glo = fmaxf(glo, C);
-          Ghi = fmaxf(ghi, C);
-          of = ghi > 700.f;
-        }
-        of = of || lhi > 700.f;
-        slo = Glo - fmaxf(lhi, C);
-        shi = Ghi - fmaxf(llo, C);
-        h = shi;
-        const float C1 = C - 1e-4f;  // margin for the rounding of ln(1e-8) to float
-        if (lhi < C1 && (b.lpos != b.lpos || ghi < C1)) {  // both clamped: score exactly 1 (ln 0)
-          one = true;
-          slo = NAN;  // excluded from the shortlist unless it is the segment's first exact tie
-          shi = h = 0.f;
-        }
-      }
+      // (score_interval: hbx_acq_impl.h, shared with the top-k bounds pass)
+      const ScoreIv v = score_interval(ea[r], eb[r]);
+      const float lpt = v.lpt, gpt = v.gpt;
+      const bool of = v.of;
+      // an exact tie at 1 is excluded from the shortlist unless it is the segment's first (first1)
+      const float slo = v.one ? NAN : v.slo;
+      if (!v.lnan) h = v.shi;
+      one = v.one;
       if (logl) logl[i] = lpt;
       if (logg) logg[i] = gpt;
       lo[i] = slo;  // (the upper bound only enters the segment minimum below)
@@ -1679,38 +1643,6 @@ __global__ __launch_bounds__(256) void kde_logpdf_exact_kernel(const double* __r
   }
 }
 
-// Bound of |exact pdf here - pdf in numpy's arithmetic| / pdf for one KDE at one candidate.  Both run
-// the same IEEE operations in the same order (SM:_kernel_base.py:509-516: per-dim kernels, dim-ordered
-// product, / prod(bw_c), numpy's pairwise sum, / n) except exp, where ocml's and numpy's results may
-// differ by ulps: per term <= (6 D + 4) u, plus 2 u per level of the summation tree (<= 40 levels up
-// to 1e5 observations) -- (8 D + 160) 2^-52 leaves a margin over both.  Sums with negative terms
-// (categorical bandwidth > 1) scale by their condition number sum|t| / |sum t|, taken pessimistically
-// from the fp32 estimate (inf when its sign is not certain).
-__device__ __forceinline__ double exact_rel(const KdeParams* __restrict__ P, const KdeEst e) {
-  const double base = (8.0 * (double)P->D + 160.0) * 0x1p-52;
-  if (!P->has_neg) return base;
-  if (e.err < -1.5f) return INFINITY;  // exact-only acquisition: no fp32 estimate of the condition
-  const float m = fmaxf(e.lpos, e.lneg);
-  if (!(m > -INFINITY)) return base;
-  const float a = __expf(e.lpos - m), b = __expf(e.lneg - m);
-  const float den = fabsf(a - b) - (e.err + 1e-6f) * (a + b);
-  if (!(den > 0.f)) return INFINITY;
-  return base * (double)((a + b) / den) * 1.01;
-}
-
-// relative bound of one candidate's score (bohb.py:129: g clamped, / l clamped): both pdfs' bounds
-// plus the division's rounding
-__device__ __forceinline__ double score_rel(const KdeParams* __restrict__ Pg, const KdeParams* __restrict__ Pb,
-                                            const KdeEst* __restrict__ el, const KdeEst* __restrict__ eg,
-                                            int64_t i) {
-  return exact_rel(Pg, el[i]) + exact_rel(Pb, eg[i]) + 0x1p-51;
-}
-
-// p may beat the winner in numpy's arithmetic only if s_p (1 - R_p) <= s_best (1 + R_best)
-__device__ __forceinline__ bool near_best(double s, double rp, double best, double rb) {
-  return s < INFINITY && s <= best * (1.0 + 1.0001 * (rp + rb));
-}
-
 // A get_config pick published to device-mapped host memory by the final argmin (hbx_kde_acquire_bound with err /
 // row_out): the record, whether any of the call's candidates hit a sampler domain error, the winning row (as
 // tagged 8-byte words: kde_final_body)
@@ -1886,9 +1818,7 @@ __global__ __launch_bounds__(256) void kde_final_kernel(const int32_t* __restric
 // (2) among the entries reaching it the smallest index (strict '<', first index -- bohb.py:149-152),
 // (3) one thread per segment writes its record.  Scores are > 0 or NaN (both factors are clamped
 // to >= 1e-8), so the bits of a finite score order like the score.
-__device__ __forceinline__ double bohb_score(double g, double l) {
-  return ((g > 1e-8) ? g : 1e-8) / ((1e-8 > l) ? 1e-8 : l);  // Python max() semantics, see kde_final
-}
+// (bohb_score: hbx_acq_impl.h)
 
 __global__ __launch_bounds__(256) void kde_batch_min_kernel(const int32_t* __restrict__ list,
                                                             const int32_t* __restrict__ count, uint32_t seg,
@@ -2813,6 +2743,107 @@ int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int32_t D
   return acquire_impl("hbx_kde_acquire_batch", cand, Nc, seg, D, index_base, params_good, table_good, X_good,
                       rows_good, variant_good, params_bad, table_bad, X_bad, rows_bad, variant_bad, dc_pad, du_pad,
                       nmax, logl_out, logg_out, (AcqResult*)results, workspace, ws_bytes, nullptr, stream);
+}
+
+// ---- top-k acquisition (hbx_topk.hip holds its kernels and the correctness argument) ----------------
+// The workspace is hbx_kde_acquire's (the near list's 4 Nc bytes hold the upper bounds' keys) followed by the
+// radix select's histograms.
+static size_t topk_hist_off(int64_t Nc, int64_t nmax) { return ws_layout(Nc, nmax).total; }
+
+int64_t hbx_kde_topk_workspace_bytes(int64_t Nc, int32_t k, int64_t nmax) {
+  if (Nc < 0 || k < 1 || k > HBX_TOPK_MAX_K) return -1;
+  return (int64_t)(topk_hist_off(Nc, nmax) + 4 * TOPK_HIST_WORDS);
+}
+
+int64_t hbx_kde_topk_result_bytes(int32_t k) {
+  if (k < 1 || k > HBX_TOPK_MAX_K) return -1;
+  return 16 + 40 * (int64_t)k;
+}
+
+// The k best candidates of one pool by (score, index): the scoring launch, its rescue pass and split merge and
+// the exact re-score as acquire_impl runs them for one acquisition; between them the bounds pass, the k-th
+// smallest upper bound and the shortlist against it, after them the ranking (hbx_topk.hip).
+int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int32_t D, int64_t index_base,
+                         const void* params_good, const float* table_good, const double* X_good,
+                         const int64_t* rows_good, int32_t variant_good, const void* params_bad,
+                         const float* table_bad, const double* X_bad, const int64_t* rows_bad, int32_t variant_bad,
+                         int32_t dc_pad, int32_t du_pad, int64_t nmax, void* results, void* workspace,
+                         int64_t ws_bytes, void* stream) {
+  const char* who = "hbx_kde_acquire_topk";
+  if ((!cand && Nc > 0) || !params_good || !table_good || !X_good || !rows_good || !params_bad || !table_bad ||
+      !X_bad || !rows_bad || !workspace || !results)
+    return hbx_fail(HBX_ERR_ARG, "%s: null pointer", who);
+  if (Nc < 0 || Nc > INT32_MAX) return hbx_fail(HBX_ERR_ARG, "Nc=%lld out of range", (long long)Nc);
+  if (k < 1 || k > HBX_TOPK_MAX_K) return hbx_fail(HBX_ERR_ARG, "%s: k=%d outside [1, %d]", who, k, HBX_TOPK_MAX_K);
+  if (D < 1 || D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "%s: D=%d", who, D);
+  const int64_t need = hbx_kde_topk_workspace_bytes(Nc, k, nmax);
+  if (ws_bytes < need)
+    return hbx_fail(HBX_ERR_ARG, "workspace too small: %lld < %lld bytes", (long long)ws_bytes, (long long)need);
+  hipStream_t s = (hipStream_t)stream;
+  if (Nc == 0) {  // count = 0 and no launch: a zeroed header
+    HBX_HIP(hipMemsetAsync(results, 0, 16, s));
+    return HBX_OK;
+  }
+  const bool exact_only = ((variant_good | variant_bad) >> 5) & 1;
+  ScoreFns fg = pick_logpdf(dc_pad, du_pad, variant_good, true);
+  ScoreFns fb = pick_logpdf(dc_pad, du_pad, variant_bad, true);
+  if (!exact_only && (!fg.main || !fb.main))
+    return hbx_fail(HBX_ERR_UNSUPPORTED, "no kernel for dc_pad=%d du_pad=%d", dc_pad, du_pad);
+  const WsLayout w = ws_layout(Nc, nmax);
+  char* ws = (char*)workspace;
+  uint32_t* U = (uint32_t*)(ws + w.U);
+  int32_t* count = (int32_t*)(ws + w.count);
+  int32_t* flags = (int32_t*)(ws + w.flags);
+  int32_t* first1 = (int32_t*)(ws + w.first1);
+  int32_t* rescue = (int32_t*)(ws + w.rescue);
+  AcqResult* res = (AcqResult*)(ws + w.res);
+  KdeEst* el = (KdeEst*)(ws + w.est_l);
+  KdeEst* eg = (KdeEst*)(ws + w.est_g);
+  float* lo = (float*)(ws + w.lo);
+  int32_t* list = (int32_t*)(ws + w.list);
+  uint32_t* hik = (uint32_t*)(ws + w.near);
+  double* exact_l = (double*)(ws + w.exact_l);
+  double* exact_g = (double*)(ws + w.exact_g);
+  double* part = (double*)(ws + w.part);
+  uint32_t* hist = (uint32_t*)(ws + w.total);
+  const KdeParams* Pg = (const KdeParams*)params_good;
+  const KdeParams* Pb = (const KdeParams*)params_bad;
+  bool inited = false;
+  int32_t nsplit[2] = {1, 1};
+  int rc;
+  if (!exact_only) {  // the scoring launch first, as acquire_impl; its rescue pass always its own launch
+    rc = launch_score2(fg, params_good, table_good, el, fb, params_bad, table_bad, eg, cand, Nc, D, nullptr, rescue, s,
+                       KdePairArgs::AcqInitPtrs{U, count, flags, first1, res}, &inited, nmax, nsplit, nullptr);
+    if (rc) return rc;
+  }
+  if (!inited) {
+    hipLaunchKernelGGL(acq_init_kernel, dim3(1), dim3(64), 0, s, U, count, flags, first1, res);
+    HBX_LAUNCH_CHECK();
+  }
+  if (exact_only) {  // no estimates: every candidate re-scored (lo = 0, the flag set), no select
+    hipLaunchKernelGGL(kde_exact_only_init_kernel, dim3((unsigned)((Nc + 255) / 256)), dim3(256), 0, s, Nc,
+                       (uint32_t)Nc, el, eg, lo, flags);
+    HBX_LAUNCH_CHECK();
+    HBX_HIP(hipMemsetAsync(hist, 0, 4 * TOPK_HIST_WORDS, s));
+  } else {
+    if (nsplit[0] > 1 || nsplit[1] > 1) {
+      hipLaunchKernelGGL(kde_merge_splits_kernel, dim3((unsigned)((2 * Nc + 255) / 256)), dim3(256), 0, s, el, eg, Nc,
+                         nsplit[0], nsplit[1]);
+      HBX_LAUNCH_CHECK();
+    }
+    rc = hbx_topk_bounds(el, eg, Nc, lo, hik, flags, hist, s);
+    if (rc) return rc;
+  }
+  rc = hbx_topk_shortlist(lo, exact_only ? nullptr : hik, Nc, k, hist, U, flags, list, count, rescue, s);
+  if (rc) return rc;
+  const int nbuf = (int)((nmax + PW_BUF - 1) / PW_BUF);
+  hipLaunchKernelGGL(kde_exact_kernel<false>, dim3(EXACT_GRID), dim3(EXACT_ACQ_THREADS), 0, s, cand, D, Pg, X_good,
+                     rows_good, Pb, X_bad, rows_bad, list, count, nbuf, part, exact_l, exact_g, ExactScan{});
+  HBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(kde_exact_combine_kernel, dim3((2 * EXACT_SPLIT_CAP + 3) / 4), dim3(256), 0, s, Pg, Pb, count,
+                     nbuf, part, exact_l, exact_g);
+  HBX_LAUNCH_CHECK();
+  return hbx_topk_final(list, count, exact_l, exact_g, flags, index_base, k, Pg, Pb, el, eg, results, s);
 }
 
 // the exact pdf stages its per-observation terms in LDS: no global scratch is needed any more (the

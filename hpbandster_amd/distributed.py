@@ -53,6 +53,29 @@ def reduce_records_host(recs):
     return best, near
 
 
+def merge_topk(parts, k):
+    """The global top-k of a candidate-sharded pool from the shards' TopK results (KDEPair.acquire_topk on each
+    shard with its ``index_base``, so the indices are global): the first k entries by (score, index) over all
+    parts -- what acquire_topk(k) over the whole pool returns, since every shard returns its own k best and
+    each entry of the global top-k is among its shard's.  Pure host code, no collective: any transport may
+    gather the blocks.  ``count`` can be below k (parts with few or no rankable candidates); ``shortlist`` adds
+    up, ``flags`` are or-ed."""
+    from .kde import TopK, TOPK_MAX_K
+    k = int(k)
+    if k < 1 or k > TOPK_MAX_K:
+        raise ValueError("k must be in [1, %d], got %d" % (TOPK_MAX_K, k))
+    parts = [p for p in parts if p is not None]
+    cat = lambda name, dt: (np.concatenate([np.asarray(getattr(p, name), dtype=dt) for p in parts])
+                            if parts else np.zeros(0, dtype=dt))
+    index, score = cat("index", np.int64), cat("score", np.float64)
+    order = np.lexsort((index, score))[:k]  # by score, ties by global index
+    flags = 0
+    for p in parts:
+        flags |= int(p.flags)
+    return TopK(index[order], score[order], cat("pdf_l", np.float64)[order], cat("pdf_g", np.float64)[order],
+                cat("rel", np.float32)[order], sum(int(p.shortlist) for p in parts), flags)
+
+
 def reduce_winners(score, index, group=None, device=None, rel=0.0):
     """All ranks' (score, index) -> global (index, score) over torch.distributed (any backend); index -1
     when no rank has a finite score.  ``score``: the exact score of the local winner."""

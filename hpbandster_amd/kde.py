@@ -139,6 +139,47 @@ class AcqResult(object):
             self.index, self.score, self.pdf_l, self.pdf_g, self.shortlist, self.near, self.flags)
 
 
+TOPK_MAX_K = 1024  # include/hbx.h HBX_TOPK_MAX_K
+TOPK_HEAD_BYTES = 16
+# one ranked entry of a top-k result block (include/hbx.h hbx_kde_acquire_topk), 40 bytes
+TOPK_REC = np.dtype([("index", "<i8"), ("score", "<f8"), ("pdf_l", "<f8"), ("pdf_g", "<f8"), ("rel", "<f4"),
+                     ("pad", "<i4")])
+
+
+class TopK(object):
+    """The k best candidates of one pool (KDEPair.acquire_topk), ranked by (score, index): numpy arrays
+    ``index`` (int64, index_base added), ``score``, ``pdf_l``, ``pdf_g`` (float64, the reference's values bit
+    for bit) and ``rel`` (float32, AcqResult.rel per entry) of ``count`` entries each; ``shortlist``: candidates
+    re-scored in fp64; ``flags``: ACQ_OVERFLOW, ACQ_NEAR_TIE (two adjacent entries, or the last one and the best
+    one left out, lie within each other's ``rel``)."""
+    __slots__ = ("index", "score", "pdf_l", "pdf_g", "rel", "count", "shortlist", "flags")
+
+    def __init__(self, index, score, pdf_l, pdf_g, rel, shortlist=0, flags=0):
+        self.index = np.asarray(index, dtype=np.int64)
+        self.score = np.asarray(score, dtype=np.float64)
+        self.pdf_l = np.asarray(pdf_l, dtype=np.float64)
+        self.pdf_g = np.asarray(pdf_g, dtype=np.float64)
+        self.rel = np.asarray(rel, dtype=np.float32)
+        self.count = int(self.index.size)
+        if not (self.score.size == self.pdf_l.size == self.pdf_g.size == self.rel.size == self.count):
+            raise ValueError("TopK: arrays of different lengths")
+        self.shortlist, self.flags = int(shortlist), int(flags)
+
+    @classmethod
+    def from_bytes(cls, b):
+        count, shortlist, flags, _ = struct.unpack("<iiii", bytes(b[:TOPK_HEAD_BYTES]))
+        r = np.frombuffer(bytes(b), dtype=TOPK_REC, count=count, offset=TOPK_HEAD_BYTES)
+        return cls(r["index"].copy(), r["score"].copy(), r["pdf_l"].copy(), r["pdf_g"].copy(), r["rel"].copy(),
+                   shortlist, flags)
+
+    def __len__(self):
+        return self.count
+
+    def __repr__(self):
+        return "TopK(count=%d, shortlist=%d, flags=%d, index=%r)" % (self.count, self.shortlist, self.flags,
+                                                                     self.index[:8].tolist())
+
+
 def _rows_of(cands, idx):
     """Candidate rows idx (host numpy) of a host array or a device tensor."""
     idx = np.asarray(idx, dtype=np.int64)
@@ -542,6 +583,49 @@ class KDEPair(object):
         if logs:
             return res, logl.cpu().numpy(), logg.cpu().numpy()
         return res
+
+    def topk_workspace_bytes(self, Nc, k):
+        return int(N.lib().hbx_kde_topk_workspace_bytes(int(Nc), int(k), self.nmax))
+
+    def acquire_topk(self, cands, k, index_base=0, stream=None, workspace=None, ties="pinned"):
+        """The k best candidates of ONE pool: the first min(k, F) entries of the stable ascending order of
+        max(1e-8, g)/max(l, 1e-8) over the F candidates whose score is not NaN -- ordered by (score, index), so
+        entry 0 is acquire()'s pick.  ``cands``: [Nc, D] float64 (numpy or a device tensor); 1 <= k <= 1024
+        (k > Nc is legal).  Returns a TopK (empty when no candidate has a score: the drop-in then falls back to
+        random configurations, as for acquire()'s index -1).  Only ties='pinned' is offered: the GPU's re-score
+        is the reference's arithmetic on the pinned numpy bit for bit."""
+        if ties != "pinned":
+            raise ValueError("acquire_topk offers ties='pinned' only")
+        k = int(k)
+        if k < 1 or k > TOPK_MAX_K:
+            raise ValueError("k must be in [1, %d], got %d" % (TOPK_MAX_K, k))
+        with N.on_device(self.good.device, stream):
+            return self._acquire_topk(cands, k, index_base, stream, workspace)
+
+    def _acquire_topk(self, cands, k, index_base, stream, workspace):
+        torch = _torch()
+        L = N.lib()
+        dev = self.good.device
+        if isinstance(cands, np.ndarray):
+            c_dev = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(dev)
+        else:
+            c_dev = cands
+            if c_dev.dtype != torch.float64 or not c_dev.is_contiguous():
+                raise N.HbxError("candidate tensor must be contiguous float64 [Nc, D]")
+        Nc = int(c_dev.shape[0])
+        D = self.good.k_vars
+        if Nc > 0 and (c_dev.dim() != 2 or int(c_dev.shape[1]) != D):
+            raise N.HbxError("candidates must be [Nc, %d], got %s" % (D, tuple(c_dev.shape)))
+        wsb = self.topk_workspace_bytes(Nc, k)
+        ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
+        if ws.numel() < wsb:
+            raise N.HbxError("workspace too small")
+        out = torch.empty(int(L.hbx_kde_topk_result_bytes(k)), dtype=torch.uint8, device=dev)
+        sh = N.stream_handle(stream, dev)
+        self._order(sh)
+        N.check(L.hbx_kde_acquire_topk(c_dev.data_ptr(), Nc, k, D, int(index_base), *self._kde_args, N.ptr(out),
+                                       ws.data_ptr(), ws.numel(), sh))
+        return TopK.from_bytes(fetch_bytes(out, stream))  # one device-to-host copy: the whole result block
 
     def _ws_offsets(self, Nc, seg):
         o = np.zeros(5, dtype=np.int64)

@@ -206,6 +206,34 @@ int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int32_t D
                           int64_t nmax, float* logl_out, float* logg_out, void* results, void* workspace,
                           int64_t ws_bytes, void* stream);
 
+/* Top-k acquisition: the k best candidates of ONE pool, ranked exactly.  Where hbx_kde_acquire keeps the
+ * first candidate of the smallest score (bohb.py:149-152: `if val < best`), this returns the first
+ * min(k, F) entries of the stable ascending order of the score s = max(1e-8, g)/max(l, 1e-8) over the F
+ * candidates whose score is not NaN: ordered by (s[i], i), so equal scores come out in index order and entry 0
+ * is hbx_kde_acquire's pick (index, score and both pdfs bit-identical).  The scoring launch and the exact fp64
+ * re-score are hbx_kde_acquire's (fast scoring instances); the shortlist is taken against the k-th smallest
+ * upper score bound instead of the smallest (csrc/hbx_topk.hip has the argument why it holds the whole top-k).
+ * 1 <= k <= HBX_TOPK_MAX_K; k > Nc is legal (at most Nc entries come back).
+ * results: device buffer of hbx_kde_topk_result_bytes(k) = 16 + 40 k bytes:
+ *   header  {i32 count, i32 shortlist, i32 flags, i32 k}
+ *           count: entries returned; shortlist: candidates re-scored in fp64; flags: HBX_ACQ_OVERFLOW (every
+ *           rankable candidate re-scored), HBX_ACQ_NEAR_TIE (two adjacent returned entries, or the last
+ *           returned one and the best re-scored one left out, lie within each other's error bounds `rel`)
+ *   records count x {i64 index, f64 score, f64 pdf_l, f64 pdf_g, f32 rel, i32 0}   (40 bytes each, ranked)
+ *           index: candidate index + index_base; score, pdf_l, pdf_g: the reference's fp64 values bit for
+ *           bit; rel: the bound hbx_kde_acquire's record reports (hbx_kde_result_ptr)
+ * Nc = 0: count = 0, nothing launched (the header zeroed).  Workspace: hbx_kde_topk_workspace_bytes(Nc, k,
+ * nmax) (-1 for k out of range, as hbx_kde_topk_result_bytes).  Bad arguments: HBX_ERR_ARG (hbx_last_error). */
+#define HBX_TOPK_MAX_K 1024
+int64_t hbx_kde_topk_workspace_bytes(int64_t Nc, int32_t k, int64_t nmax);
+int64_t hbx_kde_topk_result_bytes(int32_t k);
+int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int32_t D, int64_t index_base,
+                         const void* params_good, const float* table_good, const double* X_good,
+                         const int64_t* rows_good, int32_t variant_good,
+                         const void* params_bad, const float* table_bad, const double* X_bad,
+                         const int64_t* rows_bad, int32_t variant_bad, int32_t dc_pad, int32_t du_pad,
+                         int64_t nmax, void* results, void* workspace, int64_t ws_bytes, void* stream);
+
 /* Optional timing: `events` of hbx_kde_acquire is NULL or an array of three hipEvent_t recorded on
  * `stream` before the l scoring launch, between l and g, and after g -- or, when l and g are scored by
  * one pair launch (both KDEs on the same hmode kernel, HBX_SCORE_PAIR not 0), only [0] before and [1]
