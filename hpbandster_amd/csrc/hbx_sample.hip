@@ -275,7 +275,97 @@ __global__ __launch_bounds__(256) void kde_sample_pair_kernel(
   if (derr && domain_err) domain_err[i] = 1;  // any of the candidate's lanes (same byte, same value)
 }
 
+// The grouped sampler (hbx_kde_sample_groups): kde_sample_pair_kernel<false> per group b of a batched refit
+// (hbx_kde_fit's arrays as they lie on the device) -- X base X + seg_off[b] D, rows = order + seg_off[b] (the good
+// KDE: the head n_good[b] of the argsort), bw = bw_good + b D -- with candidate (b, i) on the Philox counter
+// counter_base + b C + i: the same draw, sample_dim and stores, so its bytes are hbx_kde_sample's for that group
+// at counter_base + b C.  Blocks: B x ceil(C / CPB), linear in blockIdx.x.  Groups without a model (n_good[b] <= 0
+// or past the segment, hbx_kde_fit's rule) get NaN rows.
+__global__ __launch_bounds__(256) void kde_sample_groups_kernel(
+    const double* __restrict__ X, int32_t D, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ order,
+    const int64_t* __restrict__ n_good, const double* __restrict__ bw_good, const int32_t* __restrict__ levels,
+    double bw_factor, uint64_t seed, uint64_t counter_base, uint32_t stream_id, int64_t C, int32_t tiles,
+    double* __restrict__ cands, uint8_t* __restrict__ domain_err) {
+  constexpr int CPB = 256 / SAMPLE_LPC;  // candidates per block
+  __shared__ int32_t sdat[CPB];
+  __shared__ double srh[HBX_MAX_D];  // 1 / bw per dim
+  const int64_t b = (int64_t)blockIdx.x / tiles;
+  const int64_t c0 = ((int64_t)blockIdx.x - b * tiles) * CPB;
+  const int nc = (int)(C - c0 < CPB ? C - c0 : CPB);
+  const int64_t s0 = seg_off[b], n = n_good[b];
+  const bool model = n > 0 && n <= seg_off[b + 1] - s0;  // (uniform)
+  const int cl = threadIdx.x / SAMPLE_LPC, g = threadIdx.x % SAMPLE_LPC;
+  const int D2 = (D + 1) >> 1;
+  if (!model) {
+    if (cl < nc) {
+      double* out = cands + (b * C + c0 + cl) * (int64_t)D;
+      for (int d = g; d < D; d += SAMPLE_LPC) out[d] = NAN;
+    }
+    return;
+  }
+  const double* bw = bw_good + b * (int64_t)D;
+  const int64_t* rows = order + s0;
+  const double* Xs = X + s0 * (int64_t)D;
+  for (int t = threadIdx.x; t < D; t += 256) srh[t] = 1.0 / bw[t];
+  if (threadIdx.x < nc) {
+    const uint64_t ctr = counter_base + (uint64_t)(b * C + c0 + threadIdx.x);
+    const uint64_t rb = hbx_bits64(draw(seed, ctr, DATUM_WORD, stream_id), 0);
+    sdat[threadIdx.x] = (int32_t)__umul64hi(rb, (uint64_t)n);  // floor(u * n), u = rb / 2^64
+  }
+  __syncthreads();
+  if (cl >= nc) return;
+  const int64_t i = b * C + c0 + cl;  // the candidate's row in cands and its byte in domain_err
+  const uint64_t ctr = counter_base + (uint64_t)i;
+  const int32_t idx = sdat[cl];
+  const double* xr = Xs + rows[idx] * (int64_t)D;
+  double* out = cands + i * (int64_t)D;
+  bool derr = false;
+  HbxU32x4 r;
+  for (int k = g; k < D2; k += SAMPLE_LPC) {
+    const int q = (k - g) / SAMPLE_LPC;  // this lane's q-th pair: a new block every second pair
+    if ((q & 1) == 0) r = draw(seed, ctr, (uint32_t)(g + SAMPLE_LPC * (q >> 1)), stream_id);
+    const uint32_t w0 = (q & 1) ? r.x[2] : r.x[0], w1 = (q & 1) ? r.x[3] : r.x[1];
+    const int d = 2 * k;
+    const double v0 = sample_dim<false>(xr, d, idx, D, bw, srh, levels, nullptr, bw_factor, w0, &derr);
+    if (d + 1 < D) {
+      const double v1 = sample_dim<false>(xr, d + 1, idx, D, bw, srh, levels, nullptr, bw_factor, w1, &derr);
+      if ((D & 1) == 0) {
+        *(double2*)(out + d) = make_double2(v0, v1);
+      } else {
+        out[d] = v0;
+        out[d + 1] = v1;
+      }
+    } else {
+      out[d] = v0;
+    }
+  }
+  if (derr && domain_err) domain_err[i] = 1;  // any of the candidate's lanes (same byte, same value)
+}
+
 extern "C" {
+
+int hbx_kde_sample_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                          const int64_t* n_good, const double* bw_good, const int32_t* levels, double bw_factor,
+                          uint64_t seed, uint64_t counter_base, uint32_t stream_id, int64_t C, double* cands,
+                          uint8_t* domain_err, void* stream) {
+  if (B < 0 || C < 0 || D < 1 || D > HBX_MAX_D)
+    return hbx_fail(HBX_ERR_ARG, "hbx_kde_sample_groups: B=%lld C=%lld D=%d", (long long)B, (long long)C, D);
+  if (B > INT32_MAX || (C > 0 && B > (int64_t)INT32_MAX / C))
+    return hbx_fail(HBX_ERR_ARG, "hbx_kde_sample_groups: B * C = %lld * %lld exceeds int32", (long long)B, (long long)C);
+  if (B == 0 || C == 0) return HBX_OK;
+  if (!X || !seg_off || !order || !n_good || !bw_good || !levels || !cands)
+    return hbx_fail(HBX_ERR_ARG, "hbx_kde_sample_groups: null pointer");
+  if ((D & 1) == 0 && ((uintptr_t)cands & 15))
+    return hbx_fail(HBX_ERR_ARG, "hbx_kde_sample_groups: cands not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (domain_err) HBX_HIP(hipMemsetAsync(domain_err, 0, (size_t)(B * C), s));
+  constexpr int CPB = 256 / SAMPLE_LPC;
+  const int64_t tiles = (C + CPB - 1) / CPB;
+  hipLaunchKernelGGL(kde_sample_groups_kernel, dim3((unsigned)(B * tiles)), dim3(256), 0, s, X, D, seg_off, order, n_good,
+                     bw_good, levels, bw_factor, seed, counter_base, stream_id, C, (int32_t)tiles, cands, domain_err);
+  HBX_LAUNCH_CHECK();
+  return HBX_OK;
+}
 
 int hbx_philox4x32_10(const uint32_t* counter, const uint32_t* key, uint32_t* out) {
   if (!counter || !key || !out) return hbx_fail(HBX_ERR_ARG, "hbx_philox4x32_10: null pointer");

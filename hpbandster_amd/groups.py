@@ -1,0 +1,243 @@
+"""Grouped KDE models: B independent brackets refit, sampled and acquired in one call each.
+
+Config #5's loop on the device from end to end::
+
+    gm = groups.fit_groups(X, losses, seg_off, var_type)      # hbx_seg_argsort_ex + hbx_kde_fit
+    rows, picks = gm.propose(64, seed, levels)                # hbx_kde_sample_groups + hbx_kde_acquire_groups
+
+Bracket b owns the rows ``X[seg_off[b]:seg_off[b+1]]``; its good / bad KDEs are the head ``n_good[b]`` / tail
+``n_bad[b]`` rows of numpy's argsort of its losses (bohb.py:220-246).  The fit's outputs (order, bandwidths, level
+counts) stay on the device and are read there by the sampler and the acquisition: no host round trip between the
+steps.  Every pick is the reference's (bohb.py:124-169 on that bracket's pair): index, score and both pdfs bit
+for bit.  The drop-in ``BOHB`` class is not involved; this is the batched engine surface.
+"""
+
+import numpy as np
+
+from . import _native as N
+from . import kde
+
+ACQ_NO_MODEL, ACQ_UNSUPPORTED = 16, 32  # include/hbx.h HBX_ACQ_*
+
+# one result record (include/hbx.h hbx_kde_result_ptr), 48 bytes
+RECORD = np.dtype([("index", "<i8"), ("score", "<f8"), ("rel", "<f4"), ("flags", "<i4"), ("shortlist", "<i4"),
+                   ("near", "<i4"), ("pdf_l", "<f8"), ("pdf_g", "<f8")])
+assert RECORD.itemsize == kde.RESULT_BYTES
+
+
+def _is_tensor(a):
+    return hasattr(a, "data_ptr")
+
+
+class GroupPicks(object):
+    """One pick per group (hbx_kde_acquire_groups), from one fetch of the B records: numpy arrays ``index``
+    (int64, relative to the group's pool, -1: no pick), ``score``, ``pdf_l``, ``pdf_g`` (float64, the reference's
+    values bit for bit), ``rel`` (float32), ``flags`` (kde.ACQ_* and ACQ_NO_MODEL / ACQ_UNSUPPORTED), ``shortlist``
+    and ``near`` (int32), each of length B."""
+    __slots__ = ("index", "score", "pdf_l", "pdf_g", "rel", "flags", "shortlist", "near")
+
+    def __init__(self, records):
+        r = np.asarray(records, dtype=RECORD)
+        for name in self.__slots__:
+            setattr(self, name, np.ascontiguousarray(r[name]))
+
+    @classmethod
+    def from_bytes(cls, b, B):
+        return cls(np.frombuffer(bytes(b), dtype=RECORD, count=B))
+
+    def __len__(self):
+        return int(self.index.size)
+
+    def rows(self, cands):
+        """The winning candidate rows, [B, D] float64 on the host; NaN rows where ``index < 0``.
+        ``cands``: [B, C, D] (numpy or a device tensor)."""
+        B = len(self)
+        D = int(cands.shape[2])
+        out = np.full((B, D), np.nan)
+        ok = np.nonzero(self.index >= 0)[0]
+        if ok.size:
+            if _is_tensor(cands):
+                torch = kde._torch()
+                bi = torch.from_numpy(ok).to(cands.device)
+                ci = torch.from_numpy(self.index[ok]).to(cands.device)
+                out[ok] = cands[bi, ci].cpu().numpy()
+            else:
+                out[ok] = np.asarray(cands, dtype=np.float64)[ok, self.index[ok]]
+        return out
+
+    def __repr__(self):
+        return "GroupPicks(B=%d, picked=%d)" % (len(self), int((self.index >= 0).sum()))
+
+
+class GroupModel(object):
+    """The KDE pairs of B brackets after one batched refit (fit_groups).  ``B``, ``D``, ``n_good`` / ``n_bad``
+    (host int64[B], 0 where the reference builds no model) and ``has_model`` (host bool[B]) are host-side facts
+    known before the fit; everything the fit computed stays in device tensors (``order``, ``bw_good``, ``bw_bad``,
+    ``nlev_good``, ``nlev_bad``)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+        self._host = None
+
+    # ---- host views (checks and debugging) --------------------------------------------------------------
+    def bandwidths(self):
+        """(bw_good, bw_bad): host float64 [B, D] (NaN rows for groups without a model)."""
+        return self.bw_good.cpu().numpy(), self.bw_bad.cpu().numpy()
+
+    def _host_state(self):
+        if self._host is None:
+            self._host = dict(X=self.X.cpu().numpy(), order=self.order.cpu().numpy(),
+                              bw=self.bandwidths(), nlev=(self.nlev_good.cpu().numpy(), self.nlev_bad.cpu().numpy()))
+        return self._host
+
+    def rows_of(self, b):
+        """(good_rows, bad_rows) of group b: positions local to its segment, in the split's order."""
+        h = self._host_state()
+        s, e = int(self.seg_host[b]), int(self.seg_host[b + 1])
+        o = h["order"][s:e]
+        return o[:int(self.n_good[b])], o[e - s - int(self.n_bad[b]):]
+
+    def pair(self, b):
+        """Group b's model as a KDEPair built through the single path (kde.fit_pair_from_rows: two
+        hbx_kde_prepare calls) -- for checks and debugging; None where the group has no model."""
+        if not self.has_model[b]:
+            return None
+        h = self._host_state()
+        s, e = int(self.seg_host[b]), int(self.seg_host[b + 1])
+        g, bd = self.rows_of(b)
+        return kde.fit_pair_from_rows(h["X"][s:e], g, bd, self.var_type, h["bw"][0][b], h["bw"][1][b],
+                                      h["nlev"][0][b], h["nlev"][1][b], device=self.device)
+
+    # ---- the grouped calls ------------------------------------------------------------------------------
+    def sample(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, stream_id=0):
+        """C candidates per group around its good KDE's rows (bohb.py:133-147; hbx_kde_sample_groups):
+        candidate (b, i) draws from the Philox counter ``counter_base + b * C + i``.  Returns device tensors
+        (cands [B, C, D] float64, domain_err [B, C] uint8); groups without a model get NaN rows."""
+        torch = kde._torch()
+        C = int(C)
+        lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
+        if lv.shape != (self.D,):
+            raise N.HbxError("levels must have %d entries" % self.D)
+        with N.on_device(self.device, stream):
+            cands = torch.empty((self.B, C, self.D), dtype=torch.float64, device=self.device)
+            err = torch.zeros((self.B, C), dtype=torch.uint8, device=self.device)
+            lvd = torch.from_numpy(lv).to(self.device)
+            N.check(N.lib().hbx_kde_sample_groups(
+                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
+                N.ptr(self.bw_good), N.ptr(lvd), float(bandwidth_factor), int(seed) & (2 ** 64 - 1),
+                int(counter_base) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF, C, N.ptr(cands), N.ptr(err),
+                N.stream_handle(stream, self.device)))
+        return cands, err
+
+    def workspace_bytes(self, C):
+        return int(N.lib().hbx_kde_groups_workspace_bytes(self.B, int(C), self.D))
+
+    def acquire(self, cands, stream=None, workspace=None, sync=True):
+        """Per group the first index minimising max(1e-8, g)/max(l, 1e-8) over its own pool ``cands[b]``
+        (hbx_kde_acquire_groups).  ``cands``: [B, C, D] float64, numpy or a device tensor.  Returns GroupPicks, or
+        with ``sync=False`` the device tensor of the B records (uint8 [B, 48])."""
+        torch = kde._torch()
+        with N.on_device(self.device, stream):
+            if _is_tensor(cands):
+                cd = cands
+                if cd.dtype != torch.float64 or not cd.is_contiguous():
+                    raise N.HbxError("candidate tensor must be contiguous float64 [B, C, D]")
+            else:
+                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
+            if cd.dim() != 3 or int(cd.shape[0]) != self.B or int(cd.shape[2]) != self.D:
+                raise N.HbxError("candidates must be [%d, C, %d], got %s" % (self.B, self.D, tuple(cd.shape)))
+            C = int(cd.shape[1])
+            wsb = self.workspace_bytes(C)
+            if wsb < 0:
+                raise N.HbxError("B * C = %d * %d exceeds int32" % (self.B, C))
+            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
+            if ws.numel() < wsb:
+                raise N.HbxError("workspace too small")
+            res = torch.empty((self.B, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device)
+            N.check(N.lib().hbx_kde_acquire_groups(
+                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
+                N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
+                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), C, N.ptr(res), N.ptr(ws), ws.numel(),
+                N.stream_handle(stream, self.device)))
+            if not sync:
+                return res
+            return GroupPicks.from_bytes(res.cpu().numpy().tobytes(), self.B)
+
+    def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None):
+        """sample + acquire: (rows [B, D] host float64 -- NaN where a group has no pick --, GroupPicks)."""
+        cands, _ = self.sample(C, seed, levels, bandwidth_factor, counter_base, stream=stream)
+        picks = self.acquire(cands, stream=stream)
+        return picks.rows(cands), picks
+
+
+def group_sizes(lens, D, min_points=None, top_n_percent=15):
+    """Per-group (n_good, n_bad) of the BOHB split (kde.split_sizes(..., 'bohb')), 0 / 0 where the reference
+    builds no model (bohb.py:234-237); host int64 arrays."""
+    mp = int(D) + 1 if min_points is None else int(min_points)
+    ng = np.zeros(len(lens), dtype=np.int64)
+    nb = np.zeros(len(lens), dtype=np.int64)
+    for b, n in enumerate(lens):
+        s = kde.split_sizes(int(n), int(D), mp, top_n_percent, "bohb")
+        if s is not None:
+            ng[b], nb[b] = s
+    return ng, nb
+
+
+def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, device=None, stream=None):
+    """Refit every bracket's good / bad KDE in one batched call (hbx_seg_argsort_ex in numpy's order, then
+    hbx_kde_fit), everything kept on the device.  ``X`` [N, D], ``losses`` [N] and ``seg_off`` [B + 1] are host
+    arrays or device tensors; ``min_points`` defaults to D + 1 (BOHB's).  Returns a GroupModel."""
+    torch = kde._torch()
+    L = N.lib()
+    D = len(var_type)
+    if device is None:
+        device = X.device if _is_tensor(X) else kde.default_device()
+    seg_h = np.ascontiguousarray((seg_off.cpu().numpy() if _is_tensor(seg_off) else np.asarray(seg_off)),
+                                 dtype=np.int64).reshape(-1)
+    if seg_h.size < 1 or np.any(np.diff(seg_h) < 0):
+        raise N.HbxError("seg_off must be a non-decreasing int64 array of B + 1 offsets")
+    B = int(seg_h.size - 1)
+    lens = np.diff(seg_h)
+    Ntot = int(seg_h[-1] - seg_h[0]) if B else 0
+    if B and seg_h[0] != 0:
+        raise N.HbxError("seg_off[0] must be 0")
+    ng, nb = group_sizes(lens, D, min_points, top_n_percent)
+    fg = np.array([kde.bandwidth_factor(int(v), D) if v else 0.0 for v in ng], dtype=np.float64)
+    fb = np.array([kde.bandwidth_factor(int(v), D) if v else 0.0 for v in nb], dtype=np.float64)
+    vt = np.ascontiguousarray(kde.var_type_codes(var_type))
+
+    def dev(a, dtype):
+        if _is_tensor(a):
+            t = a.to(device=device, dtype=dtype)
+            return t if t.is_contiguous() else t.contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a, dtype={torch.float64: np.float64, torch.int64: np.int64,
+                                                               torch.int32: np.int32}[dtype])).to(device)
+
+    with N.on_device(device, stream):
+        Xd = dev(X, torch.float64).reshape(-1, D)
+        ld = dev(losses, torch.float64).reshape(-1)
+        if int(Xd.shape[0]) < Ntot or int(ld.shape[0]) < Ntot:
+            raise N.HbxError("fit_groups: %d rows / %d losses for %d segment entries" % (Xd.shape[0], ld.shape[0], Ntot))
+        if int(Xd.shape[0]) == 0:  # every bracket empty: the calls still want non-null pointers (never read)
+            Xd = torch.zeros((1, D), dtype=torch.float64, device=device)
+            ld = torch.zeros(1, dtype=torch.float64, device=device)
+        segd, ngd, nbd, fgd, fbd = (dev(a, t) for a, t in ((seg_h, torch.int64), (ng, torch.int64), (nb, torch.int64),
+                                                          (fg, torch.float64), (fb, torch.float64)))
+        vtd = dev(vt, torch.int32)
+        order = torch.empty(max(Ntot, 1), dtype=torch.int64, device=device)
+        bwg = torch.full((B, D), float("nan"), dtype=torch.float64, device=device)
+        bwb = torch.full((B, D), float("nan"), dtype=torch.float64, device=device)
+        nlg = torch.zeros((B, D), dtype=torch.int32, device=device)
+        nlb = torch.zeros((B, D), dtype=torch.int32, device=device)
+        sh = N.stream_handle(stream, device)
+        if B and Ntot:
+            sb = int(L.hbx_sort_scratch_bytes(Ntot))
+            scr = torch.empty(sb, dtype=torch.uint8, device=device)
+            N.check(L.hbx_seg_argsort_ex(N.ptr(ld), N.ptr(segd), B, int(lens.max()), Ntot, N.ptr(order), N.ptr(scr),
+                                         sb, N.ORDER_NUMPY, sh))
+            N.check(L.hbx_kde_fit(N.ptr(Xd), D, N.ptr(segd), B, N.ptr(order), N.ptr(ngd), N.ptr(nbd), N.ptr(fgd),
+                                  N.ptr(fbd), N.ptr(vtd), N.ptr(bwg), N.ptr(bwb), N.ptr(nlg), N.ptr(nlb), sh))
+    return GroupModel(B=B, D=D, var_type=var_type, device=device, X=Xd, losses=ld, seg_off=segd, seg_host=seg_h,
+                      order=order, n_good=ng, n_bad=nb, has_model=(ng > 0), n_good_dev=ngd, n_bad_dev=nbd,
+                      fac_good_dev=fgd, fac_bad_dev=fbd, vt_dev=vtd, bw_good=bwg, bw_bad=bwb, nlev_good=nlg,
+                      nlev_bad=nlb)

@@ -20,6 +20,9 @@
  *                                      kernel_density.py:101-115)
  *   hbx_kde_acquire                 <- bohb.py:124-169 (the num_samples loop: pdf of l and g per
  *                                      candidate, minimize_me, strict-'<' argmin)
+ *   hbx_kde_acquire_groups          <- bohb.py:124-169 per bracket, after bohb.py:220-246 (B brackets' picks in
+ *                                      one call, straight from hbx_kde_fit's device outputs)
+ *   hbx_kde_sample_groups           <- bohb.py:133-147 per bracket (the candidates of B brackets in one call)
  *   hbx_kde_logpdf                  <- KDEMultivariate.pdf (kernel_density.py:162-196), fp32 log domain
  *   hbx_kde_pdf_exact               <- KDEMultivariate.pdf, fp64, reference operation order
  *   hbx_sh_promote(_ex)             <- HB_iteration.py:149-190 (SuccessiveHalving.process_results ranks)
@@ -233,6 +236,40 @@ int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int32_t D, i
                          const void* params_bad, const float* table_bad, const double* X_bad,
                          const int64_t* rows_bad, int32_t variant_bad, int32_t dc_pad, int32_t du_pad,
                          int64_t nmax, void* results, void* workspace, int64_t ws_bytes, void* stream);
+
+/* Grouped acquisition: ONE exact pick per KDE pair for B independent brackets -- what follows the batched refit
+ * (hbx_seg_argsort_ex + hbx_kde_fit) when every bracket proposes a configuration (bohb.py:124-169 per bracket).
+ * Every pointer is a device pointer.  X, seg_off, order, n_good, n_bad, vartype, bw_* and nlev_* are exactly
+ * hbx_kde_fit's inputs and outputs, read where the fit left them: with n = seg_off[b+1] - seg_off[b], group b's
+ * good KDE holds the rows X[seg_off[b] + order[seg_off[b] + j]], j < n_good[b], its bad KDE j in [n - n_bad[b], n).
+ * cand: f64[B][C][D], group b's own pool.  results: B * hbx_acq_result_bytes() bytes, record b = what
+ * hbx_kde_acquire returns for group b's pair over cand[b]: index (relative to the pool; -1: no finite score),
+ * score, pdf_l and pdf_g the reference's fp64 values bit for bit; shortlist / near / rel / HBX_ACQ_OVERFLOW /
+ * HBX_ACQ_NEAR_TIE with their meanings (hbx_kde_result_ptr) but from this path's own fp32 screen, so not the
+ * single path's numbers; NEAR_TIE is set whenever two candidates share the best score.  Groups the fit skipped get
+ * HBX_ACQ_NO_MODEL, groups with a categorical bandwidth / level count hbx_kde_prepare reports as unsupported get
+ * HBX_ACQ_UNSUPPORTED: index -1, NaN score and pdfs -- never an error return.
+ * Two launches on `stream`, no host synchronisation, no allocation, no per-group host work; B * C beyond int32:
+ * HBX_ERR_ARG.  B == 0: nothing to do; C == 0: every record is the empty one (index -1, NaN score and pdfs).
+ * workspace: hbx_kde_groups_workspace_bytes(B, C, D) bytes, 16-byte aligned (-1 for arguments out of range). */
+#define HBX_ACQ_NO_MODEL    16  /* group skipped: n_good or n_bad is <= 0 or exceeds the segment (hbx_kde_fit's rule) */
+#define HBX_ACQ_UNSUPPORTED 32  /* a categorical dim's bandwidth/levels are what hbx_kde_prepare reports as unsupported */
+int64_t hbx_kde_groups_workspace_bytes(int64_t B, int64_t C, int32_t D);
+int hbx_kde_acquire_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                           const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                           const double* bw_good, const double* bw_bad,
+                           const int32_t* nlev_good, const int32_t* nlev_bad,
+                           const double* cand, int64_t C, void* results,
+                           void* workspace, int64_t ws_bytes, void* stream);
+/* The matching sampler: C candidates per group around its good KDE's rows (hbx_kde_sample's rule).  Candidate
+ * (b, i) is byte-equal to what hbx_kde_sample draws for group b's good KDE (tab = NULL) at candidate index i of a
+ * call with counter_base + b * C.  cands: f64[B][C][D] (16-byte aligned when D is even); domain_err: nullable
+ * u8[B][C].  Groups without a model (n_good[b] <= 0 or past the segment): NaN rows, flags 0.  One launch, no host
+ * synchronisation. */
+int hbx_kde_sample_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                          const int64_t* n_good, const double* bw_good, const int32_t* levels,
+                          double bw_factor, uint64_t seed, uint64_t counter_base, uint32_t stream_id,
+                          int64_t C, double* cands, uint8_t* domain_err, void* stream);
 
 /* Optional timing: `events` of hbx_kde_acquire is NULL or an array of three hipEvent_t recorded on
  * `stream` before the l scoring launch, between l and g, and after g -- or, when l and g are scored by

@@ -1,0 +1,161 @@
+"""Grouped acquisition at config #5's shape: B = 1e4 brackets x n = 1e3 configs, 24 continuous + 8 categorical
+dims (4 levels), C = 64 candidates per bracket (the reference's num_samples).
+
+Times, with device events around REPS warmed repetitions each:
+  acquire        hbx_kde_acquire_groups alone (candidates already on the device)
+  sample+acquire hbx_kde_sample_groups + hbx_kde_acquire_groups
+  chain          hbx_seg_argsort_ex + hbx_kde_fit + sample + acquire (promote's successor: refit all, propose all)
+and the baseline the library offered before: per bracket kde.fit_pair_from_rows (two hbx_kde_prepare calls) +
+KDEPair.acquire, on a subsample of SUB brackets (wall clock per bracket, synchronised), extrapolated to B --
+reported with and without the prepare time.  The grouped picks are checked against the baseline's on the subsample.
+
+    python tools/bench_groups.py [--B 10000] [--n 1000] [--C 64] [--reps 20] [--sub 200] [--out FILE]
+
+Writes one JSON document (default profiles/groups/bench_groups.json) and prints it.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from hpbandster_amd import _native as N  # noqa: E402
+from hpbandster_amd import groups, kde  # noqa: E402
+from hpbandster_amd import synthetic as S  # noqa: E402
+
+PEAK_FP32_TFLOPS = 157.3  # MI355X peak fp32 vector rate (bench.py's basis)
+W = 92  # algorithmic flops per (candidate, observation) pair at 24c + 8u
+
+
+def timed(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=10000)
+    ap.add_argument("--n", type=int, default=1000)
+    ap.add_argument("--C", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--sub", type=int, default=200)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "groups", "bench_groups.json"))
+    a = ap.parse_args(argv)
+    dev = torch.device("cuda", 0)
+    L = N.lib()
+    B, n, C, dc, du, lev = a.B, a.n, a.C, 24, 8, 4
+    D = dc + du
+    vts = S.var_type_string(dc, du)
+    levels = [0] * dc + [lev] * du
+    # config #5's inputs as bench.py builds them: synthetic.py's losses, observations drawn on the device
+    losses = torch.from_numpy(S.make_bracket_losses(B, n).reshape(-1)).to(dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    X = torch.empty((B * n, D), dtype=torch.float64, device=dev)
+    X[:, :dc] = torch.rand((B * n, dc), dtype=torch.float64, device=dev, generator=g)
+    X[:, dc:] = torch.randint(0, lev, (B * n, du), device=dev, generator=g).to(torch.float64)
+    seg = np.arange(B + 1, dtype=np.int64) * n
+    gm = groups.fit_groups(X, losses, seg, vts, device=dev)
+    sh = N.stream_handle(None, dev)
+    cands = torch.empty((B, C, D), dtype=torch.float64, device=dev)
+    derr = torch.empty((B, C), dtype=torch.uint8, device=dev)
+    lvd = torch.tensor(levels, dtype=torch.int32, device=dev)
+    wsb = gm.workspace_bytes(C)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    res = torch.empty((B, kde.RESULT_BYTES), dtype=torch.uint8, device=dev)
+    sb = int(L.hbx_sort_scratch_bytes(B * n))
+    scr = torch.empty(sb, dtype=torch.uint8, device=dev)
+
+    def refit():
+        N.check(L.hbx_seg_argsort_ex(N.ptr(gm.losses), N.ptr(gm.seg_off), B, n, B * n, N.ptr(gm.order), N.ptr(scr), sb,
+                                     N.ORDER_NUMPY, sh))
+        N.check(L.hbx_kde_fit(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
+                              N.ptr(gm.n_bad_dev), N.ptr(gm.fac_good_dev), N.ptr(gm.fac_bad_dev), N.ptr(gm.vt_dev),
+                              N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad), sh))
+
+    def sample():
+        N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
+                                        N.ptr(gm.bw_good), N.ptr(lvd), 3.0, S.SEED_CAND, 0, 0, C, N.ptr(cands),
+                                        N.ptr(derr), sh))
+
+    def acquire():
+        N.check(L.hbx_kde_acquire_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
+                                         N.ptr(gm.n_bad_dev), N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad),
+                                         N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad), N.ptr(cands), C, N.ptr(res),
+                                         N.ptr(ws), wsb, sh))
+
+    sample()
+    ms_acq = timed(acquire, a.reps)
+    ms_sa = timed(lambda: (sample(), acquire()), a.reps)
+    ms_chain = timed(lambda: (refit(), sample(), acquire()), a.reps)
+    ms_fit = timed(refit, a.reps)
+    picks = groups.GroupPicks.from_bytes(res.cpu().numpy().tobytes(), B)
+    ng, nb = int(gm.n_good[0]), int(gm.n_bad[0])
+    pairs = float(B) * C * (ng + nb)
+    rate = pairs / (ms_acq * 1e-3)
+
+    # the per-bracket loop on a subsample
+    sub = np.unique(np.linspace(0, B - 1, min(a.sub, B)).astype(np.int64))
+    bwg, bwb = gm.bandwidths()
+    nlg, nlb = gm.nlev_good.cpu().numpy(), gm.nlev_bad.cpu().numpy()
+    order_h = gm.order.cpu().numpy()
+    t_prep, t_acq, agree = [], [], 0
+    for it, b in enumerate(np.concatenate([sub[:3], sub])):  # the first three again as warm-up
+        s, e = int(seg[b]), int(seg[b + 1])
+        Xb = gm.X[s:e].cpu().numpy()
+        o = order_h[s:e]
+        cb = cands[b]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pair = kde.fit_pair_from_rows(Xb, o[:ng], o[e - s - nb:], vts, bwg[b], bwb[b], nlg[b], nlb[b], device=dev)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        r = pair.acquire(cb)
+        t2 = time.perf_counter()
+        if it >= 3:
+            t_prep.append(t1 - t0)
+            t_acq.append(t2 - t1)
+            agree += int(r.index == picks.index[b] and r.score == picks.score[b])
+    prep_ms, acq_ms = 1e3 * float(np.mean(t_prep)), 1e3 * float(np.mean(t_acq))
+    loop_ms = B * (prep_ms + acq_ms)
+    loop_ms_noprep = B * acq_ms
+    out = {
+        "workload": "grouped_acquisition_b%d_n%d_d32_24c8u_c%d" % (B, n, C),
+        "device": torch.cuda.get_device_name(0),
+        "reps": a.reps,
+        "n_good": ng, "n_bad": nb,
+        "acquire_ms": ms_acq, "sample_acquire_ms": ms_sa, "refit_sample_acquire_ms": ms_chain, "refit_ms": ms_fit,
+        "pairs": pairs, "pairs_per_s": rate,
+        "fp32_valu": {"flops_per_pair": W, "achieved_tflops": W * rate / 1e12, "peak_tflops": PEAK_FP32_TFLOPS,
+                      "frac": W * rate / 1e12 / PEAK_FP32_TFLOPS},
+        "mean_shortlist": float(picks.shortlist.mean()), "max_shortlist": int(picks.shortlist.max()),
+        "picked": int((picks.index >= 0).sum()), "overflow_groups": int(((picks.flags & 1) != 0).sum()),
+        "near_tie_groups": int(((picks.flags & 2) != 0).sum()),
+        "baseline": {"subsample": int(sub.size), "prepare_ms_per_group": prep_ms, "acquire_ms_per_group": acq_ms,
+                     "loop_ms_extrapolated": loop_ms, "loop_ms_extrapolated_without_prepare": loop_ms_noprep,
+                     "picks_agree": agree},
+        "speedup_vs_loop": loop_ms / ms_acq, "speedup_vs_loop_without_prepare": loop_ms_noprep / ms_acq,
+    }
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+    return 0 if agree == sub.size and ms_acq < loop_ms else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
