@@ -101,19 +101,3 @@ __device__ __forceinline__ double score_rel(const KdeParams* __restrict__ Pg, co
 __device__ __forceinline__ bool near_best(double s, double rp, double best, double rb) {
   return s < INFINITY && s <= best * (1.0 + 1.0001 * (rp + rb));
 }
-
-// hbx_topk.hip: the top-k selection steps hbx_kde_acquire_topk launches around the exact re-score.
-// Workspace of the k-th bound's radix select: 4 histograms of 256 bins.
-#define TOPK_HIST_WORDS (4 * 256)
-// score intervals from the (merged, rescued) estimates: lo[i] as the shortlist predicate reads it, the
-// ordered key of hi into hik[i]; the overflow rule into flags[0]; zeroes the select's histograms
-int hbx_topk_bounds(const KdeEst* el, const KdeEst* eg, int64_t Nc, float* lo, uint32_t* hik, int32_t* flags,
-                    uint32_t* hist, hipStream_t s);
-// U[0] = the k-th smallest finite hi (+inf with fewer than k), then the shortlist {i: lo[i] == lo[i] &&
-// (flags[0] & 1 || lo[i] <= U[0])} into list / count; zeroes the scoring launch's marker count
-int hbx_topk_shortlist(const float* lo, const uint32_t* hik, int64_t Nc, int32_t k, uint32_t* hist, uint32_t* U,
-                       const int32_t* flags, int32_t* list, int32_t* count, int32_t* rescue_cnt, hipStream_t s);
-// the k smallest (score, index) of the re-scored shortlist, ranked, into the result block
-int hbx_topk_final(const int32_t* list, const int32_t* count, const double* exact_l, const double* exact_g,
-                   const int32_t* flags, int64_t index_base, int32_t k, const KdeParams* Pg, const KdeParams* Pb,
-                   const KdeEst* el, const KdeEst* eg, void* results, hipStream_t s);

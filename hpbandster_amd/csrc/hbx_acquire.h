@@ -1,0 +1,90 @@
+// hbx_acquire.h -- what the acquisitions of one KDE pair share on the launch side.  Users: hbx_kde.hip
+// (defines it; the argmin: single, bound, batched), hbx_topk.hip (the top-k of one pool, which runs the same
+// scoring and exact re-score around its own selection steps) and hbx_exact.hip (acq_exact, beside its kernels).
+#pragma once
+#include "hbx_score.h"
+
+// A prepared (good, bad) KDE pair as every acquisition entry point receives it (hbx_kde_pair_bind keeps one)
+struct KdePairRef {
+  int32_t D;
+  const void* params_good;
+  const float* table_good;
+  const double* X_good;
+  const int64_t* rows_good;
+  int32_t variant_good;
+  const void* params_bad;
+  const float* table_bad;
+  const double* X_bad;
+  const int64_t* rows_bad;
+  int32_t variant_bad, dc_pad, du_pad;
+  int64_t nmax;
+  const KdeParams* Pg() const { return (const KdeParams*)params_good; }
+  const KdeParams* Pb() const { return (const KdeParams*)params_bad; }
+};
+
+// workspace layout (bytes), shared by the *_workspace_bytes helpers and the acquisitions; B = number
+// of acquisitions (segments) of a batched call (1 for hbx_kde_acquire).  The single result record
+// comes first so its offset does not depend on the sizes.
+struct WsLayout {
+  size_t res, U, count, flags, segcnt, segnear, best, key, first1, rescue, est_l, est_g, lo, list, near, exact_l,
+      exact_g, part, total;
+};
+WsLayout ws_layout(int64_t Nc, int64_t nmax, int64_t B = 1);
+
+// the workspace's arrays as typed pointers
+struct AcqWs {
+  AcqResult* res;
+  uint32_t* U;
+  int32_t *count, *flags, *segcnt, *segnear;
+  uint64_t *best, *key;
+  int32_t *first1, *rescue;
+  KdeEst *el, *eg;
+  float* lo;
+  int32_t *list, *near;
+  double *exact_l, *exact_g, *part;
+  AcqWs(void* workspace, const WsLayout& w) {
+    char* ws = (char*)workspace;
+    res = (AcqResult*)(ws + w.res);
+    U = (uint32_t*)(ws + w.U);
+    count = (int32_t*)(ws + w.count);
+    flags = (int32_t*)(ws + w.flags);
+    segcnt = (int32_t*)(ws + w.segcnt);
+    segnear = (int32_t*)(ws + w.segnear);
+    best = (uint64_t*)(ws + w.best);
+    key = (uint64_t*)(ws + w.key);
+    first1 = (int32_t*)(ws + w.first1);
+    rescue = (int32_t*)(ws + w.rescue);
+    el = (KdeEst*)(ws + w.est_l);
+    eg = (KdeEst*)(ws + w.est_g);
+    lo = (float*)(ws + w.lo);
+    list = (int32_t*)(ws + w.list);
+    near = (int32_t*)(ws + w.near);
+    exact_l = (double*)(ws + w.exact_l);
+    exact_g = (double*)(ws + w.exact_g);
+    part = (double*)(ws + w.part);
+  }
+};
+
+// The steps every acquisition runs, in this order around its own selection steps.
+// (1) the pointer and range checks, then both KDEs' scoring instances (fast: no ln-pdf estimates reported)
+struct AcqPlan {
+  ScoreFns fg, fb;
+  bool exact_only;  // a KDE outside every fp32 scoring bucket: no scoring launch, every candidate re-scored
+};
+int acq_check(const char* who, const KdePairRef& p, const double* cand, int64_t Nc, const void* workspace);
+int acq_plan(const KdePairRef& p, bool fast, AcqPlan* plan);
+// (2) the scoring launch (first: it touches none of the per-acquisition state, so the GPU starts on it while
+// the host enqueues the rest), the state's initialisation where the launch did not do it (batch_B > 0: the
+// B segments' state instead), the launch's observation splits merged.  split_nmax: the observation count the
+// splits are sized for (0: no splits); rescue_inline (nullable: the rescue pass always a launch of its own):
+// set when the pass is left to the combine kernel
+int acq_score(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
+              int64_t batch_B, hipEvent_t* ev, int64_t split_nmax, bool* rescue_inline, hipStream_t s);
+// exact-only acquisitions instead of a combine / bounds pass: every candidate joins the re-score
+int acq_exact_only_init(int64_t Nc, uint32_t seg, const AcqWs& a, hipStream_t s);
+// (3) the exact fp64 re-score of the shortlist a.list / a.count (scan, a single acquisition of at most
+// EXACT_SCAN_MAX candidates: the blocks shortlist for themselves), then -- combine -- its unit sums into
+// a.exact_l / a.exact_g
+#define EXACT_SCAN_MAX 1024
+int acq_exact(const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a, bool scan, bool combine,
+              hipStream_t s);

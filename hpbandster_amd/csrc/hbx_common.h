@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define HBX_MAX_D 256          // largest configuration-space dimension the engine accepts
 #define HBX_WAVE 64            // CDNA wavefront width
@@ -30,6 +31,13 @@ int hbx_fail(int code, const char* fmt, ...);
       return hbx_fail(HBX_ERR_HIP, "kernel launch failed: %s (%s:%d)",               \
                       hipGetErrorString(_e), __FILE__, __LINE__);                    \
   } while (0)
+
+// An HBX_* environment switch: on when unset or non-zero.  Read on every call (tests flip the switches
+// in-process), never cached.
+static inline bool hbx_switch_on(const char* name) {
+  const char* e = getenv(name);
+  return !(e && atoi(e) == 0);
+}
 
 // ------------------------------------------------------------------------------------------
 // KDE model parameters, one block per KDE (good or bad).  Written on the device by

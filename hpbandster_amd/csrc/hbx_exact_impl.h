@@ -1,7 +1,7 @@
 // hbx_exact_impl.h -- the exact fp64 pdf in the reference's arithmetic (SM:_kernel_base.py:509-516: per-dim
-// kernels, dim-ordered product, / prod(bw_c), numpy's pairwise sum, / n; numpy's exp bit for bit), shared by the
-// single acquisition's re-score (hbx_kde.hip) and the grouped one (hbx_groups.hip).  The bodies are the ones
-// hbx_kde.hip held; only the parameter type is a template argument: a KdeParams block, or any view with the
+// kernels, dim-ordered product, / prod(bw_c), numpy's pairwise sum, / n; numpy's exp bit for bit), shared by
+// hbx_exact.hip (the acquisitions' re-score, the exact pdf entry points) and hbx_groups.hip (the grouped
+// re-score).  Only the parameter type is a template argument: a KdeParams block, or any view with the
 // members n, bw[d], vartype[d], nlev[d] and prod_bw_c (hbx_groups.hip's per-group view holds pointers into
 // hbx_kde_fit's outputs).
 #pragma once

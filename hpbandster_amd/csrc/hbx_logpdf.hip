@@ -7,9 +7,9 @@
 //                      accepts, lists the rest (two instances per call: rows from SGPRs or from LDS)
 //   kde_logpdf_classify  (signed / unbucketed KDEs) the same split over the MFMA scoring estimate
 //   kde_logpdf_tiled   fp64 log-space evaluation of the listed candidates, rows staged in LDS
-//   (hbx_kde.hip)      the per-point fp64 kernels for buckets without a tiled instance and for KDEs with
+//   (hbx_exact.hip)    the per-point fp64 kernels for buckets without a tiled instance and for KDEs with
 //                      negative categorical factors or structural NaN
-// Split from hbx_kde.hip, whose acquisition engine shares the KDE parameter block and the scoring instances.
+// The acquisition engine (hbx_kde.hip) shares the KDE parameter block and the scoring instances (hbx_score.hip).
 #include <math.h>
 #include <stdlib.h>
 
@@ -737,13 +737,13 @@ int hbx_kde_logpdf_rtol(const double* cand, int64_t Nc, int32_t D, const void* p
   // unsigned KDEs of a bucket with <= 32 continuous slots: the direct-difference fp32 pass writes every
   // candidate its bound accepts and lists the rest (its kernel lists all of a KDE it does not model)
   int cpt = 1;
-  const char* lut_env = getenv("HBX_DD_LUT");  // 0: the packed-match categorical path everywhere (tests)
-  const bool lut = ((variant >> 8) & 1) && !(lut_env && atoi(lut_env) == 0);
+  // HBX_DD_LUT=0: the packed-match categorical path everywhere (tests)
+  const bool lut = ((variant >> 8) & 1) && hbx_switch_on("HBX_DD_LUT");
   const DdFns dd = (!exact_only && !(variant & 1)) ? pick_logpdf_dd(dc_pad, du_pad, &cpt, lut) : DdFns{};
-  const char* sg_env = getenv("HBX_DD_SG");  // 0: the LDS-staged dd kernel everywhere (tests)
+  // HBX_DD_SG=0: the LDS-staged dd kernel everywhere (tests)
   // (small calls: the LDS-staged kernel alone -- the staging launch and a second dd launch would cost more than
   // the SG kernel saves, and the scratch of a few thousand candidates rarely holds the rows)
-  const bool sg = dd.sg && Nc >= 8192 && !(sg_env && atoi(sg_env) == 0);
+  const bool sg = dd.sg && Nc >= 8192 && hbx_switch_on("HBX_DD_SG");
   HBX_HIP(hipMemsetAsync(count, 0, sizeof(int32_t), s));
   if (dd.lds) {
     const dim3 g((unsigned)((Nc + 256 * cpt - 1) / (256 * cpt)));

@@ -1,5 +1,5 @@
 // hbx_pairwise.h -- numpy's pairwise summation order on the GPU (shared by the exact re-score in
-// hbx_kde.hip and the cross-validation objectives in hbx_cv.hip).
+// hbx_exact_impl.h / hbx_exact.hip, the final argmin in hbx_kde.hip and the cross-validation objectives in hbx_cv.hip).
 #pragma once
 #include "hbx_common.h"
 

@@ -1,7 +1,7 @@
 // hbx_topk.hip -- top-k acquisition on MI355X (gfx950): the k best candidates of ONE pool, ranked exactly.
 //
 // hbx_kde_acquire answers "which candidate minimises s = max(1e-8, g) / max(l, 1e-8)" (bohb.py:149-152);
-// hbx_kde_acquire_topk (hbx_kde.hip) returns the first min(k, F) entries of the stable ascending order of s
+// hbx_kde_acquire_topk (at the end of this file) returns the first min(k, F) entries of the stable ascending order of s
 // over the F candidates whose score is not NaN: ordered by (s[i], i), every value the reference's fp64 bit
 // for bit.  The scoring launch, its rescue pass and split merge, and the exact fp64 re-score are the
 // argmin's, unchanged; this file holds the three steps that differ:
@@ -17,7 +17,7 @@
 //                    their histograms (a 256-bin scan per block: no launch between the passes)
 //   topk_shortlist   the last digit, then {i : lo[i] is not NaN and (overflow flag or lo[i] <= U_k)} -> list,
 //                    one atomic add per wave.  Fewer than k finite hi: U_k = +inf, every rankable candidate.
-//   (kde_exact_kernel / kde_exact_combine_kernel, hbx_kde.hip: the fp64 pdfs of the listed candidates)
+//   (kde_exact_kernel / kde_exact_combine_kernel, hbx_exact.hip: the fp64 pdfs of the listed candidates)
 //   topk_final       one block: scores from the exact pdfs, a running best-(k+1) by (score bits, index) over
 //                    a shortlist of any length (bitonic merges in LDS, a threshold skipping what cannot
 //                    enter), the ranked records, and HBX_ACQ_NEAR_TIE
@@ -34,8 +34,10 @@
 //   header {i32 count, i32 shortlist, i32 flags, i32 k}, then `count` records of 40 bytes
 //   {i64 index, f64 score, f64 pdf_l, f64 pdf_g, f32 rel, i32 0}
 #include "hbx_acq_impl.h"
+#include "hbx_acquire.h"
 
 #define TOPK_KEY_INF 0xFF800000u  // hbx_f2ord(+inf): keys below it are finite upper bounds
+#define TOPK_HIST_WORDS (4 * 256)  // workspace of the k-th bound's radix select: 4 histograms of 256 bins
 
 struct TopkHead {
   int32_t count, shortlist, flags, k;
@@ -290,9 +292,11 @@ __global__ __launch_bounds__(TOPK_T) void topk_final_kernel(
 }
 
 // ------------------------------------------------------------------------------------------
-// launchers (hbx_kde.hip: hbx_kde_acquire_topk)
+// launchers and entry points
 
-int hbx_topk_bounds(const KdeEst* el, const KdeEst* eg, int64_t Nc, float* lo, uint32_t* hik, int32_t* flags,
+// score intervals from the (merged, rescued) estimates: lo[i] as the shortlist predicate reads it, the
+// ordered key of hi into hik[i]; the overflow rule into flags[0]; zeroes the select's histograms
+static int hbx_topk_bounds(const KdeEst* el, const KdeEst* eg, int64_t Nc, float* lo, uint32_t* hik, int32_t* flags,
                     uint32_t* hist, hipStream_t s) {
   hipLaunchKernelGGL(topk_bounds_kernel, dim3((unsigned)((Nc + 255) / 256)), dim3(256), 0, s, el, eg, Nc, lo, hik,
                      flags, hist);
@@ -300,7 +304,9 @@ int hbx_topk_bounds(const KdeEst* el, const KdeEst* eg, int64_t Nc, float* lo, u
   return HBX_OK;
 }
 
-int hbx_topk_shortlist(const float* lo, const uint32_t* hik, int64_t Nc, int32_t k, uint32_t* hist, uint32_t* U,
+// U[0] = the k-th smallest finite hi (+inf with fewer than k), then the shortlist {i: lo[i] == lo[i] &&
+// (flags[0] & 1 || lo[i] <= U[0])} into list / count; zeroes the scoring launch's marker count
+static int hbx_topk_shortlist(const float* lo, const uint32_t* hik, int64_t Nc, int32_t k, uint32_t* hist, uint32_t* U,
                        const int32_t* flags, int32_t* list, int32_t* count, int32_t* rescue_cnt, hipStream_t s) {
   if (hik) {  // the radix select (no keys: an exact-only acquisition, its histograms zero, U_k = +inf)
     const unsigned gh = (unsigned)((Nc + TOPK_HIST_PER_BLOCK - 1) / TOPK_HIST_PER_BLOCK);
@@ -315,7 +321,8 @@ int hbx_topk_shortlist(const float* lo, const uint32_t* hik, int64_t Nc, int32_t
   return HBX_OK;
 }
 
-int hbx_topk_final(const int32_t* list, const int32_t* count, const double* exact_l, const double* exact_g,
+// the k smallest (score, index) of the re-scored shortlist, ranked, into the result block
+static int hbx_topk_final(const int32_t* list, const int32_t* count, const double* exact_l, const double* exact_g,
                    const int32_t* flags, int64_t index_base, int32_t k, const KdeParams* Pg, const KdeParams* Pb,
                    const KdeEst* el, const KdeEst* eg, void* results, hipStream_t s) {
   if (k < 1 || k > HBX_TOPK_MAX_K) return hbx_fail(HBX_ERR_ARG, "top-k: k=%d outside [1, %d]", k, HBX_TOPK_MAX_K);
@@ -324,3 +331,72 @@ int hbx_topk_final(const int32_t* list, const int32_t* count, const double* exac
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }
+
+extern "C" {
+
+// The workspace is hbx_kde_acquire's (the near list's 4 Nc bytes hold the upper bounds' keys) followed by the
+// radix select's histograms.
+int64_t hbx_kde_topk_workspace_bytes(int64_t Nc, int32_t k, int64_t nmax) {
+  if (Nc < 0 || k < 1 || k > HBX_TOPK_MAX_K) return -1;
+  return (int64_t)(ws_layout(Nc, nmax).total + 4 * TOPK_HIST_WORDS);
+}
+
+int64_t hbx_kde_topk_result_bytes(int32_t k) {
+  if (k < 1 || k > HBX_TOPK_MAX_K) return -1;
+  return 16 + 40 * (int64_t)k;
+}
+
+// The k best candidates of one pool by (score, index): the scoring launch, its rescue pass and split merge and
+// the exact re-score as the argmin runs them for one acquisition (acq_score, acq_exact: hbx_acquire.h); between
+// them the bounds pass, the k-th smallest upper bound and the shortlist against it, after them the ranking.
+// Unlike the argmin, the combine never does the rescue, the exact re-score never scans and its unit sums are
+// always combined by their own launch.
+int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int32_t D, int64_t index_base,
+                         const void* params_good, const float* table_good, const double* X_good,
+                         const int64_t* rows_good, int32_t variant_good, const void* params_bad,
+                         const float* table_bad, const double* X_bad, const int64_t* rows_bad, int32_t variant_bad,
+                         int32_t dc_pad, int32_t du_pad, int64_t nmax, void* results, void* workspace,
+                         int64_t ws_bytes, void* stream) {
+  const char* who = "hbx_kde_acquire_topk";
+  const KdePairRef p{D, params_good, table_good, X_good, rows_good, variant_good, params_bad, table_bad, X_bad,
+                     rows_bad, variant_bad, dc_pad, du_pad, nmax};
+  if (!results) return hbx_fail(HBX_ERR_ARG, "%s: null pointer", who);
+  int rc = acq_check(who, p, cand, Nc, workspace);
+  if (rc) return rc;
+  if (k < 1 || k > HBX_TOPK_MAX_K) return hbx_fail(HBX_ERR_ARG, "%s: k=%d outside [1, %d]", who, k, HBX_TOPK_MAX_K);
+  if (D < 1 || D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "%s: D=%d", who, D);
+  const int64_t need = hbx_kde_topk_workspace_bytes(Nc, k, nmax);
+  if (ws_bytes < need)
+    return hbx_fail(HBX_ERR_ARG, "workspace too small: %lld < %lld bytes", (long long)ws_bytes, (long long)need);
+  hipStream_t s = (hipStream_t)stream;
+  if (Nc == 0) {  // count = 0 and no launch: a zeroed header
+    HBX_HIP(hipMemsetAsync(results, 0, 16, s));
+    return HBX_OK;
+  }
+  AcqPlan plan;
+  rc = acq_plan(p, true, &plan);
+  if (rc) return rc;
+  const WsLayout w = ws_layout(Nc, nmax);
+  const AcqWs a(workspace, w);
+  uint32_t* hik = (uint32_t*)a.near;                         // the upper bounds' keys in the near list's place
+  uint32_t* hist = (uint32_t*)((char*)workspace + w.total);  // the select's histograms after the argmin's workspace
+  rc = acq_score(plan, p, cand, Nc, a, 0, nullptr, nmax, nullptr, s);
+  if (rc) return rc;
+  if (plan.exact_only) {  // no estimates: every candidate re-scored (lo = 0, the flag set), no select
+    rc = acq_exact_only_init(Nc, (uint32_t)Nc, a, s);
+    if (rc) return rc;
+    HBX_HIP(hipMemsetAsync(hist, 0, 4 * TOPK_HIST_WORDS, s));
+  } else {
+    rc = hbx_topk_bounds(a.el, a.eg, Nc, a.lo, hik, a.flags, hist, s);
+    if (rc) return rc;
+  }
+  rc = hbx_topk_shortlist(a.lo, plan.exact_only ? nullptr : hik, Nc, k, hist, a.U, a.flags, a.list, a.count, a.rescue,
+                          s);
+  if (rc) return rc;
+  rc = acq_exact(p, cand, Nc, a, false, true, s);
+  if (rc) return rc;
+  return hbx_topk_final(a.list, a.count, a.exact_l, a.exact_g, a.flags, index_base, k, p.Pg(), p.Pb(), a.el, a.eg,
+                        results, s);
+}
+
+}  // extern "C"
