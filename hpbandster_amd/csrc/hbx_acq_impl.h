@@ -3,6 +3,7 @@
 // score interval, the score and its error bound, so both paths screen and rank by the same numbers.
 #pragma once
 #include "hbx_kde_impl.h"
+#include "hbx_score.h"  // OBS_SPLIT_MAX
 
 // ln-pdf interval [lo, hi] and point estimate from (ln S+, ln S-, relative bound); -inf means pdf <= 0
 __device__ __forceinline__ void est_interval(const KdeEst e, float* lo, float* hi, float* pt) {
@@ -61,6 +62,63 @@ __device__ __forceinline__ ScoreIv score_interval(const KdeEst a, const KdeEst b
     v.slo = v.shi = 0.f;
   }
   return v;
+}
+
+// The staged acquisition (hbx_staged.hip) did not evaluate g for this candidate: err of its a.eg entry (distinct
+// from the rescue marker -1 and exact-only's -2).  Its score interval from l alone: whatever g is,
+// max(1e-8, g) >= 1e-8, so slo = C - max(lhi, C); no upper end (shi = +inf never lowers U), never a certain
+// tie.  lnan and of come from l as in score_interval.
+#define HBX_EST_NOT_EVAL (-3.f)
+__device__ __forceinline__ ScoreIv score_interval_l_only(const KdeEst a) {
+  const float C = (float)HBX_LN_CLAMP;
+  ScoreIv v;
+  v.of = false;
+  v.one = false;
+  v.gpt = NAN;
+  v.lnan = a.lpos != a.lpos;
+  if (v.lnan) {
+    v.slo = v.shi = NAN;
+    v.lpt = NAN;
+    return v;
+  }
+  float llo, lhi;
+  est_interval(a, &llo, &lhi, &v.lpt);
+  v.of = lhi > 700.f;
+  v.slo = C - fmaxf(lhi, C);
+  v.shi = INFINITY;
+  return v;
+}
+
+// Candidate i's estimate merged over its nsplit observation-split partials (hbx_score_h32.hip; partial r at
+// e[r stride + i]): the sums add (log domain, fp32); each partial's relative bound holds for the total too (sums
+// of positive terms), plus per merge its own rounding: 2^-18 for the fp32 exp / log / addition, and the rounding
+// of the merged ln S to fp32 (<= |ln S| 2^-23 absolute, counted as 2^-22 |ln S| relative on S)
+__device__ __forceinline__ KdeEst merge_splits(const KdeEst* __restrict__ e, int64_t stride, int64_t i, int nsplit) {
+  // every partial's load issued before the first merge (a load per dependent merge step cost 14 us for 16
+  // splits of 64 candidates); fixed-size and fully unrolled, so the partials stay in registers
+  KdeEst p[OBS_SPLIT_MAX];
+#pragma unroll
+  for (int r = 0; r < OBS_SPLIT_MAX; ++r) p[r] = r < nsplit ? e[(int64_t)r * stride + i] : kde_est_neutral();
+  auto lae = [](float x, float y) {
+    const float m = fmaxf(x, y);
+    return m == -INFINITY ? m : m + __logf(__expf(x - m) + __expf(y - m));
+  };
+  KdeEst a = p[0];
+#pragma unroll
+  for (int r = 1; r < OBS_SPLIT_MAX; ++r) {
+    if (r < nsplit) {
+      const KdeEst b = p[r];
+      if (a.lpos != a.lpos || b.lpos != b.lpos) {  // structural NaN (every split carries it)
+        a.lpos = NAN;
+      } else {
+        a.lpos = lae(a.lpos, b.lpos);
+        a.lneg = lae(a.lneg, b.lneg);
+        const float ml = fmaxf(a.lpos > -INFINITY ? fabsf(a.lpos) : 0.f, a.lneg > -INFINITY ? fabsf(a.lneg) : 0.f);
+        a.err = fmaxf(a.err, b.err) + 0x1p-18f + ml * 0x1p-22f;
+      }
+    }
+  }
+  return a;
 }
 
 // bohb.py:129 with Python max(): max(1e-8, g) keeps 1e-8 unless g > 1e-8 (NaN -> 1e-8); max(l, 1e-8)

@@ -28,7 +28,13 @@ struct KdePairRef {
 struct WsLayout {
   size_t res, U, count, flags, segcnt, segnear, best, key, first1, rescue, est_l, est_g, lo, list, near, exact_l,
       exact_g, part, total;
+  // the staged single acquisition (hbx_staged.hip), appended: its state words (in the result slot's padding),
+  // the seed list (list_cap entries), the survivor list (Nc), the list launches' split partials
+  // ([OBS_SPLIT_MAX][list_cap] estimates)
+  size_t stage, seeds, surv, lpart;
+  int32_t list_cap;
 };
+#define STAGED_LIST_CAP 4096  // seeds at most, and listed candidates at most of a split list launch
 WsLayout ws_layout(int64_t Nc, int64_t nmax, int64_t B = 1);
 
 // the workspace's arrays as typed pointers
@@ -42,6 +48,10 @@ struct AcqWs {
   float* lo;
   int32_t *list, *near;
   double *exact_l, *exact_g, *part;
+  uint32_t* stage;
+  int32_t *seeds, *surv;
+  KdeEst* lpart;
+  int32_t list_cap;
   AcqWs(void* workspace, const WsLayout& w) {
     char* ws = (char*)workspace;
     res = (AcqResult*)(ws + w.res);
@@ -62,6 +72,11 @@ struct AcqWs {
     exact_l = (double*)(ws + w.exact_l);
     exact_g = (double*)(ws + w.exact_g);
     part = (double*)(ws + w.part);
+    stage = (uint32_t*)(ws + w.stage);
+    seeds = (int32_t*)(ws + w.seeds);
+    surv = (int32_t*)(ws + w.surv);
+    lpart = (KdeEst*)(ws + w.lpart);
+    list_cap = w.list_cap;
   }
 };
 
@@ -80,6 +95,18 @@ int acq_plan(const KdePairRef& p, bool fast, AcqPlan* plan);
 // set when the pass is left to the combine kernel
 int acq_score(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
               int64_t batch_B, hipEvent_t* ev, int64_t split_nmax, bool* rescue_inline, hipStream_t s);
+// (2') instead of (2) for a single acquisition without ln-pdf outputs whose KDEs both run the coarse 32x32
+// instance: the staged scoring (hbx_staged.hip) -- l for every candidate, g only where l alone does not rule the
+// candidate out; the others' a.eg holds the marker HBX_EST_NOT_EVAL, which the combine kernel reads as an
+// l-only interval.  It leaves the rescue of marked g estimates to the combine kernel (its <_, true> instance).
+// events: [0] at the first scoring launch's start, [1] and [2] after the last one.
+#ifndef HBX_STAGED_MIN_PAIRS
+#define HBX_STAGED_MIN_PAIRS 1e9  // candidates x observations from which an acquisition stages when HBX_STAGED is unset
+#endif
+int acq_staged_mode();  // HBX_STAGED (read per call): 0 never, 2 wherever supported, else by size
+bool acq_staged_supported(const AcqPlan& plan);
+int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
+                     hipEvent_t* ev, hipStream_t s);
 // exact-only acquisitions instead of a combine / bounds pass: every candidate joins the re-score
 int acq_exact_only_init(int64_t Nc, uint32_t seg, const AcqWs& a, hipStream_t s);
 // (3) the exact fp64 re-score of the shortlist a.list / a.count (scan, a single acquisition of at most

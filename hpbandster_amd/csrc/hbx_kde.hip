@@ -10,6 +10,9 @@
 //   kde_logpdf<..>   x2 (good, bad): fp32 log-domain sum over observations, one candidate per lane,
 //                    observations broadcast through the scalar path; per candidate ln S+, ln S-, bound
 //                    (hbx_score.hip dispatches, hbx_score_*.hip hold the kernels)
+//                    -- or, for a large single acquisition without ln-pdf outputs, the staged scoring
+//                    (hbx_staged.hip): l for every candidate, g only where l alone does not rule the
+//                    candidate out; the others carry an l-only interval through the steps below
 //   kde_combine      per-candidate score interval [lo, hi] (ln units) + block min of hi -> U
 //   kde_shortlist    every candidate with lo <= U (the only ones that can be the argmin)
 //   kde_exact        fp64 re-score of the shortlist in the reference's arithmetic/operation order (hbx_exact.hip)
@@ -59,37 +62,8 @@ __global__ void acq_init_batch_kernel(int64_t B, uint32_t* __restrict__ U, int32
 // (BOHB's own sampler puts most candidates there at D = 32: the truncnorm scale is 3 bw).
 // (OBS_SPLIT_MAX, the observation splits of one scoring launch at most: hbx_score.h)
 
-// Candidate i's estimate merged over its nsplit observation-split partials (hbx_score_h32.hip): the sums
-// add (log domain, fp32); each partial's relative bound holds for the total too (sums of positive terms),
-// plus per merge its own rounding: 2^-18 for the fp32 exp / log / addition, and the rounding of the merged
-// ln S to fp32 (<= |ln S| 2^-23 absolute, counted as 2^-22 |ln S| relative on S)
-__device__ __forceinline__ KdeEst merge_splits(const KdeEst* __restrict__ e, int64_t Nc, int64_t i, int nsplit) {
-  // every partial's load issued before the first merge (a load per dependent merge step cost 14 us for 16
-  // splits of 64 candidates); fixed-size and fully unrolled, so the partials stay in registers
-  KdeEst p[OBS_SPLIT_MAX];
-#pragma unroll
-  for (int r = 0; r < OBS_SPLIT_MAX; ++r) p[r] = r < nsplit ? e[(int64_t)r * Nc + i] : kde_est_neutral();
-  auto lae = [](float x, float y) {
-    const float m = fmaxf(x, y);
-    return m == -INFINITY ? m : m + __logf(__expf(x - m) + __expf(y - m));
-  };
-  KdeEst a = p[0];
-#pragma unroll
-  for (int r = 1; r < OBS_SPLIT_MAX; ++r) {
-    if (r < nsplit) {
-      const KdeEst b = p[r];
-      if (a.lpos != a.lpos || b.lpos != b.lpos) {  // structural NaN (every split carries it)
-        a.lpos = NAN;
-      } else {
-        a.lpos = lae(a.lpos, b.lpos);
-        a.lneg = lae(a.lneg, b.lneg);
-        const float ml = fmaxf(a.lpos > -INFINITY ? fabsf(a.lpos) : 0.f, a.lneg > -INFINITY ? fabsf(a.lneg) : 0.f);
-        a.err = fmaxf(a.err, b.err) + 0x1p-18f + ml * 0x1p-22f;
-      }
-    }
-  }
-  return a;
-}
+// (merge_splits, a candidate's estimate merged over its observation-split partials: hbx_acq_impl.h, shared with
+// the staged acquisition's kernels)
 
 // observation splits: each candidate's partial estimates merged into its first slot, for the combine and
 // every later step (one thread per candidate and KDE; launched only when the scoring launch split)
@@ -170,7 +144,8 @@ __global__ __launch_bounds__(256) void kde_combine_kernel(KdeEst* __restrict__ e
     const uint32_t sg = (uint32_t)(i < Nc ? i : Nc - 1) / seg;
     if (i < Nc) {
       // (score_interval: hbx_acq_impl.h, shared with the top-k bounds pass)
-      const ScoreIv v = score_interval(ea[r], eb[r]);
+      // (a staged acquisition's candidates without g: the interval l alone gives)
+      const ScoreIv v = eb[r].err == HBX_EST_NOT_EVAL ? score_interval_l_only(ea[r]) : score_interval(ea[r], eb[r]);
       const float lpt = v.lpt, gpt = v.gpt;
       const bool of = v.of;
       // an exact tie at 1 is excluded from the shortlist unless it is the segment's first (first1)
@@ -581,6 +556,15 @@ WsLayout ws_layout(int64_t Nc, int64_t nmax, int64_t B) {
   w.exact_l = take(8 * Nc);
   w.exact_g = take(8 * Nc);
   w.part = take(8 * (size_t)2 * EXACT_SPLIT_CAP * PW_SPLIT_UNITS * ((nmax + PW_BUF - 1) / PW_BUF));
+  // the staged acquisition (hbx_staged.hip): lists of whole 512-candidate tiles, 4 bytes per candidate for the
+  // survivor list, and the list launches' split partials
+  static_assert(sizeof(AcqResult) + 4 * HBX_ST_WORDS <= 256, "the state words fit the result slot's padding");
+  w.stage = w.res + sizeof(AcqResult);
+  const int64_t tiles = (Nc + 511) / 512;
+  w.list_cap = (int32_t)(512 * (tiles < 1 ? 1 : tiles > STAGED_LIST_CAP / 512 ? STAGED_LIST_CAP / 512 : tiles));
+  w.seeds = take(4 * (size_t)w.list_cap);
+  w.surv = take(4 * Nc);
+  w.lpart = take(sizeof(KdeEst) * (size_t)OBS_SPLIT_MAX * w.list_cap);
   w.total = o;
   return w;
 }
@@ -664,10 +648,22 @@ static int acquire_impl(const char* who, const KdePairRef& p, const double* cand
   const uint32_t sg = (uint32_t)(batch_res ? seg : (Nc > 0 ? Nc : 1));
   if (B == 0) return HBX_OK;  // batched call without candidates: no records
   bool rescue_inline = false;  // the rescue pass left to the combine kernel
-  rc = acq_score(plan, p, cand, Nc, a, batch_res ? B : 0,
-                 (hipEvent_t*)events,  // optional: [before l, between, after g] for timing
-                 fast ? p.nmax : 0,    // splits for the pick only: reported ln-pdfs stay unsplit
-                 batch_res ? nullptr : &rescue_inline, s);
+  // Staged scoring (hbx_staged.hip): a single acquisition without ln-pdf outputs, both KDEs on the coarse 32x32
+  // instance, and enough pairs that the bad KDE's walk outweighs the stages' eight extra launches (nmax stands
+  // for the bad KDE's observation count, which the host does not hold).  HBX_STAGED_MIN_PAIRS: measured,
+  // profiles/staged/README.md.
+  const int stg = (!batch_res && fast && Nc > 0) ? acq_staged_mode() : 0;
+  const bool staged = stg && acq_staged_supported(plan) &&
+                      (stg == 2 || (double)Nc * (double)p.nmax >= HBX_STAGED_MIN_PAIRS);
+  if (staged) {
+    rc = acq_score_staged(plan, p, cand, Nc, a, (hipEvent_t*)events, s);
+    rescue_inline = true;  // marked g estimates of the list launches: the combine kernel re-scores them
+  } else {
+    rc = acq_score(plan, p, cand, Nc, a, batch_res ? B : 0,
+                   (hipEvent_t*)events,  // optional: [before l, between, after g] for timing
+                   fast ? p.nmax : 0,    // splits for the pick only: reported ln-pdfs stay unsplit
+                   batch_res ? nullptr : &rescue_inline, s);
+  }
   if (rc) return rc;
   const dim3 grid((unsigned)((Nc + 255) / 256));
   bool fuse_combine = false;

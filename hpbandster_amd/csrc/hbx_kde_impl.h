@@ -283,9 +283,39 @@ struct KdePairArgs {
 };
 typedef void (*logpdf_pair_fn)(const double*, int64_t, int32_t, KdePairArgs);
 
-// a single acquisition's state before its combine / shortlist / exact / final steps
+// kernel arguments of a list launch (hbx_score_h32.hip kde_logpdf_h32_list_kernel; the staged acquisition,
+// hbx_staged.hip): the candidates idx[0 .. min(*count, maxcount)) against one KDE.  At most cap listed: tiles_cap
+// tiles x nsplit observation ranges, range r's partial estimate of list entry k at part[r cap + k] (merged and
+// scattered by staged_merge_kernel); more: one unsplit block per tile, entry k's estimate straight to out[idx[k]].
+// The grid is sized on the host for the list's capacity; blocks past the count exit after one load.
+struct KdeListArgs {
+  const KdeParams* P;
+  const float* table;
+  KdeEst* out;
+  KdeEst* part;
+  const int32_t* idx;
+  const int32_t* count;
+  int32_t* rescue;  // marker count (KdePairArgs::rescue)
+  int32_t cap, maxcount, nsplit;
+  unsigned tiles_cap;
+};
+typedef void (*logpdf_list_fn)(const double*, int32_t, KdeListArgs);
+
+// the staged acquisition's state words (hbx_staged.hip), in the result slot's padding right behind the record
+// (WsLayout::stage): whether the call staged, Lmax and U_seed as order-preserving uints, the seed and survivor
+// counts.  They stay in the workspace after the call (hbx_kde_acquire_stats).
+enum { HBX_ST_FLAG = 0, HBX_ST_LMAX, HBX_ST_USEED, HBX_ST_NSEED, HBX_ST_NSURV, HBX_ST_WORDS };
+
+// a single acquisition's state before its combine / shortlist / exact / final steps; res is the workspace's
+// result slot (256 bytes: the state words of a staged call follow the record)
 __device__ __forceinline__ void acq_init_state(uint32_t* U, int32_t* count, int32_t* flags, int32_t* first1,
                                                AcqResult* res) {
+  uint32_t* st = (uint32_t*)(res + 1);
+  st[HBX_ST_FLAG] = 0;
+  st[HBX_ST_LMAX] = hbx_f2ord(-INFINITY);
+  st[HBX_ST_USEED] = hbx_f2ord(INFINITY);
+  st[HBX_ST_NSEED] = 0;
+  st[HBX_ST_NSURV] = 0;
   *U = hbx_f2ord(INFINITY);
   *first1 = INT32_MAX;
   *count = 0;
@@ -354,6 +384,7 @@ logpdf_pair_fn hbx_pick_h_pair(int nsc, int kc, bool sg);  // hbx_score_h.hip (l
 logpdf_fn hbx_pick_h32(int nsc, int kp, bool sg, bool fast, bool coarse = false);  // hbx_score_h32.hip
 logpdf_pair_fn hbx_pick_h32_pair(int nsc, int kp, bool sg, bool fast, bool coarse = false);
 logpdf_pair_fn hbx_pick_h32_pair1(int nsc, int kp);  // the coarse pair kernel, one column tile per wave
+logpdf_list_fn hbx_pick_h32_list(int nsc, int kp);   // the coarse instance over an index list (staged acquisition)
 
 // what the ln-pdf contract (hbx_logpdf.hip, hbx_kde_logpdf_rtol) launches from other units: hbx_score.hip's
 // precise estimate instance of a bucket (main + rescue into est; HBX_ERR_UNSUPPORTED when it has none) ...

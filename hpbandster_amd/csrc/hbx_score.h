@@ -15,6 +15,7 @@ struct ScoreFns {
   bool split_ok = false;  // the pair kernel takes observation splits and initialises a single acquisition's
                           // state (the 32x32-tile instances); a combine kernel may then do the rescue pass
   logpdf_pair_fn pair1 = nullptr;  // the coarse pair kernel with one column tile per wave (launch_score2)
+  logpdf_list_fn list = nullptr;   // the coarse instance over an index list (the staged acquisition)
 };
 
 // variant code of a prepared KDE (hbx_kde_prepare info[0]): bit 0 = signed sums, bits 1-3 = kc,

@@ -118,6 +118,7 @@ ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast) {
                hbx_pick_h32_pair(nsc_of(dc_pad), kp, sg, fa, co),
                sg ? pick_rescue_pair<true>(dc_pad) : pick_rescue_pair<false>(dc_pad), true};
     if (co && H32C_CT > 1) f.pair1 = hbx_pick_h32_pair1(nsc_of(dc_pad), kp);
+    if (co) f.list = hbx_pick_h32_list(nsc_of(dc_pad), kp);
     return f;
   }
   if (hm) {

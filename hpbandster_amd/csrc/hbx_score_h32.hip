@@ -67,12 +67,38 @@ struct SgbH32<NM, NM, NV, NRL, RD> {
   static __device__ __forceinline__ void run() {}
 };
 
-template <int NSC, int KP, bool SG, bool FAST, bool CO = false, int CT = 1>
+// A wave gathers its nv listed candidate rows (row r = candidate idx[r]) into LDS rows of stride DS: stage_rows'
+// generic path with one index load per element (lists are short; the loads of a pass stay in flight together)
+__device__ __forceinline__ void stage_rows_list(const double* __restrict__ cand, const int32_t* __restrict__ idx,
+                                                int64_t nv, int D, int DS, double* xs, int lane) {
+  const int tot = (int)nv * D;
+  for (int e0 = 0; e0 < tot; e0 += 8 * 64) {
+    double t[8];
+    int at[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int e = min(e0 + 64 * q + lane, tot - 1);  // past the end: the last element again
+      const int row = e / D, col = e - row * D;
+      at[q] = row * DS + col;
+      t[q] = cand[(int64_t)idx[row] * D + col];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) xs[at[q]] = t[q];
+  }
+}
+
+// LIST (the staged acquisition's list launches): the block's candidates are list entries -- Nc is the list's
+// count, column k reads candidate row idx[k] and writes out[idx[k]] (scatter) or out[k] (compact: a split
+// launch's partials, the caller's out already at the range's [split] slice).  Only the prologue's row addresses
+// and the epilogue differ; the main loop is the same code.
+template <int NSC, int KP, bool SG, bool FAST, bool CO = false, int CT = 1, bool LIST = false>
 __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ cand, int64_t Nc, int32_t D,
                                                     const KdeParams* __restrict__ P,
                                                     const float* __restrict__ table, KdeEst* __restrict__ out,
                                                     const unsigned blk, int32_t* __restrict__ rescue_cnt = nullptr,
-                                                    const int split = 0, const int nsplit = 1) {
+                                                    const int split = 0, const int nsplit = 1,
+                                                    const int32_t* __restrict__ idx = nullptr,
+                                                    const bool scatter = false) {
   // CO: the coarse pre-screen (hbx_kde_impl.h coarse layout): one product per continuous dim, no lo parts
   constexpr int ND = CO ? h32c_nd(NSC) : h32_nd(NSC);  // dense 16-wide K-steps (C_j / c_i pieces + per dim)
   constexpr int KS = KP;                     // sparse 32-wide K-steps (one-hot positions), hi parts
@@ -100,7 +126,7 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
   int c0 = 0, nchunks = (P->n + OBS_CHUNK - 1) / OBS_CHUNK;
   if (nsplit > 1) {
     obs_split_range(nchunks, split, nsplit, &c0, &nchunks);
-    out += (int64_t)split * Nc;
+    if constexpr (!LIST) out += (int64_t)split * Nc;
     if (nchunks <= 0) {  // more splits than chunks: this range is empty
       const int64_t cb = (int64_t)blk * HW * 32 * CT;
       for (int k = threadIdx.x; k < HW * 32 * CT; k += blockDim.x)
@@ -136,7 +162,11 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
   const bool staged = rows_fit && cbase < Nc;
   const int64_t nv = (Nc - cbase) < 32 * CT ? (Nc - cbase) : 32 * CT;  // valid rows of this wave
   double* xs = (double*)lds + (int64_t)wave * 32 * CT * DS;
-  if (staged) stage_rows(cand + cbase * (int64_t)D, nv, D, DS, xs, lane);
+  if constexpr (LIST) {
+    if (staged) stage_rows_list(cand, idx + cbase, nv, D, DS, xs, lane);
+  } else {
+    if (staged) stage_rows(cand + cbase * (int64_t)D, nv, D, DS, xs, lane);
+  }
   __syncthreads();
 
   // B operands of candidate column c.  Dense step s, half j of the lane: slot k = 16s + 8h + j -- slots
@@ -215,6 +245,7 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
     } else {
       int64_t ii = cbase + 32 * t + c;
       if (ii >= Nc) ii = Nc - 1;
+      if constexpr (LIST) ii = idx[ii];
       build(cand + ii * (int64_t)D, t);
     }
     // the next tile's build re-reads the parameters (no values kept live across the builds: no spills)
@@ -479,7 +510,10 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
       const float ci_q = ax[0], bnd_q = ax[1], dq = ax[2];
       const bool big = ax[3] < 0.f;
       const float cer_q = big ? 0.f : ax[3];
-      const double* x = cand + ii * (int64_t)D;
+      int64_t irow = ii;  // the candidate's row, and where its estimate goes
+      if constexpr (LIST) irow = idx[ii];
+      const int64_t iout = LIST && !scatter ? ii : irow;
+      const double* x = cand + irow * (int64_t)D;
       bool nq = P->nan_all != 0;
       for (int k = 0; k < P->nconst; ++k)
         if (x[P->const_dim[k]] != P->const_level[k]) nq = true;
@@ -504,7 +538,7 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
         o.err = -1.f;
         if (rescue_cnt) atomicAdd(rescue_cnt, 1);
       }
-      out[ii] = o;
+      out[iout] = o;
     }
   }
   }
@@ -553,6 +587,25 @@ __global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu
   const int split = ns > 1 ? (int)(loc / a.tiles) : 0;
   kde_logpdf_h32_body<NSC, KP, false, false, true, 1>(cand, Nc, D, second ? a.P1 : a.P0, second ? a.table1 : a.table0,
                                                        second ? a.out1 : a.out0, tile, a.rescue, split, ns);
+}
+
+// the coarse instance over an index list with a device-side count (KdeListArgs, hbx_kde_impl.h): the staged
+// acquisition's bad-KDE launches.  Same block shape and scoring body as the pair kernel's, so a candidate's sums
+// are the ones it would get there.
+template <int NSC, int KP>
+__global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu(H32C_EU))) void kde_logpdf_h32_list_kernel(
+    const double* __restrict__ cand, int32_t D, KdeListArgs a) {
+  int32_t cnt = *a.count;  // uniform
+  if (cnt > a.maxcount) cnt = a.maxcount;
+  constexpr int CPB = 32 * H32C_CT * H32C_WAVES;
+  const bool splits = cnt <= a.cap;  // else: unsplit, one block per tile of the whole list, scattering itself
+  if (splits && blockIdx.x >= a.tiles_cap * (unsigned)a.nsplit) return;
+  const unsigned tile = splits ? blockIdx.x % a.tiles_cap : blockIdx.x;
+  const int split = splits ? (int)(blockIdx.x / a.tiles_cap) : 0;
+  if ((int64_t)tile * CPB >= cnt) return;
+  kde_logpdf_h32_body<NSC, KP, false, false, true, H32C_CT, true>(
+      cand, cnt, D, a.P, a.table, splits ? a.part + (int64_t)split * a.cap : a.out, tile, a.rescue, split,
+      splits ? a.nsplit : 1, a.idx, !splits);
 }
 
 // signed sums (the parity product and its accumulators): one 8-wave block per CU, so 2 waves per SIMD
@@ -636,6 +689,26 @@ static logpdf_pair_fn pick32_pair1_kp(int kp) {
     case 0: if constexpr (h32_ok(NSC, 0, false)) return kde_logpdf_h32_pair1_kernel<NSC, 0>; break;
     case 1: if constexpr (h32_ok(NSC, 1, false)) return kde_logpdf_h32_pair1_kernel<NSC, 1>; break;
     case 2: if constexpr (h32_ok(NSC, 2, false)) return kde_logpdf_h32_pair1_kernel<NSC, 2>; break;
+  }
+  return nullptr;
+}
+
+template <int NSC>
+static logpdf_list_fn pick32_list_kp(int kp) {
+  switch (kp) {
+    case 0: if constexpr (h32_ok(NSC, 0, false)) return kde_logpdf_h32_list_kernel<NSC, 0>; break;
+    case 1: if constexpr (h32_ok(NSC, 1, false)) return kde_logpdf_h32_list_kernel<NSC, 1>; break;
+    case 2: if constexpr (h32_ok(NSC, 2, false)) return kde_logpdf_h32_list_kernel<NSC, 2>; break;
+  }
+  return nullptr;
+}
+
+logpdf_list_fn hbx_pick_h32_list(int nsc, int kp) {
+  switch (nsc) {
+    case 1: return pick32_list_kp<1>(kp);
+    case 2: return pick32_list_kp<2>(kp);
+    case 3: return pick32_list_kp<3>(kp);
+    case 4: return pick32_list_kp<4>(kp);
   }
   return nullptr;
 }

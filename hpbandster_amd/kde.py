@@ -13,6 +13,7 @@ side does O(D) bookkeeping only: the BOHB size rule, the pow() factor of the ban
 rounds exactly like the reference's Python pow), and the small parameter block upload.
 """
 
+import ctypes
 import math
 import struct
 import threading
@@ -476,6 +477,14 @@ class KDEPair(object):
             wsb = self._wsb[Nc] = int(N.lib().hbx_kde_workspace_bytes(int(Nc), self.nmax))
         return wsb
 
+    def acquire_stats(self, workspace, Nc):
+        """What the last single acquisition over ``Nc`` candidates on ``workspace`` did (synchronises):
+        dict(staged, seeds, survivors, evaluated) -- ``evaluated`` = candidates whose bad-KDE sum was
+        computed, ``Nc`` when the call did not stage (see ``acquire``)."""
+        out = (ctypes.c_int64 * 4)()
+        N.check(N.lib().hbx_kde_acquire_stats(workspace.data_ptr(), int(Nc), self.nmax, ctypes.addressof(out)))
+        return {"staged": bool(out[0]), "seeds": int(out[1]), "survivors": int(out[2]), "evaluated": int(out[3])}
+
     def acquire(self, cands, index_base=0, logs=False, stream=None, workspace=None, sync=True, events=None,
                 ties="pinned"):
         """Select the first index minimising max(1e-8, g)/max(l, 1e-8) over the candidates.
@@ -489,6 +498,19 @@ class KDEPair(object):
         the pinned numpy 1.26.4 bit for bit, so its pick is final; 'process' -- candidates flagged
         ACQ_NEAR_TIE (within the spread another numpy build's exp could cause) are re-scored with this
         process's numpy (exact_host), reproducing what the reference would pick in this environment.
+
+        Without ``logs``, large calls whose KDEs both run the coarse 32x32 kernel are scored in stages: the
+        good KDE for every candidate, the bad KDE only where l alone does not rule the candidate out
+        (score >= 1e-8 / max(l, 1e-8) whatever g is).  The pick -- ``index``, ``score``, ``pdf_l``, ``pdf_g``,
+        and with them ``near`` and ``rel`` -- is the unstaged call's, exactly.  ``shortlist`` and
+        ``ACQ_OVERFLOW`` describe the screen, which differs: ``shortlist`` is normally equal or lower by one
+        (the first certain 1e-8/1e-8 tie, when it was pruned and cannot win); the evaluated candidates' fp32
+        estimates come from launches with their own observation splits, valid bounds but not the fused
+        launch's bits, so a candidate at the very edge of the shortlist can fall on either side; a pruned
+        candidate whose coarse g bound alone would have passed the overflow limit sets ``ACQ_OVERFLOW`` (and
+        the whole-set re-score) in the unstaged call only; and when l itself sets ``ACQ_OVERFLOW`` the staged
+        shortlist also holds the pruned certain ties, so it can be longer.  ``HBX_STAGED=0`` switches staging off, ``HBX_STAGED=2`` forces it wherever supported (read per
+        call); ``acquire_stats`` reports what a call did.
         """
         if ties not in ("pinned", "process"):
             raise ValueError("ties must be 'pinned' or 'process'")

@@ -311,6 +311,20 @@ void* hbx_kde_result_ptr(void* workspace);
  * hbx_kde_acquire).  hbx_kde_acquire's near list holds the near set's candidate indices (record.near of
  * them); hbx_kde_acquire_batch's holds a 0/1 flag per shortlist entry. */
 int hbx_kde_ws_offsets(int64_t Nc, int64_t seg, int64_t nmax, int64_t* out);
+/* Staged scoring of hbx_kde_acquire / hbx_kde_acquire_bound without ln-pdf outputs (both KDEs on the coarse
+ * 32x32 instance, Nc * nmax large enough; environment HBX_STAGED=0: never, 2: wherever supported): l is scored for
+ * every candidate, g only for the candidates l alone does not rule out (score >= 1e-8 / max(l, 1e-8) whatever g
+ * is).  The pick (index, score, pdf_l, pdf_g, and with them near and rel) is the unstaged call's, exactly.  The
+ * screen's own figures can differ: `shortlist` is normally equal or lower by one (the first certain 1e-8/1e-8 tie,
+ * when it was pruned and cannot win); the evaluated candidates' fp32 estimates come from launches with their own
+ * observation splits -- valid bounds, not the fused launch's bits -- so a candidate at the very edge of the
+ * shortlist can fall on either side; a pruned candidate whose coarse g bound alone would pass the overflow limit
+ * sets HBX_ACQ_OVERFLOW (and the whole-set re-score) in the unstaged call only; and when l itself sets
+ * HBX_ACQ_OVERFLOW the staged shortlist also holds the pruned certain ties, so it can be longer.
+ * hbx_kde_acquire_stats: what the last single acquisition on `workspace` (sized for Nc, nmax) did -- a device
+ * read, synchronising: out[0] = 1 when it staged, [1] seeds, [2] survivors, [3] candidates whose g was evaluated
+ * (Nc when it did not stage). */
+int hbx_kde_acquire_stats(const void* workspace, int64_t Nc, int64_t nmax, int64_t* out);
 
 int64_t hbx_kde_pdf_scratch_bytes(int64_t nmax);
 
