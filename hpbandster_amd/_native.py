@@ -44,25 +44,16 @@ SIGNATURES = {
     "hbx_stream_order": (c_i32, [c_vp, c_vp]),
     "hbx_kde_logpdf": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "hbx_kde_workspace_bytes": (c_i64, [c_i64, c_i64]),
-    "hbx_kde_acquire": (c_i32, [c_vp, c_i64, c_i32, c_i64,
-                                c_vp, c_vp, c_vp, c_vp, c_i32,
-                                c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
-                                c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "hbx_kde_acquire": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "hbx_kde_pair_bind": (c_vp, [c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                  c_i64]),
     "hbx_kde_acquire_bound": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "hbx_kde_pair_free": (None, [c_vp]),
     "hbx_kde_batch_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
-    "hbx_kde_acquire_batch": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_i64,
-                                      c_vp, c_vp, c_vp, c_vp, c_i32,
-                                      c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
-                                      c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_kde_acquire_batch": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "hbx_kde_topk_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64]),
     "hbx_kde_topk_result_bytes": (c_i64, [c_i32]),
-    "hbx_kde_acquire_topk": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i64,
-                                     c_vp, c_vp, c_vp, c_vp, c_i32,
-                                     c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
-                                     c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_kde_acquire_topk": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "hbx_kde_groups_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
     "hbx_kde_acquire_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),

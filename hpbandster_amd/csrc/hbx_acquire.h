@@ -1,10 +1,11 @@
 // hbx_acquire.h -- what the acquisitions of one KDE pair share on the launch side.  Users: hbx_kde.hip
-// (defines it; the argmin: single, bound, batched), hbx_topk.hip (the top-k of one pool, which runs the same
-// scoring and exact re-score around its own selection steps) and hbx_exact.hip (acq_exact, beside its kernels).
+// (defines it; the argmin: single, bound, batched), hbx_staged.hip (acq_score_staged), hbx_topk.hip (the top-k of
+// one pool, which runs the same scoring and exact re-score around its own selection steps) and hbx_exact.hip
+// (acq_exact, beside its kernels).
 #pragma once
 #include "hbx_score.h"
 
-// A prepared (good, bad) KDE pair as every acquisition entry point receives it (hbx_kde_pair_bind keeps one)
+// A prepared (good, bad) KDE pair: what hbx_kde_pair_bind returns and every acquisition entry point takes
 struct KdePairRef {
   int32_t D;
   const void* params_good;
@@ -78,6 +79,8 @@ struct AcqWs {
     lpart = (KdeEst*)(ws + w.lpart);
     list_cap = w.list_cap;
   }
+  // a single acquisition's state, for the launch that initialises it
+  KdePairArgs::AcqInitPtrs init() const { return {U, count, flags, first1, res}; }
 };
 
 // The steps every acquisition runs, in this order around its own selection steps.
@@ -86,24 +89,24 @@ struct AcqPlan {
   ScoreFns fg, fb;
   bool exact_only;  // a KDE outside every fp32 scoring bucket: no scoring launch, every candidate re-scored
 };
+const KdePairRef* acq_pair(const char* who, const void* pair);  // an entry point's handle; NULL: HBX_ERR_ARG is set
 int acq_check(const char* who, const KdePairRef& p, const double* cand, int64_t Nc, const void* workspace);
 int acq_plan(const KdePairRef& p, bool fast, AcqPlan* plan);
 // (2) the scoring launch (first: it touches none of the per-acquisition state, so the GPU starts on it while
-// the host enqueues the rest), the state's initialisation where the launch did not do it (batch_B > 0: the
-// B segments' state instead), the launch's observation splits merged.  split_nmax: the observation count the
-// splits are sized for (0: no splits); rescue_inline (nullable: the rescue pass always a launch of its own):
-// set when the pass is left to the combine kernel
-int acq_score(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
-              int64_t batch_B, hipEvent_t* ev, int64_t split_nmax, bool* rescue_inline, hipStream_t s);
+// the host enqueues the rest; launch_score2, hbx_score.h, which also documents rq and out), then the state's
+// initialisation where the launch did not do it (batch_B > 0: the B segments' state instead, rq.init empty), then
+// the launch's observation splits merged.  The estimates land in a.el / a.eg.
+int acq_score(const AcqPlan& plan, const KdePairRef& p, const AcqWs& a, const ScoreRequest& rq, int64_t batch_B,
+              ScoreResult* out);
 // (2') instead of (2) for a single acquisition without ln-pdf outputs whose KDEs both run the coarse 32x32
 // instance: the staged scoring (hbx_staged.hip) -- l for every candidate, g only where l alone does not rule the
 // candidate out; the others' a.eg holds the marker HBX_EST_NOT_EVAL, which the combine kernel reads as an
 // l-only interval.  It leaves the rescue of marked g estimates to the combine kernel (its <_, true> instance).
 // events: [0] at the first scoring launch's start, [1] and [2] after the last one.
+// Whether a call stages: HBX_STAGED (hbx_staged_mode, hbx_common.h) and, by size, HBX_STAGED_MIN_PAIRS.
 #ifndef HBX_STAGED_MIN_PAIRS
 #define HBX_STAGED_MIN_PAIRS 1e9  // candidates x observations from which an acquisition stages when HBX_STAGED is unset
 #endif
-int acq_staged_mode();  // HBX_STAGED (read per call): 0 never, 2 wherever supported, else by size
 bool acq_staged_supported(const AcqPlan& plan);
 int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
                      hipEvent_t* ev, hipStream_t s);

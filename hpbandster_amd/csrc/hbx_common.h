@@ -38,6 +38,14 @@ static inline bool hbx_switch_on(const char* name) {
   const char* e = getenv(name);
   return !(e && atoi(e) == 0);
 }
+// HBX_STAGED, the one switch with three values: 0 = never stage, 2 = wherever supported (tests), unset or
+// anything else = 1, by size.  Read on every call like the others.
+static inline int hbx_staged_mode() {
+  const char* e = getenv("HBX_STAGED");
+  if (!e) return 1;
+  const int v = atoi(e);
+  return v == 0 ? 0 : v == 2 ? 2 : 1;
+}
 
 // ------------------------------------------------------------------------------------------
 // KDE model parameters, one block per KDE (good or bad).  Written on the device by

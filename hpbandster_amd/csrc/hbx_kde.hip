@@ -577,8 +577,13 @@ int acq_check(const char* who, const KdePairRef& p, const double* cand, int64_t 
   return HBX_OK;
 }
 
+const KdePairRef* acq_pair(const char* who, const void* pair) {
+  if (!pair) hbx_fail(HBX_ERR_ARG, "%s: null pair", who);
+  return (const KdePairRef*)pair;
+}
+
 int acq_plan(const KdePairRef& p, bool fast, AcqPlan* plan) {
-  plan->exact_only = ((p.variant_good | p.variant_bad) >> 5) & 1;
+  plan->exact_only = KdeVariant::decode(p.variant_good).exact_only || KdeVariant::decode(p.variant_bad).exact_only;
   plan->fg = pick_logpdf(p.dc_pad, p.du_pad, p.variant_good, fast);
   plan->fb = pick_logpdf(p.dc_pad, p.du_pad, p.variant_bad, fast);
   if (!plan->exact_only && (!plan->fg.main || !plan->fb.main))
@@ -586,30 +591,27 @@ int acq_plan(const KdePairRef& p, bool fast, AcqPlan* plan) {
   return HBX_OK;
 }
 
-int acq_score(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
-              int64_t batch_B, hipEvent_t* ev, int64_t split_nmax, bool* rescue_inline, hipStream_t s) {
-  bool inited = false;  // a single acquisition's pair launch: it or its rescue pass initialises the state
-  int32_t nsplit[2] = {1, 1};  // the scoring launch's observation splits, good / bad
-  if (rescue_inline) *rescue_inline = false;
-  const bool scored = Nc > 0 && !plan.exact_only;
+int acq_score(const AcqPlan& plan, const KdePairRef& p, const AcqWs& a, const ScoreRequest& rq, int64_t batch_B,
+              ScoreResult* out) {
+  *out = ScoreResult{};
+  const hipStream_t s = rq.s;
+  const bool scored = rq.Nc > 0 && !plan.exact_only;
   if (scored) {
-    KdePairArgs::AcqInitPtrs ip{};
-    if (!batch_B) ip = KdePairArgs::AcqInitPtrs{a.U, a.count, a.flags, a.first1, a.res};
-    const int rc = launch_score2(plan.fg, p.params_good, p.table_good, a.el, plan.fb, p.params_bad, p.table_bad, a.eg,
-                                 cand, Nc, p.D, ev, a.rescue, s, ip, &inited, split_nmax, nsplit, rescue_inline);
+    const int rc = launch_score2({plan.fg, p.params_good, p.table_good, a.el},
+                                 {plan.fb, p.params_bad, p.table_bad, a.eg}, rq, out);
     if (rc) return rc;
   }
   if (batch_B) {
     hipLaunchKernelGGL(acq_init_batch_kernel, dim3((unsigned)((batch_B + 255) / 256)), dim3(256), 0, s, batch_B, a.U,
                        a.flags, a.segcnt, a.best, a.key, a.first1, a.count, a.segnear);
     HBX_LAUNCH_CHECK();
-  } else if (!inited) {
+  } else if (!out->inited) {  // (a single acquisition's pair launch or its rescue pass initialises the state)
     hipLaunchKernelGGL(acq_init_kernel, dim3(1), dim3(64), 0, s, a.U, a.count, a.flags, a.first1, a.res);
     HBX_LAUNCH_CHECK();
   }
-  if (scored && (nsplit[0] > 1 || nsplit[1] > 1)) {  // merged before the combine / bounds pass
-    hipLaunchKernelGGL(kde_merge_splits_kernel, dim3((unsigned)((2 * Nc + 255) / 256)), dim3(256), 0, s, a.el, a.eg,
-                       Nc, nsplit[0], nsplit[1]);
+  if (scored && (out->nsplit[0] > 1 || out->nsplit[1] > 1)) {  // merged before the combine / bounds pass
+    hipLaunchKernelGGL(kde_merge_splits_kernel, dim3((unsigned)((2 * rq.Nc + 255) / 256)), dim3(256), 0, s, a.el,
+                       a.eg, rq.Nc, out->nsplit[0], out->nsplit[1]);
     HBX_LAUNCH_CHECK();
   }
   return HBX_OK;
@@ -622,20 +624,41 @@ int acq_exact_only_init(int64_t Nc, uint32_t seg, const AcqWs& a, hipStream_t s)
   return HBX_OK;
 }
 
+// One call of acquire_impl, as its entry point fills it
+struct AcqCall {
+  const char* who;
+  const double* cand;
+  int64_t Nc, seg, index_base;
+  float *logl_out, *logg_out;  // nullable: the ln-pdf estimates
+  AcqResult* batch_res;        // nullable: one acquisition, the record stays in the workspace
+  void* workspace;
+  int64_t ws_bytes;
+  void *events, *stream;
+  // the bound call's publish target in mapped host memory: the record alone (host_res) or a pick (pick.out),
+  // tagged with the call's sequence number; neither: nothing published
+  AcqResult* host_res;
+  int32_t seq;
+  PickOut pick;
+};
+
 // Shared body of hbx_kde_acquire (batch_res == nullptr: one acquisition over all Nc candidates, the
 // record stays in the workspace) and hbx_kde_acquire_batch (B = ceil(Nc/seg) acquisitions over
 // consecutive segments of seg candidates, one record each into batch_res).
-static int acquire_impl(const char* who, const KdePairRef& p, const double* cand, int64_t Nc, int64_t seg,
-                        int64_t index_base, float* logl_out, float* logg_out, AcqResult* batch_res, void* workspace,
-                        int64_t ws_bytes, void* events, void* stream, AcqResult* host_res = nullptr, int32_t seq = 0,
-                        PickOut pick = PickOut{}) {
-  int rc = acq_check(who, p, cand, Nc, workspace);
+static int acquire_impl(const void* pair, const AcqCall& c) {
+  const KdePairRef* pp = acq_pair(c.who, pair);
+  if (!pp) return HBX_ERR_ARG;
+  const KdePairRef& p = *pp;
+  const double* cand = c.cand;
+  const int64_t Nc = c.Nc, seg = c.seg;
+  float *logl_out = c.logl_out, *logg_out = c.logg_out;
+  AcqResult* batch_res = c.batch_res;
+  int rc = acq_check(c.who, p, cand, Nc, c.workspace);
   if (rc) return rc;
-  if (seg < 1) return hbx_fail(HBX_ERR_ARG, "%s: segment length %lld", who, (long long)seg);
+  if (seg < 1) return hbx_fail(HBX_ERR_ARG, "%s: segment length %lld", c.who, (long long)seg);
   const int64_t B = batch_res ? (Nc + seg - 1) / seg : 1;
   const WsLayout w = ws_layout(Nc, p.nmax, B);
-  if ((size_t)ws_bytes < w.total)
-    return hbx_fail(HBX_ERR_ARG, "workspace too small: %lld < %lld bytes", (long long)ws_bytes,
+  if ((size_t)c.ws_bytes < w.total)
+    return hbx_fail(HBX_ERR_ARG, "workspace too small: %lld < %lld bytes", (long long)c.ws_bytes,
                     (long long)w.total);
   // no ln-pdf estimates returned: the fast scoring instances (their looser bounds only widen the shortlist
   // the exact re-score resolves)
@@ -643,8 +666,9 @@ static int acquire_impl(const char* who, const KdePairRef& p, const double* cand
   AcqPlan plan;
   rc = acq_plan(p, fast, &plan);
   if (rc) return rc;
-  const AcqWs a(workspace, w);
-  hipStream_t s = (hipStream_t)stream;
+  const AcqWs a(c.workspace, w);
+  hipStream_t s = (hipStream_t)c.stream;
+  hipEvent_t* ev = (hipEvent_t*)c.events;  // optional: [before l, between, after g] for timing
   const uint32_t sg = (uint32_t)(batch_res ? seg : (Nc > 0 ? Nc : 1));
   if (B == 0) return HBX_OK;  // batched call without candidates: no records
   bool rescue_inline = false;  // the rescue pass left to the combine kernel
@@ -652,17 +676,19 @@ static int acquire_impl(const char* who, const KdePairRef& p, const double* cand
   // instance, and enough pairs that the bad KDE's walk outweighs the stages' eight extra launches (nmax stands
   // for the bad KDE's observation count, which the host does not hold).  HBX_STAGED_MIN_PAIRS: measured,
   // profiles/staged/README.md.
-  const int stg = (!batch_res && fast && Nc > 0) ? acq_staged_mode() : 0;
+  const int stg = (!batch_res && fast && Nc > 0) ? hbx_staged_mode() : 0;
   const bool staged = stg && acq_staged_supported(plan) &&
                       (stg == 2 || (double)Nc * (double)p.nmax >= HBX_STAGED_MIN_PAIRS);
   if (staged) {
-    rc = acq_score_staged(plan, p, cand, Nc, a, (hipEvent_t*)events, s);
+    rc = acq_score_staged(plan, p, cand, Nc, a, ev, s);
     rescue_inline = true;  // marked g estimates of the list launches: the combine kernel re-scores them
   } else {
-    rc = acq_score(plan, p, cand, Nc, a, batch_res ? B : 0,
-                   (hipEvent_t*)events,  // optional: [before l, between, after g] for timing
-                   fast ? p.nmax : 0,    // splits for the pick only: reported ln-pdfs stay unsplit
-                   batch_res ? nullptr : &rescue_inline, s);
+    // splits for the pick only (reported ln-pdfs stay unsplit); a batched call's rescue pass is always a launch
+    const ScoreRequest rq{cand, Nc, p.D, ev, a.rescue, batch_res ? KdePairArgs::AcqInitPtrs{} : a.init(),
+                          fast ? p.nmax : 0, !batch_res, s};
+    ScoreResult sr;
+    rc = acq_score(plan, p, a, rq, batch_res ? B : 0, &sr);
+    rescue_inline = sr.rescue_inline;
   }
   if (rc) return rc;
   const dim3 grid((unsigned)((Nc + 255) / 256));
@@ -674,9 +700,10 @@ static int acquire_impl(const char* who, const KdePairRef& p, const double* cand
     } else {
       const CombineRescue rs{cand, p.D, p.Pg(), p.Pb(), a.rescue};
       // the rescue pass left to the combine kernel: its instance by the sign bit (a pair launch: one for both KDEs)
-      const combine_fn cf = !rescue_inline       ? kde_combine_kernel<false, false>
-                            : p.variant_good & 1 ? kde_combine_kernel<true, true>
-                                                 : kde_combine_kernel<false, true>;
+      const bool sgn = KdeVariant::decode(p.variant_good).has_neg;
+      const combine_fn cf = !rescue_inline ? kde_combine_kernel<false, false>
+                            : sgn          ? kde_combine_kernel<true, true>
+                                           : kde_combine_kernel<false, true>;
       hipLaunchKernelGGL(cf, dim3((unsigned)((Nc + 256 * COMBINE_SUB - 1) / (256 * COMBINE_SUB))), dim3(256), 0, s,
                          a.el, a.eg, Nc, sg, logl_out, logg_out, a.lo, a.U, a.flags, a.first1, rs);
       HBX_LAUNCH_CHECK();
@@ -700,9 +727,9 @@ static int acquire_impl(const char* who, const KdePairRef& p, const double* cand
   }
   if (!batch_res) {
     hipLaunchKernelGGL(kde_final_kernel, dim3(1), dim3(256), 0, s, a.list, a.count, a.exact_l, a.exact_g, a.flags,
-                       index_base, p.Pg(), p.Pb(), a.el, a.eg, a.near, a.res,
+                       c.index_base, p.Pg(), p.Pb(), a.el, a.eg, a.near, a.res,
                        (int32_t)((p.nmax + PW_BUF - 1) / PW_BUF), fuse_combine ? a.part : (const double*)nullptr,
-                       a.exact_l, a.exact_g, host_res, seq, pick);
+                       a.exact_l, a.exact_g, c.host_res, c.seq, c.pick);
     HBX_LAUNCH_CHECK();
     return HBX_OK;
   }
@@ -716,7 +743,7 @@ static int acquire_impl(const char* who, const KdePairRef& p, const double* cand
                        p.Pg(), p.Pb(), a.el, a.eg, a.near, a.segnear);
     HBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(kde_batch_final_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, a.key, a.segcnt,
-                       a.flags, a.segnear, a.list, a.exact_l, a.exact_g, p.Pg(), p.Pb(), a.el, a.eg, index_base,
+                       a.flags, a.segnear, a.list, a.exact_l, a.exact_g, p.Pg(), p.Pb(), a.el, a.eg, c.index_base,
                        batch_res);
     HBX_LAUNCH_CHECK();
   }
@@ -737,34 +764,21 @@ void* hbx_kde_result_ptr(void* workspace) { return (char*)workspace + ws_layout(
 // One acquisition: score every candidate against l (good) and g (bad), shortlist, exact re-score,
 // argmin.  index_base offsets the reported index (candidate sharding across GPUs).  The result
 // (AcqResult) stays in the workspace; hbx_kde_result_ptr() gives its device address.
-int hbx_kde_acquire(const double* cand, int64_t Nc, int32_t D, int64_t index_base,
-                    const void* params_good, const float* table_good, const double* X_good,
-                    const int64_t* rows_good, int32_t variant_good,
-                    const void* params_bad, const float* table_bad, const double* X_bad,
-                    const int64_t* rows_bad, int32_t variant_bad, int32_t dc_pad, int32_t du_pad,
-                    int64_t nmax, float* logl_out, float* logg_out, void* workspace, int64_t ws_bytes,
-                    void* events, void* stream) {
-  const KdePairRef p{D, params_good, table_good, X_good, rows_good, variant_good, params_bad, table_bad, X_bad,
-                     rows_bad, variant_bad, dc_pad, du_pad, nmax};
-  return acquire_impl("hbx_kde_acquire", p, cand, Nc, Nc > 0 ? Nc : 1, index_base, logl_out, logg_out, nullptr,
-                      workspace, ws_bytes, events, stream);
+int hbx_kde_acquire(const double* cand, int64_t Nc, int64_t index_base, const void* pair, float* logl_out,
+                    float* logg_out, void* workspace, int64_t ws_bytes, void* events, void* stream) {
+  return acquire_impl(pair, {"hbx_kde_acquire", cand, Nc, Nc > 0 ? Nc : 1, index_base, logl_out, logg_out, nullptr,
+                             workspace, ws_bytes, events, stream, nullptr, 0, PickOut{}});
 }
 
 // Batched acquisition: candidates [b*seg, min((b+1)*seg, Nc)) are the num_samples candidates of
 // get_config call b; every segment gets its own exact argmin (index relative to the segment start,
 // plus index_base) in results[b].  Same kernels as hbx_kde_acquire, one pass for all segments.
-int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int32_t D, int64_t index_base,
-                          const void* params_good, const float* table_good, const double* X_good,
-                          const int64_t* rows_good, int32_t variant_good,
-                          const void* params_bad, const float* table_bad, const double* X_bad,
-                          const int64_t* rows_bad, int32_t variant_bad, int32_t dc_pad, int32_t du_pad,
-                          int64_t nmax, float* logl_out, float* logg_out, void* results, void* workspace,
-                          int64_t ws_bytes, void* stream) {
+int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int64_t index_base, const void* pair,
+                          float* logl_out, float* logg_out, void* results, void* workspace, int64_t ws_bytes,
+                          void* stream) {
   if (!results) return hbx_fail(HBX_ERR_ARG, "hbx_kde_acquire_batch: null results");
-  const KdePairRef p{D, params_good, table_good, X_good, rows_good, variant_good, params_bad, table_bad, X_bad,
-                     rows_bad, variant_bad, dc_pad, du_pad, nmax};
-  return acquire_impl("hbx_kde_acquire_batch", p, cand, Nc, seg, index_base, logl_out, logg_out, (AcqResult*)results,
-                      workspace, ws_bytes, nullptr, stream);
+  return acquire_impl(pair, {"hbx_kde_acquire_batch", cand, Nc, seg, index_base, logl_out, logg_out,
+                             (AcqResult*)results, workspace, ws_bytes, nullptr, stream, nullptr, 0, PickOut{}});
 }
 
 void* hbx_kde_pair_bind(int32_t D, const void* params_good, const float* table_good, const double* X_good,
@@ -804,9 +818,9 @@ int hbx_kde_acquire_bound(const void* pair, const double* cand, int64_t Nc, int6
   const int32_t seq = mb->seq;
   const hipStream_t s = (hipStream_t)stream;
   const bool pick = err || row_out;  // (8 (13 + 2 D) <= PUB_BYTES for D <= HBX_MAX_D)
-  rc = acquire_impl(who, b, cand, Nc, Nc > 0 ? Nc : 1, index_base, nullptr, nullptr, nullptr, workspace, ws_bytes,
-                    events, stream, pick ? nullptr : (AcqResult*)pub, seq,
-                    pick ? PickOut{cand, err, Nc, b.D, pub} : PickOut{});
+  rc = acquire_impl(pair, {who, cand, Nc, Nc > 0 ? Nc : 1, index_base, nullptr, nullptr, nullptr, workspace, ws_bytes,
+                           events, stream, pick ? nullptr : (AcqResult*)pub, seq,
+                           pick ? PickOut{cand, err, Nc, b.D, pub} : PickOut{}});
   if (rc) return rc;
   // the final kernel's tagged words: the record, then (a pick) the flag, then the row when there is a winner
   constexpr int RW = (int)(sizeof(AcqResult) / 4);

@@ -145,6 +145,24 @@ __host__ __device__ constexpr int h32c_ktp(int nsc, int kp) { return 8 * (((h32c
 __host__ __device__ constexpr int h32c_chunk_floats(int nsc, int kp) {
   return (OBS_CHUNK * h32c_ktp(nsc, kp) / 2 + 255) & ~255;
 }
+// The variant code of a prepared KDE (hbx_kde_prepare's info[0]; the bit layout: include/hbx.h at
+// hbx_kde_prepare), the one place that packs and unpacks it.  Flags are 0 / 1.
+struct KdeVariant {
+  int has_neg;      // signed sums
+  int kc;           // one-hot K-steps (0: categorical match on the VALU)
+  int hmode;        // whole exponent on the f16 matrix cores
+  int exact_only;   // outside every fp32 scoring bucket
+  int h32;          // the 32x32-tile kernels (h32 table)
+  int coarse;       // the table carries the coarse h32 layout
+  int small_codes;  // <= 8 categorical slots, codes in [0, 3] (hbx_logpdf.hip DD_LUT)
+  __host__ __device__ int encode() const {
+    return has_neg | (kc << 1) | (hmode << 4) | (exact_only << 5) | (h32 << 6) | (coarse << 7) | (small_codes << 8);
+  }
+  __host__ __device__ static KdeVariant decode(int v) {
+    return {v & 1, (v >> 1) & 7, (v >> 4) & 1, (v >> 5) & 1, (v >> 6) & 1, (v >> 7) & 1, (v >> 8) & 1};
+  }
+};
+
 // ------------------------------------------------------------------------------------------
 // fp32 log-domain scoring
 //

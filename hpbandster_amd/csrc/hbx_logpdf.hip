@@ -733,13 +733,14 @@ int hbx_kde_logpdf_rtol(const double* cand, int64_t Nc, int32_t D, const void* p
   int32_t* count = (int32_t*)sc;
   KdeEst* est = (KdeEst*)(sc + 256);
   int32_t* list = (int32_t*)(sc + 256 + 16 * Nc);
-  const bool exact_only = (variant >> 5) & 1;
+  const KdeVariant v = KdeVariant::decode(variant);
+  const bool exact_only = v.exact_only;
   // unsigned KDEs of a bucket with <= 32 continuous slots: the direct-difference fp32 pass writes every
   // candidate its bound accepts and lists the rest (its kernel lists all of a KDE it does not model)
   int cpt = 1;
   // HBX_DD_LUT=0: the packed-match categorical path everywhere (tests)
-  const bool lut = ((variant >> 8) & 1) && hbx_switch_on("HBX_DD_LUT");
-  const DdFns dd = (!exact_only && !(variant & 1)) ? pick_logpdf_dd(dc_pad, du_pad, &cpt, lut) : DdFns{};
+  const bool lut = v.small_codes && hbx_switch_on("HBX_DD_LUT");
+  const DdFns dd = (!exact_only && !v.has_neg) ? pick_logpdf_dd(dc_pad, du_pad, &cpt, lut) : DdFns{};
   // HBX_DD_SG=0: the LDS-staged dd kernel everywhere (tests)
   // (small calls: the LDS-staged kernel alone -- the staging launch and a second dd launch would cost more than
   // the SG kernel saves, and the scratch of a few thousand candidates rarely holds the rows)

@@ -646,8 +646,12 @@ __device__ __forceinline__ int small_codes(const KdeParams* P) {
 }
 
 // Final mode of each KDE and its info record {variant, nan_all, unsupported, dc, du, nconst, dc_pad,
-// du_pad}; variant = has_neg | kc << 1 | (hmode != 0) << 4 | exact_only << 5 | (hmode == 2) << 6 |
-// (coarse table) << 7 | small_codes << 8 selects the scoring kernel.  rebuild: the table needed its f32 rebuild.
+// du_pad}; variant (KdeVariant, hbx_kde_impl.h) selects the scoring kernel.  rebuild: the table needed its f32
+// rebuild.
+__device__ __forceinline__ int prep_variant(const KdeParams* P, int hmode, int coarse_off) {
+  return KdeVariant{P->has_neg, P->kc, hmode != 0, P->exact_only, hmode == 2, hmode == 2 && coarse_off > 0,
+                    small_codes(P)}.encode();
+}
 __device__ __forceinline__ void prep_finish_p(KdeParams* P, int32_t* info, bool rebuild) {
   if (rebuild) {
     P->hmode = 0;
@@ -655,8 +659,7 @@ __device__ __forceinline__ void prep_finish_p(KdeParams* P, int32_t* info, bool 
     P->cmax = P->cmax2;
     P->coarse_off = 0;
   }
-  info[0] = P->has_neg | (P->kc << 1) | ((P->hmode != 0) << 4) | (P->exact_only << 5) | ((P->hmode == 2) << 6) |
-            ((P->hmode == 2 && P->coarse_off > 0) << 7) | (small_codes(P) << 8);
+  info[0] = prep_variant(P, P->hmode, P->coarse_off);
   info[1] = P->nan_all;
   info[2] = P->unsupported;
   info[3] = P->dc;
@@ -681,8 +684,7 @@ __device__ __forceinline__ void prep_finish_lds(const KdeParams* R, KdeParams* W
     W->cmax = cmax2;
     W->coarse_off = 0;
   }
-  vals[0] = R->has_neg | (R->kc << 1) | ((hmode != 0) << 4) | (R->exact_only << 5) | ((hmode == 2) << 6) |
-            ((hmode == 2 && coarse > 0) << 7) | (small_codes(R) << 8);
+  vals[0] = prep_variant(R, hmode, coarse);
   vals[1] = R->nan_all;
   vals[2] = R->unsupported;
   vals[3] = R->dc;

@@ -1,10 +1,13 @@
 // hbx_score.hip -- scoring dispatch on MI355X (gfx950): which fp32 scoring instance a prepared KDE runs
 // (hbx_score_f32 / _oh / _h / _h32.hip hold them), the launch of one KDE's or a pair's scoring with its rescue
 // pass, and the rescue kernels.  hbx_kde_logpdf scores candidates against one KDE; the acquisitions
-// (hbx_kde.hip, hbx_topk.hip) launch through launch_score2.
+// (hbx_kde.hip acq_score, and through it hbx_topk.hip) launch through launch_score2; pair_shape is the one rule for
+// a pair launch's kernel, tiles and splits (the fused launch here, stage 1 of hbx_staged.hip).
 #include "hbx_score.h"
 
 #include <hip/hip_ext.h>
+
+#include <type_traits>
 
 #include "hbx_prep.h"
 #include "hbx_rescue_impl.h"
@@ -71,60 +74,85 @@ int obs_splits(unsigned tiles, int64_t nmax, bool ws_sizing) {
   return sp < 1 ? 1 : (int)sp;
 }
 
-template <bool SG>
-static logpdf_pair_fn pick_rescue_pair(int dc_pad) {
-  switch (dc_pad) {
-    case 0: return kde_rescue_pair_kernel<0, SG>;
-    case 4: return kde_rescue_pair_kernel<4, SG>;
-    case 8: return kde_rescue_pair_kernel<8, SG>;
-    case 16: return kde_rescue_pair_kernel<16, SG>;
-    case 24: return kde_rescue_pair_kernel<24, SG>;
-    case 32: return kde_rescue_pair_kernel<32, SG>;
-    case 64: return kde_rescue_pair_kernel<64, SG>;
-  }
-  return nullptr;
+// observation splits of a list launch: lists are short (tens of candidates, one or two tiles), so as many
+// ranges as leave each >= 4 chunks -- 16 at the bench's 8500 bad observations: one tile's 16 blocks of 8 chunks
+int list_splits(int64_t nmax) {
+  if (!hbx_switch_on("HBX_OBS_SPLIT")) return 1;
+  const int64_t sp = ((nmax + OBS_CHUNK - 1) / OBS_CHUNK) / 4;
+  return sp < 1 ? 1 : sp > OBS_SPLIT_MAX ? OBS_SPLIT_MAX : (int)sp;
 }
 
-template <bool SG>
-static logpdf_fn pick_rescue(int dc_pad) {
+// (hbx_score.h)
+PairShape pair_shape(const ScoreFns& f, bool pair1_ok, int kdes, int64_t Nc, int64_t split_nmax) {
+  PairShape sh{f.pair, (unsigned)((Nc + f.cands_per_block - 1) / f.cands_per_block), 1};
+  // every block of the launch within one round of the chip's slots (two per CU): one column tile per wave
+  // instead, twice the waves (config #2: 52 instead of 53.5 us per acquisition; profiles/r06/ct1/).  The fused
+  // launch's rule is 2 tiles <= 512 because both KDEs' blocks share the slots; stage 1 of the staged acquisition
+  // has them to itself, so tiles <= 512.  Measured there with HBX_PAIR1=1 / 0 under HBX_STAGED=2
+  // (profiles/staged/onoff_pair1.jsonl): the staged call is 8 % faster with it at 1.4e5 candidates and equal at
+  // 2.0e5 and 2.6e5.
+  if (pair1_ok && f.pair1 && (unsigned)kdes * sh.tiles <= 512 && hbx_switch_on("HBX_PAIR1")) {
+    sh.kernel = f.pair1;
+    sh.tiles = (unsigned)((Nc + f.cands_per_block / H32C_CT - 1) / (f.cands_per_block / H32C_CT));
+  }
+  // (At about one block per CU -- config #2, 2 x 196 blocks -- splitting only the bad KDE's longer walks in two
+  // measured 3-5 us slower, like splitting both: each range repeats the block's prologue, and the merge reads
+  // twice the estimates.  So one split count for every KDE of the launch.)
+  if (f.split_ok && split_nmax > 0) sh.nsplit = obs_splits(sh.tiles, split_nmax, false);
+  return sh;
+}
+
+// the one ladder over the continuous buckets: f(integral_constant<dc_pad>) for a bucket, else nullptr
+template <class F>
+static auto by_dc_pad(int dc_pad, F f) -> decltype(f(std::integral_constant<int, 0>{})) {
   switch (dc_pad) {
-    case 0: return kde_rescue_kernel<0, SG>;
-    case 4: return kde_rescue_kernel<4, SG>;
-    case 8: return kde_rescue_kernel<8, SG>;
-    case 16: return kde_rescue_kernel<16, SG>;
-    case 24: return kde_rescue_kernel<24, SG>;
-    case 32: return kde_rescue_kernel<32, SG>;
-    case 64: return kde_rescue_kernel<64, SG>;
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 24: return f(std::integral_constant<int, 24>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: return f(std::integral_constant<int, 64>{});
   }
   return nullptr;
 }
+template <bool SG>
+static logpdf_fn pick_rescue(int dc_pad) {
+  return by_dc_pad(dc_pad, [](auto c) -> logpdf_fn { return kde_rescue_kernel<decltype(c)::value, SG>; });
+}
+template <bool SG>
+static logpdf_pair_fn pick_rescue_pair(int dc_pad) {
+  return by_dc_pad(dc_pad, [](auto c) -> logpdf_pair_fn { return kde_rescue_pair_kernel<decltype(c)::value, SG>; });
+}
+
+static const ScoreFns NO_SCORE_FNS{nullptr, nullptr, 0, 0, nullptr, nullptr};  // no instance for the bucket
 
 // (the variant code and `fast`: hbx_score.h)
 ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast) {
-  const bool sg = variant & 1;
-  const int kc = du_pad == 0 ? 0 : (variant >> 1) & 7;  // no categorical dims: kc irrelevant
-  const bool hm = (variant >> 4) & 1;
+  const KdeVariant v = KdeVariant::decode(variant);
+  const bool sg = v.has_neg;
+  const int kc = du_pad == 0 ? 0 : v.kc;  // no categorical dims: kc irrelevant
   int dcp, dup;
   bucket_dims(dc_pad, du_pad, &dcp, &dup);
-  if (dcp != dc_pad || dup != du_pad) return {nullptr, nullptr, 0, 0, nullptr, nullptr};  // not a bucket
+  if (dcp != dc_pad || dup != du_pad) return NO_SCORE_FNS;  // not a bucket
   const logpdf_fn r = sg ? pick_rescue<true>(dc_pad) : pick_rescue<false>(dc_pad);
-  if (hm && ((variant >> 6) & 1)) {
-    if (dc_pad < 8) return {nullptr, nullptr, 0, 0, nullptr, nullptr};
+  const logpdf_pair_fn rp = sg ? pick_rescue_pair<true>(dc_pad) : pick_rescue_pair<false>(dc_pad);
+  if (v.hmode && v.h32) {
+    if (dc_pad < 8) return NO_SCORE_FNS;
     const int kp = h32_kp(kc);
-    const bool co = fast && !sg && ((variant >> 7) & 1);  // the acquisition's coarse pre-screen instance
+    const bool co = fast && !sg && v.coarse;  // the acquisition's coarse pre-screen instance
     const bool fa = fast && kp > 0;
     const int hw = co ? H32C_WAVES : H16_WAVES;
     ScoreFns f{hbx_pick_h32(nsc_of(dc_pad), kp, sg, fa, co), r, 32 * hw * (co ? H32C_CT : 1), 64 * hw,
-               hbx_pick_h32_pair(nsc_of(dc_pad), kp, sg, fa, co),
-               sg ? pick_rescue_pair<true>(dc_pad) : pick_rescue_pair<false>(dc_pad), true};
+               hbx_pick_h32_pair(nsc_of(dc_pad), kp, sg, fa, co), rp, true};
     if (co && H32C_CT > 1) f.pair1 = hbx_pick_h32_pair1(nsc_of(dc_pad), kp);
     if (co) f.list = hbx_pick_h32_list(nsc_of(dc_pad), kp);
     return f;
   }
-  if (hm) {
-    if (dc_pad < 8) return {nullptr, nullptr, 0, 0, nullptr, nullptr};
+  if (v.hmode) {
+    if (dc_pad < 8) return NO_SCORE_FNS;
     return {hbx_pick_h(nsc_of(dc_pad), kc, sg), r, 16 * H16_WAVES * H_ROW_TILES, 64 * H16_WAVES,
-            hbx_pick_h_pair(nsc_of(dc_pad), kc, sg), sg ? pick_rescue_pair<true>(dc_pad) : pick_rescue_pair<false>(dc_pad)};
+            hbx_pick_h_pair(nsc_of(dc_pad), kc, sg), rp};
   }
   if (kc == 0) return {hbx_pick_f32(dc_pad, du_pad, sg), r, 16 * MFMA_WAVES, 64 * MFMA_WAVES, nullptr, nullptr};
   return {hbx_pick_oh(dc_pad, kc, sg), r, 16 * MFMA_WAVES, 64 * MFMA_WAVES, nullptr, nullptr};
@@ -141,69 +169,51 @@ int launch_score(ScoreFns f, const double* cand, int64_t Nc, int32_t D, const vo
   return HBX_OK;
 }
 
-// (hbx_score.h.)  HBX_SCORE_PAIR=0 keeps two launches; HBX_PAIR1=0 always the H32C_CT-tile coarse pair kernel
-// (both read per call: tests switch them in-process)
-int launch_score2(ScoreFns f0, const void* params0, const float* table0, KdeEst* est0, ScoreFns f1,
-                  const void* params1, const float* table1, KdeEst* est1, const double* cand, int64_t Nc, int32_t D,
-                  hipEvent_t* ev, int32_t* rescue_cnt, hipStream_t s, KdePairArgs::AcqInitPtrs init, bool* inited,
-                  int64_t nmax, int32_t* nsplit_out, bool* rescue_inline) {
-  if (nsplit_out) nsplit_out[0] = nsplit_out[1] = 1;
-  if (rescue_inline) *rescue_inline = false;
-  const bool pair = f0.pair && f0.main == f1.main && f0.rescue_pair && f0.rescue == f1.rescue &&
+// (hbx_score.h.)  HBX_SCORE_PAIR=0 keeps two launches (read per call: tests switch it in-process)
+int launch_score2(const ScoreSide& good, const ScoreSide& bad, const ScoreRequest& rq, ScoreResult* out) {
+  *out = ScoreResult{};
+  const ScoreFns& f = good.f;
+  const hipStream_t s = rq.s;
+  const bool pair = f.pair && f.main == bad.f.main && f.rescue_pair && f.rescue == bad.f.rescue &&
                     hbx_switch_on("HBX_SCORE_PAIR");
-  if (ev && !pair) HBX_HIP(hipEventRecord(ev[0], s));
-  if (pair) {
-    unsigned gm = (unsigned)((Nc + f0.cands_per_block - 1) / f0.cands_per_block);
-    logpdf_pair_fn pk = f0.pair;
-    // both KDEs' blocks within one round of the chip's slots (two per CU): one column tile per wave instead,
-    // twice the waves (config #2: 52 instead of 53.5 us per acquisition; profiles/r06/ct1/)
-    if (f0.pair1 && f0.pair1 == f1.pair1 && 2 * gm <= 512 && hbx_switch_on("HBX_PAIR1")) {
-      pk = f0.pair1;
-      gm = (unsigned)((Nc + f0.cands_per_block / H32C_CT - 1) / (f0.cands_per_block / H32C_CT));
-    }
-    const unsigned gr = (unsigned)((Nc + 255) / 256);
-    if ((uint64_t)gr * 2 > 0x7fffffffu) return hbx_fail(HBX_ERR_ARG, "too many candidates for one pair launch");
-    const bool can = f0.split_ok && nsplit_out && nmax > 0;
-    // segment 0 = params1 (the bad KDE), 1 = params0.  (At about one block per CU -- config #2, 2 x 196
-    // blocks -- splitting only the bad KDE's longer walks in two measured 3-5 us slower, like splitting
-    // both: each range repeats the block's prologue, and the merge reads twice the estimates.)
-    const int ns0 = can ? obs_splits(gm, nmax) : 1, ns1 = ns0;
-    KdePairArgs a{(const KdeParams*)params1, (const KdeParams*)params0, table1, table0, est1, est0, gm * ns0,
-                  rescue_cnt, {}};
-    a.tiles = gm;
-    a.nsplit0 = ns0;
-    a.nsplit1 = ns1;
-    if (nsplit_out) {
-      nsplit_out[0] = ns1;  // params0's (the first KDE argument's) splits
-      nsplit_out[1] = ns0;
-    }
-    const unsigned grid = gm * (unsigned)(ns0 + ns1);
-    const bool pinit = f0.split_ok && HBX_PAIR_INIT;
-    if (pinit) a.init = init;  // the 32x32 pair kernel's first workgroup sets the acquisition state
-    if (ev)  // events stamped by the dispatch itself at the kernel's start and end (rocprof's duration)
-      hipExtLaunchKernelGGL(pk, dim3(grid), dim3(f0.threads), 0, s, ev[0], ev[1], 0, cand, Nc, D, a);
-    else
-      hipLaunchKernelGGL(pk, dim3(grid), dim3(f0.threads), 0, s, cand, Nc, D, a);
-    HBX_LAUNCH_CHECK();
-    a.nblk0 = gr;
-    a.init = pinit ? KdePairArgs::AcqInitPtrs{} : init;  // else set by the rescue pass's first workgroup
-    if (inited) *inited = init.U != nullptr;
-    if (rescue_inline && pinit && rescue_cnt && ns0 == 1 && ns1 == 1) {
-      *rescue_inline = true;  // the combine kernel (kde_combine_kernel<signed, true>) re-scores the marked candidates
-      return HBX_OK;
-    }
-    // the rescue pass: grid-stride, exits at once unless the scoring kernel counted a marker
-    const unsigned grr = rescue_cnt ? (2 * gr < 1024u ? 2 * gr : 1024u) : 2 * gr;
-    hipLaunchKernelGGL(f0.rescue_pair, dim3(grr), dim3(256), 0, s, cand, Nc, D, a);
-    HBX_LAUNCH_CHECK();
+  if (!pair) {
+    if (rq.ev) HBX_HIP(hipEventRecord(rq.ev[0], s));
+    int rc = launch_score(f, rq.cand, rq.Nc, rq.D, good.params, good.table, good.est, s);
+    if (rc) return rc;
+    if (rq.ev) HBX_HIP(hipEventRecord(rq.ev[1], s));
+    rc = launch_score(bad.f, rq.cand, rq.Nc, rq.D, bad.params, bad.table, bad.est, s);
+    if (rc) return rc;
+    if (rq.ev) HBX_HIP(hipEventRecord(rq.ev[2], s));
     return HBX_OK;
   }
-  int rc = launch_score(f0, cand, Nc, D, params0, table0, est0, s);
-  if (rc) return rc;
-  if (ev) HBX_HIP(hipEventRecord(ev[1], s));
-  rc = launch_score(f1, cand, Nc, D, params1, table1, est1, s);
-  if (rc) return rc;
-  if (ev) HBX_HIP(hipEventRecord(ev[2], s));
+  const PairShape sh = pair_shape(f, f.pair1 == bad.f.pair1, 2, rq.Nc, rq.split_nmax);
+  const unsigned gr = (unsigned)((rq.Nc + 255) / 256);
+  if ((uint64_t)gr * 2 > 0x7fffffffu) return hbx_fail(HBX_ERR_ARG, "too many candidates for one pair launch");
+  // segment 0 = the bad KDE, 1 = the good one
+  KdePairArgs a{(const KdeParams*)bad.params, (const KdeParams*)good.params, bad.table, good.table, bad.est,
+                good.est, sh.tiles * sh.nsplit, rq.rescue_cnt, {}};
+  a.tiles = sh.tiles;
+  a.nsplit0 = a.nsplit1 = sh.nsplit;
+  out->nsplit[0] = out->nsplit[1] = sh.nsplit;
+  const unsigned grid = sh.tiles * (unsigned)(2 * sh.nsplit);
+  const bool pinit = f.split_ok && HBX_PAIR_INIT;
+  if (pinit) a.init = rq.init;  // the 32x32 pair kernel's first workgroup sets the acquisition state
+  if (rq.ev)  // events stamped by the dispatch itself at the kernel's start and end (rocprof's duration)
+    hipExtLaunchKernelGGL(sh.kernel, dim3(grid), dim3(f.threads), 0, s, rq.ev[0], rq.ev[1], 0, rq.cand, rq.Nc, rq.D, a);
+  else
+    hipLaunchKernelGGL(sh.kernel, dim3(grid), dim3(f.threads), 0, s, rq.cand, rq.Nc, rq.D, a);
+  HBX_LAUNCH_CHECK();
+  a.nblk0 = gr;
+  a.init = pinit ? KdePairArgs::AcqInitPtrs{} : rq.init;  // else set by the rescue pass's first workgroup
+  out->inited = rq.init.U != nullptr;
+  if (rq.combine_rescues && pinit && rq.rescue_cnt && sh.nsplit == 1) {
+    out->rescue_inline = true;  // the combine kernel (kde_combine_kernel<signed, true>) re-scores the marked candidates
+    return HBX_OK;
+  }
+  // the rescue pass: grid-stride, exits at once unless the scoring kernel counted a marker
+  const unsigned grr = rq.rescue_cnt ? (2 * gr < 1024u ? 2 * gr : 1024u) : 2 * gr;
+  hipLaunchKernelGGL(f.rescue_pair, dim3(grr), dim3(256), 0, s, rq.cand, rq.Nc, rq.D, a);
+  HBX_LAUNCH_CHECK();
   return HBX_OK;
 }
 
@@ -215,7 +225,7 @@ int hbx_kde_logpdf(const double* cand, int64_t Nc, int32_t D, const void* params
   if ((!cand || !est_out) && Nc > 0) return hbx_fail(HBX_ERR_ARG, "hbx_kde_logpdf: null pointer");
   if (!params || !table) return hbx_fail(HBX_ERR_ARG, "hbx_kde_logpdf: null pointer");
   if (Nc <= 0) return HBX_OK;
-  ScoreFns f = pick_logpdf(dc_pad, du_pad, variant);
+  ScoreFns f = pick_logpdf(dc_pad, du_pad, variant, false);
   if (!f.main) return hbx_fail(HBX_ERR_UNSUPPORTED, "no kernel for dc_pad=%d du_pad=%d", dc_pad, du_pad);
   return launch_score(f, cand, Nc, D, params, table, (KdeEst*)est_out, (hipStream_t)stream);
 }
@@ -224,7 +234,7 @@ int hbx_kde_logpdf(const double* cand, int64_t Nc, int32_t D, const void* params
 
 int hbx_logpdf_estimate(const double* cand, int64_t Nc, int32_t D, const void* params, const float* table,
                         int32_t dc_pad, int32_t du_pad, int32_t variant, KdeEst* est, hipStream_t s) {
-  ScoreFns f = pick_logpdf(dc_pad, du_pad, variant);
+  ScoreFns f = pick_logpdf(dc_pad, du_pad, variant, false);
   if (!f.main) return hbx_fail(HBX_ERR_UNSUPPORTED, "no kernel for dc_pad=%d du_pad=%d", dc_pad, du_pad);
   return launch_score(f, cand, Nc, D, params, table, est, s);
 }

@@ -238,50 +238,25 @@ __global__ __launch_bounds__(256) void staged_survivor_kernel(const float* __res
 // ------------------------------------------------------------------------------------------
 // launch side
 
-// HBX_STAGED: 0 = never, 2 = wherever supported (tests), unset / other = by size.  Read per call.
-int acq_staged_mode() {
-  const char* e = getenv("HBX_STAGED");
-  if (!e) return 1;
-  const int v = atoi(e);
-  return v == 0 ? 0 : v == 2 ? 2 : 1;
-}
-
 bool acq_staged_supported(const AcqPlan& plan) {
   return HBX_PAIR_INIT && !plan.exact_only && plan.fg.list && plan.fb.list && plan.fg.pair && plan.fg.split_ok;
 }
 
-// observation splits of a list launch: lists are short (tens of candidates, one or two tiles), so as many
-// ranges as leave each >= 4 chunks -- 16 at the bench's 8500 bad observations: one tile's 16 blocks of 8 chunks
-static int list_splits(int64_t nmax) {
-  if (!hbx_switch_on("HBX_OBS_SPLIT")) return 1;
-  const int64_t sp = ((nmax + OBS_CHUNK - 1) / OBS_CHUNK) / 4;
-  return sp < 1 ? 1 : sp > OBS_SPLIT_MAX ? OBS_SPLIT_MAX : (int)sp;
-}
-
 int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
                      hipEvent_t* ev, hipStream_t s) {
-  // stage 1: the good KDE's pair kernel with every block in its first segment
+  // stage 1: the good KDE's pair kernel with every block in its first segment; the good KDE has the chip's block
+  // slots to itself (pair_shape's kdes = 1)
   const ScoreFns& f = plan.fg;
-  unsigned gm = (unsigned)((Nc + f.cands_per_block - 1) / f.cands_per_block);
-  logpdf_pair_fn pk = f.pair;
-  // One tile per wave while the launch fits one round of the chip's block slots.  The fused launch's rule is
-  // 2 gm <= 512 because both KDEs' blocks share the slots; here the good KDE has them to itself, so gm <= 512:
-  // between 131k and 262k candidates stage 1 runs another instance than the fused path would (the sums do not
-  // depend on it).  Measured with HBX_PAIR1=1 / 0 under HBX_STAGED=2 (profiles/staged/onoff_pair1.jsonl): the
-  // staged call is 8 % faster with it at 1.4e5 candidates and equal at 2.0e5 and 2.6e5.
-  if (f.pair1 && gm <= 512 && hbx_switch_on("HBX_PAIR1")) {
-    pk = f.pair1;
-    gm = (unsigned)((Nc + f.cands_per_block / H32C_CT - 1) / (f.cands_per_block / H32C_CT));
-  }
-  const int ns = obs_splits(gm, p.nmax);
-  KdePairArgs ka{p.Pg(), p.Pg(), p.table_good, p.table_good, a.el, a.el, gm * (unsigned)ns, a.rescue,
-                 {a.U, a.count, a.flags, a.first1, a.res}};
-  ka.tiles = gm;
+  const PairShape sh = pair_shape(f, true, 1, Nc, p.nmax);
+  const int ns = sh.nsplit;
+  const unsigned grid = sh.tiles * (unsigned)ns;
+  KdePairArgs ka{p.Pg(), p.Pg(), p.table_good, p.table_good, a.el, a.el, grid, a.rescue, a.init()};
+  ka.tiles = sh.tiles;
   ka.nsplit0 = ka.nsplit1 = ns;
   if (ev)  // stamped by the dispatch at the kernel's start
-    hipExtLaunchKernelGGL(pk, dim3(gm * (unsigned)ns), dim3(f.threads), 0, s, ev[0], nullptr, 0, cand, Nc, p.D, ka);
+    hipExtLaunchKernelGGL(sh.kernel, dim3(grid), dim3(f.threads), 0, s, ev[0], nullptr, 0, cand, Nc, p.D, ka);
   else
-    hipLaunchKernelGGL(pk, dim3(gm * (unsigned)ns), dim3(f.threads), 0, s, cand, Nc, p.D, ka);
+    hipLaunchKernelGGL(sh.kernel, dim3(grid), dim3(f.threads), 0, s, cand, Nc, p.D, ka);
   HBX_LAUNCH_CHECK();
   const dim3 gsel((unsigned)((Nc + 256 * STAGED_PT - 1) / (256 * STAGED_PT)));
   hipLaunchKernelGGL(staged_l_kernel, gsel, dim3(256), 0, s, a.el, Nc, (int32_t)ns, cand, p.D, p.Pg(), a.rescue, a.lo,

@@ -351,21 +351,18 @@ int64_t hbx_kde_topk_result_bytes(int32_t k) {
 // them the bounds pass, the k-th smallest upper bound and the shortlist against it, after them the ranking.
 // Unlike the argmin, the combine never does the rescue, the exact re-score never scans and its unit sums are
 // always combined by their own launch.
-int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int32_t D, int64_t index_base,
-                         const void* params_good, const float* table_good, const double* X_good,
-                         const int64_t* rows_good, int32_t variant_good, const void* params_bad,
-                         const float* table_bad, const double* X_bad, const int64_t* rows_bad, int32_t variant_bad,
-                         int32_t dc_pad, int32_t du_pad, int64_t nmax, void* results, void* workspace,
-                         int64_t ws_bytes, void* stream) {
+int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int64_t index_base, const void* pair,
+                         void* results, void* workspace, int64_t ws_bytes, void* stream) {
   const char* who = "hbx_kde_acquire_topk";
-  const KdePairRef p{D, params_good, table_good, X_good, rows_good, variant_good, params_bad, table_bad, X_bad,
-                     rows_bad, variant_bad, dc_pad, du_pad, nmax};
   if (!results) return hbx_fail(HBX_ERR_ARG, "%s: null pointer", who);
+  const KdePairRef* pp = acq_pair(who, pair);
+  if (!pp) return HBX_ERR_ARG;
+  const KdePairRef& p = *pp;
   int rc = acq_check(who, p, cand, Nc, workspace);
   if (rc) return rc;
   if (k < 1 || k > HBX_TOPK_MAX_K) return hbx_fail(HBX_ERR_ARG, "%s: k=%d outside [1, %d]", who, k, HBX_TOPK_MAX_K);
-  if (D < 1 || D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "%s: D=%d", who, D);
-  const int64_t need = hbx_kde_topk_workspace_bytes(Nc, k, nmax);
+  if (p.D < 1 || p.D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "%s: D=%d", who, p.D);
+  const int64_t need = hbx_kde_topk_workspace_bytes(Nc, k, p.nmax);
   if (ws_bytes < need)
     return hbx_fail(HBX_ERR_ARG, "workspace too small: %lld < %lld bytes", (long long)ws_bytes, (long long)need);
   hipStream_t s = (hipStream_t)stream;
@@ -376,11 +373,14 @@ int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int32_t D, i
   AcqPlan plan;
   rc = acq_plan(p, true, &plan);
   if (rc) return rc;
-  const WsLayout w = ws_layout(Nc, nmax);
+  const WsLayout w = ws_layout(Nc, p.nmax);
   const AcqWs a(workspace, w);
   uint32_t* hik = (uint32_t*)a.near;                         // the upper bounds' keys in the near list's place
   uint32_t* hist = (uint32_t*)((char*)workspace + w.total);  // the select's histograms after the argmin's workspace
-  rc = acq_score(plan, p, cand, Nc, a, 0, nullptr, nmax, nullptr, s);
+  // (no timing events; the rescue pass always a launch of its own: the bounds pass does not rescue)
+  const ScoreRequest rq{cand, Nc, p.D, nullptr, a.rescue, a.init(), p.nmax, false, s};
+  ScoreResult sr;
+  rc = acq_score(plan, p, a, rq, 0, &sr);
   if (rc) return rc;
   if (plan.exact_only) {  // no estimates: every candidate re-scored (lo = 0, the flag set), no select
     rc = acq_exact_only_init(Nc, (uint32_t)Nc, a, s);

@@ -234,6 +234,7 @@ class DeviceKDE(object):
         self._ordered = set()    # other streams already ordered after that
         self.variant, self.nan_all, unsupported, self.dc, self.du, self.nconst, self.dc_pad, self.du_pad = \
             info.tolist()
+        # the variant code's bits: include/hbx.h at hbx_kde_prepare
         self.has_neg, self.kc = self.variant & 1, (self.variant >> 1) & 7
         self.exact_only = bool((self.variant >> 5) & 1)
         if unsupported:
@@ -421,9 +422,9 @@ class KDEPair(object):
         if (good.dc_pad, good.du_pad) != (bad.dc_pad, bad.du_pad):
             raise N.HbxError("good/bad KDEs prepared for different kernel buckets")
         self.nmax = max(good.nobs, bad.nobs)
-        # per-call constants of acquire(): the prepared KDEs' device pointers and variant codes, the
-        # workspace size per candidate count, the result record's offset (host overhead of a
-        # get_config at the reference's 64 candidates is of the order of the GPU work)
+        # what hbx_kde_pair_bind binds: the prepared KDEs' device pointers and variant codes.  Per-call constants
+        # of acquire() beside the handle: the workspace size per candidate count, the result record's offset (host
+        # overhead of a get_config at the reference's 64 candidates is of the order of the GPU work)
         self._kde_args = (good.params.data_ptr(), good.table.data_ptr(), good.X_dev.data_ptr(),
                           good.rows_dev.data_ptr(), good.variant, bad.params.data_ptr(), bad.table.data_ptr(),
                           bad.X_dev.data_ptr(), bad.rows_dev.data_ptr(), bad.variant, good.dc_pad, good.du_pad,
@@ -437,8 +438,7 @@ class KDEPair(object):
         self._cur_dev, self._raw_stream = _torch_fast_fns()
         L = N.lib()
         self._ws_cache = {}  # (thread, Nc) -> workspace of synchronous calls made without one
-        # the fixed arguments bound once on the native side: the synchronous call converts 11 arguments
-        # instead of 25 (hbx_kde_acquire_bound)
+        # the fixed arguments bound once on the native side: every acquisition takes the handle
         self._bound = None
         self._bound_fn = L.hbx_kde_acquire_bound
         self._free_fn = L.hbx_kde_pair_free
@@ -559,12 +559,11 @@ class KDEPair(object):
                                events.address if events is not None else None, sh, rec, None))
         return AcqResult.from_bytes(rec.raw[:RESULT_BYTES])
 
-    def _acquire(self, cands, index_base, logs, stream, workspace, sync, events, ties):
+    def _stage_cands(self, cands):
+        """The general paths' candidates on the model's device, checked: (device tensor, Nc)."""
         torch = _torch()
-        L = N.lib()
-        dev = self.good.device
         if isinstance(cands, np.ndarray):
-            c_dev = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(dev)
+            c_dev = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.good.device)
         else:
             c_dev = cands
             if c_dev.dtype != torch.float64 or not c_dev.is_contiguous():
@@ -573,10 +572,27 @@ class KDEPair(object):
         D = self.good.k_vars
         if Nc > 0 and (c_dev.dim() != 2 or int(c_dev.shape[1]) != D):
             raise N.HbxError("candidates must be [Nc, %d], got %s" % (D, tuple(c_dev.shape)))
-        wsb = self.workspace_bytes(Nc)
-        ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
+        return c_dev, Nc
+
+    def _workspace(self, workspace, wsb):
+        """The caller's workspace, or a new one, of at least ``wsb`` bytes."""
+        torch = _torch()
+        ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.good.device)
         if ws.numel() < wsb:
             raise N.HbxError("workspace too small")
+        return ws
+
+    def _resolve_if_near(self, ties, res, ws, Nc, cands, c_dev, index_base):
+        """ties='process' and a NEAR_TIE record: the host re-resolution (_resolve)."""
+        if ties == "process" and res.flags & ACQ_NEAR_TIE:
+            self._resolve(res, ws, Nc, Nc, cands if isinstance(cands, np.ndarray) else c_dev, int(index_base))
+
+    def _acquire(self, cands, index_base, logs, stream, workspace, sync, events, ties):
+        torch = _torch()
+        L = N.lib()
+        dev = self.good.device
+        c_dev, Nc = self._stage_cands(cands)
+        ws = self._workspace(workspace, self.workspace_bytes(Nc))
         logl = torch.empty(Nc, dtype=torch.float32, device=dev) if logs else None
         logg = torch.empty(Nc, dtype=torch.float32, device=dev) if logs else None
         wsp = ws.data_ptr()
@@ -587,12 +603,10 @@ class KDEPair(object):
             N.check(self._bound_fn(self._bound, c_dev.data_ptr(), Nc, int(index_base), wsp, ws.numel(), None,
                                    events.address if events is not None else None, sh, rec, None))
             res = AcqResult.from_bytes(rec.raw[:RESULT_BYTES])
-            if ties == "process" and res.flags & ACQ_NEAR_TIE:
-                self._resolve(res, ws, Nc, Nc, cands if isinstance(cands, np.ndarray) else c_dev, int(index_base))
+            self._resolve_if_near(ties, res, ws, Nc, cands, c_dev, index_base)
             return res
-        N.check(L.hbx_kde_acquire(c_dev.data_ptr(), Nc, D, int(index_base), *self._kde_args,
-                                  N.ptr(logl), N.ptr(logg), wsp, ws.numel(),
-                                  events.address if events is not None else None, sh))
+        N.check(L.hbx_kde_acquire(c_dev.data_ptr(), Nc, int(index_base), self._bound, N.ptr(logl), N.ptr(logg), wsp,
+                                  ws.numel(), events.address if events is not None else None, sh))
         if self._roff is None:
             self._roff = int(L.hbx_kde_result_ptr(wsp)) - wsp
         off = self._roff
@@ -600,8 +614,7 @@ class KDEPair(object):
         if not sync:
             return rview
         res = AcqResult.from_bytes(fetch_bytes(rview, stream))
-        if ties == "process" and res.flags & ACQ_NEAR_TIE:
-            self._resolve(res, ws, Nc, Nc, cands if isinstance(cands, np.ndarray) else c_dev, int(index_base))
+        self._resolve_if_near(ties, res, ws, Nc, cands, c_dev, index_base)
         if logs:
             return res, logl.cpu().numpy(), logg.cpu().numpy()
         return res
@@ -628,24 +641,12 @@ class KDEPair(object):
         torch = _torch()
         L = N.lib()
         dev = self.good.device
-        if isinstance(cands, np.ndarray):
-            c_dev = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(dev)
-        else:
-            c_dev = cands
-            if c_dev.dtype != torch.float64 or not c_dev.is_contiguous():
-                raise N.HbxError("candidate tensor must be contiguous float64 [Nc, D]")
-        Nc = int(c_dev.shape[0])
-        D = self.good.k_vars
-        if Nc > 0 and (c_dev.dim() != 2 or int(c_dev.shape[1]) != D):
-            raise N.HbxError("candidates must be [Nc, %d], got %s" % (D, tuple(c_dev.shape)))
-        wsb = self.topk_workspace_bytes(Nc, k)
-        ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
-        if ws.numel() < wsb:
-            raise N.HbxError("workspace too small")
+        c_dev, Nc = self._stage_cands(cands)
+        ws = self._workspace(workspace, self.topk_workspace_bytes(Nc, k))
         out = torch.empty(int(L.hbx_kde_topk_result_bytes(k)), dtype=torch.uint8, device=dev)
         sh = N.stream_handle(stream, dev)
         self._order(sh)
-        N.check(L.hbx_kde_acquire_topk(c_dev.data_ptr(), Nc, k, D, int(index_base), *self._kde_args, N.ptr(out),
+        N.check(L.hbx_kde_acquire_topk(c_dev.data_ptr(), Nc, k, int(index_base), self._bound, N.ptr(out),
                                        ws.data_ptr(), ws.numel(), sh))
         return TopK.from_bytes(fetch_bytes(out, stream))  # one device-to-host copy: the whole result block
 
@@ -737,34 +738,19 @@ class KDEPair(object):
         torch = _torch()
         L = N.lib()
         dev = self.good.device
-        if isinstance(cands, np.ndarray):
-            c_dev = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(dev)
-        else:
-            c_dev = cands
-            if c_dev.dtype != torch.float64 or not c_dev.is_contiguous():
-                raise N.HbxError("candidate tensor must be contiguous float64 [Nc, D]")
-        Nc, seg = int(c_dev.shape[0]), int(seg)
-        D = self.good.k_vars
+        seg = int(seg)
         if seg < 1:
             raise N.HbxError("segment length must be >= 1")
-        if Nc > 0 and (c_dev.dim() != 2 or int(c_dev.shape[1]) != D):
-            raise N.HbxError("candidates must be [Nc, %d], got %s" % (D, tuple(c_dev.shape)))
+        c_dev, Nc = self._stage_cands(cands)
         B = (Nc + seg - 1) // seg
-        wsb = self.batch_workspace_bytes(Nc, seg)
-        ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
-        if ws.numel() < wsb:
-            raise N.HbxError("workspace too small")
+        ws = self._workspace(workspace, self.batch_workspace_bytes(Nc, seg))
         out = results if results is not None else torch.empty(max(B, 1) * RESULT_BYTES, dtype=torch.uint8, device=dev)
         if out.numel() < B * RESULT_BYTES:
             raise N.HbxError("result buffer too small")
-        g, b = self.good, self.bad
         sh = N.stream_handle(stream, dev)
         self._order(sh)
-        N.check(L.hbx_kde_acquire_batch(N.ptr(c_dev), Nc, seg, D, 0,
-                                        N.ptr(g.params), N.ptr(g.table), N.ptr(g.X_dev), N.ptr(g.rows_dev), g.variant,
-                                        N.ptr(b.params), N.ptr(b.table), N.ptr(b.X_dev), N.ptr(b.rows_dev), b.variant,
-                                        g.dc_pad, g.du_pad, self.nmax, None, None, N.ptr(out), N.ptr(ws), ws.numel(),
-                                        sh))
+        N.check(L.hbx_kde_acquire_batch(N.ptr(c_dev), Nc, seg, 0, self._bound, None, None, N.ptr(out), N.ptr(ws),
+                                        ws.numel(), sh))
         if not sync:
             return out[:B * RESULT_BYTES]
         raw = fetch_bytes(out[:B * RESULT_BYTES], stream)

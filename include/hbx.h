@@ -136,9 +136,17 @@ int64_t hbx_kde_table_floats(int32_t n, int32_t dc_pad, int32_t du_pad);
 /* Build one KDE for scoring.  X: device f64[*][D]; rows: device i64[n] (this KDE's rows, in
  * the reference's order); vartype/bw/nlev: host arrays of length D.  params: device buffer of
  * hbx_kde_param_bytes(); table: device f32[hbx_kde_table_floats(n, dc_pad, du_pad)].  info: host i32[8] =
- * {variant, nan_all, unsupported, dc, du, nconst, dc_pad, du_pad}; variant = has_neg | kc << 1 selects
- * the scoring kernel (kc = 0: categorical matching on the VALU; kc >= 1: categorical one-hot product
- * on the f16 matrix cores with kc K-steps) and is passed back to hbx_kde_logpdf / hbx_kde_acquire. */
+ * {variant, nan_all, unsupported, dc, du, nconst, dc_pad, du_pad}.  variant selects the scoring kernel and is
+ * passed back to hbx_kde_logpdf / hbx_kde_logpdf_rtol / hbx_kde_pair_bind; its bits:
+ *   bit 0     has_neg: a categorical dim has a negative match factor (signed sums)
+ *   bits 1-3  kc: 0 = categorical matching on the VALU; >= 1 = categorical one-hot product on the f16 matrix
+ *             cores with kc K-steps
+ *   bit 4     hmode: the whole exponent on the f16 matrix cores
+ *   bit 5     exact_only: outside every fp32 scoring bucket (> 64 continuous / > 32 categorical dims): every
+ *             candidate is evaluated in fp64
+ *   bit 6     h32: the 32x32-tile kernels (with bit 4)
+ *   bit 7     coarse: the table also holds the coarse layout of the acquisition's pre-screen instance
+ *   bit 8     small_codes: <= 8 categorical slots, every code in [0, 3] (hbx_kde_logpdf_rtol's table look-up) */
 int hbx_kde_prepare(const double* X, int32_t D, const int64_t* rows, int32_t n, const int32_t* vartype,
                     const double* bw, const int32_t* nlev, void* params, float* table, int64_t table_floats,
                     int32_t* info, void* stream);
@@ -162,22 +170,21 @@ int64_t hbx_kde_workspace_bytes(int64_t Nc, int64_t nmax);
  * the scoring runs the fast instance (the
  * one-hot deltas' f16 lo parts moved into the bound: looser estimates, the same exact selection).  The
  * result record lives in the workspace: hbx_kde_result_ptr(workspace).
+ * pair: the KDE pair's handle (hbx_kde_pair_bind, below; NULL: HBX_ERR_ARG).
  * events: NULL or hipEvent_t[3] (see hbx_event_create). */
-int hbx_kde_acquire(const double* cand, int64_t Nc, int32_t D, int64_t index_base,
-                    const void* params_good, const float* table_good, const double* X_good,
-                    const int64_t* rows_good, int32_t variant_good,
-                    const void* params_bad, const float* table_bad, const double* X_bad,
-                    const int64_t* rows_bad, int32_t variant_bad, int32_t dc_pad, int32_t du_pad,
-                    int64_t nmax, float* logl_out, float* logg_out, void* workspace, int64_t ws_bytes,
-                    void* events, void* stream);
+int hbx_kde_acquire(const double* cand, int64_t Nc, int64_t index_base, const void* pair, float* logl_out,
+                    float* logg_out, void* workspace, int64_t ws_bytes, void* events, void* stream);
 
-/* The synchronous acquisition (bohb.py:124-169 returns the pick to get_config's caller) on a KDE pair whose
- * fixed arguments (D, params_good .. nmax) are bound once: the drop-in binds each model it fits
- * (bohb.py:248-251 replaces the pair on every refit), and a call passes only what changes -- about 2 us less
- * host time per acquisition than converting all of them.  The handle holds the pointers only: the caller keeps
- * the KDEs' device buffers alive while it is in use, and frees it with hbx_kde_pair_free.  NULL on bad
- * arguments (hbx_last_error).
- * hbx_kde_acquire_bound: hbx_kde_acquire (fast scoring instances, no ln-pdf outputs) whose final kernel also
+/* A prepared (good, bad) KDE pair as every acquisition takes it -- hbx_kde_acquire, hbx_kde_acquire_bound,
+ * hbx_kde_acquire_batch and hbx_kde_acquire_topk: its fixed arguments (D, each KDE's parameter block, table,
+ * data, rows and variant as hbx_kde_prepare took / reported them, the shared bucket, nmax = the larger
+ * observation count) are bound once.  The drop-in binds each model it fits (bohb.py:248-251 replaces the pair
+ * on every refit), and a call passes only what changes -- about 2 us less host time per acquisition than
+ * converting all of them.  The handle holds the pointers only: for all four calls the caller keeps the KDEs'
+ * device buffers alive while it is in use, and frees it with hbx_kde_pair_free.  NULL on bad arguments
+ * (hbx_last_error).
+ * hbx_kde_acquire_bound: the synchronous acquisition (bohb.py:124-169 returns the pick to get_config's
+ * caller): hbx_kde_acquire (fast scoring instances, no ln-pdf outputs) whose final kernel also
  * stores the 48-byte record into this thread's device-mapped host buffer, every 32-bit word as an 8-byte word
  * tagged with the call's sequence number; the call spins until every word carries its tag (bounded, then it
  * synchronises `stream`) and copies the record to rec_out (host, 48 bytes;
@@ -201,13 +208,9 @@ void hbx_kde_pair_free(void* pair);
  * the index relative to its segment start (+ index_base), -1 when the segment has no finite score.
  * Workspace: hbx_kde_batch_workspace_bytes(Nc, seg, nmax). */
 int64_t hbx_kde_batch_workspace_bytes(int64_t Nc, int64_t seg, int64_t nmax);
-int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int32_t D, int64_t index_base,
-                          const void* params_good, const float* table_good, const double* X_good,
-                          const int64_t* rows_good, int32_t variant_good,
-                          const void* params_bad, const float* table_bad, const double* X_bad,
-                          const int64_t* rows_bad, int32_t variant_bad, int32_t dc_pad, int32_t du_pad,
-                          int64_t nmax, float* logl_out, float* logg_out, void* results, void* workspace,
-                          int64_t ws_bytes, void* stream);
+int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int64_t index_base, const void* pair,
+                          float* logl_out, float* logg_out, void* results, void* workspace, int64_t ws_bytes,
+                          void* stream);
 
 /* Top-k acquisition: the k best candidates of ONE pool, ranked exactly.  Where hbx_kde_acquire keeps the
  * first candidate of the smallest score (bohb.py:149-152: `if val < best`), this returns the first
@@ -230,12 +233,8 @@ int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int32_t D
 #define HBX_TOPK_MAX_K 1024
 int64_t hbx_kde_topk_workspace_bytes(int64_t Nc, int32_t k, int64_t nmax);
 int64_t hbx_kde_topk_result_bytes(int32_t k);
-int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int32_t D, int64_t index_base,
-                         const void* params_good, const float* table_good, const double* X_good,
-                         const int64_t* rows_good, int32_t variant_good,
-                         const void* params_bad, const float* table_bad, const double* X_bad,
-                         const int64_t* rows_bad, int32_t variant_bad, int32_t dc_pad, int32_t du_pad,
-                         int64_t nmax, void* results, void* workspace, int64_t ws_bytes, void* stream);
+int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int64_t index_base, const void* pair,
+                         void* results, void* workspace, int64_t ws_bytes, void* stream);
 
 /* Grouped acquisition: ONE exact pick per KDE pair for B independent brackets -- what follows the batched refit
  * (hbx_seg_argsort_ex + hbx_kde_fit) when every bracket proposes a configuration (bohb.py:124-169 per bracket).

@@ -49,11 +49,28 @@ def test_host_side_helpers():
 def test_errors_are_reported_not_swallowed():
     from hpbandster_amd import _native as N
     L = N.lib()
-    rc = L.hbx_kde_acquire(None, 10, 3, 0, None, None, None, None, 0, None, None, None, None, 0, 4, 0,
-                           10, None, None, None, 0, None, None)
+    rc = L.hbx_kde_acquire(None, 10, 0, None, None, None, None, 0, None, None)  # a NULL pair
     assert rc == -1
     with pytest.raises(N.HbxError):
         N.check(rc)
+
+
+def test_acquisitions_refuse_a_null_pair():
+    """hbx_kde_acquire, _batch and _topk take the handle of hbx_kde_pair_bind: NULL is HBX_ERR_ARG, with the
+    entry point's name in the message, before anything else is looked at or launched."""
+    from hpbandster_amd import _native as N
+    L = N.lib()
+    buf = np.zeros(64)
+    p = N.ptr(buf)  # a valid host address for every other pointer
+    calls = {
+        "hbx_kde_acquire": lambda: L.hbx_kde_acquire(p, 8, 0, None, None, None, p, 1 << 30, None, None),
+        "hbx_kde_acquire_batch": lambda: L.hbx_kde_acquire_batch(p, 8, 4, 0, None, None, None, p, p, 1 << 30, None),
+        "hbx_kde_acquire_topk": lambda: L.hbx_kde_acquire_topk(p, 8, 4, 0, None, p, p, 1 << 30, None),
+    }
+    for name, call in calls.items():
+        assert call() == -1, name
+        msg = L.hbx_last_error()
+        assert name.encode() + b":" in msg and b"pair" in msg, (name, msg)
 
 
 # Philox4x32-10 known-answer vectors (Random123 kat_vectors: counter, key -> output)

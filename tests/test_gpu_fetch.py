@@ -68,7 +68,7 @@ def test_acquire_host_record_equals_workspace_record(device):
 
 def test_bound_pair_record_equals_the_async_record(device):
     """hbx_kde_acquire_bound (the drop-in's synchronous call: the pair's fixed arguments bound once) stores the
-    same 48 bytes as hbx_kde_acquire with every argument passed (fetched from its workspace), and the record
+    same 48 bytes as hbx_kde_acquire on the same handle (fetched from its workspace), and the record
     published to mapped memory equals the workspace's -- over many back-to-back calls (the completion word per
     call); with err and row_out (one wait for the whole pick) the record is the same, the row is the winner's,
     and a set error flag comes back as HBX_ACQ_DOMAIN_ERR."""
@@ -89,8 +89,8 @@ def test_bound_pair_record_equals_the_async_record(device):
         N.check(L.hbx_kde_acquire_bound(pair._bound, C.data_ptr(), 20000, base, ws.data_ptr(), ws.numel(), None,
                                         None, sh, a, None))
         w = ws[off:off + kde.RESULT_BYTES].cpu().numpy().tobytes()
-        N.check(L.hbx_kde_acquire(C.data_ptr(), 20000, 32, base, *pair._kde_args, None, None, ws.data_ptr(),
-                                  ws.numel(), None, sh))
+        N.check(L.hbx_kde_acquire(C.data_ptr(), 20000, base, pair._bound, None, None, ws.data_ptr(), ws.numel(),
+                                  None, sh))
         b = kde.fetch_bytes(ws[off:off + kde.RESULT_BYTES])
         assert a.raw[:kde.RESULT_BYTES] == b == w
         r = kde.AcqResult.from_bytes(a.raw[:kde.RESULT_BYTES])

@@ -86,11 +86,15 @@ def test_c_abi_sizes_and_bad_arguments():
     assert L.hbx_kde_topk_workspace_bytes(700, 0, 1000) == -1
     buf = np.zeros(64)
     p = N.ptr(buf)  # a valid host address: the checks below return before any pointer is used
-    kde_args = (p, p, p, p, 0, p, p, p, p, 0, 8, 0, 1000)
-    for k in (0, 1025):
-        assert L.hbx_kde_acquire_topk(p, 8, k, 8, 0, *kde_args, p, p, 1 << 30, None) != 0
-        assert b"k=" in L.hbx_last_error()
-    assert L.hbx_kde_acquire_topk(p, 8, 4, 8, 0, *kde_args, None, p, 1 << 30, None) != 0  # no result buffer
-    assert b"null" in L.hbx_last_error()
-    assert L.hbx_kde_acquire_topk(p, 8, 4, 8, 0, *kde_args, p, p, 16, None) != 0  # workspace too small
-    assert b"workspace" in L.hbx_last_error()
+    pair = L.hbx_kde_pair_bind(8, p, p, p, p, 0, p, p, p, p, 0, 8, 0, 1000)  # a pair over the dummy address
+    assert pair
+    try:
+        for k in (0, 1025):
+            assert L.hbx_kde_acquire_topk(p, 8, k, 0, pair, p, p, 1 << 30, None) != 0
+            assert b"k=" in L.hbx_last_error()
+        assert L.hbx_kde_acquire_topk(p, 8, 4, 0, pair, None, p, 1 << 30, None) != 0  # no result buffer
+        assert b"null" in L.hbx_last_error()
+        assert L.hbx_kde_acquire_topk(p, 8, 4, 0, pair, p, p, 16, None) != 0  # workspace too small
+        assert b"workspace" in L.hbx_last_error()
+    finally:
+        L.hbx_kde_pair_free(pair)

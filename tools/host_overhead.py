@@ -40,7 +40,7 @@ def main():
     L = N.lib()
     sync = torch.cuda.synchronize
     sh = N.stream_handle(None, dev)
-    args = (C.data_ptr(), Nc, C.shape[1], 0) + tuple(pair._kde_args) + (None, None, ws.data_ptr(), ws.numel(), None, sh)
+    args = (C.data_ptr(), Nc, 0, pair._bound, None, None, ws.data_ptr(), ws.numel(), None, sh)
     rv = pair.acquire(C, workspace=ws, sync=False)
     out = {
         "on_device_ctx": per_call(lambda: N.on_device(dev).__enter__().__exit__(None, None, None), 20000),
