@@ -171,17 +171,40 @@ def ptr(t):
     return t.ctypes.data
 
 
+_RAW = None
+
+
+def _raw_fns():
+    """torch's raw (current device, current stream of a device) accessors, looked up once per process (None
+    where this torch lacks one)."""
+    global _RAW
+    if _RAW is None:
+        import torch
+        _RAW = (getattr(torch._C, "_cuda_getDevice", None), getattr(torch._C, "_cuda_getCurrentRawStream", None))
+    return _RAW
+
+
 def stream_handle(stream=None, device=None):
     """hipStream_t of ``stream``, else torch's current stream of ``device`` (not of the calling thread's
     current device: a dispatcher thread's current device is 0 whatever device the model lives on)."""
-    import torch
     if stream is not None:
         return stream.cuda_stream
-    raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+    import torch
+    raw = _raw_fns()[1]
     if raw is not None:  # the raw handle, without building a Stream object per engine call
         idx = None if device is None else device if isinstance(device, int) else torch.device(device).index
         return raw(torch.cuda.current_device() if idx is None else int(idx))
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def home_stream(dev_index):
+    """The calling thread's current stream handle on device ``dev_index`` when that is the thread's current
+    device -- an engine call can then go straight through, without the ``on_device`` context -- else None
+    (also where torch lacks the raw accessors).  A handle may be 0 (the default stream): test ``is None``."""
+    cur, raw = _RAW or _raw_fns()
+    if cur is not None and raw is not None and cur() == dev_index:
+        return raw(dev_index)
+    return None
 
 
 class on_device(object):

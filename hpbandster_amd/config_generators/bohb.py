@@ -15,318 +15,18 @@ reference's order), so a seeded run proposes the same configurations.  What move
 ``.bw`` and ``.pdf`` like the statsmodels objects of the reference.
 """
 
-import ctypes
 import logging
 import threading
 import traceback
 
 import numpy as np
-import scipy.stats as sps
 
 from .. import _native
+# the host draws (the benchmark reads _HostModel, _draw_rvs, _global_mt, host_draw_ok and _HOSTDRAW from this module)
+from ..host_draw import _HOSTDRAW, _MT, _HostModel, _draw_fast, _draw_rvs, _global_mt, host_draw_ok  # noqa: F401
 from ..kde import ACQ_DOMAIN_ERR, ObservationStore, mapped_candidates
 from .base import base_config_generator
 from ._cs import ConfigSpace
-
-
-class _MT(object):
-    """The raw MT19937 state (key[624] words + position: 2500 bytes) of a legacy ``RandomState`` -- a
-    snapshot, compare or restore in ~1 us, where ``get_state`` / ``set_state`` cost ~60 us each (they
-    build and parse the state tuple).  The Gaussian cache of the legacy generator is not part of it:
-    BOHB's draws (``rand``, ``randint``, scipy's truncnorm by inversion of a uniform) never touch it.
-    The layout is numpy's ``mt19937_state``; ``mt_layout_ok()`` checks it against ``get_state`` /
-    ``set_state`` once per process before anything relies on it."""
-    NB = 624 * 4 + 4
-
-    def __init__(self, rs):
-        bg = rs._bit_generator
-        if type(bg).__name__ != "MT19937":
-            raise TypeError("not an MT19937 RandomState")
-        self.rs, self.addr, self.lock = rs, bg.ctypes.state_address, bg.lock
-
-    def snap(self):
-        return ctypes.string_at(self.addr, self.NB)
-
-    def load(self, raw):
-        ctypes.memmove(self.addr, raw, self.NB)
-
-
-_LAYOUT = [None]
-
-
-def mt_layout_ok():
-    """Once per process: the raw bytes at the bit generator's state address are get_state()'s key words
-    and position, and load() of another state's bytes gives that state's get_state() (and its next
-    draws).  False (never raising) when numpy's layout is not the one assumed: the raw-state users then
-    step aside -- speculative batches are not made, the host draws take scipy's per-element path."""
-    if _LAYOUT[0] is None:
-        try:
-            a, b = np.random.RandomState(20240917), np.random.RandomState(77)
-            a.random_sample(700)  # position off the block boundary
-            ma, mb = _MT(a), _MT(b)
-            st = a.get_state(legacy=True)
-            ok = ma.snap() == np.asarray(st[1], dtype="<u4").tobytes() + np.int32(st[2]).tobytes()
-            mb.load(ma.snap())
-            sb = b.get_state(legacy=True)
-            ok = ok and np.array_equal(sb[1], st[1]) and sb[2] == st[2]
-            ok = ok and np.array_equal(a.random_sample(3), b.random_sample(3))
-            _LAYOUT[0] = bool(ok)
-        except Exception:
-            _LAYOUT[0] = False
-        if not _LAYOUT[0]:
-            logging.getLogger('hpbandster').warning(
-                "numpy's MT19937 state layout is not the assumed one: speculative batches and the fast host draws "
-                "are off (results unchanged)")
-    return _LAYOUT[0]
-
-
-_GLOBAL = [None]
-
-
-def _global_mt():
-    """_MT of numpy's global RandomState (the one np.random.rand / randint / scipy's rvs draw from), or
-    None when its raw state cannot be used."""
-    R = np.random.mtrand._rand
-    g = _GLOBAL[0]
-    if g is None or g.rs is not R:
-        if not mt_layout_ok():
-            return None
-        try:
-            g = _GLOBAL[0] = _MT(R)
-        except (TypeError, AttributeError):
-            return None
-    return g
-
-
-_HOSTDRAW = [None]
-
-
-def host_draw_ok():
-    """Once per process: hbx_bohb_draw (libhbx's restatement of the draws, on numpy's own state) agrees with
-    numpy and scipy -- random_sample and randint streams, and a small get_config draw against the
-    per-element scipy path, values and final state bit for bit.  False (never raising) otherwise: the
-    per-element path then runs."""
-    if _HOSTDRAW[0] is None:
-        ok = False
-        try:
-            ok = mt_layout_ok() and int(_native.lib().hbx_mt_state_bytes()) == _MT.NB
-            if ok:
-                L = _native.lib()
-                a, b = np.random.RandomState(5), np.random.RandomState(5)
-                ma = _MT(a)
-                out = np.empty(1500)
-                _native.check(L.hbx_mt_draw(ma.addr, 0, out.size, 0, out.ctypes.data))
-                ok = np.array_equal(out, b.random_sample(out.size))
-                for high in (1, 2, 3, 4, 7, 100, 1000, 65537, 2 ** 31 + 5):
-                    o = np.empty(64)
-                    _native.check(L.hbx_mt_draw(ma.addr, 1, o.size, high, o.ctypes.data))
-                    ok = ok and np.array_equal(o, [b.randint(0, high) for _ in range(o.size)])
-                ok = ok and ma.snap() == _MT(b).snap()
-            if ok:
-                rs = np.random.RandomState(11)
-                data = np.column_stack([rs.rand(9, 3), rs.randint(0, 3, (9, 2))]).astype(np.float64)
-                data[4, 0], data[2, 1] = 0.0, 1.0
-                kde = _HostModel(data, np.array([0.2, 0.05, 0.6, 0.4, 0.9]))
-                lv = np.array([0, 0, 0, 3, 4])
-                a, b = np.random.RandomState(6), np.random.RandomState(6)
-                fast = _draw_fast(kde, lv, 3, 16, a, _MT(a))
-                slow = _draw_rvs(kde, lv, 3, 16, b)
-                ok = np.array_equal(fast, slow) and _MT(a).snap() == _MT(b).snap()
-        except Exception:
-            ok = False
-        _HOSTDRAW[0] = bool(ok)
-        if not ok:
-            logging.getLogger('hpbandster').warning(
-                "hbx_bohb_draw disagrees with numpy/scipy here: BOHB draws candidates element by element")
-    return _HOSTDRAW[0]
-
-
-class _HostModel(object):
-    """The two fields of a KDE the draws read (``data`` rows and ``bw``)."""
-
-    def __init__(self, data, bw):
-        self.data, self.bw = data, bw
-
-
-def _draw_rvs(kde_good, levels, bw_factor, num_samples, R):
-    """bohb.py:133-147 element by element: R.randint for the datum, one scipy truncnorm.rvs per continuous
-    dim (bounds from bw, scale bw_factor * bw), keep-or-resample per categorical dim."""
-    D = len(levels)
-    cands = np.empty((num_samples, D), dtype=np.float64)
-    data = kde_good.data
-    bws = kde_good.bw
-    for i in range(num_samples):
-        idx = R.randint(0, len(data))
-        for d, (m, bw, t) in enumerate(zip(data[idx], bws, levels)):
-            if t == 0:
-                cands[i, d] = sps.truncnorm.rvs(-m / bw, (1 - m) / bw, loc=m, scale=bw_factor * bw, random_state=R)
-            else:
-                if R.rand() < (1 - bw):
-                    cands[i, d] = m
-                else:
-                    cands[i, d] = R.randint(t)
-    return cands
-
-
-class _TruncnormTerms(object):
-    """The uniform-independent terms of scipy's ``truncnorm._ppf`` for one KDE's observation rows, filled
-    row by row as draws first pick them (a model serves every call until the next refit, and BOHB's datum is
-    one of its good rows: after a call or two every row is in).  Per (row, continuous dim), with a = -m/bw,
-    b = (1 - m)/bw (scipy 1.15 ``_continuous_distns.py``, ``truncnorm_gen._ppf`` / ``_log_gauss_mass``):
-    ``lp`` = log_ndtr(a) where a < 0 (``ppf_left``), log_ndtr(-b) otherwise (``ppf_right``); ``mass`` =
-    log1p(-ndtr(a) - ndtr(-b)), the central case of ``_log_gauss_mass``; ``ok`` False where that case does not
-    apply (b <= 0: a datum at the upper bound, a > 0, non-finite bounds) -- those elements take scipy's own
-    ``_ppf``."""
-
-    def __init__(self, data, bw):
-        self.data, self.bw = data, bw
-        n, D = data.shape
-        self.lp = np.empty((n, D))
-        self.mass = np.empty((n, D))
-        self.left = np.zeros((n, D), dtype=np.bool_)
-        self.ok = np.zeros((n, D), dtype=np.bool_)
-        self.have = np.zeros(n, dtype=np.bool_)
-
-    def fill(self, rows, cont):
-        import scipy.special as sc
-        r = np.unique(rows[~self.have[rows]])
-        if r.size:
-            m = self.data[np.ix_(r, cont)]
-            h = self.bw[cont]
-            with np.errstate(all="ignore"):  # (a zero bandwidth: no inversion is asked for that dim)
-                a, b = -m / h, (1 - m) / h
-                left = a < 0
-                self.lp[np.ix_(r, cont)] = sc.log_ndtr(np.where(left, a, -b))
-                self.mass[np.ix_(r, cont)] = sc.log1p(-sc.ndtr(a) - sc.ndtr(-b))
-            self.left[np.ix_(r, cont)] = left
-            self.ok[np.ix_(r, cont)] = (b > 0) & (a <= 0) & np.isfinite(a) & np.isfinite(b)
-            self.have[r] = True
-
-
-_LOG2 = [None]
-
-
-def _ppf_from_terms(q, lp, mass, left):
-    """scipy's truncnorm._ppf at uniforms q from the terms above, the same numpy / scipy.special ufuncs in the
-    same order: log_Phi_x = logsumexp([lp, log(q) + mass]) (log1p(-q) on the right), scipy 1.15's
-    ``_logsumexp`` for two real rows (the larger one taken out of the sum: (log1p(exp(lo - hi)) + log(m)) + hi,
-    m the number of rows equal to the larger), then ndtri_exp (negated on the right).  Formed here as
-    log1p(exp(min - max)) + max: for m = 1, log(m) = 0 adds nothing to log1p(.) >= 0; for m = 2 (the rows
-    equal), exp(0) = 1 and log1p(1) is log(2) (checked by ppf_terms_ok), where scipy adds log(2) to log1p(0) = 0.
-    Elementwise, so a subset gives the values the whole array would.  Non-finite log_Phi_x inputs come back as
-    ``bad`` positions for scipy's own _ppf."""
-    import scipy.special as sc
-    with np.errstate(all="ignore"):
-        x = np.where(left, np.log(q), np.log1p(-q))
-        x += mass
-        hi = np.maximum(lp, x)
-        s = np.minimum(lp, x)
-        s -= hi
-        np.exp(s, out=s)
-        np.log1p(s, out=s)
-        s += hi
-        y = sc.ndtri_exp(s)
-    np.negative(y, out=y, where=~left)
-    return y, ~np.isfinite(hi)
-
-
-_PPF = [None]
-
-
-def ppf_terms_ok():
-    """Once per process: _ppf_from_terms equals scipy's own truncnorm._ppf bit for bit over BOHB's range and its
-    edges (uniforms 0, tiny, near 1; a datum at 0 (a = -0: the right case), at 1 (b = 0: scipy's path), near the
-    bounds; narrow and wide bandwidths).  False (never raising) otherwise: the draws then invert through scipy's
-    _ppf, as before."""
-    if _PPF[0] is None:
-        ok = False
-        try:
-            rs = np.random.RandomState(17)
-            nr, nd = 200, 20
-            m = rs.rand(nr, nd)
-            m[:4] = 0.0
-            m[4:6] = 1.0
-            m[6:10] = rs.choice([1e-12, 1 - 1e-12, 1e-300, 0.5], (4, nd))
-            h = np.exp(rs.uniform(np.log(1e-4), np.log(5.0), nd))
-            q = rs.rand(nr, nd)
-            q[10:12] = 0.0
-            q[12:16] = rs.choice([1e-300, 1e-17, 1 - 2 ** -53, 0.5], (4, nd))
-            t = _TruncnormTerms(m, h)
-            t.fill(np.arange(nr), np.arange(nd))
-            with np.errstate(all="ignore"):
-                ref = sps.truncnorm._ppf(q, -m / h, (1 - m) / h)
-            y, bad = _ppf_from_terms(q, t.lp, t.mass, t.left)
-            use = t.ok & ~bad
-            ok = bool(use.sum() > nr * nd - 3 * nd) and np.array_equal(y[use].view(np.uint64),
-                                                                       ref[use].view(np.uint64))
-            one = np.ones(4)  # the equal-rows case of the logsumexp (_ppf_from_terms)
-            ok = ok and np.array_equal(np.log1p(one).view(np.uint64), np.log(one + one).view(np.uint64))
-        except Exception:
-            ok = False
-        _PPF[0] = bool(ok)
-        if not ok:
-            logging.getLogger('hpbandster').warning(
-                "the truncnorm inversion terms disagree with scipy's truncnorm._ppf here: BOHB inverts through scipy")
-    return _PPF[0]
-
-
-def _draw_fast(kde_good, levels, bw_factor, num_samples, R, mt, out=None):
-    """The same draws in one native call on R's own MT19937 state (hbx_bohb_draw, the reference's
-    consumption order), then the truncnorm inversion of the call's uniforms and rvs's ``* scale + loc`` --
-    the arithmetic rvs applies to each uniform, elementwise, so the values are the per-element path's bit for
-    bit (checked by host_draw_ok and tests/test_host_draw.py).  The inversion reuses the model's per-row terms
-    (``_TruncnormTerms``; scipy's own ``truncnorm._ppf`` when ppf_terms_ok() fails and for the elements the
-    terms do not cover).  A domain error raises ValueError with R left where scipy's raise leaves it."""
-    data = kde_good.data
-    if not (isinstance(data, np.ndarray) and data.dtype == np.float64 and data.flags.c_contiguous):
-        data = np.ascontiguousarray(data, dtype=np.float64)
-    bws = np.ascontiguousarray(kde_good.bw, dtype=np.float64)
-    lv = np.ascontiguousarray(levels, dtype=np.int64)
-    n, D = data.shape
-    vals = np.empty((num_samples, D)) if out is None else out
-    if not vals.flags.c_contiguous:
-        raise ValueError("_draw_fast: out must be C-contiguous")
-    cap = num_samples * D
-    uni = np.empty(cap)
-    comp = np.empty(2 * cap, dtype=np.int64)
-    datum = np.empty(num_samples, dtype=np.int64)
-    stop = ctypes.c_int64(-1)
-    nc = ctypes.c_int64(0)
-    with mt.lock:
-        rc = _native.lib().hbx_bohb_draw(mt.addr, data.ctypes.data, n, D, bws.ctypes.data, lv.ctypes.data,
-                                         float(bw_factor), num_samples, vals.ctypes.data, uni.ctypes.data, None,
-                                         datum.ctypes.data, ctypes.addressof(stop), comp.ctypes.data,
-                                         ctypes.addressof(nc))
-    if rc == 1:
-        raise ValueError("Domain error in arguments (truncnorm bounds of candidate %d, dim %d; bohb.py:141)"
-                         % divmod(stop.value, D))
-    _native.check(rc)
-    k = nc.value
-    if k == 0:
-        return vals
-    # the elements to invert, in draw order: uniform q, element index e, term index ti = datum D + dim
-    q, e, ti = uni[:k], comp[:k], comp[cap:cap + k]
-    flat = vals.reshape(-1)
-    loc = flat.take(e)
-    h = bws.take(ti % D)
-    if ppf_terms_ok():
-        t = getattr(kde_good, "_tn_terms", None)
-        if t is None or t.data is not data or t.bw is not bws or t.lp.shape != (n, D):
-            t = _TruncnormTerms(data, bws)
-            try:
-                kde_good._tn_terms = t
-            except AttributeError:  # (an object that takes no attributes: terms for this call only)
-                pass
-        t.fill(datum, np.flatnonzero(lv == 0))
-        y, bad = _ppf_from_terms(q, t.lp.reshape(-1).take(ti), t.mass.reshape(-1).take(ti),
-                                 t.left.reshape(-1).take(ti))
-        rest = bad | ~t.ok.reshape(-1).take(ti)
-        if rest.any():
-            y[rest] = sps.truncnorm._ppf(q[rest], -loc[rest] / h[rest], (1 - loc[rest]) / h[rest])
-    else:
-        y = sps.truncnorm._ppf(q, -loc / h, (1 - loc) / h)
-    flat[e] = y * (bw_factor * h) + loc
-    return vals
 
 
 class SpeculativeBatch(object):
@@ -349,8 +49,8 @@ class SpeculativeBatch(object):
         return len(self.entries)
 
     def _valid_at(self, j):
-        g = self.gen
-        return g._model_version == self.version and g._sample_counter == self.counters[j]
+        gen = self.gen
+        return gen._model_version == self.version and gen._sample_counter == self.counters[j]
 
     def take(self):
         """The next result, or None when it is not the sequential call's (or the batch is used up)."""
@@ -470,8 +170,7 @@ class BOHB(base_config_generator):
 
         if sample is None:
             try:
-                budget = max(self.kde_models.keys())  # always the largest-budget model (bohb.py:124)
-                pair = self.kde_models[budget]        # immutable snapshot (new_result swaps entries)
+                pair = self._top_pair()
                 if self.sampler == "gpu":
                     # one wait: the draws, the acquisition, the domain-error flag and the winning row come back
                     # together (no separate device reduction and row copy)
@@ -485,8 +184,7 @@ class BOHB(base_config_generator):
                     res = pair.acquire_mapped(cands)
                     best_vector = cands[res.index].copy() if res.index >= 0 else None
                 if res.index < 0:
-                    self.logger.debug("Sampling based optimization with %i samples failed -> using random configuration"
-                                      % self.num_samples)
+                    self.logger.debug(self._failed("no score"))
                     sample = self.configspace.sample_configuration().get_dictionary()
                     info_dict['model_based_pick'] = False
                 else:
@@ -497,53 +195,46 @@ class BOHB(base_config_generator):
             except _native.HbxError:
                 raise  # the engine failed: never hide it behind a random configuration
             except Exception:
-                self.logger.warning("Sampling based optimization with %i samples failed\n %s \nUsing random configuration"
-                                    % (self.num_samples, traceback.format_exc()))
+                self.logger.warning(self._failed("traceback"))
                 sample = self.configspace.sample_configuration().get_dictionary()
                 info_dict['model_based_pick'] = False
         return sample, info_dict
 
+    def _top_pair(self):
+        """Always the largest budget's model (bohb.py:124): an immutable snapshot, new_result swaps entries."""
+        return self.kde_models[max(self.kde_models.keys())]
+
+    def _failed(self, case, then="Using random configuration"):
+        """The messages of a model-based call that ends without a pick (bohb.py:155-166), by ``case``: 'traceback'
+        (an exception, its traceback included), 'domain' (the GPU sampler's truncnorm domain error) and 'no score'
+        (no candidate has a finite score)."""
+        head = "Sampling based optimization with %i samples failed" % self.num_samples
+        if case == "traceback":
+            return "%s\n %s \n%s" % (head, traceback.format_exc(), then)
+        if case == "domain":
+            return "%s (truncnorm domain error)\n%s" % (head, then)
+        return head + " -> using random configuration"
+
     # -- one GPU-sampler call: draws and acquisition, one wait ----------------------------------------
     def _pick(self, pair, counter):
-        """The call's num_samples draws on the Philox `counter` (hbx_kde_sample) and their acquisition with the
-        pick on the host (hbx_kde_acquire_bound with the draws' error flags and the winning row): (AcqResult,
-        winning row or None).  The draw buffers are kept per thread and reused; the native calls go straight
-        through when the thread's current device is the model's and the draw needs no Phi table."""
+        """The call's num_samples draws on the Philox `counter` (DeviceKDE.sample into this thread's kept buffers)
+        and their acquisition with the pick on the host (KDEPair.acquire_pick with the draws' error flags and the
+        winning row): (AcqResult, winning row or None).  Both go straight to their native calls when the thread's
+        current device is the model's, each on the thread's current stream."""
         import torch
-        g = pair.good
+        dev = pair.good.device
         n, D = self.num_samples, len(self.vartypes)
         t = self._pick_tls
         keep = getattr(t, "keep", None)
         wsb = pair.workspace_bytes(n)
-        if keep is None or keep[3].numel() < wsb or keep[0].device != g.device:
-            keep = t.keep = (torch.empty((n, D), dtype=torch.float64, device=g.device),
-                             torch.empty(n, dtype=torch.int64, device=g.device),
-                             torch.empty(n, dtype=torch.uint8, device=g.device),
-                             torch.empty(wsb, dtype=torch.uint8, device=g.device), np.empty(D))
-        cands, datum, err, ws, row = keep
-        if (pair._cur_dev is not None and pair._raw_stream is not None and pair._cur_dev() == pair._dev_index
-                and n < 4 * g.nobs):
-            from ..kde import _levels_on_device
-            L = _native.lib()
-            lvb = getattr(self, "_lv_bytes", None)
-            if lvb is None:
-                self._lv_np = np.ascontiguousarray(self.vartypes, dtype=np.int32)
-                lvb = self._lv_bytes = self._lv_np.tobytes()
-                self._bw_off = int(L.hbx_kde_param_bw_offset())
-            lvd = _levels_on_device(lvb, self._lv_np, g.device)
-            sh = pair._raw_stream(pair._dev_index)
-            if sh != pair._home:
-                pair._order(sh)
-            _native.check(L.hbx_kde_sample(g.X_dev.data_ptr(), g.k_vars, g.rows_dev.data_ptr(), g.nobs,
-                                           g.params.data_ptr() + self._bw_off, lvd.data_ptr(), None,
-                                           float(self.bw_factor), int(self.sampler_seed) & (2 ** 64 - 1),
-                                           int(counter) & (2 ** 64 - 1), 0, n, cands.data_ptr(), datum.data_ptr(),
-                                           err.data_ptr(), sh))
-            res = pair.acquire_pick(cands, err, ws, row, sh)
-        else:
-            with _native.on_device(g.device):
-                g.sample(self.vartypes, self.bw_factor, n, self.sampler_seed, counter, out=keep[:3])
-                res = pair.acquire_pick(cands, err, ws, row)
+        if keep is None or keep[3].numel() < wsb or keep[0].device != dev:
+            keep = t.keep = (torch.empty((n, D), dtype=torch.float64, device=dev),
+                             torch.empty(n, dtype=torch.int64, device=dev),
+                             torch.empty(n, dtype=torch.uint8, device=dev),
+                             torch.empty(wsb, dtype=torch.uint8, device=dev), np.empty(D))
+        cands, _, err, ws, row = keep
+        pair.good.sample(self.vartypes, self.bw_factor, n, self.sampler_seed, counter, out=keep[:3])
+        res = pair.acquire_pick(cands, err, ws, row)
         return res, (row.copy() if res.index >= 0 else None)
 
     # -- the k best candidates of one pool --------------------------------------------------------
@@ -564,7 +255,7 @@ class BOHB(base_config_generator):
             return []
         np.random.rand()  # get_config's random_fraction draw
         try:
-            pair = self.kde_models[max(self.kde_models.keys())]  # bohb.py:124
+            pair = self._top_pair()
             if self.sampler == "gpu":
                 cands, _, err = pair['good'].sample(self.vartypes, self.bw_factor, self.num_samples,
                                                     self.sampler_seed, self._sample_counter)
@@ -580,8 +271,7 @@ class BOHB(base_config_generator):
         except _native.HbxError:
             raise  # the engine failed: never hide it
         except Exception:
-            self.logger.warning("Sampling based optimization with %i samples failed\n %s \nNo model-based "
-                                "configurations" % (self.num_samples, traceback.format_exc()))
+            self.logger.warning(self._failed("traceback", "No model-based configurations"))
             return []
         return [(ConfigSpace.Configuration(self.configspace, vector=rows[j]).get_dictionary(),
                  {'model_based_pick': True, 'score': float(top.score[j])}) for j in range(top.count)]
@@ -645,7 +335,7 @@ class BOHB(base_config_generator):
                 plan.append(None)
             else:
                 if pair is None:
-                    pair = self.kde_models[max(self.kde_models.keys())]  # bohb.py:124
+                    pair = self._top_pair()
                 if self.sampler == "gpu":
                     plan.append(len(blocks) * self.num_samples)
                     blocks.append(None)
@@ -657,8 +347,7 @@ class BOHB(base_config_generator):
                         plan.append(len(blocks) * self.num_samples)
                         blocks.append(block)
                     except Exception:
-                        plan.append(("err", "Sampling based optimization with %i samples failed\n %s \nUsing random "
-                                            "configuration" % (self.num_samples, traceback.format_exc())))
+                        plan.append(("err", self._failed("traceback")))
             if states is not None:
                 states.append(mt.snap())
                 counters.append(counter)
@@ -694,12 +383,9 @@ class BOHB(base_config_generator):
                 if bad is not None and bad[off // self.num_samples]:
                     if res.index >= 0:
                         w += 1
-                    entries.append(("random", "warning", "Sampling based optimization with %i samples failed "
-                                                         "(truncnorm domain error)\nUsing random configuration"
-                                                         % self.num_samples))
+                    entries.append(("random", "warning", self._failed("domain")))
                 elif res.index < 0:
-                    entries.append(("random", "debug", "Sampling based optimization with %i samples failed -> "
-                                                       "using random configuration" % self.num_samples))
+                    entries.append(("random", "debug", self._failed("no score")))
                 else:
                     entries.append(("model", rows[w], res.score))
                     w += 1

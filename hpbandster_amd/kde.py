@@ -71,7 +71,6 @@ _pinned_tls = threading.local()
 
 def _record_buffer():
     """This thread's host buffer for one result record (hbx_kde_acquire_bound writes it)."""
-    import ctypes
     b = getattr(_pinned_tls, "rec", None)
     if b is None:
         b = _pinned_tls.rec = ctypes.create_string_buffer(64)
@@ -83,7 +82,6 @@ def mapped_candidates(n, D):
     address is the device's), as a numpy array: the host sampler draws straight into it and the acquisition's
     kernels read it in place (KDEPair.acquire_mapped) -- no host-to-device copy per get_config.  Reused by
     every call of the thread (each acquisition on it is synchronous); grown on demand."""
-    import ctypes
     nbytes = 8 * n * D
     b = getattr(_pinned_tls, "cands", None)
     if b is None or b[1] < nbytes:
@@ -232,6 +230,9 @@ class DeviceKDE(object):
             self.params, self.table, info = prepared
         self._home = home        # the stream the parameter block and table were written on
         self._ordered = set()    # other streams already ordered after that
+        # the sampler's constants, set by the first draw: the levels object last seen, its bytes and device copy,
+        # the address of the parameter block's bandwidths, the Phi table
+        self._lv_src = self._lv_key = self._lv_dev = self._bw_ptr = self._tab = None
         self.variant, self.nan_all, unsupported, self.dc, self.du, self.nconst, self.dc_pad, self.du_pad = \
             info.tolist()
         # the variant code's bits: include/hbx.h at hbx_kde_prepare
@@ -285,32 +286,45 @@ class DeviceKDE(object):
 
         ``levels``: per dim 0 (continuous) or the number of choices.  Candidate i draws from the
         Philox stream (seed, counter_base + i, stream_id).  Returns (cands [Nc, D] f64, datum [Nc] i64,
-        domain_err [Nc] u8) device tensors (``out``: those three tensors to fill instead of new ones)."""
+        domain_err [Nc] u8) device tensors (``out``: those three tensors to fill instead of new ones).
+        ``levels`` is remembered by identity, so a caller passing one array for every call (BOHB's vartypes)
+        pays its conversion once per model: do not change such an array in place."""
+        sh = N.home_stream(self.device.index) if stream is None else None
+        if sh is not None:  # the thread is on the model's device already: no context to enter
+            return self._sample(levels, bw_factor, Nc, seed, counter_base, stream_id, sh, table, out)
         with N.on_device(self.device, stream):
-            return self._sample(levels, bw_factor, Nc, seed, counter_base, stream_id, stream, table, out)
+            return self._sample(levels, bw_factor, Nc, seed, counter_base, stream_id,
+                                N.stream_handle(stream, self.device), table, out)
 
-    def _sample(self, levels, bw_factor, Nc, seed, counter_base, stream_id, stream, table, out=None):
+    def _sample(self, levels, bw_factor, Nc, seed, counter_base, stream_id, sh, table, out):
         torch = _torch()
         L = N.lib()
         D = self.k_vars
-        sh = N.stream_handle(stream, self.device)
         self._order(sh)
+        if levels is not self._lv_src:
+            lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
+            if lv.shape != (D,):
+                raise N.HbxError("levels must have %d entries" % D)
+            key = lv.tobytes()
+            if self._lv_key != key:
+                self._lv_dev, self._lv_key = _levels_on_device(key, lv, self.device), key
+                self._tab = None
+            self._lv_src = levels
         # the bandwidths the sampler reads: the prepared parameter block's own fp64 bw[D] (bit-identical
         # to self.bw, which was read back from it) -- no upload per refit
-        bw_ptr = N.ptr(self.params) + int(L.hbx_kde_param_bw_offset())
-        lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
-        if lv.shape != (D,):
-            raise N.HbxError("levels must have %d entries" % D)
-        key = lv.tobytes()
-        if getattr(self, "_lv_key", None) != key:
-            self._lv_dev, self._lv_key = _levels_on_device(key, lv, self.device), key
-            self._tab = None
+        bw_ptr = self._bw_ptr
+        if bw_ptr is None:
+            bw_ptr = self._bw_ptr = N.ptr(self.params) + int(L.hbx_kde_param_bw_offset())
         Nc = int(Nc)
         if table is None:
-            table = Nc >= 4 * self.nobs  # the Phi table pays off when draws outnumber (row, dim) pairs
+            # THE rule for the Phi table: it pays off when draws outnumber (row, dim) pairs.  BOHB's per-call
+            # draw (num_samples candidates, sample(..., out=...)) comes through here with table=None like any
+            # other: below 4 * nobs draws the native call gets no table, from there on the table is built
+            # (once per model) and used -- the branch get_config has always taken for the same (Nc, nobs)
+            table = Nc >= 4 * self.nobs
         tab = None
         if table:
-            if getattr(self, "_tab", None) is None:
+            if self._tab is None:
                 self._tab = torch.empty(int(L.hbx_kde_sample_table_bytes(self.nobs, D)) // 8, dtype=torch.float64,
                                         device=self.device)
                 N.check(L.hbx_kde_sample_table(N.ptr(self.X_dev), D, N.ptr(self.rows_dev), self.nobs,
@@ -397,18 +411,6 @@ def _levels_on_device(key, lv, device):
     return t
 
 
-_FAST_FNS = None
-
-
-def _torch_fast_fns():
-    """torch's raw current-device and current-stream accessors (None where this torch lacks them)."""
-    global _FAST_FNS
-    if _FAST_FNS is None:
-        torch = _torch()
-        _FAST_FNS = (getattr(torch._C, "_cuda_getDevice", None), getattr(torch._C, "_cuda_getCurrentRawStream", None))
-    return _FAST_FNS
-
-
 class KDEPair(object):
     """The (good, bad) KDE pair of one budget -- BOHB's ``kde_models[budget]`` entry.
 
@@ -422,27 +424,25 @@ class KDEPair(object):
         if (good.dc_pad, good.du_pad) != (bad.dc_pad, bad.du_pad):
             raise N.HbxError("good/bad KDEs prepared for different kernel buckets")
         self.nmax = max(good.nobs, bad.nobs)
-        # what hbx_kde_pair_bind binds: the prepared KDEs' device pointers and variant codes.  Per-call constants
-        # of acquire() beside the handle: the workspace size per candidate count, the result record's offset (host
-        # overhead of a get_config at the reference's 64 candidates is of the order of the GPU work)
-        self._kde_args = (good.params.data_ptr(), good.table.data_ptr(), good.X_dev.data_ptr(),
-                          good.rows_dev.data_ptr(), good.variant, bad.params.data_ptr(), bad.table.data_ptr(),
-                          bad.X_dev.data_ptr(), bad.rows_dev.data_ptr(), bad.variant, good.dc_pad, good.du_pad,
-                          self.nmax)
+        # per-call constants of acquire() beside the bound handle: the workspace size per candidate count, the
+        # result record's offset (host overhead of a get_config at the reference's 64 candidates is of the order
+        # of the GPU work)
         self._wsb = {}
         self._roff = None
         self._home = good._home if good._home == bad._home else None  # (None: each KDE checks for itself)
-        # the synchronous fast path's constants (acquire: a call on the model's own device)
         dev = good.device
         self._dev_index = dev.index if dev.index is not None else _torch().cuda.current_device()
-        self._cur_dev, self._raw_stream = _torch_fast_fns()
         L = N.lib()
         self._ws_cache = {}  # (thread, Nc) -> workspace of synchronous calls made without one
-        # the fixed arguments bound once on the native side: every acquisition takes the handle
+        # the fixed arguments bound once on the native side (the prepared KDEs' device pointers and variant
+        # codes): every acquisition takes the handle
         self._bound = None
         self._bound_fn = L.hbx_kde_acquire_bound
         self._free_fn = L.hbx_kde_pair_free
-        self._bound = L.hbx_kde_pair_bind(good.k_vars, *self._kde_args)
+        self._bound = L.hbx_kde_pair_bind(
+            good.k_vars, good.params.data_ptr(), good.table.data_ptr(), good.X_dev.data_ptr(),
+            good.rows_dev.data_ptr(), good.variant, bad.params.data_ptr(), bad.table.data_ptr(),
+            bad.X_dev.data_ptr(), bad.rows_dev.data_ptr(), bad.variant, good.dc_pad, good.du_pad, self.nmax)
         if not self._bound:
             raise N.HbxError("hbx_kde_pair_bind: %s" % L.hbx_last_error().decode())
 
@@ -469,13 +469,39 @@ class KDEPair(object):
 
     def result_offset(self):
         """Byte offset of the AcqResult record inside an acquisition workspace."""
-        return int(N.lib().hbx_kde_result_ptr(4096)) - 4096
+        if self._roff is None:
+            self._roff = int(N.lib().hbx_kde_result_ptr(4096)) - 4096
+        return self._roff
 
     def workspace_bytes(self, Nc):
         wsb = self._wsb.get(Nc)
         if wsb is None:
             wsb = self._wsb[Nc] = int(N.lib().hbx_kde_workspace_bytes(int(Nc), self.nmax))
         return wsb
+
+    def _thread_workspace(self, Nc):
+        """This thread's workspace for synchronous calls over ``Nc`` candidates made without one: allocated on
+        first use (workspace_bytes), kept for the pair's lifetime."""
+        key = (threading.get_ident(), Nc)
+        ws = self._ws_cache.get(key)
+        if ws is None:
+            ws = self._ws_cache[key] = _torch().empty(self.workspace_bytes(Nc), dtype=_torch().uint8,
+                                                      device=self.good.device)
+        return ws
+
+    def _acquire_bound(self, cand_ptr, Nc, index_base, ws, sh, err=None, events=None, row=None):
+        """THE synchronous acquisition (hbx_kde_acquire_bound): ``Nc`` candidates at address ``cand_ptr`` scored
+        on stream handle ``sh`` (ordered after the model's preparation first) with workspace ``ws``, the record
+        published to this thread's host buffer when the call returns -> AcqResult.  ``err`` (device u8 [Nc]):
+        any set flag comes back as ACQ_DOMAIN_ERR; ``row`` (host f64 [D]): receives the winning row."""
+        if sh != self._home:
+            self._order(sh)
+        rec = _record_buffer()
+        N.check(self._bound_fn(self._bound, cand_ptr, Nc, int(index_base), ws.data_ptr(), ws.numel(),
+                               err.data_ptr() if err is not None else None,
+                               events.address if events is not None else None, sh, rec,
+                               row.ctypes.data if row is not None else None))
+        return AcqResult.from_bytes(rec.raw[:RESULT_BYTES])
 
     def acquire_stats(self, workspace, Nc):
         """What the last single acquisition over ``Nc`` candidates on ``workspace`` did (synchronises):
@@ -514,24 +540,23 @@ class KDEPair(object):
         """
         if ties not in ("pinned", "process"):
             raise ValueError("ties must be 'pinned' or 'process'")
-        if (sync and not logs and stream is None and self._cur_dev is not None and self._raw_stream is not None
-                and self._cur_dev() == self._dev_index):
-            r = self._acquire_sync(cands, index_base, workspace, events)
+        sh = N.home_stream(self._dev_index) if sync and not logs and stream is None else None
+        if sh is not None:
+            r = self._acquire_sync(cands, index_base, workspace, events, sh)
             if r is not None:
                 if ties == "process" and r.flags & ACQ_NEAR_TIE:
                     with N.on_device(self.good.device):
-                        ws = workspace if workspace is not None else self._ws_cache[(threading.get_ident(), len(cands))]
+                        ws = workspace if workspace is not None else self._thread_workspace(len(cands))
                         self._resolve(r, ws, len(cands), len(cands), cands, int(index_base))
                 return r
         with N.on_device(self.good.device, stream):
             return self._acquire(cands, index_base, logs, stream, workspace, sync, events, ties)
 
-    def _acquire_sync(self, cands, index_base, workspace, events):
+    def _acquire_sync(self, cands, index_base, workspace, events, sh):
         """The drop-in's common call -- synchronous, the winner only, on the model's device and its current
-        stream, which is this thread's current device (no device switch): one native call
-        (hbx_kde_acquire_bound) with the fewest host steps around it; a workspace is kept per thread and
-        candidate count when none is given.  None when the candidates need staging (host arrays, other
-        dtypes): the general path then runs."""
+        stream ``sh``, which is this thread's current device (no device switch): the bound call with the fewest
+        host steps around it; a workspace is kept per thread and candidate count when none is given.  None when
+        the candidates need staging (host arrays, other dtypes): the general path then runs."""
         torch = _torch()
         if type(cands) is not torch.Tensor or cands.dtype is not torch.float64 or not cands.is_cuda:
             return None
@@ -540,24 +565,11 @@ class KDEPair(object):
                 cands.device.index != self._dev_index:
             return None
         Nc = cands.shape[0]
-        wsb = self._wsb.get(Nc)
-        if wsb is None:
-            wsb = self.workspace_bytes(Nc)
         if workspace is None:
-            key = (threading.get_ident(), Nc)
-            workspace = self._ws_cache.get(key)
-            if workspace is None:
-                workspace = self._ws_cache[key] = torch.empty(wsb, dtype=torch.uint8, device=cands.device)
-        n = workspace.numel()
-        if n < wsb:
+            workspace = self._thread_workspace(Nc)
+        elif workspace.numel() < self.workspace_bytes(Nc):
             raise N.HbxError("workspace too small")
-        rec = _record_buffer()
-        sh = self._raw_stream(self._dev_index)
-        if sh != self._home:
-            self._order(sh)
-        N.check(self._bound_fn(self._bound, cands.data_ptr(), Nc, int(index_base), workspace.data_ptr(), n, None,
-                               events.address if events is not None else None, sh, rec, None))
-        return AcqResult.from_bytes(rec.raw[:RESULT_BYTES])
+        return self._acquire_bound(cands.data_ptr(), Nc, index_base, workspace, sh, None, events)
 
     def _stage_cands(self, cands):
         """The general paths' candidates on the model's device, checked: (device tensor, Nc)."""
@@ -595,21 +607,15 @@ class KDEPair(object):
         ws = self._workspace(workspace, self.workspace_bytes(Nc))
         logl = torch.empty(Nc, dtype=torch.float32, device=dev) if logs else None
         logg = torch.empty(Nc, dtype=torch.float32, device=dev) if logs else None
-        wsp = ws.data_ptr()
         sh = N.stream_handle(stream, dev)
-        self._order(sh)
         if sync and not logs:  # one native call: the acquisition and its record on the host
-            rec = _record_buffer()
-            N.check(self._bound_fn(self._bound, c_dev.data_ptr(), Nc, int(index_base), wsp, ws.numel(), None,
-                                   events.address if events is not None else None, sh, rec, None))
-            res = AcqResult.from_bytes(rec.raw[:RESULT_BYTES])
+            res = self._acquire_bound(c_dev.data_ptr(), Nc, index_base, ws, sh, None, events)
             self._resolve_if_near(ties, res, ws, Nc, cands, c_dev, index_base)
             return res
-        N.check(L.hbx_kde_acquire(c_dev.data_ptr(), Nc, int(index_base), self._bound, N.ptr(logl), N.ptr(logg), wsp,
-                                  ws.numel(), events.address if events is not None else None, sh))
-        if self._roff is None:
-            self._roff = int(L.hbx_kde_result_ptr(wsp)) - wsp
-        off = self._roff
+        self._order(sh)
+        N.check(L.hbx_kde_acquire(c_dev.data_ptr(), Nc, int(index_base), self._bound, N.ptr(logl), N.ptr(logg),
+                                  ws.data_ptr(), ws.numel(), events.address if events is not None else None, sh))
+        off = self.result_offset()
         rview = ws[off:off + RESULT_BYTES]
         if not sync:
             return rview
@@ -655,72 +661,56 @@ class KDEPair(object):
         N.check(N.lib().hbx_kde_ws_offsets(int(Nc), int(max(seg, 1)), self.nmax, N.ptr(o)))
         return [int(v) for v in o]
 
-    def _resolve(self, res, ws, Nc, seg, cands, index_base):
-        """HBX_ACQ_NEAR_TIE on a single acquisition: re-score the near set in the reference's numpy
-        arithmetic and take its strict-'<' first-index minimum (exact_host.resolve)."""
+    def _ws_ints(self, ws, off, count):
+        """``count`` int32 entries at byte ``off`` of a workspace, on the host as int64."""
+        return ws[off:off + 4 * count].view(_torch().int32).cpu().numpy().astype(np.int64)
+
+    def _repick(self, res, cands, idx, shift):
+        """Record ``res`` re-decided among candidates ``idx``: re-scored in the reference's numpy arithmetic, its
+        strict-'<' first-index minimum taken (exact_host.resolve), the index stored with ``shift`` added."""
         from . import exact_host
-        o = self._ws_offsets(Nc, seg)
-        idx = ws[o[2]:o[2] + 4 * res.near].view(_torch().int32).cpu().numpy().astype(np.int64)
         pick = exact_host.resolve(self.good, self.bad, _rows_of(cands, idx), idx)
         if pick is not None:
-            res.index, res.score, res.pdf_l, res.pdf_g = pick[0] + index_base, pick[1], pick[2], pick[3]
+            res.index, res.score, res.pdf_l, res.pdf_g = pick[0] + shift, pick[1], pick[2], pick[3]
         res.flags |= ACQ_RESOLVED
+
+    def _resolve(self, res, ws, Nc, seg, cands, index_base):
+        """HBX_ACQ_NEAR_TIE on a single acquisition: the pick re-decided among its near set (_repick)."""
+        o = self._ws_offsets(Nc, seg)
+        self._repick(res, cands, self._ws_ints(ws, o[2], res.near), index_base)
 
     def _resolve_batch(self, recs, ws, Nc, seg, cands):
         """HBX_ACQ_NEAR_TIE in a batched acquisition: the same, per flagged segment."""
-        from . import exact_host
-        torch = _torch()
         o = self._ws_offsets(Nc, seg)
-        cnt = int(ws[o[0]:o[0] + 4].view(torch.int32).item())
-        lst = ws[o[1]:o[1] + 4 * cnt].view(torch.int32).cpu().numpy().astype(np.int64)
-        flg = ws[o[2]:o[2] + 4 * cnt].view(torch.int32).cpu().numpy()
+        cnt = int(self._ws_ints(ws, o[0], 1)[0])
+        lst, flg = self._ws_ints(ws, o[1], cnt), self._ws_ints(ws, o[2], cnt)
         for b, r in enumerate(recs):
-            if not r.flags & ACQ_NEAR_TIE:
-                continue
-            idx = np.sort(lst[(flg != 0) & (lst // seg == b)])
-            pick = exact_host.resolve(self.good, self.bad, _rows_of(cands, idx), idx)
-            if pick is not None:
-                r.index, r.score, r.pdf_l, r.pdf_g = pick[0] - b * seg, pick[1], pick[2], pick[3]
-            r.flags |= ACQ_RESOLVED
+            if r.flags & ACQ_NEAR_TIE:
+                self._repick(r, cands, np.sort(lst[(flg != 0) & (lst // seg == b)]), -b * seg)
 
     def acquire_mapped(self, cands):
         """acquire(cands) for a host array from mapped_candidates(): the kernels read the candidates in host
         memory (zero copy), the pick comes back in the same synchronous call (hbx_kde_acquire_bound).  Falls
         back to acquire() off the fast path's conditions (another current device)."""
-        if self._cur_dev is None or self._raw_stream is None or self._cur_dev() != self._dev_index:
+        sh = N.home_stream(self._dev_index)
+        if sh is None:
             return self.acquire(np.array(cands))
-        torch = _torch()
         Nc = cands.shape[0]
-        wsb = self._wsb.get(Nc)
-        if wsb is None:
-            wsb = self.workspace_bytes(Nc)
-        key = (threading.get_ident(), Nc)
-        workspace = self._ws_cache.get(key)
-        if workspace is None:
-            workspace = self._ws_cache[key] = torch.empty(wsb, dtype=torch.uint8, device=self.good.device)
-        rec = _record_buffer()
-        sh = self._raw_stream(self._dev_index)
-        if sh != self._home:
-            self._order(sh)
-        N.check(self._bound_fn(self._bound, cands.ctypes.data, Nc, 0, workspace.data_ptr(), workspace.numel(), None,
-                               None, sh, rec, None))
-        return AcqResult.from_bytes(rec.raw[:RESULT_BYTES])
+        return self._acquire_bound(cands.ctypes.data, Nc, 0, self._thread_workspace(Nc), sh)
 
     def acquire_pick(self, cands, err, workspace, row, sh=None):
         """One synchronous acquisition of ``cands`` (a device [Nc, D] f64 tensor on the model's device) with its
         whole pick on the host after ONE wait (hbx_kde_acquire_bound with err and row_out): the record, whether
         any ``err`` flag (the GPU sampler's per-candidate domain errors, a device u8 tensor or None) is set
         (ACQ_DOMAIN_ERR in ``flags``), and the winning row written into ``row`` (a host f64 array of D).
-        ``sh``: the stream handle (default: the device's current stream).  Returns the AcqResult."""
+        ``sh``: the stream handle (default: the device's current stream; a thread on another device makes the
+        call with the model's device current).  Returns the AcqResult."""
         if sh is None:
-            sh = N.stream_handle(None, self.good.device)
-        if sh != self._home:
-            self._order(sh)
-        rec = _record_buffer()
-        N.check(self._bound_fn(self._bound, cands.data_ptr(), int(cands.shape[0]), 0, workspace.data_ptr(),
-                               workspace.numel(), err.data_ptr() if err is not None else None, None, sh, rec,
-                               row.ctypes.data))
-        return AcqResult.from_bytes(rec.raw[:RESULT_BYTES])
+            sh = N.home_stream(self._dev_index)
+            if sh is None:
+                with N.on_device(self.good.device):
+                    return self.acquire_pick(cands, err, workspace, row, N.stream_handle(None, self.good.device))
+        return self._acquire_bound(cands.data_ptr(), int(cands.shape[0]), 0, workspace, sh, err, None, row)
 
     def batch_workspace_bytes(self, Nc, seg):
         return int(N.lib().hbx_kde_batch_workspace_bytes(int(Nc), int(seg), self.nmax))
@@ -764,7 +754,6 @@ class ScoreEvents(object):
     """Three hipEvents bracketing the two scoring launches of one acquisition (bench timing)."""
 
     def __init__(self):
-        import ctypes
         L = N.lib()
         self._ev = (ctypes.c_void_p * 3)()
         for i in range(3):
@@ -776,7 +765,6 @@ class ScoreEvents(object):
     def elapsed_ms(self, fused=False):
         """(l launch ms, g launch ms) of the last recorded acquisition (events must be complete).
         ``fused``: l and g ran as one pair launch, which records only events 0 and 1 -> (l+g, 0)."""
-        import ctypes
         L = N.lib()
         a, b = ctypes.c_float(), ctypes.c_float()
         N.check(L.hbx_event_elapsed_ms(self._ev[0], self._ev[1], ctypes.addressof(a)))
@@ -829,15 +817,6 @@ class _DevSlice(object):
 
     def numel(self):
         return self._numel
-
-
-def _raw_stream(device):
-    """The device's current HIP stream handle (torch's raw accessor where it exists)."""
-    torch = _torch()
-    f = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-    if f is not None:
-        return f(device.index if device.index is not None else torch.cuda.current_device())
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 class ObservationStore(object):
@@ -920,20 +899,19 @@ class ObservationStore(object):
         sizes = split_sizes(n, self.D, min_points, top_n_percent, split_rule)
         if sizes is None:
             return None
-        cur, _ = _torch_fast_fns()
-        if stream is None and cur is not None and self.device.index is not None and cur() == self.device.index:
-            return self._refit(self._Xh[:n], self._lh[:n], n, sizes, stream)  # (already current: no context)
+        sh = N.home_stream(self.device.index) if stream is None else None
+        if sh is not None:
+            return self._refit(self._Xh[:n], self._lh[:n], n, sizes, sh)  # (already current: no context)
         with N.on_device(self.device, stream):
-            return self._refit(self._Xh[:n], self._lh[:n], n, sizes, stream)
+            return self._refit(self._Xh[:n], self._lh[:n], n, sizes, N.stream_handle(stream, self.device))
 
-    def _refit(self, X_host, losses, n, sizes, stream):
+    def _refit(self, X_host, losses, n, sizes, sh):
         torch = _torch()
         L = N.lib()
         D = self.D
         n_good, n_bad = sizes
         n_new = n - self.n
         self._reserve(n)
-        sh = stream.cuda_stream if stream is not None else _raw_stream(self.device)
         # the new rows then their losses, from host memory: the native call carries up to 256 doubles in the
         # refit launch's arguments (no copy), more through its scratch
         staged = None

@@ -5,7 +5,8 @@ call byte for byte, and domain errors at the same element with the same state.""
 import numpy as np
 import pytest
 
-from hpbandster_amd.config_generators import bohb as B
+from hpbandster_amd import host_draw as B
+from hpbandster_amd.config_generators.bohb import BOHB
 
 
 def _model(rs, n, dc, du, levels, bw_c=None, bw_u=None):
@@ -110,7 +111,7 @@ def test_sample_candidates_uses_the_global_rng_like_the_reference():
     for i in range(5):
         space.add_hyperparameter(CS.UniformFloatHyperparameter("x%d" % i, lower=0, upper=1))
     space.add_hyperparameter(CS.CategoricalHyperparameter("y", ["a", "b", "c"]))
-    cg = B.BOHB(space)
+    cg = BOHB(space)
     rs = np.random.RandomState(2)
     kde = B._HostModel(np.column_stack([rs.rand(30, 5), rs.randint(0, 3, 30)]).astype(np.float64),
                        np.array([0.1, 0.2, 0.3, 0.15, 0.25, 0.4]))
@@ -167,3 +168,20 @@ def test_draws_reuse_the_models_terms():
         assert ea is None and eb is None and same
         assert np.array_equal(fa, fb)
     assert kde._tn_terms.have.sum() > 30
+
+
+def test_bohb_module_keeps_the_names_the_benchmark_reads():
+    """bench.py reads _HostModel, _draw_rvs, _global_mt, host_draw_ok and the _HOSTDRAW memo (which it sets to time
+    the per-element path) from config_generators.bohb: they are host_draw's own objects there; and host_draw is
+    importable on its own, without the config generators (a fresh interpreter: this process has them loaded)."""
+    import os
+    import subprocess
+    import sys
+    import hpbandster_amd
+    from hpbandster_amd.config_generators import bohb as Bm
+    for name in ("_HostModel", "_draw_rvs", "_global_mt", "host_draw_ok", "_HOSTDRAW"):
+        assert getattr(Bm, name) is getattr(B, name), name
+    code = ("import sys; import hpbandster_amd.host_draw; "
+            "sys.exit(any(m.startswith('hpbandster_amd.config_generators') for m in sys.modules))")
+    assert subprocess.run([sys.executable, "-c", code],
+                          cwd=os.path.dirname(os.path.dirname(hpbandster_amd.__file__))).returncode == 0

@@ -39,7 +39,7 @@ def main():
             n_good, n_bad = sizes
             n_new = n - self.n
             self._reserve(n)
-            sh = kde._raw_stream(dev)
+            sh = N.stream_handle(None, dev)
             t.append(time.perf_counter())
             staged = np.empty(n_new * (D + 1), dtype=np.float64)
             staged[:n_new * D] = X_host[self.n:].reshape(-1)
