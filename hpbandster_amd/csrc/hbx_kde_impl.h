@@ -46,6 +46,13 @@
 #ifndef H32C_CT
 #define H32C_CT 2  // phases in snake order (hbx_score_h32.hip chunk2s); 1 / 3 / 4 measured no faster
 #endif
+// ... and the widest candidate row (doubles, odd stride) it stages through LDS one column tile at a time: the
+// block's LDS object holds 32 such rows per wave, 68 672 bytes with the parameters at 8 waves -- two blocks per CU
+#define H32C_ROW_DS 33
+// ... and the narrowest: from one 128-byte cache line per row on.  Below it two lanes' rows share a line, a load
+// of the direct path touches 16 lines at most, and the copy through LDS only adds latency (measured at D = 8:
+// config #2's scoring launch 22.2 us direct, 23.3 us staged; at D = 16: 31.7 against 27.1 us)
+#define H32C_ROW_DMIN 16
 
 // Observation table, chunked for the MFMA scoring kernel.  Chunk c holds observations 64c..64c+63:
 //   [KP k-rows][KROW]   B operand, k-major: k=0 -> C_j, k=1 -> 1, k=2+c -> X'_jc, rest 0
@@ -298,8 +305,13 @@ struct KdePairArgs {
   // them).  1: one block covers all of the KDE's observations.
   unsigned tiles = 0;
   int32_t nsplit0 = 1, nsplit1 = 1;
+  // the coarse 32x32 instances stage their candidate rows through LDS (0: HBX_ROW_STAGE=0, every lane reads its
+  // row from global memory; the other instances do not look at it)
+  int32_t row_stage = 1;
 };
 typedef void (*logpdf_pair_fn)(const double*, int64_t, int32_t, KdePairArgs);
+// the coarse 32x32 instance over one KDE: logpdf_fn's arguments and KdePairArgs::row_stage
+typedef void (*logpdf_co_fn)(const double*, int64_t, int32_t, const KdeParams*, const float*, KdeEst*, int32_t);
 
 // kernel arguments of a list launch (hbx_score_h32.hip kde_logpdf_h32_list_kernel; the staged acquisition,
 // hbx_staged.hip): the candidates idx[0 .. min(*count, maxcount)) against one KDE.  At most cap listed: tiles_cap
@@ -316,6 +328,7 @@ struct KdeListArgs {
   int32_t* rescue;  // marker count (KdePairArgs::rescue)
   int32_t cap, maxcount, nsplit;
   unsigned tiles_cap;
+  int32_t row_stage;  // KdePairArgs::row_stage
 };
 typedef void (*logpdf_list_fn)(const double*, int32_t, KdeListArgs);
 
@@ -399,7 +412,8 @@ logpdf_fn hbx_pick_f32(int dc_pad, int du_pad, bool sg);   // hbx_score_f32.hip
 logpdf_fn hbx_pick_oh(int dc_pad, int kc, bool sg);        // hbx_score_oh.hip
 logpdf_fn hbx_pick_h(int nsc, int kc, bool sg);            // hbx_score_h.hip
 logpdf_pair_fn hbx_pick_h_pair(int nsc, int kc, bool sg);  // hbx_score_h.hip (l + g in one launch)
-logpdf_fn hbx_pick_h32(int nsc, int kp, bool sg, bool fast, bool coarse = false);  // hbx_score_h32.hip
+logpdf_fn hbx_pick_h32(int nsc, int kp, bool sg, bool fast);  // hbx_score_h32.hip
+logpdf_co_fn hbx_pick_h32_co(int nsc, int kp);                // the coarse instance over one KDE (unsigned sums)
 logpdf_pair_fn hbx_pick_h32_pair(int nsc, int kp, bool sg, bool fast, bool coarse = false);
 logpdf_pair_fn hbx_pick_h32_pair1(int nsc, int kp);  // the coarse pair kernel, one column tile per wave
 logpdf_list_fn hbx_pick_h32_list(int nsc, int kp);   // the coarse instance over an index list (staged acquisition)

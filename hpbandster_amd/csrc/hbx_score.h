@@ -16,6 +16,7 @@ struct ScoreFns {
                           // state (the 32x32-tile instances); a combine kernel may then do the rescue pass
   logpdf_pair_fn pair1 = nullptr;  // the coarse pair kernel with one column tile per wave (pair_shape)
   logpdf_list_fn list = nullptr;   // the coarse instance over an index list (the staged acquisition)
+  logpdf_co_fn main_co = nullptr;  // the coarse instance over one KDE: launch_score runs it in main's place
 };
 
 // variant: a prepared KDE's code (KdeVariant, hbx_kde_impl.h)
@@ -36,12 +37,15 @@ int list_splits(int64_t nmax);
 // acquisition: tiles <= 512, so between 131k and 262k candidates it runs another instance than the fused launch
 // would; the sums do not depend on it).  pair1_ok: every KDE of the launch has the same pair1 instance.
 // HBX_PAIR1=0: always f.pair; HBX_OBS_SPLIT=0: no splits (both read per call: tests switch them in-process).
+// HBX_ROW_STAGE=0 (hbx_row_stage, read per call like them): the coarse instances read their candidate rows in
+// place instead of staging them through LDS (KdePairArgs::row_stage; the sums do not depend on it).
 struct PairShape {
   logpdf_pair_fn kernel;
   unsigned tiles;
   int nsplit;
 };
 PairShape pair_shape(const ScoreFns& f, bool pair1_ok, int kdes, int64_t Nc, int64_t split_nmax);
+static inline int32_t hbx_row_stage() { return hbx_switch_on("HBX_ROW_STAGE") ? 1 : 0; }
 
 // launch main + rescue scoring for one KDE
 int launch_score(ScoreFns f, const double* cand, int64_t Nc, int32_t D, const void* params, const float* table,

@@ -143,10 +143,12 @@ ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast) {
     const bool co = fast && !sg && v.coarse;  // the acquisition's coarse pre-screen instance
     const bool fa = fast && kp > 0;
     const int hw = co ? H32C_WAVES : H16_WAVES;
-    ScoreFns f{hbx_pick_h32(nsc_of(dc_pad), kp, sg, fa, co), r, 32 * hw * (co ? H32C_CT : 1), 64 * hw,
+    ScoreFns f{hbx_pick_h32(nsc_of(dc_pad), kp, sg, fa), r, 32 * hw * (co ? H32C_CT : 1), 64 * hw,
                hbx_pick_h32_pair(nsc_of(dc_pad), kp, sg, fa, co), rp, true};
     if (co && H32C_CT > 1) f.pair1 = hbx_pick_h32_pair1(nsc_of(dc_pad), kp);
     if (co) f.list = hbx_pick_h32_list(nsc_of(dc_pad), kp);
+    if (co) f.main_co = hbx_pick_h32_co(nsc_of(dc_pad), kp);
+    if (co && !f.main_co) return NO_SCORE_FNS;
     return f;
   }
   if (v.hmode) {
@@ -161,7 +163,11 @@ ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast) {
 int launch_score(ScoreFns f, const double* cand, int64_t Nc, int32_t D, const void* params, const float* table,
                  KdeEst* est, hipStream_t s) {
   const unsigned gm = (unsigned)((Nc + f.cands_per_block - 1) / f.cands_per_block);
-  hipLaunchKernelGGL(f.main, dim3(gm), dim3(f.threads), 0, s, cand, Nc, D, (const KdeParams*)params, table, est);
+  if (f.main_co)
+    hipLaunchKernelGGL(f.main_co, dim3(gm), dim3(f.threads), 0, s, cand, Nc, D, (const KdeParams*)params, table, est,
+                       hbx_row_stage());
+  else
+    hipLaunchKernelGGL(f.main, dim3(gm), dim3(f.threads), 0, s, cand, Nc, D, (const KdeParams*)params, table, est);
   HBX_LAUNCH_CHECK();
   hipLaunchKernelGGL(f.rescue, dim3((unsigned)((Nc + 255) / 256)), dim3(256), 0, s, cand, Nc, D,
                      (const KdeParams*)params, table, est);
@@ -174,8 +180,8 @@ int launch_score2(const ScoreSide& good, const ScoreSide& bad, const ScoreReques
   *out = ScoreResult{};
   const ScoreFns& f = good.f;
   const hipStream_t s = rq.s;
-  const bool pair = f.pair && f.main == bad.f.main && f.rescue_pair && f.rescue == bad.f.rescue &&
-                    hbx_switch_on("HBX_SCORE_PAIR");
+  const bool pair = f.pair && f.main == bad.f.main && f.main_co == bad.f.main_co && f.rescue_pair &&
+                    f.rescue == bad.f.rescue && hbx_switch_on("HBX_SCORE_PAIR");
   if (!pair) {
     if (rq.ev) HBX_HIP(hipEventRecord(rq.ev[0], s));
     int rc = launch_score(f, rq.cand, rq.Nc, rq.D, good.params, good.table, good.est, s);
@@ -194,6 +200,7 @@ int launch_score2(const ScoreSide& good, const ScoreSide& bad, const ScoreReques
                 good.est, sh.tiles * sh.nsplit, rq.rescue_cnt, {}};
   a.tiles = sh.tiles;
   a.nsplit0 = a.nsplit1 = sh.nsplit;
+  a.row_stage = hbx_row_stage();
   out->nsplit[0] = out->nsplit[1] = sh.nsplit;
   const unsigned grid = sh.tiles * (unsigned)(2 * sh.nsplit);
   const bool pinit = f.split_ok && HBX_PAIR_INIT;

@@ -98,7 +98,7 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
                                                     const unsigned blk, int32_t* __restrict__ rescue_cnt = nullptr,
                                                     const int split = 0, const int nsplit = 1,
                                                     const int32_t* __restrict__ idx = nullptr,
-                                                    const bool scatter = false) {
+                                                    const bool scatter = false, const bool row_stage = true) {
   // CO: the coarse pre-screen (hbx_kde_impl.h coarse layout): one product per continuous dim, no lo parts
   constexpr int ND = CO ? h32c_nd(NSC) : h32_nd(NSC);  // dense 16-wide K-steps (C_j / c_i pieces + per dim)
   constexpr int KS = KP;                     // sparse 32-wide K-steps (one-hot positions), hi parts
@@ -119,7 +119,18 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
   constexpr int GP = CHF * 4 / 1024;  // 1-KB LDS-DMA pieces per chunk: GL per wave, one more for NX waves
   constexpr int GL = GP / HW, NX = GP % HW;
   static_assert(GP * 1024 == CHF * 4, "chunk must be a multiple of 1 KB");
-  __shared__ __align__(16) float lds[NBUF * CHF + AUXF];  // the kernel's only LDS object
+  struct ContPrm { double scale, center; float xmax; int32_t col; };
+  struct OhPrm { double val; int32_t col, pad; };
+  constexpr int PRM_BYTES = 8 * NSC * (int)sizeof(ContPrm) + 32 * (KP > 0 ? KP : 1) * (int)sizeof(OhPrm);
+  // the coarse instances' prologue stages candidate rows one column tile at a time (below): room for 32 rows per
+  // wave and the parameters, where the ring is smaller.  RDS: the widest row stride staged -- the instance's own
+  // dims (8 NSC continuous, at most 16 categorical per one-hot step), H32C_ROW_DS at most; an instance whose rows
+  // all lie below H32C_ROW_DMIN keeps the ring's size and no staging code (<1, 0>: D = 8)
+  constexpr int RDS = !CO ? 0 : ((8 * NSC + 16 * KP) | 1) < H32C_ROW_DS ? ((8 * NSC + 16 * KP) | 1) : H32C_ROW_DS;
+  constexpr int RSF = RDS >= (H32C_ROW_DMIN | 1) ? (HW * 32 * RDS * 8 + PRM_BYTES) / 4 : 0;
+  constexpr int LDSF = NBUF * CHF + AUXF > RSF ? NBUF * CHF + AUXF : RSF;
+  static_assert(2 * LDSF * 4 <= 160 * 1024, "two blocks per CU");
+  __shared__ __align__(16) float lds[LDSF];  // the kernel's only LDS object
   float* aux = lds + NBUF * CHF;
   if constexpr (CO) table += P->coarse_off;  // the coarse layout follows the precise table
   // observation split: this block's chunk range, its partial estimates at out + split Nc
@@ -142,15 +153,18 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
   const bool xpiece = wave < NX;
   const int dc = P->dc;
 
-  // per-dim parameters and the block's candidate rows staged in the (not yet used) ring
-  struct ContPrm { double scale, center; float xmax; int32_t col; };
-  struct OhPrm { double val; int32_t col, pad; };
-  constexpr int PRM_BYTES = 8 * NSC * (int)sizeof(ContPrm) + 32 * (KP > 0 ? KP : 1) * (int)sizeof(OhPrm);
+  // per-dim parameters and the block's candidate rows staged in the (not yet used) ring: all of them at once
+  // where they fit (rows_fit); the coarse instances otherwise one column tile at a time, each wave's 32 rows in
+  // its own slice (tile_fit: H32C_ROW_DMIN <= D, stride <= RDS), copied coalesced instead of every lane
+  // walking its own row in global memory; wider and narrower rows, and a coarse launch with HBX_ROW_STAGE=0
+  // (row_stage false), are read in place
   static_assert(PRM_BYTES <= NBUF * CHF * 4, "parameters must fit in the ring");
   const int DS = D | 1;  // odd row stride in doubles: conflict-free
   const int64_t rows_bytes = (int64_t)HW * 32 * CT * DS * 8;
-  const bool rows_fit = rows_bytes + PRM_BYTES <= (int64_t)NBUF * CHF * 4;
-  ContPrm* cprm = (ContPrm*)((char*)lds + (rows_fit ? rows_bytes : 0));
+  const bool stage_on = !CO || row_stage;
+  const bool rows_fit = stage_on && rows_bytes + PRM_BYTES <= (int64_t)NBUF * CHF * 4;
+  const bool tile_fit = RSF > 0 && stage_on && !rows_fit && D >= H32C_ROW_DMIN && DS <= RDS;
+  ContPrm* cprm = (ContPrm*)((char*)lds + (rows_fit ? rows_bytes : tile_fit ? (int64_t)HW * 32 * DS * 8 : 0));
   OhPrm* oprm = (OhPrm*)(cprm + 8 * NSC);
   const int tid = threadIdx.x;
   if (tid < 8 * NSC) {
@@ -161,12 +175,27 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
   if (tid < 32 * KP) oprm[tid] = OhPrm{P->oh_val[tid], P->oh_col[tid], 0};  // padding: NaN, never equal
   const bool staged = rows_fit && cbase < Nc;
   const int64_t nv = (Nc - cbase) < 32 * CT ? (Nc - cbase) : 32 * CT;  // valid rows of this wave
-  double* xs = (double*)lds + (int64_t)wave * 32 * CT * DS;
+  double* xs = (double*)lds + (int64_t)wave * 32 * (tile_fit ? 1 : CT) * DS;
   if constexpr (LIST) {
     if (staged) stage_rows_list(cand, idx + cbase, nv, D, DS, xs, lane);
   } else {
     if (staged) stage_rows(cand + cbase * (int64_t)D, nv, D, DS, xs, lane);
   }
+  // coarse, one column tile at a time: the wave's rows of column tile t into its slice.  A wave reads only what
+  // it wrote, and LDS runs a wave's instructions in order: no barrier between a tile's copy, its build and the
+  // next tile's copy
+  const bool tstaged = tile_fit && cbase < Nc;
+  auto stage_tile = [&](const int t) -> int {  // the tile's valid rows
+    const int nt = (int)nv - 32 * t < 32 ? (int)nv - 32 * t : 32;
+    if (nt > 0) {
+      if constexpr (LIST) stage_rows_list(cand, idx + cbase + 32 * t, nt, D, DS, xs, lane);
+      else stage_rows(cand + (cbase + 32 * t) * (int64_t)D, nt, D, DS, xs, lane);
+    }
+    return nt;
+  };
+  int nt0 = 0;
+  if constexpr (RSF > 0)
+    if (tstaged) nt0 = stage_tile(0);
   __syncthreads();
 
   // B operands of candidate column c.  Dense step s, half j of the lane: slot k = 16s + 8h + j -- slots
@@ -239,8 +268,14 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
   };
 #pragma unroll
   for (int t = 0; t < CT; ++t) {
-    const int loc = 32 * t + c < nv ? 32 * t + c : (int)nv - 1;
-    if (staged) {
+    int loc = 32 * t + c < nv ? 32 * t + c : (int)nv - 1;
+    if (staged || (RSF > 0 && tstaged)) {
+      if constexpr (RSF > 0) {
+        if (tstaged) {  // (an empty tile builds from the previous tile's rows: its columns are never written out)
+          const int nt = t == 0 ? nt0 : stage_tile(t);
+          loc = c < nt ? c : nt > 0 ? nt - 1 : 0;
+        }
+      }
       build(xs + loc * DS, t);
     } else {
       int64_t ii = cbase + 32 * t + c;
@@ -546,11 +581,20 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
 
 // unsigned sums: 128 VGPRs, 4 waves per SIMD (two blocks per CU); the coarse instance: H32C_WAVES-wave
 // blocks at >= H32C_EU waves per SIMD
-template <int NSC, int KP, bool FAST, bool CO>
-__global__ __launch_bounds__(64 * (CO ? H32C_WAVES : H16_WAVES)) __attribute__((amdgpu_waves_per_eu(CO ? H32C_EU : 4))) void kde_logpdf_h32_kernel(
+template <int NSC, int KP, bool FAST>
+__global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(4))) void kde_logpdf_h32_kernel(
     const double* __restrict__ cand, int64_t Nc, int32_t D, const KdeParams* __restrict__ P,
     const float* __restrict__ table, KdeEst* __restrict__ out) {
-  kde_logpdf_h32_body<NSC, KP, false, FAST, CO, CO ? H32C_CT : 1>(cand, Nc, D, P, table, out, blockIdx.x);
+  kde_logpdf_h32_body<NSC, KP, false, FAST>(cand, Nc, D, P, table, out, blockIdx.x);
+}
+
+// ... and the coarse instance over one KDE (logpdf_co_fn: row_stage as in KdePairArgs)
+template <int NSC, int KP>
+__global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu(H32C_EU))) void kde_logpdf_h32_co_kernel(
+    const double* __restrict__ cand, int64_t Nc, int32_t D, const KdeParams* __restrict__ P,
+    const float* __restrict__ table, KdeEst* __restrict__ out, int32_t row_stage) {
+  kde_logpdf_h32_body<NSC, KP, false, false, true, H32C_CT>(cand, Nc, D, P, table, out, blockIdx.x, nullptr, 0, 1, nullptr,
+                                                             false, row_stage != 0);
 }
 
 // both KDEs of an acquisition in one grid (see kde_logpdf_h_pair_kernel)
@@ -567,7 +611,8 @@ __global__ __launch_bounds__(64 * (CO ? H32C_WAVES : H16_WAVES)) __attribute__((
   const unsigned tile = ns > 1 ? loc % a.tiles : loc;  // blocks of one chunk range are consecutive
   const int split = ns > 1 ? (int)(loc / a.tiles) : 0;
   kde_logpdf_h32_body<NSC, KP, false, FAST, CO, CO ? H32C_CT : 1>(cand, Nc, D, second ? a.P1 : a.P0, second ? a.table1 : a.table0,
-                                                second ? a.out1 : a.out0, tile, a.rescue, split, ns);
+                                                second ? a.out1 : a.out0, tile, a.rescue, split, ns, nullptr, false,
+                                                a.row_stage != 0);
 }
 
 // the coarse pair kernel with ONE candidate column tile per wave (32 candidates, half a block's): for launches
@@ -586,7 +631,8 @@ __global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu
   const unsigned tile = ns > 1 ? loc % a.tiles : loc;
   const int split = ns > 1 ? (int)(loc / a.tiles) : 0;
   kde_logpdf_h32_body<NSC, KP, false, false, true, 1>(cand, Nc, D, second ? a.P1 : a.P0, second ? a.table1 : a.table0,
-                                                       second ? a.out1 : a.out0, tile, a.rescue, split, ns);
+                                                       second ? a.out1 : a.out0, tile, a.rescue, split, ns, nullptr, false,
+                                                       a.row_stage != 0);
 }
 
 // the coarse instance over an index list with a device-side count (KdeListArgs, hbx_kde_impl.h): the staged
@@ -605,7 +651,7 @@ __global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu
   if ((int64_t)tile * CPB >= cnt) return;
   kde_logpdf_h32_body<NSC, KP, false, false, true, H32C_CT, true>(
       cand, cnt, D, a.P, a.table, splits ? a.part + (int64_t)split * a.cap : a.out, tile, a.rescue, split,
-      splits ? a.nsplit : 1, a.idx, !splits);
+      splits ? a.nsplit : 1, a.idx, !splits, a.row_stage != 0);
 }
 
 // signed sums (the parity product and its accumulators): one 8-wave block per CU, so 2 waves per SIMD
@@ -633,21 +679,23 @@ __global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(
                                            second ? a.out1 : a.out0, tile, a.rescue, split, ns);
 }
 
-// instances: h32_ok (hbx_kde_impl.h); FAST where there is a one-hot part; CO (coarse) for unsigned sums
+// instances: h32_ok (hbx_kde_impl.h); FAST where there is a one-hot part; CO (coarse) for unsigned sums (pair
+// launches; one KDE's coarse instance has its own type: hbx_pick_h32_co)
 template <int NSC, int KP, bool SG, bool PAIR, bool FAST, bool CO>
 static constexpr auto h32_inst() {
   if constexpr (PAIR) {
     if constexpr (SG) return (logpdf_pair_fn)kde_logpdf_h32s_pair_kernel<NSC, KP, FAST>;
     else return (logpdf_pair_fn)kde_logpdf_h32_pair_kernel<NSC, KP, FAST, CO>;
   } else {
+    static_assert(!CO, "hbx_pick_h32_co");
     if constexpr (SG) return (logpdf_fn)kde_logpdf_h32s_kernel<NSC, KP, FAST>;
-    else return (logpdf_fn)kde_logpdf_h32_kernel<NSC, KP, FAST, CO>;
+    else return (logpdf_fn)kde_logpdf_h32_kernel<NSC, KP, FAST>;
   }
 }
 
 template <int NSC, int KP, bool SG, bool PAIR>
 static auto pick32_fast(bool fast, bool coarse) {
-  if constexpr (!SG)
+  if constexpr (!SG && PAIR)
     if (coarse) return h32_inst<NSC, KP, SG, PAIR, false, true>();
   if constexpr (KP > 0)
     if (fast) return h32_inst<NSC, KP, SG, PAIR, true, false>();
@@ -675,8 +723,8 @@ static auto pick32(int nsc, int kp, bool fast, bool coarse) {
   return decltype(pick32_kp<1, SG, PAIR>(0, false, false))(nullptr);
 }
 
-logpdf_fn hbx_pick_h32(int nsc, int kp, bool sg, bool fast, bool coarse) {
-  return sg ? pick32<true, false>(nsc, kp, fast, false) : pick32<false, false>(nsc, kp, fast, coarse);
+logpdf_fn hbx_pick_h32(int nsc, int kp, bool sg, bool fast) {
+  return sg ? pick32<true, false>(nsc, kp, fast, false) : pick32<false, false>(nsc, kp, fast, false);
 }
 
 logpdf_pair_fn hbx_pick_h32_pair(int nsc, int kp, bool sg, bool fast, bool coarse) {
@@ -709,6 +757,26 @@ logpdf_list_fn hbx_pick_h32_list(int nsc, int kp) {
     case 2: return pick32_list_kp<2>(kp);
     case 3: return pick32_list_kp<3>(kp);
     case 4: return pick32_list_kp<4>(kp);
+  }
+  return nullptr;
+}
+
+template <int NSC>
+static logpdf_co_fn pick32_co_kp(int kp) {
+  switch (kp) {
+    case 0: if constexpr (h32_ok(NSC, 0, false)) return kde_logpdf_h32_co_kernel<NSC, 0>; break;
+    case 1: if constexpr (h32_ok(NSC, 1, false)) return kde_logpdf_h32_co_kernel<NSC, 1>; break;
+    case 2: if constexpr (h32_ok(NSC, 2, false)) return kde_logpdf_h32_co_kernel<NSC, 2>; break;
+  }
+  return nullptr;
+}
+
+logpdf_co_fn hbx_pick_h32_co(int nsc, int kp) {
+  switch (nsc) {
+    case 1: return pick32_co_kp<1>(kp);
+    case 2: return pick32_co_kp<2>(kp);
+    case 3: return pick32_co_kp<3>(kp);
+    case 4: return pick32_co_kp<4>(kp);
   }
   return nullptr;
 }

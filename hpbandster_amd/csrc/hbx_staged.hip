@@ -253,6 +253,7 @@ int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* can
   KdePairArgs ka{p.Pg(), p.Pg(), p.table_good, p.table_good, a.el, a.el, grid, a.rescue, a.init()};
   ka.tiles = sh.tiles;
   ka.nsplit0 = ka.nsplit1 = ns;
+  ka.row_stage = hbx_row_stage();
   if (ev)  // stamped by the dispatch at the kernel's start
     hipExtLaunchKernelGGL(sh.kernel, dim3(grid), dim3(f.threads), 0, s, ev[0], nullptr, 0, cand, Nc, p.D, ka);
   else
@@ -271,7 +272,7 @@ int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* can
   const int ls = list_splits(p.nmax);
   const unsigned tcap = (unsigned)(cap / fb.cands_per_block);
   KdeListArgs la{p.Pb(), p.table_bad, a.eg, a.lpart, a.seeds, (const int32_t*)a.stage + HBX_ST_NSEED, a.rescue, cap,
-                 cap, ls, tcap};
+                 cap, ls, tcap, ka.row_stage};
   hipLaunchKernelGGL(fb.list, dim3(tcap * (unsigned)ls), dim3(fb.threads), 0, s, cand, p.D, la);
   HBX_LAUNCH_CHECK();
   const dim3 gmerge((unsigned)((cap + 255) / 256));
