@@ -1,5 +1,6 @@
 // hbx_groups.hip -- grouped acquisition: one exact pick per KDE pair for B independent brackets in two
-// launches (hbx_kde_acquire_groups; bohb.py:124-169 per bracket, after the batched refit bohb.py:220-246).
+// launches (hbx_kde_acquire_groups; bohb.py:124-169 per bracket, after the batched refit bohb.py:220-246), and one
+// per get_config request when a bracket issues S of them (hbx_kde_acquire_groups_batch, below).
 //
 // Inputs are hbx_kde_fit's, as they lie on the device: group b's rows are X[seg_off[b] + order[seg_off[b] + j]],
 // good KDE j < n_good[b], bad KDE j in [n - n_bad[b], n); its bandwidths and level counts are bw_*[b][D],
@@ -45,7 +46,7 @@
 //     => err = 1.05 E_t + (2 n + 40) u (32 for the merge and the flushes, 8 for log2 of the sum), relative, per sum,
 //       against S+ + S-: exactly what est_interval() expects; its own slack covers the final rounding to float.
 //
-// Launch 2, groups_select_kernel: one block per group.  U = min shi over the certified candidates; the shortlist
+// Launch 2, groups_select_kernel: one block per group (per request, below).  U = min shi over the certified candidates; the shortlist
 //   is {slo <= U} plus the uncertified ones, and of the candidates whose score is certainly exactly 1 (both pdfs
 //   certainly below the 1e-8 clamps) only the first index.  Every shortlisted candidate gets both exact fp64 pdfs
 //   in the reference's arithmetic (hbx_exact_impl.h: the single path's functions, fed a per-group parameter view),
@@ -54,6 +55,35 @@
 //   categorical dim has a single level (c == 1, h == 0), the dims exceed the bucket, or a pdf bound leaves fp64's
 //   exp range.  Correctness never rests on the screen: it only decides what is re-scored.
 //   The exact scores are kept in the candidates' GScreen slots for the near-tie count (no second buffer).
+//
+// S requests per group (hbx_kde_acquire_groups_batch; bohb.py:124-169 once per get_config call of a stage,
+// HB_iteration.py:136-138): cand is [B][S][C][D], request q = b S + s has its own pool, its own record q and its own
+// select block (grid B S: screen slots from q C, candidates from q C D; U, the first certain 1, the shortlist, the
+// argmin and the near count never leave the request).  The screen is per candidate, so it sees group b's S C
+// candidates as one flattened pool P of ceil(S C / 64) tiles (a tile may straddle two requests).  Which screen runs
+// is grp_tile_screen()'s rule, in one place: S == 1 is hbx_kde_acquire_groups itself, launch 1 above; from
+// GRP_TILES_MIN tiles per group on, the tile screen below; under that, launch 1 over the flattened pool.
+//
+// The tile screen, groups_tiles_kernel<DCP, DUP, NW, DT>: grid = B x slabs, a block is one group and a slab of NW
+//   of its tiles (slabs = ceil(tiles / NW)); wave w owns tile tile0 + w, lane = candidate.  Every wave walks every
+//   chunk of a KDE for its own candidates: no partial sums, no merge.  The group's status, slots, centres, scales,
+//   lb, deltas and norms are derived once per block and serve the slab's NW tiles.  (Slabs of 2, 4 and 8 tiles per
+//   wave -- the rows walked again per tile, the constants shared further -- measured within 0.8 % of one tile per
+//   wave either way; the loop over them is not kept.)  The rows of the good, then the bad KDE
+//   form one stream of chunks of 32 NW rows;
+//   chunk g lives in LDS buffer g & 1, each wave stages 32 of its rows exactly as in launch 1 (gather through
+//   `order`, centred, scaled, fp32).  One barrier per chunk: past barrier g, chunk g is complete and chunk g - 1 is
+//   read by everyone, so each wave first stages its rows of chunk g + 1 into the other buffer and then runs its
+//   candidates against chunk g -- a wave's gather is in flight while the other waves of the SIMD do pairs.  The two
+//   buffers together are launch 1's LDS rows.  s_bmax is kept per KDE: every row of a KDE is staged before the last
+//   barrier of its walk and the bound is formed after that barrier (the bad KDE's first chunk, staged meanwhile,
+//   goes to its own maxima) -- so a candidate's bound does not depend on timing.
+//   Error bound: E_t is launch 1's, term for term (same a, b, dd, fma chain, same T with B_c from s_bmax).  The sum:
+//   one lane adds the n terms of a KDE in row order into one running (m, S+, S-); rescaling is exact, each term
+//   carries 0.372 u + 2 u e, each addition u, so the sum is within (2 + 0.75 n) u + n u <= (2 n + 40) u -- launch 1's
+//   allowance with its 32 u for the merge left unused.  err = 1.05 E_t + (2 n + 40) u as above.
+//   The screens' sums differ in the last bits (another order of additions), so shortlist / near / rel may differ
+//   between them; index, score and the pdfs come from the fp64 re-score and do not.
 //
 // The grouped sampler (hbx_kde_sample_groups) lives in hbx_sample.hip beside the draw functions it shares with
 // hbx_kde_sample, so the byte-equality of the draws holds by construction.
@@ -102,9 +132,11 @@ struct GrpArgs {
   const int32_t* nlev_good;
   const int32_t* nlev_bad;
   const double* cand;
-  int64_t B, C;
-  int32_t D, tiles;  // tiles = ceil(C / 64)
+  int64_t B, S, C;  // groups, requests per group (1: hbx_kde_acquire_groups), candidates per request
+  int64_t P;        // S * C: the group's flattened pool, what the screen sees
+  int32_t D, tiles;  // tiles = ceil(P / 64)
   int32_t dcp, dup;  // slots of the screen instance launched
+  int32_t slabs;     // tile screen: blocks per group, one tile per wave
   GScreen* scr;
   AcqResult* res;
 };
@@ -317,8 +349,8 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
   const int64_t b = (int64_t)blockIdx.x / A.tiles;
   const int tile = (int)((int64_t)blockIdx.x - b * A.tiles);
   const int64_t i = (int64_t)tile * 64 + lane;
-  const bool valid = i < A.C;
-  GScreen* out = A.scr + b * A.C + i;
+  const bool valid = i < A.P;  // (the group's flattened pool: S requests of C candidates)
+  GScreen* out = A.scr + b * A.P + i;
   if (wave == 0) {
     int dc, du;
     const int st = grp_status(A, b, &dc, &du);
@@ -428,7 +460,7 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
     s_tfix[kd] = (fabsf((float)lb) + sad) * 1.0001f;  // |lb| + sum |delta|
   }
   __syncthreads();
-  const double* x = A.cand + (b * A.C + (valid ? i : (int64_t)tile * 64)) * D;
+  const double* x = A.cand + (b * A.P + (valid ? i : (int64_t)tile * 64)) * D;
   bool certified = true;
   KdeEst est_l = kde_est_neutral(), est_g = kde_est_neutral();
 #pragma unroll 1
@@ -575,6 +607,301 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
   *out = g;
 }
 
+// The tile screen (header: "The tile screen"): the block is a slab of NW tiles of one group, wave w owns tile
+// tile0 + w and walks every chunk of both KDEs itself; the chunks are staged once for the block, 32 NW rows at a
+// time in two buffers.  The per-group constants, the staging of a wave's rows, the pair
+// loops, the bound and the GScreen are groups_screen_kernel's, statement for statement; they are repeated here and
+// not shared, because groups_screen_kernel<32, 32, 4, 40> sits at 255 VGPRs: as one kernel with a compile-time
+// switch and the common steps as lambdas it came out at 256 VGPRs + 4 AGPRs, one wave per SIMD instead of two (and
+// the 8-slot instance at 174 instead of 165, two waves instead of three).
+template <int DCP, int DUP, int NW, int DT>
+__global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kernel(GrpArgs A) {
+  constexpr int NT = 64 * NW;
+  __shared__ __align__(16) float sobs[NW * 64 * (DT + 4)];
+  __shared__ double s_scale[2][DCP], s_mu[DCP], s_lnh[2][DCP], s_lb[2][DUP];
+  __shared__ float s_delta[2][DUP], s_negf[2][DUP];
+  __shared__ int32_t s_cdim[DCP], s_udim[DUP];
+  __shared__ uint32_t s_bmax[2][DCP];
+  __shared__ int32_t s_doff[DCP + DUP];  // dim -> float offset of its slot in a staged row
+  __shared__ double s_dsc[2][DCP + DUP], s_dmu[DCP + DUP];  // dim -> scale (categorical: 1) and centre (0)
+  __shared__ int32_t s_i[4];
+  __shared__ double s_norm[2];
+  __shared__ float s_lbs[2], s_tfix[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int D = A.D;
+  const int64_t b = (int64_t)blockIdx.x / A.slabs;
+  const int tile0 = (int)((int64_t)blockIdx.x - b * A.slabs) * NW;  // the slab's first tile
+  if (wave == 0) {
+    int dc, du;
+    const int st = grp_status(A, b, &dc, &du);
+    if (lane == 0) {
+      s_i[0] = st;
+      s_i[1] = dc;
+      s_i[2] = du;
+    }
+    if (!(st & (GRP_NO_MODEL | GRP_UNSUPPORTED | GRP_EXACT_ONLY))) {  // (then dc <= DCP, du <= DUP): slots in dim order
+      int kc = 0, ku = 0;
+      for (int d0 = 0; d0 < D; d0 += 64) {
+        const int d = d0 + lane;
+        const bool cont = d < D && A.vartype[d] == 0, cat = d < D && !cont;
+        const uint64_t mc = __ballot(cont), mu = __ballot(cat), below = (1ull << lane) - 1ull;
+        if (cont) s_cdim[kc + __popcll(mc & below)] = d;
+        if (cat) s_udim[ku + __popcll(mu & below)] = d;
+        kc += __popcll(mc);
+        ku += __popcll(mu);
+      }
+    }
+  }
+  __syncthreads();
+  const int st = s_i[0], dc = s_i[1], du = s_i[2];
+  if (st & (GRP_NO_MODEL | GRP_UNSUPPORTED | GRP_EXACT_ONLY)) {  // no screen: the select kernel re-scores (or skips)
+    GScreen g;
+    g.slo = g.shi = NAN;
+    g.rel = (float)((grp_exact_rel(D, st & GRP_NEG_G, nullptr) + grp_exact_rel(D, st & GRP_NEG_B, nullptr) + 0x1p-51) *
+                    1.000001);
+    g.fl = GS_FORCE;
+    const int64_t iw = (int64_t)(tile0 + wave) * 64 + lane;
+    if (iw < A.P) A.scr[b * A.P + iw] = g;
+    return;
+  }
+  const int64_t s0 = A.seg_off[b], n = A.seg_off[b + 1] - s0;
+  const int64_t ng = A.n_good[b], nb = A.n_bad[b];
+  const double* Xs = A.X + s0 * D;
+  const int64_t* ord = A.order + s0;
+  // the row layout: continuous slots from 0, categorical slots from 4 dcq.  Branch-free instances (grp_pairs_fast)
+  // serve dc <= 32 in 2 / 4 / 6 / 8 pieces with du <= 8 in 0 / 2 pieces; the rest takes grp_pairs' exact piece counts
+  const int qcs = dc <= 8 ? 2 : dc <= 16 ? 4 : dc <= 24 ? 6 : 8;
+  const bool fast = dc <= 32 && du <= 8 && 4 * qcs <= DCP;
+  const int dcq = fast ? qcs : (dc + 3) >> 2;
+  const int dc4 = 4 * dcq, du4 = fast ? (du ? 8 : 0) : (du + 3) & ~3;
+  const int rs = dc4 + du4 + 4;  // <= DT + 4
+  const int rpp = D <= 64 ? 64 / D : 1;  // rows per staging pass
+  for (int e = tid; e < NT * rs; e += NT) sobs[e] = 0.f;  // (the padding slots stay 0)
+  for (int k = tid; k < 2 * DCP; k += NT) s_bmax[k / DCP][k % DCP] = 0u;
+  // per-group constants of both KDEs
+  for (int k = tid; k < DCP; k += NT) {
+    if (k < dc) {
+      const int d = s_cdim[k];
+      const int nm = (int)(ng < 64 ? ng : 64);
+      double sum = 0.0;
+#pragma unroll 16
+      for (int j = 0; j < nm; ++j) sum += Xs[ord[j] * D + d];
+      double mu = sum / (double)nm;
+      if (!(mu - mu == 0.0)) mu = 0.0;
+      s_mu[k] = mu;
+      s_dmu[d] = mu;
+      s_doff[d] = k;
+#pragma unroll
+      for (int kd = 0; kd < 2; ++kd) {
+        const double h = (kd ? A.bw_bad : A.bw_good)[b * D + d];
+        s_scale[kd][k] = sqrt(M_LOG2E / 2.0) / h;
+        s_dsc[kd][d] = s_scale[kd][k];
+        s_lnh[kd][k] = log(h);
+      }
+    } else {
+      s_mu[k] = 0.0;
+      s_scale[0][k] = s_scale[1][k] = 0.0;
+    }
+  }
+  for (int u = tid; u < DUP; u += NT) {
+#pragma unroll
+    for (int kd = 0; kd < 2; ++kd) {
+      float dl = 0.f, ngf = 0.f;
+      double lb = 0.0;
+      if (u < du) {
+        const int d = s_udim[u];
+        s_doff[d] = dc4 + u;
+        s_dsc[kd][d] = 1.0;
+        s_dmu[d] = 0.0;
+        const double h = (kd ? A.bw_bad : A.bw_good)[b * D + d];
+        const int c = (kd ? A.nlev_bad : A.nlev_good)[b * D + d];
+        const double a = 1.0 - h;
+        lb = log2(h / (double)(c - 1));
+        dl = (a == 0.0) ? -1e30f : (float)(log2(fabs(a)) - lb);
+        ngf = a < 0.0 ? 1.f : 0.f;
+      }
+      s_delta[kd][u] = dl;
+      s_negf[kd][u] = ngf;
+      s_lb[kd][u] = lb;
+    }
+  }
+  __syncthreads();
+  if (tid < 2) {  // the sums in slot order (deterministic)
+    const int kd = tid;
+    double sl = 0.0, lb = 0.0;
+    float sad = 0.f;
+    for (int k = 0; k < dc; ++k) sl += s_lnh[kd][k];
+    for (int u = 0; u < du; ++u) {
+      lb += s_lb[kd][u];
+      if (s_delta[kd][u] > -1e29f) sad += fabsf(s_delta[kd][u]);
+    }
+    s_norm[kd] = -log((double)(kd ? nb : ng)) - sl - 0.5 * (double)dc * log(2.0 * M_PI);
+    s_lbs[kd] = (float)lb;
+    s_tfix[kd] = (fabsf((float)lb) + sad) * 1.0001f;  // |lb| + sum |delta|
+  }
+  __syncthreads();
+  // this lane's candidate x against KDE kd: its scaled coordinates, its codes and the KDE's deltas in registers
+  auto load_cand = [&](int kd, const double* x, float(&xc)[DCP], float(&xu)[DUP], float(&dl)[DUP], float(&nf)[DUP],
+                       bool& certified) {
+#pragma unroll
+    for (int k = 0; k < DCP; ++k) {
+      xc[k] = 0.f;
+      if (k < dc) {
+        const double xv = x[s_cdim[k]];
+        certified = certified && (xv - xv == 0.0);
+        xc[k] = (float)(s_scale[kd][k] * (xv - s_mu[k]));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < DUP; ++u) {
+      xu[u] = 0.f;
+      if (u < du) {
+        const double xv = x[s_udim[u]];
+        certified = certified && (xv - xv == 0.0);
+        xu[u] = cand_code(xv);
+      }
+      dl[u] = grp_uniform(s_delta[kd][u]);
+      nf[u] = s_negf[kd][u];  // (vector registers: 2 DUP uniform values exceed the scalar file)
+    }
+  };
+  // one wave stages rows[j0 .. j0 + jmax) of KDE kd (jmax <= 64) into wrows.  The candidate's registers are live
+  // here (the next chunk is staged before this one is read), so the 32-slot instance keeps 8 loads in flight, not 16
+  constexpr int SL = DCP >= 32 ? 8 : 16;
+  auto stage =[&](int kd, const int64_t* rows, int64_t j0, int jmax, float* wrows) {
+    // lane = (row in pass, dim): a row's D doubles are read by consecutive lanes (coalesced), SL passes of
+    // loads in flight; dims past 64 take further rounds (db).  The chunk's row positions come in one coalesced
+    // load and reach the lanes by a lane exchange (no dependent global load per pass).
+    const int myrow = (int)rows[j0 + (lane < jmax ? lane : 0)];  // (positions local to the segment: < 2^31)
+    for (int db = 0; db < D; db += 64) {
+      const int lr = D <= 64 ? lane / D : 0;
+      const int ld = db + (D <= 64 ? lane - lr * D : lane);
+      const bool act = lr < rpp && ld < D;
+      const int off = act ? s_doff[ld] : 0;
+      const double sc = act ? s_dsc[kd][ld] : 0.0, mu = act ? s_dmu[ld] : 0.0;
+      uint32_t bm = 0u;  // |b| maximum of this lane's dim (non-negative floats order as their bits; NaN above all)
+      for (int p0 = 0; p0 < jmax; p0 += SL * rpp) {
+        double t[SL];
+#pragma unroll
+        for (int q = 0; q < SL; ++q) {
+          const int r = p0 + q * rpp + lr;
+          const int ri = __shfl(myrow, r < jmax ? r : 0);  // (every lane takes part in the exchange)
+          t[q] = (act && r < jmax) ? Xs[(int64_t)ri * D + ld] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < SL; ++q) {
+          const int r = p0 + q * rpp + lr;
+          if (act && r < jmax) {
+            const float v = (float)(sc * (t[q] - mu));
+            wrows[r * rs + off] = v;
+            bm = max(bm, __float_as_uint(fabsf(v)));
+          }
+        }
+      }
+      if (act && off < dc) atomicMax(&s_bmax[kd][off], bm);
+    }
+  };
+  // this lane's candidate against jmax staged rows
+  auto pairs = [&](bool sg, const float* srows, int jmax, const float(&xc)[DCP], const float(&xu)[DUP],
+                   const float(&dl)[DUP], const float(&nf)[DUP], float lbs, float& m, float& sp, float& sn) {
+    const int cat = du == 0 ? 0 : sg ? 2 : 1;
+    if (fast && qcs == 2)
+      grp_pairs_qc<DCP, DUP, 2>(cat, srows, rs, jmax, xc, xu, dl, nf, lbs, m, sp, sn);
+    else if (fast && qcs == 4)
+      grp_pairs_qc<DCP, DUP, 4>(cat, srows, rs, jmax, xc, xu, dl, nf, lbs, m, sp, sn);
+    else if (fast && qcs == 6)
+      grp_pairs_qc<DCP, DUP, 6>(cat, srows, rs, jmax, xc, xu, dl, nf, lbs, m, sp, sn);
+    else if (fast)
+      grp_pairs_qc<DCP, DUP, 8>(cat, srows, rs, jmax, xc, xu, dl, nf, lbs, m, sp, sn);
+    else if (sg)
+      grp_pairs<DCP, DUP, true>(srows, rs, jmax, dc, du, dcq, xc, xu, dl, nf, lbs, m, sp, sn);
+    else
+      grp_pairs<DCP, DUP, false>(srows, rs, jmax, dc, du, dcq, xc, xu, dl, nf, lbs, m, sp, sn);
+  };
+  // the candidate's sums over KDE kd's nk rows (in units of 2^M) -> KdeEst with the header's bound
+  auto estimate = [&](int kd, int64_t nk, const float(&xc)[DCP], float M, float Sp, float Sn, bool bad,
+                      bool& certified) {
+    float T = s_tfix[kd];
+#pragma unroll
+    for (int k = 0; k < DCP; ++k)
+      if (k < dc) {
+        const float r = fabsf(xc[k]) + __uint_as_float(s_bmax[kd][k]);
+        T = fmaf(r, r, T);
+      }
+    const float u24 = 0x1p-24f;
+    const float Et = 1.02f * u24 * (float)(dc + du + 8) * T;
+    KdeEst e;
+    e.pad = 0.f;
+    e.err = 1.05f * Et + (2.f * (float)nk + 40.f) * u24;
+    if (!(Et < 0.5f) || bad || !(Sp - Sp == 0.f) || !(Sn - Sn == 0.f) || !(M - M == 0.f)) certified = false;
+    const double nrm = s_norm[kd];
+    e.lpos = Sp > 0.f ? (float)(((double)__log2f(Sp) + (double)M) * M_LN2 + nrm) : -INFINITY;
+    e.lneg = Sn > 0.f ? (float)(((double)__log2f(Sn) + (double)M) * M_LN2 + nrm) : -INFINITY;
+    return e;
+  };
+  auto emit = [&](GScreen* out, bool certified, const KdeEst& est_l, const KdeEst& est_g) {
+    GScreen g;
+    if (!certified) {
+      g.slo = g.shi = NAN;
+      g.rel = (float)((grp_exact_rel(D, st & GRP_NEG_G, nullptr) + grp_exact_rel(D, st & GRP_NEG_B, nullptr) + 0x1p-51) *
+                      1.000001);
+      g.fl = GS_FORCE;
+    } else {
+      const ScoreIv v = score_interval(est_l, est_g);
+      g.slo = v.slo;
+      g.shi = v.shi;
+      g.rel = (float)((grp_exact_rel(D, st & GRP_NEG_G, &est_l) + grp_exact_rel(D, st & GRP_NEG_B, &est_g) + 0x1p-51) *
+                      1.000001);
+      g.fl = (v.one ? GS_ONE : 0u) | (v.of ? GS_OF : 0u) | ((v.lnan || v.slo != v.slo || v.shi != v.shi) ? GS_FORCE : 0u);
+    }
+    *out = g;
+  };
+  // The rows of the good, then the bad KDE as one stream of chunks of CH = 32 NW rows: chunk g lies in buffer
+  // g & 1, every wave stages 32 of its rows.  One barrier per chunk: past it chunk g is staged and chunk g - 1 is
+  // read by every wave, so the waves stage chunk g + 1 into the other buffer and then read chunk g -- a wave's
+  // gather of the next chunk overlaps the other waves' pairs of this one.
+  constexpr int CW = 32, CH = CW * NW;
+  auto stage_chunk = [&](int kd, int64_t c, int buf) {
+    const int64_t nk = kd ? nb : ng, j0 = c * CH + (int64_t)wave * CW;
+    const int jmax = (int)(nk - j0 < CW ? (nk - j0 > 0 ? nk - j0 : 0) : CW);
+    if (jmax > 0) stage(kd, ord + (kd ? n - nb : 0), j0, jmax, sobs + ((size_t)buf * CH + (size_t)wave * CW) * rs);
+  };
+  __syncthreads();  // (s_bmax and the padding slots are zeroed)
+  stage_chunk(0, 0, 0);
+  int g = 0;
+  bool certified = true;
+  KdeEst est_l = kde_est_neutral();
+  const int tw = tile0 + wave;  // this wave's tile
+  const int64_t iw = (int64_t)tw * 64 + lane;
+  const bool vw = iw < A.P;
+  const bool live = tw < A.tiles;  // (wave-uniform; a wave without a tile still stages its rows)
+  const double* x = A.cand + (b * A.P + (vw ? iw : live ? (int64_t)tw * 64 : 0)) * D;
+#pragma unroll 1
+  for (int kd = 0; kd < 2; ++kd) {
+    const int64_t nk = kd ? nb : ng;
+    const bool sg = st & (kd ? GRP_NEG_B : GRP_NEG_G);
+    float xc[DCP], xu[DUP], dl[DUP], nf[DUP];
+    load_cand(kd, x, xc, xu, dl, nf, certified);
+    const float lbs = grp_uniform(s_lbs[kd]);
+    float m = -INFINITY, sp = 0.f, sn = 0.f;
+    const int64_t nch = (nk + CH - 1) / CH;
+    for (int64_t c = 0; c < nch; ++c, ++g) {  // uniform trip counts: the barriers are block-wide
+      __syncthreads();
+      if (c + 1 < nch)
+        stage_chunk(kd, c + 1, (g + 1) & 1);
+      else if (kd == 0)
+        stage_chunk(1, 0, (g + 1) & 1);
+      const int jmax = (int)(nk - c * CH < CH ? nk - c * CH : CH);
+      if (live) pairs(sg, sobs + (size_t)(g & 1) * CH * rs, jmax, xc, xu, dl, nf, lbs, m, sp, sn);
+    }
+    // (every row of KDE kd was staged before the walk's last barrier: s_bmax[kd] is complete)
+    const KdeEst e = estimate(kd, nk, xc, m, sp, sn, m != m, certified);
+    if (kd == 0)
+      est_l = e;
+    else if (vw)
+      emit(A.scr + b * A.P + iw, certified, est_l, e);
+  }
+}
+
 // the per-group parameter view the exact functions read (hbx_exact_impl.h)
 struct GrpView {
   int32_t n;
@@ -604,7 +931,7 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
   __shared__ uint32_t s_U;
   __shared__ int32_t s_st, s_of, s_first1, s_none, s_near;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t b = blockIdx.x;
+  const int64_t q = blockIdx.x, b = q / A.S;  // request q = b S + s of group b
   const int D = A.D;
   const int64_t C = A.C;
   if (wv == 0) {
@@ -622,7 +949,7 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
   __syncthreads();
   const int st = s_st;
   if (st & (GRP_NO_MODEL | GRP_UNSUPPORTED)) {
-    if (tid == 0) A.res[b] = grp_empty_record((st & GRP_NO_MODEL) ? HBX_ACQ_NO_MODEL : HBX_ACQ_UNSUPPORTED);
+    if (tid == 0) A.res[q] = grp_empty_record((st & GRP_NO_MODEL) ? HBX_ACQ_NO_MODEL : HBX_ACQ_UNSUPPORTED);
     return;
   }
   const int64_t s0 = A.seg_off[b], n = A.seg_off[b + 1] - s0;
@@ -641,8 +968,8 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
     v.prod_bw_c = p;
     vw[tid] = v;
   }
-  GScreen* scr = A.scr + b * C;
-  const double* cand = A.cand + b * C * D;
+  GScreen* scr = A.scr + q * C;
+  const double* cand = A.cand + q * C * D;
   // pass 1: U = min shi over the certified candidates, the overflow rule, the first certain score 1
   {
     uint32_t u = hbx_f2ord(INFINITY);
@@ -750,7 +1077,7 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
       r.pdf_l = bl;
       r.pdf_g = bg;
     }
-    A.res[b] = r;
+    A.res[q] = r;
   }
 }
 
@@ -761,41 +1088,84 @@ __global__ void groups_empty_kernel(AcqResult* res, int64_t B) {
 
 #define GRP_WS_HEAD 256
 
-extern "C" {
-
-int64_t hbx_kde_groups_workspace_bytes(int64_t B, int64_t C, int32_t D) {
-  if (B < 0 || C < 0 || D < 1 || D > HBX_MAX_D) return -1;
-  if (C > 0 && B > (int64_t)INT32_MAX / C) return -1;
-  return GRP_WS_HEAD + B * C * (int64_t)sizeof(GScreen);
+// B * S * C within int32 (what every grid and every screen slot index relies on)
+static bool grp_counts_ok(int64_t B, int64_t S, int64_t C) {
+  if (B < 0 || S < 0 || C < 0 || B > INT32_MAX || S > INT32_MAX) return false;
+  if (S > 0 && B > (int64_t)INT32_MAX / S) return false;
+  return !(C > 0 && B * S > (int64_t)INT32_MAX / C);
 }
 
-int hbx_kde_acquire_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
-                           const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
-                           const double* bw_good, const double* bw_bad, const int32_t* nlev_good,
-                           const int32_t* nlev_bad, const double* cand, int64_t C, void* results, void* workspace,
-                           int64_t ws_bytes, void* stream) {
-  if (D < 1 || D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "hbx_kde_acquire_groups: D=%d outside [1, %d]", D, HBX_MAX_D);
-  if (B < 0 || C < 0)
-    return hbx_fail(HBX_ERR_ARG, "hbx_kde_acquire_groups: B=%lld C=%lld", (long long)B, (long long)C);
-  if (B > INT32_MAX || (C > 0 && B > (int64_t)INT32_MAX / C))
-    return hbx_fail(HBX_ERR_ARG, "hbx_kde_acquire_groups: B * C = %lld * %lld exceeds int32", (long long)B, (long long)C);
-  if (B == 0) return HBX_OK;
-  if (!results) return hbx_fail(HBX_ERR_ARG, "hbx_kde_acquire_groups: null pointer (results)");
+// Which screen a call runs -- the one rule.  One request per group is hbx_kde_acquire_groups' own case: the
+// chunk-splitting screen, always.  Several requests flatten to tiles = ceil(S C / 64) tiles per group: from
+// GRP_TILES_MIN tiles on the tile screen runs, below that the chunk-splitting screen over the flattened pool.
+// Measured at config #5's shape: 2 tiles 10.7 ms against 9.1 ms for the chunk-splitting screen,
+// 3 tiles 12.1 against 13.3 (one of the four waves without a tile, and still ahead), 4 tiles 13.7 against 17.7.
+// HBX_GROUPS_SCREEN = 1 / 2 forces the chunk-splitting / the tile screen for S > 1 (tests, A/B); read on every call
+// like the other switches.
+#define GRP_TILES_MIN 3
+static bool grp_tile_screen(int64_t S, int64_t tiles) {
+  if (S == 1) return false;
+  const char* e = getenv("HBX_GROUPS_SCREEN");
+  const int v = e ? atoi(e) : 0;
+  if (v == 1 || v == 2) return v == 2;
+  return tiles >= GRP_TILES_MIN;
+}
+
+// One screen launch: the slot bucket from D alone (vartype is on the device), up to D <= 32 any mix of kinds fits
+template <bool TILES>
+static void grp_launch_screen(GrpArgs& A, hipStream_t s) {
+  const int nw = A.D <= 32 ? 4 : 2;  // waves of the bucket's instance
+  A.slabs = (A.tiles + nw - 1) / nw;  // the tile screen: one tile per wave
+  const dim3 grid((unsigned)(A.B * (TILES ? A.slabs : A.tiles)));  // <= B * S * C <= INT32_MAX
+#define GRP_LAUNCH(DCP, DUP, NW, DT)                                                                          \
+  do {                                                                                                        \
+    A.dcp = DCP;                                                                                              \
+    A.dup = DUP;                                                                                              \
+    if (TILES)                                                                                                \
+      hipLaunchKernelGGL((groups_tiles_kernel<DCP, DUP, NW, DT>), grid, dim3(64 * NW), 0, s, A);              \
+    else                                                                                                      \
+      hipLaunchKernelGGL((groups_screen_kernel<DCP, DUP, NW, DT>), grid, dim3(64 * NW), 0, s, A);             \
+  } while (0)
+  if (A.D <= 8)
+    GRP_LAUNCH(8, 8, 4, 16);
+  else if (A.D <= 16)
+    GRP_LAUNCH(16, 16, 4, 24);
+  else if (A.D <= 32)
+    GRP_LAUNCH(32, 32, 4, 40);
+  else  // D <= 96 with <= 64 continuous and <= 32 categorical dims; anything larger is exact-only
+    GRP_LAUNCH(64, 32, 2, 104);
+#undef GRP_LAUNCH
+}
+
+// hbx_kde_acquire_groups (S = 1) and hbx_kde_acquire_groups_batch: the checks, the screen, the select
+static int grp_acquire(const char* who, const double* X, int32_t D, const int64_t* seg_off, int64_t B,
+                       const int64_t* order, const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                       const double* bw_good, const double* bw_bad, const int32_t* nlev_good, const int32_t* nlev_bad,
+                       const double* cand, int64_t S, int64_t C, void* results, void* workspace, int64_t ws_bytes,
+                       void* stream) {
+  if (D < 1 || D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "%s: D=%d outside [1, %d]", who, D, HBX_MAX_D);
+  if (B < 0 || S < 0 || C < 0)
+    return hbx_fail(HBX_ERR_ARG, "%s: B=%lld S=%lld C=%lld", who, (long long)B, (long long)S, (long long)C);
+  if (!grp_counts_ok(B, S, C))
+    return hbx_fail(HBX_ERR_ARG, "%s: B * S * C = %lld * %lld * %lld exceeds int32", who, (long long)B, (long long)S,
+                    (long long)C);
+  if (B == 0 || S == 0) return HBX_OK;
+  if (!results) return hbx_fail(HBX_ERR_ARG, "%s: null pointer (results)", who);
   hipStream_t s = (hipStream_t)stream;
   if (C == 0) {  // nothing to score: every record is the empty one
-    hipLaunchKernelGGL(groups_empty_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, (AcqResult*)results, B);
+    hipLaunchKernelGGL(groups_empty_kernel, dim3((unsigned)((B * S + 255) / 256)), dim3(256), 0, s, (AcqResult*)results,
+                       B * S);
     HBX_LAUNCH_CHECK();
     return HBX_OK;
   }
   if (!X || !seg_off || !order || !n_good || !n_bad || !vartype || !bw_good || !bw_bad || !nlev_good || !nlev_bad ||
       !cand || !workspace)
-    return hbx_fail(HBX_ERR_ARG, "hbx_kde_acquire_groups: null pointer");
-  const int64_t need = hbx_kde_groups_workspace_bytes(B, C, D);
+    return hbx_fail(HBX_ERR_ARG, "%s: null pointer", who);
+  const int64_t need = hbx_kde_groups_batch_workspace_bytes(B, S, C, D);
   if (ws_bytes < need)
-    return hbx_fail(HBX_ERR_ARG, "hbx_kde_acquire_groups: workspace too small: %lld < %lld bytes", (long long)ws_bytes,
-                    (long long)need);
+    return hbx_fail(HBX_ERR_ARG, "%s: workspace too small: %lld < %lld bytes", who, (long long)ws_bytes, (long long)need);
   if (((uintptr_t)workspace & 15) || ((uintptr_t)results & 7))
-    return hbx_fail(HBX_ERR_ARG, "hbx_kde_acquire_groups: workspace must be 16-byte, results 8-byte aligned");
+    return hbx_fail(HBX_ERR_ARG, "%s: workspace must be 16-byte, results 8-byte aligned", who);
   GrpArgs A;
   A.X = X;
   A.seg_off = seg_off;
@@ -809,31 +1179,50 @@ int hbx_kde_acquire_groups(const double* X, int32_t D, const int64_t* seg_off, i
   A.nlev_bad = nlev_bad;
   A.cand = cand;
   A.B = B;
+  A.S = S;
   A.C = C;
+  A.P = S * C;
   A.D = D;
-  A.tiles = (int32_t)((C + 63) / 64);
+  A.tiles = (int32_t)((A.P + 63) / 64);
   A.scr = (GScreen*)((char*)workspace + GRP_WS_HEAD);
   A.res = (AcqResult*)results;
-  const dim3 grid((unsigned)(B * A.tiles));  // <= B * C <= INT32_MAX
-  // the slot bucket from D alone (vartype is on the device): up to D <= 32 any mix of kinds fits
-  if (D <= 8) {
-    A.dcp = A.dup = 8;
-    hipLaunchKernelGGL((groups_screen_kernel<8, 8, 4, 16>), grid, dim3(256), 0, s, A);
-  } else if (D <= 16) {
-    A.dcp = A.dup = 16;
-    hipLaunchKernelGGL((groups_screen_kernel<16, 16, 4, 24>), grid, dim3(256), 0, s, A);
-  } else if (D <= 32) {
-    A.dcp = A.dup = 32;
-    hipLaunchKernelGGL((groups_screen_kernel<32, 32, 4, 40>), grid, dim3(256), 0, s, A);
-  } else {  // D <= 96 with <= 64 continuous and <= 32 categorical dims; anything larger is exact-only
-    A.dcp = 64;
-    A.dup = 32;
-    hipLaunchKernelGGL((groups_screen_kernel<64, 32, 2, 104>), grid, dim3(128), 0, s, A);
-  }
+  if (grp_tile_screen(S, A.tiles))
+    grp_launch_screen<true>(A, s);
+  else
+    grp_launch_screen<false>(A, s);
   HBX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(groups_select_kernel, dim3((unsigned)B), dim3(GRP_SEL_THREADS), 0, s, A);
+  hipLaunchKernelGGL(groups_select_kernel, dim3((unsigned)(B * S)), dim3(GRP_SEL_THREADS), 0, s, A);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
+}
+
+extern "C" {
+
+int64_t hbx_kde_groups_batch_workspace_bytes(int64_t B, int64_t S, int64_t C, int32_t D) {
+  if (D < 1 || D > HBX_MAX_D || !grp_counts_ok(B, S, C)) return -1;
+  return GRP_WS_HEAD + B * S * C * (int64_t)sizeof(GScreen);
+}
+
+int64_t hbx_kde_groups_workspace_bytes(int64_t B, int64_t C, int32_t D) {
+  return hbx_kde_groups_batch_workspace_bytes(B, 1, C, D);
+}
+
+int hbx_kde_acquire_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                           const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                           const double* bw_good, const double* bw_bad, const int32_t* nlev_good,
+                           const int32_t* nlev_bad, const double* cand, int64_t C, void* results, void* workspace,
+                           int64_t ws_bytes, void* stream) {
+  return grp_acquire("hbx_kde_acquire_groups", X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad,
+                     nlev_good, nlev_bad, cand, 1, C, results, workspace, ws_bytes, stream);
+}
+
+int hbx_kde_acquire_groups_batch(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                 const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                 const double* bw_good, const double* bw_bad, const int32_t* nlev_good,
+                                 const int32_t* nlev_bad, const double* cand, int64_t S, int64_t C, void* results,
+                                 void* workspace, int64_t ws_bytes, void* stream) {
+  return grp_acquire("hbx_kde_acquire_groups_batch", X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad,
+                     nlev_good, nlev_bad, cand, S, C, results, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

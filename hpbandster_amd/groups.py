@@ -4,6 +4,7 @@ Config #5's loop on the device from end to end::
 
     gm = groups.fit_groups(X, losses, seg_off, var_type)      # hbx_seg_argsort_ex + hbx_kde_fit
     rows, picks = gm.propose(64, seed, levels)                # hbx_kde_sample_groups + hbx_kde_acquire_groups
+    rows, picks = gm.propose(64, seed, levels, requests=S)    # S picks per bracket: hbx_kde_acquire_groups_batch
 
 Bracket b owns the rows ``X[seg_off[b]:seg_off[b+1]]``; its good / bad KDEs are the head ``n_good[b]`` / tail
 ``n_bad[b]`` rows of numpy's argsort of its losses (bohb.py:220-246).  The fit's outputs (order, bandwidths, level
@@ -33,7 +34,8 @@ class GroupPicks(object):
     """One pick per group (hbx_kde_acquire_groups), from one fetch of the B records: numpy arrays ``index``
     (int64, relative to the group's pool, -1: no pick), ``score``, ``pdf_l``, ``pdf_g`` (float64, the reference's
     values bit for bit), ``rel`` (float32), ``flags`` (kde.ACQ_* and ACQ_NO_MODEL / ACQ_UNSUPPORTED), ``shortlist``
-    and ``near`` (int32), each of length B."""
+    and ``near`` (int32), each of length B -- or, one pick per request (hbx_kde_acquire_groups_batch), of shape
+    [B, S] with ``index`` relative to the request's own pool.  ``len()`` is B either way."""
     __slots__ = ("index", "score", "pdf_l", "pdf_g", "rel", "flags", "shortlist", "near")
 
     def __init__(self, records):
@@ -42,30 +44,38 @@ class GroupPicks(object):
             setattr(self, name, np.ascontiguousarray(r[name]))
 
     @classmethod
-    def from_bytes(cls, b, B):
-        return cls(np.frombuffer(bytes(b), dtype=RECORD, count=B))
+    def from_bytes(cls, b, B, S=None):
+        """B records (``S`` None), or B * S records in request order b * S + s, as arrays of shape [B, S]."""
+        if S is None:
+            return cls(np.frombuffer(bytes(b), dtype=RECORD, count=B))
+        return cls(np.frombuffer(bytes(b), dtype=RECORD, count=B * S).reshape(B, S))
 
     def __len__(self):
-        return int(self.index.size)
+        return int(self.index.shape[0])
 
     def rows(self, cands):
-        """The winning candidate rows, [B, D] float64 on the host; NaN rows where ``index < 0``.
-        ``cands``: [B, C, D] (numpy or a device tensor)."""
-        B = len(self)
-        D = int(cands.shape[2])
-        out = np.full((B, D), np.nan)
-        ok = np.nonzero(self.index >= 0)[0]
+        """The winning candidate rows on the host, float64; NaN rows where ``index < 0``.  ``cands`` (numpy or a
+        device tensor): [B, C, D] gives [B, D]; [B, S, C, D], with picks of shape [B, S], gives [B, S, D]."""
+        lead = tuple(int(v) for v in cands.shape[:-2])
+        if lead != self.index.shape:
+            raise N.HbxError("candidates %s do not match picks %s" % (tuple(cands.shape), self.index.shape))
+        C, D = int(cands.shape[-2]), int(cands.shape[-1])
+        index = self.index.reshape(-1)
+        out = np.full((index.size, D), np.nan)
+        ok = np.nonzero(index >= 0)[0]
         if ok.size:
             if _is_tensor(cands):
                 torch = kde._torch()
                 bi = torch.from_numpy(ok).to(cands.device)
-                ci = torch.from_numpy(self.index[ok]).to(cands.device)
-                out[ok] = cands[bi, ci].cpu().numpy()
+                ci = torch.from_numpy(index[ok]).to(cands.device)
+                out[ok] = cands.reshape(-1, C, D)[bi, ci].cpu().numpy()
             else:
-                out[ok] = np.asarray(cands, dtype=np.float64)[ok, self.index[ok]]
-        return out
+                out[ok] = np.asarray(cands, dtype=np.float64).reshape(-1, C, D)[ok, index[ok]]
+        return out.reshape(lead + (D,))
 
     def __repr__(self):
+        if self.index.ndim == 2:
+            return "GroupPicks(B=%d, S=%d, picked=%d)" % (self.index.shape + (int((self.index >= 0).sum()),))
         return "GroupPicks(B=%d, picked=%d)" % (len(self), int((self.index >= 0).sum()))
 
 
@@ -109,10 +119,17 @@ class GroupModel(object):
                                       h["nlev"][0][b], h["nlev"][1][b], device=self.device)
 
     # ---- the grouped calls ------------------------------------------------------------------------------
-    def sample(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, stream_id=0):
+    def sample(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, stream_id=0, requests=None):
         """C candidates per group around its good KDE's rows (bohb.py:133-147; hbx_kde_sample_groups):
         candidate (b, i) draws from the Philox counter ``counter_base + b * C + i``.  Returns device tensors
-        (cands [B, C, D] float64, domain_err [B, C] uint8); groups without a model get NaN rows."""
+        (cands [B, C, D] float64, domain_err [B, C] uint8); groups without a model get NaN rows.
+        With ``requests=S``: S pools of C candidates per group, (cands [B, S, C, D], domain_err [B, S, C]) -- the
+        same call with pool size S * C, so candidate (b, s, i) draws from the Philox counter
+        ``counter_base + (b * S + s) * C + i`` and the bytes equal ``sample(S * C, ...)``'s."""
+        if requests is not None:
+            S = int(requests)
+            cands, err = self.sample(S * int(C), seed, levels, bandwidth_factor, counter_base, stream, stream_id)
+            return cands.view(self.B, S, int(C), self.D), err.view(self.B, S, int(C))
         torch = kde._torch()
         C = int(C)
         lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
@@ -129,8 +146,8 @@ class GroupModel(object):
                 N.stream_handle(stream, self.device)))
         return cands, err
 
-    def workspace_bytes(self, C):
-        return int(N.lib().hbx_kde_groups_workspace_bytes(self.B, int(C), self.D))
+    def workspace_bytes(self, C, requests=1):
+        return int(N.lib().hbx_kde_groups_batch_workspace_bytes(self.B, int(requests), int(C), self.D))
 
     def acquire(self, cands, stream=None, workspace=None, sync=True):
         """Per group the first index minimising max(1e-8, g)/max(l, 1e-8) over its own pool ``cands[b]``
@@ -163,10 +180,48 @@ class GroupModel(object):
                 return res
             return GroupPicks.from_bytes(res.cpu().numpy().tobytes(), self.B)
 
-    def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None):
-        """sample + acquire: (rows [B, D] host float64 -- NaN where a group has no pick --, GroupPicks)."""
-        cands, _ = self.sample(C, seed, levels, bandwidth_factor, counter_base, stream=stream)
-        picks = self.acquire(cands, stream=stream)
+    def acquire_requests(self, cands, stream=None, workspace=None, sync=True):
+        """S get_config requests per group in one call (hbx_kde_acquire_groups_batch; HB_iteration.py:136-138 issues
+        a stage's requests back to back against one model): request (b, s) is ``acquire`` for group b over its own
+        pool ``cands[b, s]`` and sees no other request.  ``cands``: [B, S, C, D] float64, numpy or a device tensor.
+        Returns GroupPicks with arrays of shape [B, S], or with ``sync=False`` the device tensor of the records
+        (uint8 [B, S, 48])."""
+        torch = kde._torch()
+        with N.on_device(self.device, stream):
+            if _is_tensor(cands):
+                cd = cands
+                if cd.dtype != torch.float64 or not cd.is_contiguous():
+                    raise N.HbxError("candidate tensor must be contiguous float64 [B, S, C, D]")
+            else:
+                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
+            if cd.dim() != 4 or int(cd.shape[0]) != self.B or int(cd.shape[3]) != self.D:
+                raise N.HbxError("candidates must be [%d, S, C, %d], got %s" % (self.B, self.D, tuple(cd.shape)))
+            S, C = int(cd.shape[1]), int(cd.shape[2])
+            wsb = self.workspace_bytes(C, S)
+            if wsb < 0:
+                raise N.HbxError("B * S * C = %d * %d * %d exceeds int32" % (self.B, S, C))
+            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
+            if ws.numel() < wsb:
+                raise N.HbxError("workspace too small")
+            res = torch.empty((self.B, S, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device)
+            N.check(N.lib().hbx_kde_acquire_groups_batch(
+                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
+                N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
+                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), S, C, N.ptr(res), N.ptr(ws), ws.numel(),
+                N.stream_handle(stream, self.device)))
+            if not sync:
+                return res
+            return GroupPicks.from_bytes(res.cpu().numpy().tobytes(), self.B, S)
+
+    def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, requests=None):
+        """sample + acquire: (rows [B, D] host float64 -- NaN where a group has no pick --, GroupPicks).
+        With ``requests=S``: sample + acquire_requests, (rows [B, S, D], GroupPicks of shape [B, S])."""
+        if requests is None:
+            cands, _ = self.sample(C, seed, levels, bandwidth_factor, counter_base, stream=stream)
+            picks = self.acquire(cands, stream=stream)
+        else:
+            cands, _ = self.sample(C, seed, levels, bandwidth_factor, counter_base, stream=stream, requests=requests)
+            picks = self.acquire_requests(cands, stream=stream)
         return picks.rows(cands), picks
 
 

@@ -22,6 +22,8 @@
  *                                      candidate, minimize_me, strict-'<' argmin)
  *   hbx_kde_acquire_groups          <- bohb.py:124-169 per bracket, after bohb.py:220-246 (B brackets' picks in
  *                                      one call, straight from hbx_kde_fit's device outputs)
+ *   hbx_kde_acquire_groups_batch    <- bohb.py:124-169 once per get_config request of a stage, HB_iteration.py:136-138
+ *                                      (S requests per bracket, B brackets, one call)
  *   hbx_kde_sample_groups           <- bohb.py:133-147 per bracket (the candidates of B brackets in one call)
  *   hbx_kde_logpdf                  <- KDEMultivariate.pdf (kernel_density.py:162-196), fp32 log domain
  *   hbx_kde_pdf_exact               <- KDEMultivariate.pdf, fp64, reference operation order
@@ -260,6 +262,29 @@ int hbx_kde_acquire_groups(const double* X, int32_t D, const int64_t* seg_off, i
                            const int32_t* nlev_good, const int32_t* nlev_bad,
                            const double* cand, int64_t C, void* results,
                            void* workspace, int64_t ws_bytes, void* stream);
+/* The same for S get_config requests per bracket in one call: a successive-halving stage issues num_configs[stage]
+ * get_config calls back to back against one model (HB_iteration.py:136-138), each with its own num_samples
+ * candidates and its own strict-'<' argmin (bohb.py:124-169).  The model arguments are hbx_kde_acquire_groups',
+ * unchanged.  cand: f64[B][S][C][D], request (b, s)'s own pool of C candidates.  results: B * S records, record
+ * b * S + s = what hbx_kde_acquire_groups returns for group b over cand[b][s]: index (relative to the request's
+ * pool), score, pdf_l and pdf_g the reference's fp64 values bit for bit; HBX_ACQ_NO_MODEL / HBX_ACQ_UNSUPPORTED as
+ * there.  Requests never see one another: the bound, the shortlist, the first-certain-1 rule, the argmin and the
+ * near count are per request.  shortlist / near / rel / HBX_ACQ_OVERFLOW / HBX_ACQ_NEAR_TIE keep their meanings but
+ * may come from another fp32 screen than the one-request call's (a group's S * C candidates are screened as one
+ * flattened pool, by a kernel chosen from its size) -- except with S == 1, which runs hbx_kde_acquire_groups' own
+ * two launches: the B records are byte-identical.  Two launches on `stream`, no host synchronisation, no
+ * allocation, no per-group host work, never an error return for a bad group; B * S * C beyond int32: HBX_ERR_ARG
+ * (the size helper: -1).  B == 0 or S == 0: nothing to do; C == 0: B * S empty records.  workspace:
+ * hbx_kde_groups_batch_workspace_bytes(B, S, C, D) bytes, 16-byte aligned.
+ * Candidates: hbx_kde_sample_groups with pool size S * C -- candidate (b, s, i) then draws from the Philox counter
+ * counter_base + (b * S + s) * C + i. */
+int64_t hbx_kde_groups_batch_workspace_bytes(int64_t B, int64_t S, int64_t C, int32_t D);
+int hbx_kde_acquire_groups_batch(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                 const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                 const double* bw_good, const double* bw_bad,
+                                 const int32_t* nlev_good, const int32_t* nlev_bad,
+                                 const double* cand, int64_t S, int64_t C, void* results,
+                                 void* workspace, int64_t ws_bytes, void* stream);
 /* The matching sampler: C candidates per group around its good KDE's rows (hbx_kde_sample's rule).  Candidate
  * (b, i) is byte-equal to what hbx_kde_sample draws for group b's good KDE (tab = NULL) at candidate index i of a
  * call with counter_base + b * C.  cands: f64[B][C][D] (16-byte aligned when D is even); domain_err: nullable

@@ -12,6 +12,11 @@ reported with and without the prepare time.  The grouped picks are checked again
     python tools/bench_groups.py [--B 10000] [--n 1000] [--C 64] [--reps 20] [--sub 200] [--out FILE]
 
 Writes one JSON document (default profiles/groups/bench_groups.json) and prints it.
+
+    python tools/bench_groups.py --requests S [--loop-only] [--out FILE]
+
+times S get_config requests per bracket instead (requests_bench below): the batched call under each screen against S
+one-request calls; prints one JSON line and writes it only where --out says.
 """
 import argparse
 import json
@@ -45,6 +50,73 @@ def timed(fn, reps, warm=3):
     return e0.elapsed_time(e1) / reps
 
 
+def requests_bench(a, gm, L, sh, lvd):
+    """--requests R: R pools of C candidates per bracket (one hbx_kde_sample_groups call with pool R C), then
+      loop         R back-to-back hbx_kde_acquire_groups calls over the R request slices (--loop-only: nothing
+                   else, so a library from before the batched call can be timed through HBX_LIB_PATH)
+      batch        hbx_kde_acquire_groups_batch, the screen chosen by the library's rule
+      batch_chunk  the same with HBX_GROUPS_SCREEN=1 (the chunk-splitting screen over the flattened pool)
+      batch_tile   the same with HBX_GROUPS_SCREEN=2 (the tile screen)
+    The loop reads request s of every bracket from its own contiguous [B, C, D] copy: the one-request call takes no
+    stride.  Prints one JSON line; --out writes it too."""
+    dev = gm.device
+    B, R, C, D = gm.B, a.requests, a.C, gm.D
+    pool = torch.empty((B, R * C, D), dtype=torch.float64, device=dev)
+    derr = torch.empty((B, R * C), dtype=torch.uint8, device=dev)
+    N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
+                                    N.ptr(gm.bw_good), N.ptr(lvd), 3.0, S.SEED_CAND, 0, 0, R * C, N.ptr(pool),
+                                    N.ptr(derr), sh))
+    cands = pool.view(B, R, C, D)
+    model = (N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
+             N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad))
+    slices = [cands[:, s].contiguous() for s in range(R)]
+    wsb1 = int(L.hbx_kde_groups_workspace_bytes(B, C, D))
+    ws1 = torch.empty(wsb1, dtype=torch.uint8, device=dev)
+    res1 = torch.empty((R, B, kde.RESULT_BYTES), dtype=torch.uint8, device=dev)
+
+    def loop():
+        for s in range(R):
+            N.check(L.hbx_kde_acquire_groups(*model, N.ptr(slices[s]), C, N.ptr(res1[s]), N.ptr(ws1), wsb1, sh))
+
+    out = {"workload": "grouped_requests_b%d_n%d_d32_24c8u_s%d_c%d" % (B, a.n, R, C),
+           "device": torch.cuda.get_device_name(0), "reps": a.reps, "requests": R,
+           "library": N.LIB_PATH, "loop_ms": timed(loop, a.reps)}
+    if not a.loop_only:
+        wsb = int(L.hbx_kde_groups_batch_workspace_bytes(B, R, C, D))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        res = torch.empty((B, R, kde.RESULT_BYTES), dtype=torch.uint8, device=dev)
+
+        def batch():
+            N.check(L.hbx_kde_acquire_groups_batch(*model, N.ptr(cands), R, C, N.ptr(res), N.ptr(ws), wsb, sh))
+
+        for key, screen in (("batch_ms", None), ("batch_chunk_screen_ms", "1"), ("batch_tile_screen_ms", "2")):
+            if screen is None:
+                os.environ.pop("HBX_GROUPS_SCREEN", None)
+            else:
+                os.environ["HBX_GROUPS_SCREEN"] = screen
+            out[key] = timed(batch, a.reps)
+            picks = groups.GroupPicks.from_bytes(res.cpu().numpy().tobytes(), B, R)
+            out[key.replace("_ms", "_mean_shortlist_per_request")] = float(picks.shortlist.mean())
+        os.environ.pop("HBX_GROUPS_SCREEN", None)
+        batch()
+        picks = groups.GroupPicks.from_bytes(res.cpu().numpy().tobytes(), B, R)
+        one = np.frombuffer(res1.cpu().numpy().tobytes(), dtype=groups.RECORD).reshape(R, B)
+        agree = int(sum(np.array_equal(picks.index[:, s], one["index"][s]) and
+                        np.array_equal(picks.score[:, s], one["score"][s], equal_nan=True) for s in range(R)))
+        out.update({"workspace_bytes": wsb, "candidate_bytes": int(cands.numel()) * 8,
+                    "picked": int((picks.index >= 0).sum()), "max_shortlist": int(picks.shortlist.max()),
+                    "overflow_requests": int(((picks.flags & 1) != 0).sum()),
+                    "near_tie_requests": int(((picks.flags & 2) != 0).sum()),
+                    "requests_agreeing_with_loop": agree, "speedup_vs_loop": out["loop_ms"] / out["batch_ms"]})
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+            f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+    return 0 if a.loop_only or out["requests_agreeing_with_loop"] == R else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=10000)
@@ -52,7 +124,10 @@ def main(argv=None):
     ap.add_argument("--C", type=int, default=64)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sub", type=int, default=200)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "groups", "bench_groups.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--requests", type=int, default=1, help="S get_config requests per bracket (requests_bench)")
+    ap.add_argument("--loop-only", action="store_true",
+                    help="time only the S one-request calls (what a library without the batched call offers)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     L = N.lib()
@@ -70,6 +145,9 @@ def main(argv=None):
     seg = np.arange(B + 1, dtype=np.int64) * n
     gm = groups.fit_groups(X, losses, seg, vts, device=dev)
     sh = N.stream_handle(None, dev)
+    if a.requests > 1 or a.loop_only:
+        return requests_bench(a, gm, L, sh, torch.tensor(levels, dtype=torch.int32, device=dev))
+    a.out = a.out or os.path.join(ROOT, "profiles", "groups", "bench_groups.json")
     cands = torch.empty((B, C, D), dtype=torch.float64, device=dev)
     derr = torch.empty((B, C), dtype=torch.uint8, device=dev)
     lvd = torch.tensor(levels, dtype=torch.int32, device=dev)
