@@ -85,6 +85,11 @@
 //   The screens' sums differ in the last bits (another order of additions), so shortlist / near / rel may differ
 //   between them; index, score and the pdfs come from the fp64 re-score and do not.
 //
+// The k best candidates per group (hbx_kde_acquire_groups_topk): launch 1 as above, then groups_topk_kernel in
+// launch 2's place -- the k-th smallest upper bound, the shortlist against it, the same re-score, and the ranking of
+// hbx_topk_rank.h (shared with hbx_topk.hip).  Its comment, before the kernel, has the steps and the argument why the
+// shortlist holds the whole top-k.
+//
 // The grouped sampler (hbx_kde_sample_groups) lives in hbx_sample.hip beside the draw functions it shares with
 // hbx_kde_sample, so the byte-equality of the draws holds by construction.
 //
@@ -97,6 +102,7 @@
 //   - C == 0 launches one small kernel: the B empty records have to be written by something (NaN is not a byte fill).
 #include "hbx_acq_impl.h"
 #include "hbx_exact_impl.h"
+#include "hbx_topk_rank.h"
 
 struct GScreen {
   union {
@@ -1086,6 +1092,271 @@ __global__ void groups_empty_kernel(AcqResult* res, int64_t B) {
   if (b < B) res[b] = grp_empty_record(0);
 }
 
+// ------------------------------------------------------------------------------------------
+// Grouped top-k (hbx_kde_acquire_groups_topk): the k best candidates of every group's pool, ranked exactly.
+// Launch 1 is groups_screen_kernel as hbx_kde_acquire_groups launches it; launch 2 is groups_topk_kernel, one block
+// per group, in place of groups_select_kernel:
+//   bound      U_k = the k-th smallest shi over the certified candidates (no GS_FORCE; a GS_ONE candidate counts
+//              with its interval [0, 0]); fewer than k of them: +inf.  A radix select over the hbx_f2ord keys' four
+//              8-bit digits from the top: per digit an LDS histogram of the keys matching the digits chosen so far
+//              (the group's slots re-read, so any C), a scan over its 256 bins, the digit that holds the rank.  Counts
+//              are integers: no dependence on thread timing.
+//   shortlist  in index order, 256 candidates at a time: everything if the group is exact-only or a GS_OF is
+//              present; every GS_FORCE candidate; every certified candidate that is not GS_ONE with slo <= U_k; and,
+//              only when 0 <= U_k, the first k GS_ONE candidates by index.
+//   re-score   both fp64 pdfs of every shortlisted candidate by the whole block (exact_setup / exact_pdf, driven as
+//              groups_select_kernel drives them), then bohb_score; the pdfs go to the group's spill in the workspace.
+//   ranking    the running best-(k+1) of hbx_topk_rank.h over (score bits, index, index); its LDS arrays are the
+//              launch's dynamic LDS, sized from k (grp_topk_cap), beside ExactShared.  An entry's pdfs and rel are not
+//              carried through the merges: they stay in the spill / the screen slot and are read by index at the end.
+//   result     header and records by ordinary vector stores; HBX_ACQ_NEAR_TIE as the single top-k sets it (adjacent
+//              returned entries; the last one and the best re-scored one left out), and also when the last returned
+//              entry scores exactly 1 while certain exact-1 candidates were left unlisted.
+//
+// Why the shortlist holds the whole top-k.  Every certified candidate's true ln score lies in its [slo, shi]; a
+// GS_ONE candidate's true score is exactly 1 (ln 0).  With k certified candidates, at least k have shi <= U_k, so at
+// least k true scores are <= U_k and the k-th smallest true score is <= U_k: every member of the true top-k, ties by
+// index included, has a true score <= U_k, hence slo <= U_k -- or is uncertified, and those are all listed.  (Fewer
+// than k certified: U_k = +inf, everything certified passes.)  The added step, for the certain exact 1s: they all
+// have the same exact score, so among themselves they rank by index.  One that is preceded by k others of lower
+// index is preceded by k candidates of a score not above its own and a lower index, so it cannot be among the first
+// k of the order by (score, index): only the first k by index can be returned, and with U_k < 0 none can (k true
+// scores are below 1).  The ranking itself is over exact scores only, so the shortlist decides cost, never the
+// result.
+struct GrpTopk {
+  char* out;     // B result blocks of 16 + 40 k bytes
+  double2* pdf;  // [B][C] {pdf_l, pdf_g} of the re-scored candidates: the per-group spill
+  int32_t k, cap;
+};
+
+// entries of the ranking's LDS arrays for k: a power of two with k + 1 + GRP_SEL_THREADS <= cap
+static int grp_topk_cap(int32_t k) {
+  const int need = k + 1 + GRP_SEL_THREADS;
+  return need <= 512 ? 512 : need <= 1024 ? 1024 : 2048;
+}
+static_assert(HBX_TOPK_MAX_K + 1 + GRP_SEL_THREADS <= 2048, "a chunk fits behind the kept entries after a merge");
+
+__global__ __launch_bounds__(GRP_SEL_THREADS) void groups_topk_kernel(GrpArgs A, GrpTopk K) {
+  constexpr int T = GRP_SEL_THREADS;
+  extern __shared__ __align__(16) unsigned char s_dyn[];  // the ranking's arrays: cap x (u64, i32, i32)
+  __shared__ ExactShared sh;
+  __shared__ GrpView vw[2];
+  __shared__ int32_t slist[T];
+  __shared__ double s_l[T], s_g[T];
+  __shared__ int32_t swc[T / 64], swo[T / 64];
+  __shared__ uint32_t s_hist[256], s_wsum[T / 64];
+  __shared__ uint32_t s_prefix, s_rank;
+  __shared__ int32_t s_st, s_of, s_ncert, s_none;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const int D = A.D;
+  const int64_t C = A.C;
+  const int32_t k = K.k;
+  TopkHead* head = (TopkHead*)(K.out + b * (int64_t)(sizeof(TopkHead) + sizeof(TopkRec) * (size_t)k));
+  TopkRec* rec = (TopkRec*)(head + 1);
+  if (wv == 0) {
+    int dc, du;
+    const int st0 = grp_status(A, b, &dc, &du);
+    if (lane == 0) s_st = st0;
+  }
+  if (tid == 0) {
+    s_of = 0;
+    s_ncert = 0;
+    s_none = 0;
+    s_prefix = 0u;
+    s_rank = (uint32_t)k;
+  }
+  __syncthreads();
+  const int st = s_st;
+  if (st & (GRP_NO_MODEL | GRP_UNSUPPORTED)) {
+    if (tid == 0) *head = TopkHead{0, 0, (st & GRP_NO_MODEL) ? HBX_ACQ_NO_MODEL : HBX_ACQ_UNSUPPORTED, k};
+    return;
+  }
+  const int64_t s0 = A.seg_off[b], n = A.seg_off[b + 1] - s0;
+  const int64_t ng = A.n_good[b], nb = A.n_bad[b];
+  const double* Xs = A.X + s0 * D;
+  const int64_t* rows_g = A.order + s0;
+  const int64_t* rows_b = A.order + s0 + (n - nb);
+  if (tid < 2) {  // prod(bw[iscontinuous]) sequentially in dim order: the reference's order
+    GrpView v;
+    v.n = (int32_t)(tid ? nb : ng);
+    v.bw = (tid ? A.bw_bad : A.bw_good) + b * D;
+    v.nlev = (tid ? A.nlev_bad : A.nlev_good) + b * D;
+    v.vartype = A.vartype;
+    double p = 1.0;
+    for (int d = 0; d < D; ++d) p *= (A.vartype[d] == 0) ? v.bw[d] : 1.0;
+    v.prod_bw_c = p;
+    vw[tid] = v;
+  }
+  const GScreen* scr = A.scr + b * C;
+  const double* cand = A.cand + b * C * D;
+  double2* pdf = K.pdf + b * C;
+  // pass 1: the certified candidates, the certain 1s among them, the overflow rule
+  {
+    int of = 0, nc = 0, n1 = 0;
+    for (int64_t i = tid; i < C; i += T) {
+      const uint32_t fl = scr[i].fl;
+      if (fl & GS_FORCE) continue;
+      ++nc;
+      of |= (fl & GS_OF) ? 1 : 0;
+      n1 += (fl & GS_ONE) ? 1 : 0;
+    }
+    if (of) atomicOr(&s_of, 1);
+    if (nc) atomicAdd(&s_ncert, nc);
+    if (n1) atomicAdd(&s_none, n1);
+  }
+  __syncthreads();
+  const bool all = (st & GRP_EXACT_ONLY) || s_of;
+  const int32_t none = s_none;
+  // the bound: U_k by radix select over the keys of shi, the top digit first
+  float U = INFINITY;
+  if (!all && s_ncert >= k) {  // uniform
+    for (int pass = 0; pass < 4; ++pass) {
+      const int shift = 24 - 8 * pass;
+      const uint32_t himask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
+      s_hist[tid] = 0u;  // (T == 256 bins)
+      __syncthreads();
+      const uint32_t prefix = s_prefix, rank = s_rank;
+      for (int64_t i = tid; i < C; i += T) {
+        const GScreen g = scr[i];
+        if (g.fl & GS_FORCE) continue;
+        const uint32_t key = hbx_f2ord(g.shi);
+        if (((key ^ prefix) & himask) == 0) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
+      }
+      __syncthreads();
+      const uint32_t c = s_hist[tid];
+      uint32_t incl = c;  // inclusive scan over the 256 bins: within the wave, then the waves before
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+      }
+      if (lane == 63) s_wsum[wv] = incl;
+      __syncthreads();
+#pragma unroll
+      for (int w = 0; w < T / 64; ++w) incl += w < wv ? s_wsum[w] : 0u;
+      const uint32_t excl = incl - c;
+      if (excl < rank && rank <= incl) {  // exactly one bin: the matching keys number >= rank
+        s_prefix = prefix | ((uint32_t)tid << shift);
+        s_rank = rank - excl;
+      }
+      __syncthreads();
+    }
+    U = hbx_ord2f(s_prefix);
+  }
+  static_assert(T == 256, "one thread per histogram bin");
+  TopkRank<T> rank;
+  rank.init((uint64_t*)s_dyn, (int32_t*)(s_dyn + 8 * (size_t)K.cap), (int32_t*)(s_dyn + 12 * (size_t)K.cap), swc, K.cap,
+            k + 1);  // the k best and the best excluded one (the near-tie test's last pair)
+  // pass 2: the shortlist in index order, 256 candidates at a time; each entry's exact pdfs by the whole block
+  const bool ones_in = U >= 0.f;
+  int32_t nshort = 0, ones_seen = 0;
+  for (int64_t c0 = 0; c0 < C; c0 += T) {
+    const int64_t i = c0 + tid;
+    GScreen g;
+    g.fl = GS_FORCE;
+    g.slo = g.shi = NAN;
+    const bool live = i < C;
+    if (live) g = scr[i];
+    const bool one = live && !(g.fl & GS_FORCE) && (g.fl & GS_ONE);
+    const uint64_t bo = __ballot(one);
+    if (lane == 0) swo[wv] = __popcll(bo);
+    __syncthreads();
+    int obefore = ones_seen, otot = 0;
+#pragma unroll
+    for (int w = 0; w < T / 64; ++w) {
+      obefore += w < wv ? swo[w] : 0;
+      otot += swo[w];
+    }
+    ones_seen += otot;
+    bool in = false;
+    if (live) {
+      if (all || (g.fl & GS_FORCE))
+        in = true;
+      else if (one)
+        in = ones_in && obefore + (int)__popcll(bo & ((1ull << lane) - 1)) < k;  // the first k certain 1s by index
+      else
+        in = g.slo <= U;
+    }
+    const uint64_t bal = __ballot(in);
+    if (lane == 0) swc[wv] = __popcll(bal);
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < T / 64; ++w) {
+      off += w < wv ? swc[w] : 0;
+      tot += swc[w];
+    }
+    if (in) slist[off + __popcll(bal & ((1ull << lane) - 1))] = tid;
+    __syncthreads();
+    for (int p = 0; p < tot; ++p) {
+      const int64_t ip = c0 + slist[p];
+      exact_setup(&vw[0], D, cand + ip * D, &sh);
+      const double l = exact_pdf(Xs, D, rows_g, &vw[0], &sh);
+      __syncthreads();
+      exact_setup(&vw[1], D, cand + ip * D, &sh);
+      const double gd = exact_pdf(Xs, D, rows_b, &vw[1], &sh);
+      if (tid == 0) {
+        s_l[p] = l;
+        s_g[p] = gd;
+      }
+      __syncthreads();
+    }
+    // the chunk's re-scored entries, one per thread in index order: pdfs to the spill, the score to the ranking
+    bool acc = false;
+    uint64_t key = 0;
+    int32_t idx = 0;
+    if (tid < tot) {
+      const double l = s_l[tid], gd = s_g[tid];
+      idx = (int32_t)(c0 + slist[tid]);
+      pdf[idx] = make_double2(l, gd);
+      const double s = bohb_score(gd, l);
+      if (s == s) {  // NaN scores are never returned
+        key = (uint64_t)__double_as_longlong(s);
+        acc = rank.enters(key, idx);
+      }
+    }
+    rank.push(acc, key, idx, idx);  // (its last barrier: slist, s_l, s_g are free again)
+    nshort += tot;
+  }
+  rank.finish();
+  __threadfence_block();
+  __syncthreads();  // (the spill's stores are visible to the block)
+  const int nbest = rank.nb;
+  const int nout = nbest < k ? nbest : k;
+  // the ranked records; HBX_ACQ_NEAR_TIE: an entry and the next one (the last returned one's next is the best
+  // excluded entry, position k) cannot be told apart by the re-score's error bounds
+  bool near = false;
+  for (int j = tid; j < nout; j += T) {
+    const int32_t idx = rank.si[j];
+    const double s = __longlong_as_double((long long)rank.sk[j]);
+    const float r = scr[idx].rel;
+    const double2 lg = pdf[idx];
+    TopkRec o;
+    o.index = idx;
+    o.score = s;
+    o.pdf_l = lg.x;
+    o.pdf_g = lg.y;
+    o.rel = r;
+    o.pad = 0;
+    rec[j] = o;
+    if (j + 1 < nbest) {
+      const double s2 = __longlong_as_double((long long)rank.sk[j + 1]);
+      near = near || near_best(s2, (double)scr[rank.si[j + 1]].rel, s, (double)r);
+    }
+    // the certain 1s left unlisted tie with a last returned entry whose score is 1
+    if (j == nout - 1 && s == 1.0 && !all && none > (ones_in ? (none < k ? none : k) : 0)) near = true;
+  }
+  const int any_near = __syncthreads_or(near);
+  if (tid == 0)
+    *head = TopkHead{nout, nshort, (all ? HBX_ACQ_OVERFLOW : 0) | (any_near ? HBX_ACQ_NEAR_TIE : 0), k};
+}
+
+__global__ void groups_topk_empty_kernel(char* out, int64_t B, int32_t k) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) *(TopkHead*)(out + b * (int64_t)(sizeof(TopkHead) + sizeof(TopkRec) * (size_t)k)) = TopkHead{0, 0, 0, k};
+}
+
 #define GRP_WS_HEAD 256
 
 // B * S * C within int32 (what every grid and every screen slot index relies on)
@@ -1137,6 +1408,34 @@ static void grp_launch_screen(GrpArgs& A, hipStream_t s) {
 #undef GRP_LAUNCH
 }
 
+// the argument block of one call: the model, the pools, the screen slots behind the workspace's head
+static GrpArgs grp_args(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                        const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype, const double* bw_good,
+                        const double* bw_bad, const int32_t* nlev_good, const int32_t* nlev_bad, const double* cand,
+                        int64_t S, int64_t C, void* results, void* workspace) {
+  GrpArgs A;
+  A.X = X;
+  A.seg_off = seg_off;
+  A.order = order;
+  A.n_good = n_good;
+  A.n_bad = n_bad;
+  A.vartype = vartype;
+  A.bw_good = bw_good;
+  A.bw_bad = bw_bad;
+  A.nlev_good = nlev_good;
+  A.nlev_bad = nlev_bad;
+  A.cand = cand;
+  A.B = B;
+  A.S = S;
+  A.C = C;
+  A.P = S * C;
+  A.D = D;
+  A.tiles = (int32_t)((A.P + 63) / 64);
+  A.scr = (GScreen*)((char*)workspace + GRP_WS_HEAD);
+  A.res = (AcqResult*)results;
+  return A;
+}
+
 // hbx_kde_acquire_groups (S = 1) and hbx_kde_acquire_groups_batch: the checks, the screen, the select
 static int grp_acquire(const char* who, const double* X, int32_t D, const int64_t* seg_off, int64_t B,
                        const int64_t* order, const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
@@ -1166,32 +1465,56 @@ static int grp_acquire(const char* who, const double* X, int32_t D, const int64_
     return hbx_fail(HBX_ERR_ARG, "%s: workspace too small: %lld < %lld bytes", who, (long long)ws_bytes, (long long)need);
   if (((uintptr_t)workspace & 15) || ((uintptr_t)results & 7))
     return hbx_fail(HBX_ERR_ARG, "%s: workspace must be 16-byte, results 8-byte aligned", who);
-  GrpArgs A;
-  A.X = X;
-  A.seg_off = seg_off;
-  A.order = order;
-  A.n_good = n_good;
-  A.n_bad = n_bad;
-  A.vartype = vartype;
-  A.bw_good = bw_good;
-  A.bw_bad = bw_bad;
-  A.nlev_good = nlev_good;
-  A.nlev_bad = nlev_bad;
-  A.cand = cand;
-  A.B = B;
-  A.S = S;
-  A.C = C;
-  A.P = S * C;
-  A.D = D;
-  A.tiles = (int32_t)((A.P + 63) / 64);
-  A.scr = (GScreen*)((char*)workspace + GRP_WS_HEAD);
-  A.res = (AcqResult*)results;
+  GrpArgs A = grp_args(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad, cand, S,
+                       C, results, workspace);
   if (grp_tile_screen(S, A.tiles))
     grp_launch_screen<true>(A, s);
   else
     grp_launch_screen<false>(A, s);
   HBX_LAUNCH_CHECK();
   hipLaunchKernelGGL(groups_select_kernel, dim3((unsigned)(B * S)), dim3(GRP_SEL_THREADS), 0, s, A);
+  HBX_LAUNCH_CHECK();
+  return HBX_OK;
+}
+
+// hbx_kde_acquire_groups_topk: grp_acquire's checks with S = 1, the same screen, groups_topk_kernel as the select
+static int grp_acquire_topk(const char* who, const double* X, int32_t D, const int64_t* seg_off, int64_t B,
+                            const int64_t* order, const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                            const double* bw_good, const double* bw_bad, const int32_t* nlev_good,
+                            const int32_t* nlev_bad, const double* cand, int64_t C, int32_t k, void* results,
+                            void* workspace, int64_t ws_bytes, void* stream) {
+  if (D < 1 || D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "%s: D=%d outside [1, %d]", who, D, HBX_MAX_D);
+  if (B < 0 || C < 0) return hbx_fail(HBX_ERR_ARG, "%s: B=%lld C=%lld", who, (long long)B, (long long)C);
+  if (k < 1 || k > HBX_TOPK_MAX_K) return hbx_fail(HBX_ERR_ARG, "%s: k=%d outside [1, %d]", who, k, HBX_TOPK_MAX_K);
+  if (!grp_counts_ok(B, 1, C))
+    return hbx_fail(HBX_ERR_ARG, "%s: B * C = %lld * %lld exceeds int32", who, (long long)B, (long long)C);
+  if (B == 0) return HBX_OK;
+  if (!results) return hbx_fail(HBX_ERR_ARG, "%s: null pointer (results)", who);
+  if ((uintptr_t)results & 7) return hbx_fail(HBX_ERR_ARG, "%s: results must be 8-byte aligned", who);
+  hipStream_t s = (hipStream_t)stream;
+  if (C == 0) {  // nothing to score: B headers with count 0
+    hipLaunchKernelGGL(groups_topk_empty_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, (char*)results, B,
+                       k);
+    HBX_LAUNCH_CHECK();
+    return HBX_OK;
+  }
+  if (!X || !seg_off || !order || !n_good || !n_bad || !vartype || !bw_good || !bw_bad || !nlev_good || !nlev_bad ||
+      !cand || !workspace)
+    return hbx_fail(HBX_ERR_ARG, "%s: null pointer", who);
+  const int64_t need = hbx_kde_groups_topk_workspace_bytes(B, C, k, D);
+  if (ws_bytes < need)
+    return hbx_fail(HBX_ERR_ARG, "%s: workspace too small: %lld < %lld bytes", who, (long long)ws_bytes, (long long)need);
+  if ((uintptr_t)workspace & 15) return hbx_fail(HBX_ERR_ARG, "%s: workspace must be 16-byte aligned", who);
+  GrpArgs A = grp_args(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad, cand, 1,
+                       C, nullptr, workspace);
+  GrpTopk K;
+  K.out = (char*)results;
+  K.pdf = (double2*)((char*)workspace + GRP_WS_HEAD + B * C * (int64_t)sizeof(GScreen));  // behind the screen slots
+  K.k = k;
+  K.cap = grp_topk_cap(k);
+  grp_launch_screen<false>(A, s);
+  HBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(groups_topk_kernel, dim3((unsigned)B), dim3(GRP_SEL_THREADS), (size_t)K.cap * 16, s, A, K);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }
@@ -1223,6 +1546,23 @@ int hbx_kde_acquire_groups_batch(const double* X, int32_t D, const int64_t* seg_
                                  void* workspace, int64_t ws_bytes, void* stream) {
   return grp_acquire("hbx_kde_acquire_groups_batch", X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad,
                      nlev_good, nlev_bad, cand, S, C, results, workspace, ws_bytes, stream);
+}
+
+// the grouped workspace (the screen slots) followed by the re-scored candidates' pdfs, 16 bytes per candidate: the
+// ranking's entries refer to them by index, so the spill does not grow with k
+int64_t hbx_kde_groups_topk_workspace_bytes(int64_t B, int64_t C, int32_t k, int32_t D) {
+  if (k < 1 || k > HBX_TOPK_MAX_K) return -1;
+  const int64_t base = hbx_kde_groups_batch_workspace_bytes(B, 1, C, D);
+  return base < 0 ? -1 : base + B * C * (int64_t)sizeof(double2);
+}
+
+int hbx_kde_acquire_groups_topk(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                const double* bw_good, const double* bw_bad, const int32_t* nlev_good,
+                                const int32_t* nlev_bad, const double* cand, int64_t C, int32_t k, void* results,
+                                void* workspace, int64_t ws_bytes, void* stream) {
+  return grp_acquire_topk("hbx_kde_acquire_groups_topk", X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good,
+                          bw_bad, nlev_good, nlev_bad, cand, C, k, results, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -35,20 +35,10 @@
 //   {i64 index, f64 score, f64 pdf_l, f64 pdf_g, f32 rel, i32 0}
 #include "hbx_acq_impl.h"
 #include "hbx_acquire.h"
+#include "hbx_topk_rank.h"
 
 #define TOPK_KEY_INF 0xFF800000u  // hbx_f2ord(+inf): keys below it are finite upper bounds
 #define TOPK_HIST_WORDS (4 * 256)  // workspace of the k-th bound's radix select: 4 histograms of 256 bins
-
-struct TopkHead {
-  int32_t count, shortlist, flags, k;
-};
-struct TopkRec {
-  int64_t index;
-  double score, pdf_l, pdf_g;
-  float rel;
-  int32_t pad;
-};
-static_assert(sizeof(TopkHead) == 16 && sizeof(TopkRec) == 40, "the documented result block layout");
 
 __global__ __launch_bounds__(256) void topk_bounds_kernel(const KdeEst* __restrict__ el,
                                                           const KdeEst* __restrict__ eg, int64_t Nc,
@@ -166,66 +156,20 @@ __global__ __launch_bounds__(256) void topk_shortlist_kernel(const float* __rest
 #define TOPK_CAP 2048     // entries of its LDS array: <= k + 1 kept + pending ones
 static_assert(HBX_TOPK_MAX_K + 1 + TOPK_T <= TOPK_CAP, "a chunk fits behind the kept entries after a merge");
 
-__device__ __forceinline__ bool topk_less(uint64_t ka, int32_t ia, uint64_t kb, int32_t ib) {
-  return ka < kb || (ka == kb && ia < ib);
-}
-
 __global__ __launch_bounds__(TOPK_T) void topk_final_kernel(
     const int32_t* __restrict__ list, const int32_t* __restrict__ count, const double* __restrict__ exact_l,
     const double* __restrict__ exact_g, const int32_t* __restrict__ flags, int64_t index_base, int32_t k,
     const KdeParams* __restrict__ Pg, const KdeParams* __restrict__ Pb, const KdeEst* __restrict__ el,
     const KdeEst* __restrict__ eg, TopkHead* __restrict__ head, TopkRec* __restrict__ rec) {
-  // entries (score bits, candidate index, shortlist position): [0, nb) the best so far in ascending
-  // (score, index) order, [nb, nb + pend) accepted since the last merge, unordered
+  // the running best-(k+1) (hbx_topk_rank.h): entries (score bits, candidate index, shortlist position)
   __shared__ uint64_t sk[TOPK_CAP];
   __shared__ int32_t si[TOPK_CAP];
   __shared__ int32_t sp[TOPK_CAP];
   __shared__ int32_t swc[TOPK_T / 64];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int t = threadIdx.x;
   const int cnt = *count;
-  const int keep = k + 1;  // the k best and the best excluded one (the near-tie test's last pair)
-  int nb = 0, pend = 0;    // uniform
-  // only entries below the keep-th best so far can still enter (everything, until that many are held)
-  uint64_t tkey = ~0ull;
-  int32_t tidx = INT32_MAX;
-  auto merge = [&]() {  // whole block, uniform: sort [0, nb + pend), keep the first `keep`
-    const int n = nb + pend;
-    int W = 2;
-    while (W < n) W <<= 1;
-    for (int j = n + t; j < W; j += TOPK_T) {  // padding sorts last (no score has these bits: a NaN's)
-      sk[j] = ~0ull;
-      si[j] = INT32_MAX;
-      sp[j] = -1;
-    }
-    for (int size = 2; size <= W; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        __syncthreads();
-        for (int pr = t; pr < W / 2; pr += TOPK_T) {
-          const int i = 2 * pr - (pr & (stride - 1)), j = i + stride;
-          const bool asc = (i & size) == 0;
-          const uint64_t ka = sk[i], kb = sk[j];
-          const int32_t ia = si[i], ib = si[j];
-          if (asc ? topk_less(kb, ib, ka, ia) : topk_less(ka, ia, kb, ib)) {
-            sk[i] = kb;
-            sk[j] = ka;
-            si[i] = ib;
-            si[j] = ia;
-            const int32_t pa = sp[i];
-            sp[i] = sp[j];
-            sp[j] = pa;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    nb = n < keep ? n : keep;
-    pend = 0;
-    if (nb == keep) {
-      tkey = sk[keep - 1];
-      tidx = si[keep - 1];
-    }
-    __syncthreads();  // (the threshold is read before anything is appended behind the kept entries)
-  };
+  TopkRank<TOPK_T> rank;
+  rank.init(sk, si, sp, swc, TOPK_CAP, k + 1);  // the k best and the best excluded one (the near-tie test's last pair)
   for (int base = 0; base < cnt; base += TOPK_T) {
     const int p = base + t;
     bool acc = false;
@@ -236,29 +180,13 @@ __global__ __launch_bounds__(TOPK_T) void topk_final_kernel(
       if (s == s) {  // NaN scores are never returned
         key = (uint64_t)__double_as_longlong(s);
         idx = list[p];
-        acc = topk_less(key, idx, tkey, tidx);
+        acc = rank.enters(key, idx);
       }
     }
-    const uint64_t b = __ballot(acc);
-    if (lane == 0) swc[wv] = (int32_t)__popcll(b);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < TOPK_T / 64; ++w) {
-      off += w < wv ? swc[w] : 0;
-      tot += swc[w];
-    }
-    if (nb + pend + tot > TOPK_CAP) merge();  // uniform; afterwards nb <= keep and pend = 0: the chunk fits
-    if (acc) {
-      const int at = nb + pend + off + (int)__popcll(b & ((1ull << lane) - 1));
-      sk[at] = key;
-      si[at] = idx;
-      sp[at] = p;
-    }
-    pend += tot;
-    __syncthreads();
+    rank.push(acc, key, idx, p);
   }
-  if (nb + pend > 0) merge();
+  rank.finish();
+  const int nb = rank.nb;
   const int nout = nb < k ? nb : k;
   // the ranked records; HBX_ACQ_NEAR_TIE: an entry and the next one (the last returned one's next is the
   // best excluded entry, position k) cannot be told apart by the re-score's error bounds

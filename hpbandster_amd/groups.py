@@ -5,6 +5,7 @@ Config #5's loop on the device from end to end::
     gm = groups.fit_groups(X, losses, seg_off, var_type)      # hbx_seg_argsort_ex + hbx_kde_fit
     rows, picks = gm.propose(64, seed, levels)                # hbx_kde_sample_groups + hbx_kde_acquire_groups
     rows, picks = gm.propose(64, seed, levels, requests=S)    # S picks per bracket: hbx_kde_acquire_groups_batch
+    rows, top = gm.propose(64, seed, levels, topk=k)          # the k best of each pool: hbx_kde_acquire_groups_topk
 
 Bracket b owns the rows ``X[seg_off[b]:seg_off[b+1]]``; its good / bad KDEs are the head ``n_good[b]`` / tail
 ``n_bad[b]`` rows of numpy's argsort of its losses (bohb.py:220-246).  The fit's outputs (order, bandwidths, level
@@ -77,6 +78,74 @@ class GroupPicks(object):
         if self.index.ndim == 2:
             return "GroupPicks(B=%d, S=%d, picked=%d)" % (self.index.shape + (int((self.index >= 0).sum()),))
         return "GroupPicks(B=%d, picked=%d)" % (len(self), int((self.index >= 0).sum()))
+
+
+class GroupTopK(object):
+    """The k best candidates of every group's pool (hbx_kde_acquire_groups_topk), ranked by (score, index), from one
+    fetch of the B result blocks: ``count``, ``shortlist``, ``flags`` (int32 [B]; kde.ACQ_* and ACQ_NO_MODEL /
+    ACQ_UNSUPPORTED); ``index`` (int64 [B, k], relative to the group's pool, -1 past ``count``); ``score``,
+    ``pdf_l``, ``pdf_g`` (float64 [B, k], the reference's values bit for bit, NaN past ``count``); ``rel`` (float32
+    [B, k], 0 past ``count``).  ``len()`` is B."""
+    __slots__ = ("k", "count", "shortlist", "flags", "index", "score", "pdf_l", "pdf_g", "rel")
+
+    def __init__(self, B, k):
+        self.k = int(k)
+        self.count = np.zeros(B, dtype=np.int32)
+        self.shortlist = np.zeros(B, dtype=np.int32)
+        self.flags = np.zeros(B, dtype=np.int32)
+        self.index = np.full((B, self.k), -1, dtype=np.int64)
+        self.score = np.full((B, self.k), np.nan)
+        self.pdf_l = np.full((B, self.k), np.nan)
+        self.pdf_g = np.full((B, self.k), np.nan)
+        self.rel = np.zeros((B, self.k), dtype=np.float32)
+
+    @classmethod
+    def from_bytes(cls, b, B, k):
+        """B blocks of 16 + 40 k bytes (include/hbx.h hbx_kde_acquire_groups_topk); the bytes of a block past its
+        ``count`` records are not read."""
+        B, k = int(B), int(k)
+        step = kde.TOPK_HEAD_BYTES + kde.TOPK_REC.itemsize * k
+        raw = np.frombuffer(bytes(b), dtype=np.uint8, count=B * step).reshape(B, step)
+        out = cls(B, k)
+        head = np.ascontiguousarray(raw[:, :kde.TOPK_HEAD_BYTES]).view("<i4").reshape(B, 4)
+        out.count[:], out.shortlist[:], out.flags[:] = head[:, 0], head[:, 1], head[:, 2]
+        if np.any(out.count < 0) or np.any(out.count > k):
+            raise N.HbxError("top-k blocks: a count outside [0, %d]" % k)
+        rec = np.ascontiguousarray(raw[:, kde.TOPK_HEAD_BYTES:]).view(kde.TOPK_REC).reshape(B, k)
+        live = np.arange(k)[None, :] < out.count[:, None]
+        for name in ("index", "score", "pdf_l", "pdf_g", "rel"):
+            getattr(out, name)[live] = rec[name][live]
+        return out
+
+    def __len__(self):
+        return int(self.count.shape[0])
+
+    def top(self, b):
+        """Group b's entries as a kde.TopK."""
+        c = int(self.count[b])
+        return kde.TopK(self.index[b, :c].copy(), self.score[b, :c].copy(), self.pdf_l[b, :c].copy(),
+                        self.pdf_g[b, :c].copy(), self.rel[b, :c].copy(), int(self.shortlist[b]), int(self.flags[b]))
+
+    def rows(self, cands):
+        """The ranked candidate rows on the host, float64 [B, k, D]; NaN rows past ``count``.  ``cands``: [B, C, D],
+        numpy or a device tensor."""
+        if len(cands.shape) != 3 or int(cands.shape[0]) != len(self):
+            raise N.HbxError("candidates %s do not match %d groups" % (tuple(cands.shape), len(self)))
+        D = int(cands.shape[2])
+        out = np.full((len(self), self.k, D), np.nan)
+        bi, ji = np.nonzero(self.index >= 0)
+        if bi.size:
+            ci = self.index[bi, ji]
+            if _is_tensor(cands):
+                torch = kde._torch()
+                out[bi, ji] = cands[torch.from_numpy(bi).to(cands.device), torch.from_numpy(ci).to(cands.device)] \
+                    .cpu().numpy()
+            else:
+                out[bi, ji] = np.asarray(cands, dtype=np.float64)[bi, ci]
+        return out
+
+    def __repr__(self):
+        return "GroupTopK(B=%d, k=%d, returned=%d)" % (len(self), self.k, int(self.count.sum()))
 
 
 class GroupModel(object):
@@ -213,9 +282,56 @@ class GroupModel(object):
                 return res
             return GroupPicks.from_bytes(res.cpu().numpy().tobytes(), self.B, S)
 
-    def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, requests=None):
+    def workspace_bytes_topk(self, C, k):
+        return int(N.lib().hbx_kde_groups_topk_workspace_bytes(self.B, int(C), int(k), self.D))
+
+    def acquire_topk(self, cands, k, stream=None, workspace=None, sync=True):
+        """Per group the first min(k, F) entries of the ascending order by (score, index) over the F candidates of
+        its own pool ``cands[b]`` whose score is not NaN (hbx_kde_acquire_groups_topk); entry 0 is ``acquire``'s
+        pick.  ``cands``: [B, C, D] float64, numpy or a device tensor; 1 <= k <= kde.TOPK_MAX_K, k > C is legal.
+        Returns GroupTopK, or with ``sync=False`` the device tensor of the B result blocks (uint8 [B, 16 + 40 k])."""
+        torch = kde._torch()
+        k = int(k)
+        if k < 1 or k > kde.TOPK_MAX_K:
+            raise ValueError("k must be in [1, %d], got %d" % (kde.TOPK_MAX_K, k))
+        with N.on_device(self.device, stream):
+            if _is_tensor(cands):
+                cd = cands
+                if cd.dtype != torch.float64 or not cd.is_contiguous():
+                    raise N.HbxError("candidate tensor must be contiguous float64 [B, C, D]")
+            else:
+                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
+            if cd.dim() != 3 or int(cd.shape[0]) != self.B or int(cd.shape[2]) != self.D:
+                raise N.HbxError("candidates must be [%d, C, %d], got %s" % (self.B, self.D, tuple(cd.shape)))
+            C = int(cd.shape[1])
+            wsb = self.workspace_bytes_topk(C, k)
+            if wsb < 0:
+                raise N.HbxError("B * C = %d * %d exceeds int32" % (self.B, C))
+            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
+            if ws.numel() < wsb:
+                raise N.HbxError("workspace too small")
+            res = torch.empty((self.B, kde.TOPK_HEAD_BYTES + kde.TOPK_REC.itemsize * k), dtype=torch.uint8,
+                              device=self.device)
+            N.check(N.lib().hbx_kde_acquire_groups_topk(
+                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
+                N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
+                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), C, k, N.ptr(res), N.ptr(ws), ws.numel(),
+                N.stream_handle(stream, self.device)))
+            if not sync:
+                return res
+            return GroupTopK.from_bytes(res.cpu().numpy().tobytes(), self.B, k)
+
+    def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, requests=None, topk=None):
         """sample + acquire: (rows [B, D] host float64 -- NaN where a group has no pick --, GroupPicks).
-        With ``requests=S``: sample + acquire_requests, (rows [B, S, D], GroupPicks of shape [B, S])."""
+        With ``requests=S``: sample + acquire_requests, (rows [B, S, D], GroupPicks of shape [B, S]).
+        With ``topk=k``: sample + acquire_topk, (rows [B, k, D] -- NaN rows past a group's count --, GroupTopK);
+        not together with ``requests``."""
+        if topk is not None:
+            if requests is not None:
+                raise N.HbxError("propose: topk and requests cannot be combined")
+            cands, _ = self.sample(C, seed, levels, bandwidth_factor, counter_base, stream=stream)
+            top = self.acquire_topk(cands, topk, stream=stream)
+            return top.rows(cands), top
         if requests is None:
             cands, _ = self.sample(C, seed, levels, bandwidth_factor, counter_base, stream=stream)
             picks = self.acquire(cands, stream=stream)

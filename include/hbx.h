@@ -24,6 +24,8 @@
  *                                      one call, straight from hbx_kde_fit's device outputs)
  *   hbx_kde_acquire_groups_batch    <- bohb.py:124-169 once per get_config request of a stage, HB_iteration.py:136-138
  *                                      (S requests per bracket, B brackets, one call)
+ *   hbx_kde_acquire_groups_topk     <- bohb.py:124-169 per bracket, the scores ranked: the k best candidates of
+ *                                      every bracket's pool by (score, index), one call
  *   hbx_kde_sample_groups           <- bohb.py:133-147 per bracket (the candidates of B brackets in one call)
  *   hbx_kde_logpdf                  <- KDEMultivariate.pdf (kernel_density.py:162-196), fp32 log domain
  *   hbx_kde_pdf_exact               <- KDEMultivariate.pdf, fp64, reference operation order
@@ -285,6 +287,32 @@ int hbx_kde_acquire_groups_batch(const double* X, int32_t D, const int64_t* seg_
                                  const int32_t* nlev_good, const int32_t* nlev_bad,
                                  const double* cand, int64_t S, int64_t C, void* results,
                                  void* workspace, int64_t ws_bytes, void* stream);
+/* Grouped top-k: the k best candidates of every bracket's own pool in one call -- hbx_kde_acquire_topk's answer for
+ * each of hbx_kde_acquire_groups' B groups.  The model arguments are hbx_kde_acquire_groups', unchanged; cand:
+ * f64[B][C][D]; 1 <= k <= HBX_TOPK_MAX_K, k > C is legal.  results: B blocks of hbx_kde_topk_result_bytes(k) =
+ * 16 + 40 k bytes, block b at b * hbx_kde_topk_result_bytes(k), each with hbx_kde_acquire_topk's layout: header
+ * {i32 count, i32 shortlist, i32 flags, i32 k}, then `count` ranked records {i64 index, f64 score, f64 pdf_l,
+ * f64 pdf_g, f32 rel, i32 0}; the bytes of a block past its `count` records are unspecified.  Block b holds the first
+ * min(k, F) entries of the ascending order by (score, index) over the F candidates of cand[b] whose score is not NaN:
+ * index relative to the pool, score and both pdfs the reference's fp64 values bit for bit, entry 0 =
+ * hbx_kde_acquire_groups' record for the group (index, score, pdfs).  count = 0 when no score is rankable; groups
+ * without a model / with an unsupported dim: count = 0 and HBX_ACQ_NO_MODEL / HBX_ACQ_UNSUPPORTED in flags, never an
+ * error return.  HBX_ACQ_OVERFLOW: every candidate of the group was re-scored.  HBX_ACQ_NEAR_TIE: two adjacent
+ * returned entries, or the last returned one and the best re-scored one left out, lie within each other's `rel` --
+ * or the last returned entry scores exactly 1 and candidates whose score is certainly exactly 1 were not listed
+ * (only the first k of them by index are re-scored: csrc/hbx_groups.hip has the argument).
+ * Two launches on `stream` (hbx_kde_acquire_groups' screen, then one select block per group), no host
+ * synchronisation, no allocation, no per-group host work.  B == 0: nothing to do; C == 0: B headers {0, 0, 0, k}.
+ * B * C beyond int32, k out of range, null pointers, misalignment (workspace 16, results 8 bytes) or a short
+ * workspace: HBX_ERR_ARG (hbx_last_error).  workspace: hbx_kde_groups_topk_workspace_bytes(B, C, k, D) bytes (the
+ * grouped call's plus 16 bytes per candidate for the re-scored pdfs; -1 for arguments out of range). */
+int64_t hbx_kde_groups_topk_workspace_bytes(int64_t B, int64_t C, int32_t k, int32_t D);
+int hbx_kde_acquire_groups_topk(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                const double* bw_good, const double* bw_bad,
+                                const int32_t* nlev_good, const int32_t* nlev_bad,
+                                const double* cand, int64_t C, int32_t k, void* results,
+                                void* workspace, int64_t ws_bytes, void* stream);
 /* The matching sampler: C candidates per group around its good KDE's rows (hbx_kde_sample's rule).  Candidate
  * (b, i) is byte-equal to what hbx_kde_sample draws for group b's good KDE (tab = NULL) at candidate index i of a
  * call with counter_base + b * C.  cands: f64[B][C][D] (16-byte aligned when D is even); domain_err: nullable

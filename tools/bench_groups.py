@@ -17,6 +17,11 @@ Writes one JSON document (default profiles/groups/bench_groups.json) and prints 
 
 times S get_config requests per bracket instead (requests_bench below): the batched call under each screen against S
 one-request calls; prints one JSON line and writes it only where --out says.
+
+    python tools/bench_groups.py --topk K [--out FILE]
+
+times the k best candidates per bracket (topk_bench below): hbx_kde_acquire_groups_topk against the batched call with
+S = K pools and the per-bracket acquire_topk loop; prints one JSON line and writes it only where --out says.
 """
 import argparse
 import json
@@ -117,6 +122,103 @@ def requests_bench(a, gm, L, sh, lvd):
     return 0 if a.loop_only or out["requests_agreeing_with_loop"] == R else 1
 
 
+def topk_bench(a, gm, L, sh, lvd):
+    """--topk K: K configurations per bracket out of one call.
+      topk         hbx_kde_acquire_groups_topk over one pool of C candidates per bracket, k = K
+      batch        hbx_kde_acquire_groups_batch with S = K pools per bracket: the device route to K picks per
+                   bracket the library offered before (it screens K pools where the top-k screens one)
+      acquire      hbx_kde_acquire_groups over the same pool (one pick: the screen both share plus its select)
+      loop         per bracket kde.fit_pair_from_rows + KDEPair.acquire_topk on --sub subsampled brackets (wall
+                   clock, synchronised), extrapolated to B; its ranked entries are compared with topk's
+    and reports the shortlist per group (mean, maximum) and the share of groups flagged NEAR_TIE."""
+    dev = gm.device
+    B, K, C, D = gm.B, a.topk, a.C, gm.D
+    model = (N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
+             N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad))
+    pool = torch.empty((B, K * C, D), dtype=torch.float64, device=dev)
+    derr = torch.empty((B, K * C), dtype=torch.uint8, device=dev)
+    N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
+                                    N.ptr(gm.bw_good), N.ptr(lvd), 3.0, S.SEED_CAND, 0, 0, K * C, N.ptr(pool),
+                                    N.ptr(derr), sh))
+    cands_s = pool.view(B, K, C, D)
+    cands = cands_s[:, 0].contiguous()  # the top-k's one pool: request 0's
+    step = kde.TOPK_HEAD_BYTES + kde.TOPK_REC.itemsize * K
+    wsk = int(L.hbx_kde_groups_topk_workspace_bytes(B, C, K, D))
+    wsb = int(L.hbx_kde_groups_batch_workspace_bytes(B, K, C, D))
+    ws1 = int(L.hbx_kde_groups_workspace_bytes(B, C, D))
+    ws = torch.empty(max(wsk, wsb, ws1), dtype=torch.uint8, device=dev)
+    res_k = torch.empty((B, step), dtype=torch.uint8, device=dev)
+    res_s = torch.empty((B, K, kde.RESULT_BYTES), dtype=torch.uint8, device=dev)
+    res_1 = torch.empty((B, kde.RESULT_BYTES), dtype=torch.uint8, device=dev)
+
+    def topk():
+        N.check(L.hbx_kde_acquire_groups_topk(*model, N.ptr(cands), C, K, N.ptr(res_k), N.ptr(ws), wsk, sh))
+
+    def batch():
+        N.check(L.hbx_kde_acquire_groups_batch(*model, N.ptr(cands_s), K, C, N.ptr(res_s), N.ptr(ws), wsb, sh))
+
+    def acquire():
+        N.check(L.hbx_kde_acquire_groups(*model, N.ptr(cands), C, N.ptr(res_1), N.ptr(ws), ws1, sh))
+
+    ms_topk, ms_batch, ms_acq = timed(topk, a.reps), timed(batch, a.reps), timed(acquire, a.reps)
+    picks = groups.GroupPicks.from_bytes(res_1.cpu().numpy().tobytes(), B)
+    batch()
+    picks_s = groups.GroupPicks.from_bytes(res_s.cpu().numpy().tobytes(), B, K)
+    topk()
+    top = groups.GroupTopK.from_bytes(res_k.cpu().numpy().tobytes(), B, K)
+    first_ok = int(np.sum((top.index[:, 0] == picks.index) & (top.score[:, 0] == picks.score)))
+    # the per-bracket loop on a subsample
+    sub = np.unique(np.linspace(0, B - 1, min(a.sub, B)).astype(np.int64))
+    ng, nb = int(gm.n_good[0]), int(gm.n_bad[0])
+    bwg, bwb = gm.bandwidths()
+    nlg, nlb = gm.nlev_good.cpu().numpy(), gm.nlev_bad.cpu().numpy()
+    order_h = gm.order.cpu().numpy()
+    seg = gm.seg_host
+    vts = gm.var_type
+    t_prep, t_acq, agree = [], [], 0
+    for it, b in enumerate(np.concatenate([sub[:3], sub])):  # the first three again as warm-up
+        s, e = int(seg[b]), int(seg[b + 1])
+        Xb = gm.X[s:e].cpu().numpy()
+        o = order_h[s:e]
+        cb = cands[b]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pair = kde.fit_pair_from_rows(Xb, o[:ng], o[e - s - nb:], vts, bwg[b], bwb[b], nlg[b], nlb[b], device=dev)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        r = pair.acquire_topk(cb, K)
+        t2 = time.perf_counter()
+        if it >= 3:
+            t_prep.append(t1 - t0)
+            t_acq.append(t2 - t1)
+            c = int(top.count[b])
+            agree += int(r.count == c and np.array_equal(r.index, top.index[b, :c]) and
+                         np.array_equal(r.score, top.score[b, :c]) and np.array_equal(r.pdf_l, top.pdf_l[b, :c]) and
+                         np.array_equal(r.pdf_g, top.pdf_g[b, :c]))
+    prep_ms, acq_ms = 1e3 * float(np.mean(t_prep)), 1e3 * float(np.mean(t_acq))
+    out = {"workload": "grouped_topk_b%d_n%d_d32_24c8u_c%d_k%d" % (B, a.n, C, K),
+           "device": torch.cuda.get_device_name(0), "reps": a.reps, "k": K, "library": N.LIB_PATH,
+           "topk_ms": ms_topk, "batch_s_eq_k_ms": ms_batch, "acquire_one_pick_ms": ms_acq,
+           "select_over_one_pick_ms": ms_topk - ms_acq,
+           "mean_shortlist": float(top.shortlist.mean()), "max_shortlist": int(top.shortlist.max()),
+           "one_pick_mean_shortlist": float(picks.shortlist.mean()),
+           "batch_mean_shortlist_per_request": float(picks_s.shortlist.mean()),
+           "returned_per_group_mean": float(top.count.mean()),
+           "near_tie_share": float(((top.flags & 2) != 0).mean()),
+           "overflow_groups": int(((top.flags & 1) != 0).sum()),
+           "entry0_equals_one_pick": first_ok, "workspace_bytes": wsk,
+           "loop": {"subsample": int(sub.size), "prepare_ms_per_group": prep_ms, "acquire_topk_ms_per_group": acq_ms,
+                    "loop_ms_extrapolated": B * (prep_ms + acq_ms), "blocks_agree": agree},
+           "speedup_vs_batch": ms_batch / ms_topk}
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+            f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+    return 0 if agree == sub.size and first_ok == B else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=10000)
@@ -128,6 +230,7 @@ def main(argv=None):
     ap.add_argument("--requests", type=int, default=1, help="S get_config requests per bracket (requests_bench)")
     ap.add_argument("--loop-only", action="store_true",
                     help="time only the S one-request calls (what a library without the batched call offers)")
+    ap.add_argument("--topk", type=int, default=0, help="the K best candidates per bracket (topk_bench)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     L = N.lib()
@@ -145,6 +248,8 @@ def main(argv=None):
     seg = np.arange(B + 1, dtype=np.int64) * n
     gm = groups.fit_groups(X, losses, seg, vts, device=dev)
     sh = N.stream_handle(None, dev)
+    if a.topk:
+        return topk_bench(a, gm, L, sh, torch.tensor(levels, dtype=torch.int32, device=dev))
     if a.requests > 1 or a.loop_only:
         return requests_bench(a, gm, L, sh, torch.tensor(levels, dtype=torch.int32, device=dev))
     a.out = a.out or os.path.join(ROOT, "profiles", "groups", "bench_groups.json")
