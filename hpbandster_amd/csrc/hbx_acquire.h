@@ -100,16 +100,20 @@ int acq_score(const AcqPlan& plan, const KdePairRef& p, const AcqWs& a, const Sc
               ScoreResult* out);
 // (2') instead of (2) for a single acquisition without ln-pdf outputs whose KDEs both run the coarse 32x32
 // instance: the staged scoring (hbx_staged.hip) -- l for every candidate, g only where l alone does not rule the
-// candidate out; the others' a.eg holds the marker HBX_EST_NOT_EVAL, which the combine kernel reads as an
-// l-only interval.  It leaves the rescue of marked g estimates to the combine kernel (its <_, true> instance).
+// candidate out; without the short tail (below) the others' a.eg holds the marker HBX_EST_NOT_EVAL, which the
+// combine kernel reads as an l-only interval, and the rescue of marked g estimates is left to that kernel (its
+// <_, true> instance).
 // events: [0] at the first scoring launch's start, [1] and [2] after the last one.
 // Whether a call stages: HBX_STAGED (hbx_staged_mode, hbx_common.h) and, by size, HBX_STAGED_MIN_PAIRS.
 #ifndef HBX_STAGED_MIN_PAIRS
 #define HBX_STAGED_MIN_PAIRS 1e9  // candidates x observations from which an acquisition stages when HBX_STAGED is unset
 #endif
+// tail (HBX_STAGED_TAIL, hbx_common.h): the short tail -- the call also leaves every candidate's a.lo, a.U,
+// a.first1, the overflow flag, the shortlist a.list / a.count and the marker count zeroed, the unevaluated
+// candidates' a.eg unwritten: no combine and no shortlist launch behind it.
 bool acq_staged_supported(const AcqPlan& plan);
 int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
-                     hipEvent_t* ev, hipStream_t s);
+                     hipEvent_t* ev, hipStream_t s, bool tail);
 // exact-only acquisitions instead of a combine / bounds pass: every candidate joins the re-score
 int acq_exact_only_init(int64_t Nc, uint32_t seg, const AcqWs& a, hipStream_t s);
 // (3) the exact fp64 re-score of the shortlist a.list / a.count (scan, a single acquisition of at most

@@ -46,6 +46,10 @@ static inline int hbx_staged_mode() {
   const int v = atoi(e);
   return v == 0 ? 0 : v == 2 ? 2 : 1;
 }
+// HBX_STAGED_TAIL=0: a staged acquisition runs its earlier launch sequence behind the scoring (second merge,
+// combine, shortlist, exact, final as launches of their own) instead of the short tail (hbx_staged.hip); for
+// tests and A/B runs
+static inline bool hbx_staged_tail() { return hbx_switch_on("HBX_STAGED_TAIL"); }
 
 // ------------------------------------------------------------------------------------------
 // KDE model parameters, one block per KDE (good or bad).  Written on the device by

@@ -679,8 +679,10 @@ static int acquire_impl(const void* pair, const AcqCall& c) {
   const int stg = (!batch_res && fast && Nc > 0) ? hbx_staged_mode() : 0;
   const bool staged = stg && acq_staged_supported(plan) &&
                       (stg == 2 || (double)Nc * (double)p.nmax >= HBX_STAGED_MIN_PAIRS);
+  // the short tail (HBX_STAGED_TAIL): the staged launches leave the intervals and the shortlist as well
+  const bool tail = staged && hbx_staged_tail();
   if (staged) {
-    rc = acq_score_staged(plan, p, cand, Nc, a, ev, s);
+    rc = acq_score_staged(plan, p, cand, Nc, a, ev, s, tail);
     rescue_inline = true;  // marked g estimates of the list launches: the combine kernel re-scores them
   } else {
     // splits for the pick only (reported ln-pdfs stay unsplit); a batched call's rescue pass is always a launch
@@ -697,7 +699,7 @@ static int acquire_impl(const void* pair, const AcqCall& c) {
     if (plan.exact_only) {
       rc = acq_exact_only_init(Nc, sg, a, s);
       if (rc) return rc;
-    } else {
+    } else if (!tail) {
       const CombineRescue rs{cand, p.D, p.Pg(), p.Pb(), a.rescue};
       // the rescue pass left to the combine kernel: its instance by the sign bit (a pair launch: one for both KDEs)
       const bool sgn = KdeVariant::decode(p.variant_good).has_neg;
@@ -709,8 +711,9 @@ static int acquire_impl(const void* pair, const AcqCall& c) {
       HBX_LAUNCH_CHECK();
     }
     // a single acquisition of few candidates: the exact re-score's blocks shortlist for themselves
-    const bool scan = !batch_res && Nc <= EXACT_SCAN_MAX;
-    if (!scan) {
+    // (the short tail of a staged acquisition has built the shortlist already)
+    const bool scan = !batch_res && Nc <= EXACT_SCAN_MAX && !tail;
+    if (!scan && !tail) {
       hipLaunchKernelGGL(kde_shortlist_kernel, grid, dim3(256), 0, s, a.lo, Nc, sg, a.U, a.flags, a.list, a.count,
                          batch_res ? a.segcnt : (int32_t*)nullptr, a.first1, a.rescue);
       HBX_LAUNCH_CHECK();

@@ -334,8 +334,17 @@ typedef void (*logpdf_list_fn)(const double*, int32_t, KdeListArgs);
 
 // the staged acquisition's state words (hbx_staged.hip), in the result slot's padding right behind the record
 // (WsLayout::stage): whether the call staged, Lmax and U_seed as order-preserving uints, the seed and survivor
-// counts.  They stay in the workspace after the call (hbx_kde_acquire_stats).
-enum { HBX_ST_FLAG = 0, HBX_ST_LMAX, HBX_ST_USEED, HBX_ST_NSEED, HBX_ST_NSURV, HBX_ST_WORDS };
+// counts, the length of the short tail's preliminary shortlist.  They stay in the workspace after the call
+// (hbx_kde_acquire_stats).
+enum {
+  HBX_ST_FLAG = 0,
+  HBX_ST_LMAX,
+  HBX_ST_USEED,
+  HBX_ST_NSEED,
+  HBX_ST_NSURV,
+  HBX_ST_NPRE,
+  HBX_ST_WORDS
+};
 
 // a single acquisition's state before its combine / shortlist / exact / final steps; res is the workspace's
 // result slot (256 bytes: the state words of a staged call follow the record)
@@ -347,6 +356,7 @@ __device__ __forceinline__ void acq_init_state(uint32_t* U, int32_t* count, int3
   st[HBX_ST_USEED] = hbx_f2ord(INFINITY);
   st[HBX_ST_NSEED] = 0;
   st[HBX_ST_NSURV] = 0;
+  st[HBX_ST_NPRE] = 0;
   *U = hbx_f2ord(INFINITY);
   *first1 = INT32_MAX;
   *count = 0;

@@ -11,20 +11,32 @@
 //   1 score l      the good KDE's coarse 32x32 pair kernel over all candidates (observation splits as in the
 //                  fused launch), its first workgroup initialising the acquisition's and the stages' state
 //     staged_l     rescue of marked candidates, merge of the splits, [llo, lhi] per candidate (est_interval),
-//                  lhi kept in a.lo until the combine overwrites it, Lmax = max llo (ordered-uint atomic max)
+//                  lhi kept in a.lo until stage 4 / 5 overwrites it, Lmax = max llo (ordered-uint atomic max)
 //   2 seed         every candidate with lhi >= Lmax - ln 4 joins the seed list (at most the list capacity;
-//                  the rest fall through to stage 4); every other candidate's g estimate becomes the marker
-//                  "g not evaluated" (err = HBX_EST_NOT_EVAL); NaN-l candidates are never seeded
+//                  the rest fall through to stage 4); NaN-l candidates are never seeded.  (HBX_STAGED_TAIL=0:
+//                  every other candidate's g estimate becomes the marker "g not evaluated", err =
+//                  HBX_EST_NOT_EVAL, for the combine kernel)
 //   3 score seeds  the bad KDE's list instance (kde_logpdf_h32_list_kernel: candidates through an index list
 //                  with a device-side count, observation splits into a compact [split][capacity] area), then
 //                  staged_merge: splits merged, scattered to a.eg, U_seed = min over seeds of the score
 //                  interval's upper end
 //   4 survivors    every unseeded candidate with C - max(lhi, C) <= U_seed (C = ln 1e-8; the shortlist's own
 //                  '<=', so ties survive) joins the survivor list and is scored like the seeds (more
-//                  survivors than the split capacity: one unsplit launch over the list, scattering itself)
-//   5 combine      kde_combine_kernel takes a marked candidate's interval from l alone
-//                  (score_interval_l_only: slo = C - max(lhi, C), shi = +inf); everything from there on --
-//                  shortlist, exact re-score, final argmin -- is the unstaged path's code.
+//                  survivors than the split capacity: one unsplit launch over the list, scattering itself).
+//                  The same pass turns every unseeded candidate's a.lo entry from lhi into its l-only lower
+//                  score bound C - max(lhi, C) (score_interval_l_only's slo; NaN stays NaN) and raises the
+//                  overflow flag where lhi > 700: a pruned candidate's whole contribution to what follows
+//   5 tail         staged_tail_kernel, over the evaluated candidates only (seeds and survivors): the
+//                  survivors' partials merged and scattered, marked g estimates re-scored, score_interval as
+//                  the combine kernel computes it -> a.lo, U, first1, the flag, and a preliminary shortlist
+//                  against an upper bound of U; staged_shortlist_kernel (one block) filters that list with
+//                  the final U.  No pass over all candidates, and nothing reads the g estimate of an
+//                  unevaluated candidate (the final kernel's score_rel takes it only for a signed KDE, and
+//                  staged pairs are unsigned), so the marker is not written.  Then the unstaged path's exact
+//                  re-score and final argmin.
+//                  HBX_STAGED_TAIL=0 (tests, A/B): the earlier sequence instead -- the survivors' merge, then
+//                  kde_combine_kernel over all candidates (a marked candidate's interval from l alone) and
+//                  kde_shortlist_kernel over all candidates.  Same functions, same operands: same bits.
 //
 // Why the pick is unchanged.  For a pruned candidate the unstaged path computes
 //   slo = max(glo, C) - max(lhi, C) >= C - max(lhi, C) > U_seed >= U,
@@ -133,11 +145,12 @@ __device__ __forceinline__ int32_t staged_reserve(int n, int32_t* __restrict__ c
   return base + woff + incl - n;
 }
 
-// Seeds: lhi >= Lmax - ln 4, up to cap.  A seeded candidate's lhi becomes NaN (stage 4 skips it); every other
-// candidate's g estimate becomes the marker.
+// Seeds: lhi >= Lmax - ln 4, up to cap.  A seeded candidate's lhi becomes NaN (stage 4 skips it); mark_rest (the
+// combine kernel follows): every other candidate's g estimate becomes the marker.
 __global__ __launch_bounds__(256) void staged_seed_kernel(float* __restrict__ lhi, int64_t Nc,
                                                           KdeEst* __restrict__ eg, int32_t* __restrict__ seeds,
-                                                          int32_t cap, uint32_t* __restrict__ stage) {
+                                                          int32_t cap, uint32_t* __restrict__ stage,
+                                                          int32_t mark_rest) {
   const float thr = hbx_ord2f(stage[HBX_ST_LMAX]) - HBX_LN4f;
   bool f[STAGED_PT];
   int n = 0;
@@ -166,7 +179,7 @@ __global__ __launch_bounds__(256) void staged_seed_kernel(float* __restrict__ lh
       ++off;
     }
     if (seeded) lhi[i] = NAN;
-    else eg[i] = none;
+    else if (mark_rest) eg[i] = none;  // (uniform; the short tail reads no g estimate of an unevaluated candidate)
   }
 }
 
@@ -209,9 +222,13 @@ __global__ __launch_bounds__(256) void staged_merge_kernel(const KdeEst* __restr
 }
 
 // Survivors: unseeded, l not NaN, l-only lower score bound <= U_seed.
-__global__ __launch_bounds__(256) void staged_survivor_kernel(const float* __restrict__ lhi, int64_t Nc,
+// flags (the short tail; null: the combine kernel follows): lhi[i], which is a.lo, becomes the l-only interval's
+// lower end C - max(lhi, C) in place -- score_interval_l_only's slo from the same lhi -- NaN staying NaN (l is NaN,
+// or a seed, whose entry the tail kernel writes), and lhi > 700 raises the overflow flag as that interval's `of`.
+__global__ __launch_bounds__(256) void staged_survivor_kernel(float* __restrict__ lhi, int64_t Nc,
                                                               int32_t* __restrict__ surv,
-                                                              uint32_t* __restrict__ stage) {
+                                                              uint32_t* __restrict__ stage,
+                                                              int32_t* __restrict__ flags) {
   const float U = hbx_ord2f(stage[HBX_ST_USEED]);
   const float C = (float)HBX_LN_CLAMP;
   bool f[STAGED_PT];
@@ -223,6 +240,10 @@ __global__ __launch_bounds__(256) void staged_survivor_kernel(const float* __res
     if (i < Nc) {
       const float h = lhi[i];
       f[r] = h == h && (C - fmaxf(h, C)) <= U;
+      if (flags && h == h) {  // (flags: uniform)
+        lhi[i] = C - fmaxf(h, C);
+        if (h > 700.f) atomicOr(flags, 1);
+      }
     }
     n += f[r] ? 1 : 0;
   }
@@ -235,6 +256,222 @@ __global__ __launch_bounds__(256) void staged_survivor_kernel(const float* __res
   if (blockIdx.x == 0 && threadIdx.x == 0) stage[HBX_ST_FLAG] = 1;  // this call staged (hbx_kde_acquire_stats)
 }
 
+// The short tail (HBX_STAGED_TAIL): what the second merge, the combine and the shortlist launches did, in two
+// launches over the evaluated candidates only -- the seeds (their g estimates merged and scattered by the first merge) and the
+// survivors (their split partials merged here; an unsplit survivor launch scattered its own).  Every other
+// candidate's interval is a function of lhi alone and the survivor pass has written it.
+struct StagedTailArgs {
+  const KdeEst* part;  // the survivor launch's split partials [ns][cap]
+  int32_t cap, ns;
+  const int32_t* seeds;
+  const int32_t* surv;
+  int64_t Nc;
+  const double* cand;
+  int32_t D;
+  const KdeParams* Pb;
+  const KdeEst* el;
+  KdeEst* eg;
+  float* lo;
+  uint32_t* U;
+  int32_t* flags;
+  int32_t* first1;
+  int32_t* list;
+  int32_t* count;
+  int32_t* rescue_cnt;
+  uint32_t* stage;
+};
+
+// agent-scope loads of words other blocks of the same launch lower (never through the scalar or a stale vector cache)
+__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int32_t ld_agent(const int32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Entry k of the evaluated candidates (seeds first, then survivors); a block owns 1024 consecutive entries, TAIL_PT
+// per thread (their loads in flight together, their indices and lower bounds kept in registers), and the blocks
+// past the last entry exit at once:
+//   1  its g estimate: merged from the partials (a marker in any: the marker) or as scattered; a marked one
+//      re-scored (kde_rescue_one, the RESCUE combine's call) and stored; score_interval(el, eg) as the combine
+//      computes it: lo[i] (NaN for a certain tie), U, first1 and the overflow flag lowered / raised per wave, an
+//      atomic only where it changes the value
+//   2  the preliminary shortlist: its entries with lo <= u, u an upper bound of the final U (U only falls: U_seed,
+//      and U as read after the block's atomics), and each certain tie that lowered first1; slots by one atomic
+//      per block.  The final U is known only when every block has run: staged_shortlist_kernel.
+// (Measured, profiles/staged_tail: one launch for both -- a fence and a ticket per block, the last block to
+// finish filtering -- takes 76-97 us where every one of 1e6 candidates is evaluated, against 26 us for the three
+// launches it replaced; the device-scope release of each of its blocks is what costs.  Two launches need none.)
+#define TAIL_THREADS 1024  // of the one-block shortlist kernel
+#define TAIL_PT 4
+__global__ __launch_bounds__(256) void staged_tail_kernel(StagedTailArgs t) {
+  constexpr int TAIL_THREADS_A = 256;
+  constexpr int NW = TAIL_THREADS_A / 64;
+  __shared__ int32_t swc[NW];
+  __shared__ uint32_t pbase;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int64_t nseed = (int32_t)t.stage[HBX_ST_NSEED], nsurv = (int32_t)t.stage[HBX_ST_NSURV];
+  if (nseed > t.cap) nseed = t.cap;
+  if (nsurv > t.Nc) nsurv = t.Nc;
+  const bool split = nsurv <= t.cap;  // else the unsplit launch scattered its estimates itself
+  const int64_t total = nseed + nsurv;
+  constexpr int64_t EPB = (int64_t)TAIL_PT * TAIL_THREADS_A;
+  const int64_t nwork = (total + EPB - 1) / EPB;  // (<= the grid, sized for Nc + cap entries)
+  if (blockIdx.x >= nwork) return;  // no entries
+  const int32_t nres = *t.rescue_cnt;  // markers counted by the scoring launches (a hint, as in the combine)
+  // 1
+  int32_t idx[TAIL_PT];
+  KdeEst ea[TAIL_PT], eb[TAIL_PT];
+  float slo[TAIL_PT];
+#pragma unroll
+  for (int r = 0; r < TAIL_PT; ++r) {
+    const int64_t k = (int64_t)blockIdx.x * EPB + r * TAIL_THREADS_A + threadIdx.x;
+    idx[r] = -1;
+    if (k < total) idx[r] = k < nseed ? t.seeds[k] : t.surv[k - nseed];
+  }
+#pragma unroll
+  for (int r = 0; r < TAIL_PT; ++r) {
+    const int64_t k = (int64_t)blockIdx.x * EPB + r * TAIL_THREADS_A + threadIdx.x;
+    if (idx[r] < 0) continue;
+    ea[r] = t.el[idx[r]];
+    if (k < nseed || !split) eb[r] = t.eg[idx[r]];
+  }
+  float h = INFINITY;
+  int32_t f1 = INT32_MAX;
+  bool of = false;
+#pragma unroll
+  for (int r = 0; r < TAIL_PT; ++r) {
+    const int64_t k = (int64_t)blockIdx.x * EPB + r * TAIL_THREADS_A + threadIdx.x;
+    slo[r] = NAN;
+    if (idx[r] < 0) continue;
+    const int64_t i = idx[r];
+    bool store = false;
+    if (!(k < nseed || !split)) {
+      const int64_t ks = k - nseed;
+      bool mark = false;
+      for (int q = 0; q < t.ns; ++q) mark = mark || t.part[(int64_t)q * t.cap + ks].err == -1.f;
+      eb[r] = {0.f, -INFINITY, -1.f, 0.f};
+      if (!mark) eb[r] = merge_splits(t.part, t.cap, ks, t.ns);
+      store = true;
+    }
+    if (nres != 0 && eb[r].err == -1.f) {  // rare
+      eb[r] = kde_rescue_one<0, false, true>(t.cand, i, t.D, t.Pb);
+      store = true;
+    }
+    if (store) t.eg[i] = eb[r];
+    const ScoreIv v = score_interval(ea[r], eb[r]);
+    slo[r] = v.one ? NAN : v.slo;
+    t.lo[i] = slo[r];
+    if (!v.lnan) h = fminf(h, v.shi);
+    if (v.one && (int32_t)i < f1) f1 = (int32_t)i;
+    of = of || v.of;
+  }
+  float hw = h;
+  int32_t fw = f1;
+  for (int o = 32; o > 0; o >>= 1) {
+    hw = fminf(hw, __shfl_xor(hw, o));
+    fw = min(fw, __shfl_xor(fw, o));
+  }
+  const bool ofw = __ballot(of) != 0;
+  bool lowered = false;  // lane 0: the wave's first certain tie lowered first1
+  if (lane == 0) {
+    const uint32_t o = hbx_f2ord(hw);
+    if (hw < INFINITY && o < ld_agent(t.U)) atomicMin(t.U, o);
+    if (fw != INT32_MAX && fw < ld_agent(t.first1)) lowered = atomicMin(t.first1, fw) > fw;
+    if (ofw) atomicOr(t.flags, 1);
+  }
+  lowered = __shfl(lowered ? 1 : 0, 0) != 0;
+  // 2 (behind a barrier: U has this block's minima, and those of the blocks that run at its pace)
+  __syncthreads();
+  const float useed = hbx_ord2f(t.stage[HBX_ST_USEED]);  // (final since the first merge)
+  const float u = fminf(useed, hbx_ord2f(ld_agent(t.U)));
+  int n = 0;
+#pragma unroll
+  for (int r = 0; r < TAIL_PT; ++r) {
+    const float l = slo[r];
+    if (!(idx[r] >= 0 && ((l == l && l <= u) || (lowered && idx[r] == fw)))) idx[r] = -1;
+    n += idx[r] >= 0 ? 1 : 0;
+  }
+  {  // the block's slots: one atomic per block, as staged_reserve
+    int incl = n;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) swc[wv] = incl;
+    __syncthreads();
+    int off = incl - n, tot = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      off += w < wv ? swc[w] : 0;
+      tot += swc[w];
+    }
+    if (threadIdx.x == 0) pbase = tot > 0 ? atomicAdd(t.stage + HBX_ST_NPRE, (uint32_t)tot) : 0u;
+    __syncthreads();
+    off += (int)pbase;
+#pragma unroll
+    for (int r = 0; r < TAIL_PT; ++r)
+      if (idx[r] >= 0) t.list[off++] = idx[r];
+  }
+}
+
+// ... and the shortlist from the preliminary one, by one block behind the launch above (every interval is stored, U,
+// first1 and the flag are final): the entries with lo <= U or the index first1, compacted in place
+// (kde_shortlist_kernel's predicate; a pruned candidate has lo > U_seed >= U).  Overflow flag set: every candidate
+// whose lo is not NaN instead (slow; the fp64 re-score of the whole set behind it dominates).  It zeroes the marker
+// count for the next call, as the shortlist kernel does.
+__global__ __launch_bounds__(TAIL_THREADS) void staged_shortlist_kernel(StagedTailArgs t) {
+  constexpr int NW = TAIL_THREADS / 64;
+  constexpr int64_t EPB = (int64_t)TAIL_PT * TAIL_THREADS;
+  __shared__ int32_t swc[NW];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t npre = t.stage[HBX_ST_NPRE];
+  const float uf = hbx_ord2f(t.U[0]);
+  const int32_t ff = t.first1[0];
+  const bool all = (t.flags[0] & 1) != 0;
+  const int64_t nscan = all ? t.Nc : npre;
+  int64_t base = 0;
+  for (int64_t c0 = 0; c0 < nscan; c0 += EPB) {  // TAIL_PT consecutive entries per thread: the order is kept
+    const int64_t c = c0 + (int64_t)TAIL_PT * threadIdx.x;
+    int32_t ci[TAIL_PT];
+    float cl[TAIL_PT];
+#pragma unroll
+    for (int r = 0; r < TAIL_PT; ++r) ci[r] = c + r < nscan ? (all ? (int32_t)(c + r) : t.list[c + r]) : -1;
+#pragma unroll
+    for (int r = 0; r < TAIL_PT; ++r) cl[r] = ci[r] >= 0 ? t.lo[ci[r]] : NAN;
+    int n = 0;
+#pragma unroll
+    for (int r = 0; r < TAIL_PT; ++r) {
+      if (!(ci[r] >= 0 && ((cl[r] == cl[r] && (all || cl[r] <= uf)) || ci[r] == ff))) ci[r] = -1;
+      n += ci[r] >= 0 ? 1 : 0;
+    }
+    int incl = n;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) swc[wv] = incl;
+    __syncthreads();  // (and every read of this round's entries before a store: base <= c0, in place)
+    int64_t off = base + incl - n;
+    int tot = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      off += w < wv ? swc[w] : 0;
+      tot += swc[w];
+    }
+#pragma unroll
+    for (int r = 0; r < TAIL_PT; ++r)
+      if (ci[r] >= 0) t.list[off++] = ci[r];
+    base += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    *t.count = (int32_t)base;
+    *t.rescue_cnt = 0;  // (the preliminary list's length stays, like the counts: the next call's first scoring
+                        // block zeroes it)
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // launch side
 
@@ -243,7 +480,7 @@ bool acq_staged_supported(const AcqPlan& plan) {
 }
 
 int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
-                     hipEvent_t* ev, hipStream_t s) {
+                     hipEvent_t* ev, hipStream_t s, bool tail) {
   // stage 1: the good KDE's pair kernel with every block in its first segment; the good KDE has the chip's block
   // slots to itself (pair_shape's kdes = 1)
   const ScoreFns& f = plan.fg;
@@ -265,7 +502,8 @@ int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* can
   HBX_LAUNCH_CHECK();
   // stage 2
   const int32_t cap = a.list_cap;
-  hipLaunchKernelGGL(staged_seed_kernel, gsel, dim3(256), 0, s, a.lo, Nc, a.eg, a.seeds, cap, a.stage);
+  hipLaunchKernelGGL(staged_seed_kernel, gsel, dim3(256), 0, s, a.lo, Nc, a.eg, a.seeds, cap, a.stage,
+                     (int32_t)(tail ? 0 : 1));
   HBX_LAUNCH_CHECK();
   // stage 3
   const ScoreFns& fb = plan.fb;
@@ -280,7 +518,8 @@ int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* can
                      a.el, a.eg, p.Pb(), a.stage, 1);
   HBX_LAUNCH_CHECK();
   // stage 4
-  hipLaunchKernelGGL(staged_survivor_kernel, gsel, dim3(256), 0, s, a.lo, Nc, a.surv, a.stage);
+  hipLaunchKernelGGL(staged_survivor_kernel, gsel, dim3(256), 0, s, a.lo, Nc, a.surv, a.stage,
+                     tail ? a.flags : (int32_t*)nullptr);
   HBX_LAUNCH_CHECK();
   la.idx = a.surv;
   la.count = (const int32_t*)a.stage + HBX_ST_NSURV;
@@ -289,8 +528,18 @@ int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* can
   const unsigned gsplit = tcap * (unsigned)ls;
   hipLaunchKernelGGL(fb.list, dim3(gfull > gsplit ? gfull : gsplit), dim3(fb.threads), 0, s, cand, p.D, la);
   HBX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(staged_merge_kernel, gmerge, dim3(256), 0, s, a.lpart, cap, (int32_t)ls, a.surv, la.count,
-                     (int32_t)Nc, a.el, a.eg, p.Pb(), a.stage, 0);
+  if (tail) {
+    // a block per 1024 entries if every candidate is evaluated (blocks without entries exit at once), then one block
+    const StagedTailArgs ta{a.lpart, cap,     (int32_t)ls, a.seeds,  a.surv, Nc,      cand,     p.D,      p.Pb(),
+                            a.el,    a.eg,    a.lo,        a.U,      a.flags, a.first1, a.list, a.count, a.rescue,
+                            a.stage};
+    hipLaunchKernelGGL(staged_tail_kernel, dim3((unsigned)((Nc + cap + 1023) / 1024)), dim3(256), 0, s, ta);
+    HBX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(staged_shortlist_kernel, dim3(1), dim3(TAIL_THREADS), 0, s, ta);
+  } else {
+    hipLaunchKernelGGL(staged_merge_kernel, gmerge, dim3(256), 0, s, a.lpart, cap, (int32_t)ls, a.surv, la.count,
+                       (int32_t)Nc, a.el, a.eg, p.Pb(), a.stage, 0);
+  }
   HBX_LAUNCH_CHECK();
   if (ev) {  // [0]->[1]: the staged scoring, first launch's start to the last launch's end
     HBX_HIP(hipEventRecord(ev[1], s));
