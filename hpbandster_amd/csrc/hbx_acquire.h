@@ -108,12 +108,35 @@ int acq_score(const AcqPlan& plan, const KdePairRef& p, const AcqWs& a, const Sc
 #ifndef HBX_STAGED_MIN_PAIRS
 #define HBX_STAGED_MIN_PAIRS 1e9  // candidates x observations from which an acquisition stages when HBX_STAGED is unset
 #endif
+// The top-k of one pool (hbx_topk.hip "Staged scoring") stages from a higher size: its selection costs eight more
+// launches than the argmin's, so where l prunes everything it breaks even at 9e8 pairs and gains 1.9-2.4x at
+// 4.9e9, and where nothing is pruned it pays 16-17 % at 1e10 (measured, profiles/staged_topk/README.md).
+#ifndef HBX_STAGED_TOPK_MIN_PAIRS
+#define HBX_STAGED_TOPK_MIN_PAIRS 4e9
+#endif
 // tail (HBX_STAGED_TAIL, hbx_common.h): the short tail -- the call also leaves every candidate's a.lo, a.U,
 // a.first1, the overflow flag, the shortlist a.list / a.count and the marker count zeroed, the unevaluated
 // candidates' a.eg unwritten: no combine and no shortlist launch behind it.
 bool acq_staged_supported(const AcqPlan& plan);
 int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
                      hipEvent_t* ev, hipStream_t s, bool tail);
+// acq_score_staged's launches step by step, shared with the staged top-k (hbx_topk.hip), which puts its own
+// thresholds between them:
+//   staged_score_l          stage 1: the good KDE's pair kernel, then staged_l_kernel (lhi into a.lo, Lmax into the
+//                           state words).  lkey non-null: also every candidate's ordered key of -llo (+inf: no finite
+//                           llo) and the hist_words words at hist zeroed
+//   staged_score_seeds      stages 2 and 3: the seed list against the threshold in the state words' Lmax, the bad
+//                           KDE's list launch over it, its partials merged and scattered (update_u: U_seed lowered
+//                           to the seeds' smallest upper score bound)
+//   staged_score_survivors  stage 4: the survivor list against the state words' U_seed (lonly: a.lo becomes the
+//                           l-only lower score bound, lhi > 700 raises the overflow flag) and the list launch over it;
+//                           its partials, where it ran split, are left to the caller
+int staged_score_l(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
+                   hipEvent_t* ev, hipStream_t s, uint32_t* lkey, uint32_t* hist, int32_t hist_words);
+int staged_score_seeds(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
+                       hipStream_t s, bool mark_rest, bool update_u);
+int staged_score_survivors(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
+                           hipStream_t s, bool lonly);
 // exact-only acquisitions instead of a combine / bounds pass: every candidate joins the re-score
 int acq_exact_only_init(int64_t Nc, uint32_t seg, const AcqWs& a, hipStream_t s);
 // (3) the exact fp64 re-score of the shortlist a.list / a.count (scan, a single acquisition of at most

@@ -73,11 +73,20 @@
 
 // Rescue + split merge + interval of l: afterwards el[i] is the final estimate (what the unstaged path's rescue
 // pass and kde_merge_splits_kernel leave), lhi[i] = the interval's upper end (NaN: l is NaN), Lmax raised.
+// KEYS (the staged top-k, hbx_topk.hip): also lkey[i] = the ordered key of -llo (+inf: l is NaN or llo = -inf), for the
+// radix select of the (k+1)-th largest llo, whose histograms (hist_words words) the first block zeroes.
+template <bool KEYS>
 __global__ __launch_bounds__(256) void staged_l_kernel(KdeEst* __restrict__ el, int64_t Nc, int32_t ns,
                                                        const double* __restrict__ cand, int32_t D,
                                                        const KdeParams* __restrict__ Pl,
                                                        const int32_t* __restrict__ rescue_cnt,
-                                                       float* __restrict__ lhi, uint32_t* __restrict__ stage) {
+                                                       float* __restrict__ lhi, uint32_t* __restrict__ stage,
+                                                       uint32_t* __restrict__ lkey, uint32_t* __restrict__ hist,
+                                                       int32_t hist_words) {
+  if constexpr (KEYS) {
+    if (blockIdx.x == 0)
+      for (int j = threadIdx.x; j < hist_words; j += 256) hist[j] = 0;
+  }
   const int32_t nres = *rescue_cnt;  // markers counted by the scoring launch (a hint: garbage only costs time)
   KdeEst e[STAGED_PT];
   if (ns == 1) {
@@ -102,12 +111,13 @@ __global__ __launch_bounds__(256) void staged_l_kernel(KdeEst* __restrict__ el, 
     }
     if (mark) e[r] = kde_rescue_one<0, false, true>(cand, i, D, Pl);
     if (ns > 1 || mark) el[i] = e[r];
-    float lo, hi = NAN, pt;
+    float lo = -INFINITY, hi = NAN, pt;
     if (e[r].lpos == e[r].lpos) {
       est_interval(e[r], &lo, &hi, &pt);
       best = fmaxf(best, lo);
     }
     lhi[i] = hi;
+    if constexpr (KEYS) lkey[i] = hbx_f2ord(-lo);
   }
   __shared__ float rb[4];
   for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o));
@@ -479,8 +489,19 @@ bool acq_staged_supported(const AcqPlan& plan) {
   return HBX_PAIR_INIT && !plan.exact_only && plan.fg.list && plan.fb.list && plan.fg.pair && plan.fg.split_ok;
 }
 
-int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
-                     hipEvent_t* ev, hipStream_t s, bool tail) {
+// the selection kernels' grid: 1024 candidates per block
+static dim3 staged_gsel(int64_t Nc) { return dim3((unsigned)((Nc + 256 * STAGED_PT - 1) / (256 * STAGED_PT))); }
+
+// the list launches' arguments: the bad KDE's list instance over the seed list
+static KdeListArgs staged_list_args(const AcqPlan& plan, const KdePairRef& p, const AcqWs& a) {
+  const int32_t cap = a.list_cap;
+  return KdeListArgs{p.Pb(), p.table_bad, a.eg, a.lpart, a.seeds, (const int32_t*)a.stage + HBX_ST_NSEED, a.rescue,
+                     cap,    cap,         list_splits(p.nmax), (unsigned)(cap / plan.fb.cands_per_block),
+                     hbx_row_stage()};
+}
+
+int staged_score_l(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
+                   hipEvent_t* ev, hipStream_t s, uint32_t* lkey, uint32_t* hist, int32_t hist_words) {
   // stage 1: the good KDE's pair kernel with every block in its first segment; the good KDE has the chip's block
   // slots to itself (pair_shape's kdes = 1)
   const ScoreFns& f = plan.fg;
@@ -496,49 +517,73 @@ int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* can
   else
     hipLaunchKernelGGL(sh.kernel, dim3(grid), dim3(f.threads), 0, s, cand, Nc, p.D, ka);
   HBX_LAUNCH_CHECK();
-  const dim3 gsel((unsigned)((Nc + 256 * STAGED_PT - 1) / (256 * STAGED_PT)));
-  hipLaunchKernelGGL(staged_l_kernel, gsel, dim3(256), 0, s, a.el, Nc, (int32_t)ns, cand, p.D, p.Pg(), a.rescue, a.lo,
-                     a.stage);
+  if (lkey)
+    hipLaunchKernelGGL(staged_l_kernel<true>, staged_gsel(Nc), dim3(256), 0, s, a.el, Nc, (int32_t)ns, cand, p.D,
+                       p.Pg(), a.rescue, a.lo, a.stage, lkey, hist, hist_words);
+  else
+    hipLaunchKernelGGL(staged_l_kernel<false>, staged_gsel(Nc), dim3(256), 0, s, a.el, Nc, (int32_t)ns, cand, p.D,
+                       p.Pg(), a.rescue, a.lo, a.stage, (uint32_t*)nullptr, (uint32_t*)nullptr, 0);
   HBX_LAUNCH_CHECK();
+  return HBX_OK;
+}
+
+int staged_score_seeds(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
+                       hipStream_t s, bool mark_rest, bool update_u) {
   // stage 2
   const int32_t cap = a.list_cap;
-  hipLaunchKernelGGL(staged_seed_kernel, gsel, dim3(256), 0, s, a.lo, Nc, a.eg, a.seeds, cap, a.stage,
-                     (int32_t)(tail ? 0 : 1));
+  hipLaunchKernelGGL(staged_seed_kernel, staged_gsel(Nc), dim3(256), 0, s, a.lo, Nc, a.eg, a.seeds, cap, a.stage,
+                     (int32_t)(mark_rest ? 1 : 0));
   HBX_LAUNCH_CHECK();
   // stage 3
   const ScoreFns& fb = plan.fb;
-  const int ls = list_splits(p.nmax);
-  const unsigned tcap = (unsigned)(cap / fb.cands_per_block);
-  KdeListArgs la{p.Pb(), p.table_bad, a.eg, a.lpart, a.seeds, (const int32_t*)a.stage + HBX_ST_NSEED, a.rescue, cap,
-                 cap, ls, tcap, ka.row_stage};
-  hipLaunchKernelGGL(fb.list, dim3(tcap * (unsigned)ls), dim3(fb.threads), 0, s, cand, p.D, la);
+  const KdeListArgs la = staged_list_args(plan, p, a);
+  hipLaunchKernelGGL(fb.list, dim3(la.tiles_cap * (unsigned)la.nsplit), dim3(fb.threads), 0, s, cand, p.D, la);
   HBX_LAUNCH_CHECK();
-  const dim3 gmerge((unsigned)((cap + 255) / 256));
-  hipLaunchKernelGGL(staged_merge_kernel, gmerge, dim3(256), 0, s, a.lpart, cap, (int32_t)ls, a.seeds, la.count, cap,
-                     a.el, a.eg, p.Pb(), a.stage, 1);
+  hipLaunchKernelGGL(staged_merge_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, a.lpart, cap,
+                     la.nsplit, a.seeds, la.count, cap, a.el, a.eg, p.Pb(), a.stage, (int32_t)(update_u ? 1 : 0));
   HBX_LAUNCH_CHECK();
+  return HBX_OK;
+}
+
+int staged_score_survivors(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
+                           hipStream_t s, bool lonly) {
   // stage 4
-  hipLaunchKernelGGL(staged_survivor_kernel, gsel, dim3(256), 0, s, a.lo, Nc, a.surv, a.stage,
-                     tail ? a.flags : (int32_t*)nullptr);
+  const ScoreFns& fb = plan.fb;
+  hipLaunchKernelGGL(staged_survivor_kernel, staged_gsel(Nc), dim3(256), 0, s, a.lo, Nc, a.surv, a.stage,
+                     lonly ? a.flags : (int32_t*)nullptr);
   HBX_LAUNCH_CHECK();
+  KdeListArgs la = staged_list_args(plan, p, a);
   la.idx = a.surv;
   la.count = (const int32_t*)a.stage + HBX_ST_NSURV;
   la.maxcount = (int32_t)Nc;
   const unsigned gfull = (unsigned)((Nc + fb.cands_per_block - 1) / fb.cands_per_block);
-  const unsigned gsplit = tcap * (unsigned)ls;
+  const unsigned gsplit = la.tiles_cap * (unsigned)la.nsplit;
   hipLaunchKernelGGL(fb.list, dim3(gfull > gsplit ? gfull : gsplit), dim3(fb.threads), 0, s, cand, p.D, la);
   HBX_LAUNCH_CHECK();
+  return HBX_OK;
+}
+
+int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
+                     hipEvent_t* ev, hipStream_t s, bool tail) {
+  int rc = staged_score_l(plan, p, cand, Nc, a, ev, s, nullptr, nullptr, 0);
+  if (rc) return rc;
+  rc = staged_score_seeds(plan, p, cand, Nc, a, s, !tail, true);
+  if (rc) return rc;
+  rc = staged_score_survivors(plan, p, cand, Nc, a, s, tail);
+  if (rc) return rc;
+  const int32_t cap = a.list_cap;
+  const int32_t ls = list_splits(p.nmax);
   if (tail) {
     // a block per 1024 entries if every candidate is evaluated (blocks without entries exit at once), then one block
-    const StagedTailArgs ta{a.lpart, cap,     (int32_t)ls, a.seeds,  a.surv, Nc,      cand,     p.D,      p.Pb(),
-                            a.el,    a.eg,    a.lo,        a.U,      a.flags, a.first1, a.list, a.count, a.rescue,
+    const StagedTailArgs ta{a.lpart, cap,     ls,   a.seeds, a.surv,  Nc,       cand,   p.D,     p.Pb(),
+                            a.el,    a.eg,    a.lo, a.U,     a.flags, a.first1, a.list, a.count, a.rescue,
                             a.stage};
     hipLaunchKernelGGL(staged_tail_kernel, dim3((unsigned)((Nc + cap + 1023) / 1024)), dim3(256), 0, s, ta);
     HBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(staged_shortlist_kernel, dim3(1), dim3(TAIL_THREADS), 0, s, ta);
   } else {
-    hipLaunchKernelGGL(staged_merge_kernel, gmerge, dim3(256), 0, s, a.lpart, cap, (int32_t)ls, a.surv, la.count,
-                       (int32_t)Nc, a.el, a.eg, p.Pb(), a.stage, 0);
+    hipLaunchKernelGGL(staged_merge_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, a.lpart, cap, ls,
+                       a.surv, (const int32_t*)a.stage + HBX_ST_NSURV, (int32_t)Nc, a.el, a.eg, p.Pb(), a.stage, 0);
   }
   HBX_LAUNCH_CHECK();
   if (ev) {  // [0]->[1]: the staged scoring, first launch's start to the last launch's end

@@ -504,9 +504,12 @@ class KDEPair(object):
         return AcqResult.from_bytes(rec.raw[:RESULT_BYTES])
 
     def acquire_stats(self, workspace, Nc):
-        """What the last single acquisition over ``Nc`` candidates on ``workspace`` did (synchronises):
-        dict(staged, seeds, survivors, evaluated) -- ``evaluated`` = candidates whose bad-KDE sum was
-        computed, ``Nc`` when the call did not stage (see ``acquire``)."""
+        """What the last single acquisition -- ``acquire`` or ``acquire_topk`` -- over ``Nc`` candidates on
+        ``workspace`` did (synchronises): dict(staged, seeds, survivors, evaluated) -- ``evaluated`` =
+        candidates whose bad-KDE sum was computed, ``Nc`` when the call did not stage (see ``acquire``).  Every
+        such call leaves the counts valid: an unstaged call after a staged one on the same workspace reports
+        ``staged`` False.  A staged call changes no field of the pick or of the ranked entries; only
+        ``shortlist``, which describes the screen, may differ from the unstaged call's."""
         out = (ctypes.c_int64 * 4)()
         N.check(N.lib().hbx_kde_acquire_stats(workspace.data_ptr(), int(Nc), self.nmax, ctypes.addressof(out)))
         return {"staged": bool(out[0]), "seeds": int(out[1]), "survivors": int(out[2]), "evaluated": int(out[3])}
@@ -634,7 +637,15 @@ class KDEPair(object):
         entry 0 is acquire()'s pick.  ``cands``: [Nc, D] float64 (numpy or a device tensor); 1 <= k <= 1024
         (k > Nc is legal).  Returns a TopK (empty when no candidate has a score: the drop-in then falls back to
         random configurations, as for acquire()'s index -1).  Only ties='pinned' is offered: the GPU's re-score
-        is the reference's arithmetic on the pinned numpy bit for bit."""
+        is the reference's arithmetic on the pinned numpy bit for bit.
+
+        Large calls whose KDEs both run the coarse 32x32 kernel are scored in stages like ``acquire``'s (the
+        same ``HBX_STAGED`` switch; unset, from 4e9 candidates x observations): the good KDE for every candidate, the bad KDE only for
+        the seeds around the (k+1)-th largest l and for the candidates whose bound 1e-8 / max(l, 1e-8) does not
+        exceed the seeds' (k+1)-th smallest upper score bound.  ``count``, ``flags`` and every entry's
+        ``index``, ``score``, ``pdf_l``, ``pdf_g`` and ``rel`` are the unstaged call's, exactly; ``shortlist``
+        may differ (the evaluated candidates' fp32 estimates come from launches with other observation
+        splits).  ``acquire_stats(workspace, Nc)`` on the call's workspace reports what it did."""
         if ties != "pinned":
             raise ValueError("acquire_topk offers ties='pinned' only")
         k = int(k)

@@ -233,7 +233,14 @@ int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int64_t i
  *           index: candidate index + index_base; score, pdf_l, pdf_g: the reference's fp64 values bit for
  *           bit; rel: the bound hbx_kde_acquire's record reports (hbx_kde_result_ptr)
  * Nc = 0: count = 0, nothing launched (the header zeroed).  Workspace: hbx_kde_topk_workspace_bytes(Nc, k,
- * nmax) (-1 for k out of range, as hbx_kde_topk_result_bytes).  Bad arguments: HBX_ERR_ARG (hbx_last_error). */
+ * nmax) (-1 for k out of range, as hbx_kde_topk_result_bytes).  Bad arguments: HBX_ERR_ARG (hbx_last_error).
+ * Large calls on pairs the staged scoring serves (below, at hbx_kde_acquire_stats; the same HBX_STAGED switch, a
+ * size threshold of its own, 4e9 candidates x observations) score g only for the candidates that can still rank: the seeds around the (k+1)-th largest l
+ * and the candidates whose l-only bound 1e-8 / max(l, 1e-8) does not exceed the seeds' (k+1)-th smallest upper
+ * score bound.  count, flags and every record's index, score, pdf_l, pdf_g and rel are the unstaged call's,
+ * exactly; the header's `shortlist` describes the screen and may differ (the evaluated candidates' fp32 estimates
+ * come from launches with other observation splits).  The workspace begins with hbx_kde_acquire's, so
+ * hbx_kde_acquire_stats(workspace, Nc, nmax) reports what the call did. */
 #define HBX_TOPK_MAX_K 1024
 int64_t hbx_kde_topk_workspace_bytes(int64_t Nc, int32_t k, int64_t nmax);
 int64_t hbx_kde_topk_result_bytes(int32_t k);
@@ -373,9 +380,10 @@ int hbx_kde_ws_offsets(int64_t Nc, int64_t seg, int64_t nmax, int64_t* out);
  * shortlist can fall on either side; a pruned candidate whose coarse g bound alone would pass the overflow limit
  * sets HBX_ACQ_OVERFLOW (and the whole-set re-score) in the unstaged call only; and when l itself sets
  * HBX_ACQ_OVERFLOW the staged shortlist also holds the pruned certain ties, so it can be longer.
- * hbx_kde_acquire_stats: what the last single acquisition on `workspace` (sized for Nc, nmax) did -- a device
- * read, synchronising: out[0] = 1 when it staged, [1] seeds, [2] survivors, [3] candidates whose g was evaluated
- * (Nc when it did not stage). */
+ * hbx_kde_acquire_stats: what the last single acquisition or top-k call (hbx_kde_acquire_topk) on `workspace`
+ * (sized for Nc, nmax) did -- a device read, synchronising: out[0] = 1 when it staged, [1] seeds, [2] survivors,
+ * [3] candidates whose g was evaluated (Nc when it did not stage).  Every such call leaves these words valid: an
+ * unstaged call on a workspace an earlier staged call used reports 0. */
 int hbx_kde_acquire_stats(const void* workspace, int64_t Nc, int64_t nmax, int64_t* out);
 
 int64_t hbx_kde_pdf_scratch_bytes(int64_t nmax);
