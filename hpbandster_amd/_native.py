@@ -63,6 +63,10 @@ SIGNATURES = {
     "hbx_kde_groups_topk_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "hbx_kde_acquire_groups_topk": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_kde_logpdf_groups_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "hbx_kde_logpdf_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_i64, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_kde_logpdf_groups_stats": (c_i32, [c_vp, c_vp]),
     "hbx_kde_sample_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, ctypes.c_double,
                                       ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp]),
     "hbx_philox4x32_10": (c_i32, [c_vp, c_vp, c_vp]),

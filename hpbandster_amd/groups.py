@@ -6,6 +6,7 @@ Config #5's loop on the device from end to end::
     rows, picks = gm.propose(64, seed, levels)                # hbx_kde_sample_groups + hbx_kde_acquire_groups
     rows, picks = gm.propose(64, seed, levels, requests=S)    # S picks per bracket: hbx_kde_acquire_groups_batch
     rows, top = gm.propose(64, seed, levels, topk=k)          # the k best of each pool: hbx_kde_acquire_groups_topk
+    lp = gm.logpdf(cands)                                     # ln l, ln g of every candidate: hbx_kde_logpdf_groups
 
 Bracket b owns the rows ``X[seg_off[b]:seg_off[b+1]]``; its good / bad KDEs are the head ``n_good[b]`` / tail
 ``n_bad[b]`` rows of numpy's argsort of its losses (bohb.py:220-246).  The fit's outputs (order, bandwidths, level
@@ -146,6 +147,34 @@ class GroupTopK(object):
 
     def __repr__(self):
         return "GroupTopK(B=%d, k=%d, returned=%d)" % (len(self), self.k, int(self.count.sum()))
+
+
+GRP_EXACT_L, GRP_EXACT_G = 64, 128  # include/hbx.h HBX_GRP_EXACT_*
+LOGPDF_FP64_ONLY = 1                 # include/hbx.h HBX_LOGPDF_FP64_ONLY
+
+
+class GroupLogPdf(object):
+    """Both KDEs' log densities at every candidate of every group's pool (hbx_kde_logpdf_groups): ``ln_l`` and
+    ``ln_g`` (float64, shaped like the pool's leading dims -- [B, C] or [B, S, C] --, None when not requested; -inf
+    where the pdf is 0, NaN where the reference's is NaN or negative and for groups without a usable model),
+    ``status`` (int32 [B]: ACQ_NO_MODEL / ACQ_UNSUPPORTED, GRP_EXACT_L / GRP_EXACT_G) and ``stats`` (4 ints: values
+    written by the fp32 pass, the fp64 log-space pass, through the exact pdf, NaN-filled; None before a
+    synchronisation).  With ``sync=False`` the arrays are device tensors.  ``len()`` is B."""
+    __slots__ = ("ln_l", "ln_g", "status", "stats")
+
+    def __init__(self, ln_l, ln_g, status, stats=None, lead=None):
+        if lead is not None:
+            ln_l = None if ln_l is None else ln_l.reshape(lead)
+            ln_g = None if ln_g is None else ln_g.reshape(lead)
+        self.ln_l, self.ln_g, self.status = ln_l, ln_g, status
+        self.stats = None if stats is None else tuple(int(v) for v in stats)
+
+    def __len__(self):
+        return int(self.status.shape[0])
+
+    def __repr__(self):
+        shape = tuple((self.ln_l if self.ln_l is not None else self.ln_g).shape)
+        return "GroupLogPdf(shape=%s, stats=%s)" % (shape, self.stats)
 
 
 class GroupModel(object):
@@ -320,6 +349,61 @@ class GroupModel(object):
             if not sync:
                 return res
             return GroupTopK.from_bytes(res.cpu().numpy().tobytes(), self.B, k)
+
+    def workspace_bytes_logpdf(self, C):
+        return int(N.lib().hbx_kde_logpdf_groups_workspace_bytes(self.B, int(C), self.D))
+
+    def logpdf(self, cands, rtol=1e-5, which="both", fp64_only=True, stream=None, workspace=None, sync=True):
+        """ln l(x) and ln g(x) of every candidate of every group's own pool (hbx_kde_logpdf_groups): each value within
+        ``rtol * max(1, |ln p|)`` of the reference's KDEMultivariate.pdf.  ``cands``: [B, C, D] or [B, S, C, D]
+        float64, numpy or a contiguous device tensor; ``which``: "both", "good" (ln_l only) or "bad" (ln_g only);
+        ``fp64_only=False`` runs the fp32 first pass before the fp64 one (the C ABI's flags = 0): the same contract,
+        3 % faster at config #5's shape and half as fast at 8 continuous dims (DESIGN section 4 "Grouped ln-pdf"), so
+        the fp64 pass alone is the default here.  Returns GroupLogPdf with host arrays, or with ``sync=False`` with
+        device tensors (and ``stats`` None: reading the counters synchronises)."""
+        if which not in ("both", "good", "bad"):
+            raise ValueError("which must be 'both', 'good' or 'bad', got %r" % (which,))
+        if not float(rtol) > 0.0:
+            raise ValueError("rtol must be positive, got %r" % (rtol,))
+        torch = kde._torch()
+        with N.on_device(self.device, stream):
+            if _is_tensor(cands):
+                cd = cands
+                if cd.dtype != torch.float64 or not cd.is_contiguous():
+                    raise N.HbxError("candidate tensor must be contiguous float64 [B, C, D] or [B, S, C, D]")
+            else:
+                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
+            if cd.dim() not in (3, 4) or int(cd.shape[0]) != self.B or int(cd.shape[-1]) != self.D:
+                raise N.HbxError("candidates must be [%d, C, %d] or [%d, S, C, %d], got %s" %
+                                 (self.B, self.D, self.B, self.D, tuple(cd.shape)))
+            lead = tuple(int(v) for v in cd.shape[:-1])
+            C = int(np.prod(lead[1:], dtype=np.int64))  # S requests: the flattened pool
+            wsb = self.workspace_bytes_logpdf(C)
+            if wsb < 0:
+                raise N.HbxError("B * C = %d * %d exceeds int32" % (self.B, C))
+            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
+            if ws.numel() < wsb:
+                raise N.HbxError("workspace too small")
+            ll = torch.empty((self.B, C), dtype=torch.float64, device=self.device) if which != "bad" else None
+            lg = torch.empty((self.B, C), dtype=torch.float64, device=self.device) if which != "good" else None
+            status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            launched = self.B > 0 and C > 0
+            if launched:
+                N.check(N.lib().hbx_kde_logpdf_groups(
+                    N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
+                    N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
+                    N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), C, float(rtol),
+                    LOGPDF_FP64_ONLY if fp64_only else 0, N.ptr(ll), N.ptr(lg), N.ptr(status), N.ptr(ws), ws.numel(),
+                    N.stream_handle(stream, self.device)))
+            if not sync:
+                return GroupLogPdf(ll, lg, status, None, lead)
+            stats = np.zeros(4, dtype=np.int64)
+            if launched:
+                N.check(N.lib().hbx_kde_logpdf_groups_stats(N.ptr(ws), stats.ctypes.data))
+            elif stream is not None:
+                stream.synchronize()
+            return GroupLogPdf(None if ll is None else ll.cpu().numpy(), None if lg is None else lg.cpu().numpy(),
+                               status.cpu().numpy(), stats, lead)
 
     def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, requests=None, topk=None):
         """sample + acquire: (rows [B, D] host float64 -- NaN where a group has no pick --, GroupPicks).

@@ -27,6 +27,8 @@
  *   hbx_kde_acquire_groups_topk     <- bohb.py:124-169 per bracket, the scores ranked: the k best candidates of
  *                                      every bracket's pool by (score, index), one call
  *   hbx_kde_sample_groups           <- bohb.py:133-147 per bracket (the candidates of B brackets in one call)
+ *   hbx_kde_logpdf_groups           <- KDEMultivariate.pdf (kernel_density.py:162-196) of both KDEs of every bracket
+ *                                      at every candidate of its pool, as ln pdf within a relative tolerance, one call
  *   hbx_kde_logpdf                  <- KDEMultivariate.pdf (kernel_density.py:162-196), fp32 log domain
  *   hbx_kde_pdf_exact               <- KDEMultivariate.pdf, fp64, reference operation order
  *   hbx_sh_promote(_ex)             <- HB_iteration.py:149-190 (SuccessiveHalving.process_results ranks)
@@ -320,6 +322,37 @@ int hbx_kde_acquire_groups_topk(const double* X, int32_t D, const int64_t* seg_o
                                 const int32_t* nlev_good, const int32_t* nlev_bad,
                                 const double* cand, int64_t C, int32_t k, void* results,
                                 void* workspace, int64_t ws_bytes, void* stream);
+/* Grouped ln-pdf: ln l(x) and ln g(x) for every candidate of every bracket's pool in one call -- hbx_kde_logpdf_rtol's
+ * contract for each of hbx_kde_acquire_groups' B groups.  The model arguments are hbx_kde_acquire_groups', unchanged,
+ * read where hbx_kde_fit left them (no KdeParams, no table, no prepare); cand: f64[B][C][D] (S requests per group:
+ * the flattened pool, C := S * C).  ln_l, ln_g: f64[B][C], either may be NULL (that KDE is skipped; both NULL is
+ * HBX_ERR_ARG).  Every value is ln pdf within rtol * max(1, |ln p|) of the reference's KDEMultivariate.pdf, -inf
+ * where the pdf is 0, NaN where the reference's pdf is NaN or negative.  status: i32[B]: HBX_ACQ_NO_MODEL /
+ * HBX_ACQ_UNSUPPORTED by hbx_kde_acquire_groups' rules -- all of that group's outputs are NaN, never an error return
+ * -- and HBX_GRP_EXACT_L / HBX_GRP_EXACT_G where that KDE's values are ln of the bit-exact fp64 pdf (a negative
+ * categorical match factor h > 1, a single observed level, a continuous bandwidth that is not positive and finite,
+ * dims beyond the slot bucket): NaN where that pdf is negative or NaN, -inf where it underflows to 0.
+ * flags: HBX_LOGPDF_FP64_ONLY skips the fp32 first pass (the fp64 pass alone meets the contract; the fp32 pass only
+ * writes values its own rigorous bound certifies).  rtol > 0; below 1e-5 the fp64 pass uses fp64 exponentials.
+ * Launches on `stream` only: no host synchronisation, no allocation, no per-group host work.  B == 0 or C == 0:
+ * nothing to do (status is not written).  B * C beyond int32, D outside [1, hbx_max_dims()], null or misaligned
+ * pointers (f64 / i64: 8 bytes, i32: 4, workspace: 16) or a short workspace: HBX_ERR_ARG (hbx_last_error), before the
+ * first launch.  workspace: hbx_kde_logpdf_groups_workspace_bytes(B, C, D) bytes (-1 for arguments out of range); its
+ * header holds four counters of output values, read by hbx_kde_logpdf_groups_stats (synchronises the device):
+ * out4[0] written by the fp32 pass, [1] by the fp64 log-space pass, [2] through the exact pdf, [3] NaN-filled for
+ * groups without a usable model; their sum is B * C times the number of non-NULL outputs. */
+#define HBX_GRP_EXACT_L 64
+#define HBX_GRP_EXACT_G 128
+#define HBX_LOGPDF_FP64_ONLY 1
+int64_t hbx_kde_logpdf_groups_workspace_bytes(int64_t B, int64_t C, int32_t D);
+int hbx_kde_logpdf_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                          const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                          const double* bw_good, const double* bw_bad,
+                          const int32_t* nlev_good, const int32_t* nlev_bad,
+                          const double* cand, int64_t C, double rtol, int32_t flags,
+                          double* ln_l, double* ln_g, int32_t* status,
+                          void* workspace, int64_t ws_bytes, void* stream);
+int hbx_kde_logpdf_groups_stats(const void* workspace, int64_t* out4);
 /* The matching sampler: C candidates per group around its good KDE's rows (hbx_kde_sample's rule).  Candidate
  * (b, i) is byte-equal to what hbx_kde_sample draws for group b's good KDE (tab = NULL) at candidate index i of a
  * call with counter_base + b * C.  cands: f64[B][C][D] (16-byte aligned when D is even); domain_err: nullable

@@ -22,6 +22,11 @@ one-request calls; prints one JSON line and writes it only where --out says.
 
 times the k best candidates per bracket (topk_bench below): hbx_kde_acquire_groups_topk against the batched call with
 S = K pools and the per-bracket acquire_topk loop; prints one JSON line and writes it only where --out says.
+
+    python tools/bench_groups.py --logpdf [--out FILE]
+
+times hbx_kde_logpdf_groups (logpdf_bench below) in default and FP64_ONLY mode at config #5's shape and at a plain
+unsigned shape (8c) against the per-bracket prepare + logpdf loop; writes profiles/groups_logpdf/bench_groups_logpdf.json.
 """
 import argparse
 import json
@@ -219,6 +224,129 @@ def topk_bench(a, gm, L, sh, lvd):
     return 0 if agree == sub.size and first_ok == B else 1
 
 
+def _same_within(a, b, rtol):
+    """a and b agree entry by entry: the same NaNs, finite values within rtol * max(1, |b|); -inf on one side against
+    a finite log-space value on the other is accepted (the fp64 pdf underflowed to 0: either answer is in contract)."""
+    a, b = np.asarray(a), np.asarray(b)
+    if not np.array_equal(np.isnan(a), np.isnan(b)):
+        return False
+    fin = np.isfinite(a) & np.isfinite(b)
+    rest = ~np.isnan(a) & ~fin
+    if not np.all(np.isneginf(a[rest]) | np.isneginf(b[rest])):
+        return False
+    return bool(np.all(np.abs(a[fin] - b[fin]) <= rtol * np.maximum(1.0, np.abs(b[fin]))))
+
+
+def logpdf_shape(a, dev, L, name, dc, du, lev):
+    """One shape of --logpdf: B brackets of n rows, dc continuous + du categorical dims, C sampled candidates each."""
+    B, n, C, D = a.B, a.n, a.C, dc + du
+    vts = S.var_type_string(dc, du)
+    losses = torch.from_numpy(S.make_bracket_losses(B, n).reshape(-1)).to(dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    X = torch.empty((B * n, D), dtype=torch.float64, device=dev)
+    X[:, :dc] = torch.rand((B * n, dc), dtype=torch.float64, device=dev, generator=g)
+    if du:
+        X[:, dc:] = torch.randint(0, lev, (B * n, du), device=dev, generator=g).to(torch.float64)
+    seg = np.arange(B + 1, dtype=np.int64) * n
+    gm = groups.fit_groups(X, losses, seg, vts, device=dev)
+    sh = N.stream_handle(None, dev)
+    lvd = torch.tensor([0] * dc + [lev] * du, dtype=torch.int32, device=dev)
+    cands = torch.empty((B, C, D), dtype=torch.float64, device=dev)
+    derr = torch.empty((B, C), dtype=torch.uint8, device=dev)
+    N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
+                                    N.ptr(gm.bw_good), N.ptr(lvd), 3.0, S.SEED_CAND, 0, 0, C, N.ptr(cands),
+                                    N.ptr(derr), sh))
+    model = (N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
+             N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad))
+    wsb = gm.workspace_bytes_logpdf(C)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ll = torch.empty((B, C), dtype=torch.float64, device=dev)
+    lg = torch.empty((B, C), dtype=torch.float64, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    out = {"dims": "%dc+%du" % (dc, du), "n_good": int(gm.n_good[0]), "n_bad": int(gm.n_bad[0]), "workspace_bytes": wsb}
+    host = {}
+    for key, flags in (("default", 0), ("fp64_only", groups.LOGPDF_FP64_ONLY)):
+        def call():
+            N.check(L.hbx_kde_logpdf_groups(*model, N.ptr(cands), C, 1e-5, flags, N.ptr(ll), N.ptr(lg), N.ptr(status),
+                                            N.ptr(ws), wsb, sh))
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+        for e0, e1 in ev:  # every repetition between its own pair of device events
+            e0.record()
+            call()
+            e1.record()
+        torch.cuda.synchronize()
+        ms = [e0.elapsed_time(e1) for e0, e1 in ev]
+        stats = np.zeros(4, dtype=np.int64)
+        N.check(L.hbx_kde_logpdf_groups_stats(N.ptr(ws), stats.ctypes.data))
+        out[key] = {"ms_mean": float(np.mean(ms)), "ms_min": float(np.min(ms)), "ms_max": float(np.max(ms)),
+                    "stats": [int(v) for v in stats], "fp32_share": float(stats[0]) / float(2 * B * C)}
+        host[key] = (ll.cpu().numpy(), lg.cpu().numpy())
+    st = status.cpu().numpy()
+    out["groups_exact_l"] = int(((st & groups.GRP_EXACT_L) != 0).sum())
+    out["groups_exact_g"] = int(((st & groups.GRP_EXACT_G) != 0).sum())
+    out["modes_agree"] = bool(_same_within(host["default"][0], host["fp64_only"][0], 2e-5) and
+                              _same_within(host["default"][1], host["fp64_only"][1], 2e-5))
+    # the per-bracket loop on a subsample: what the library offered before
+    sub = np.unique(np.linspace(0, B - 1, min(a.sub, B)).astype(np.int64))
+    ng, nb = int(gm.n_good[0]), int(gm.n_bad[0])
+    bwg, bwb = gm.bandwidths()
+    nlg, nlb = gm.nlev_good.cpu().numpy(), gm.nlev_bad.cpu().numpy()
+    order_h = gm.order.cpu().numpy()
+    cands_h = cands.cpu().numpy()
+    t_prep, t_lp, agree = [], [], 0
+    for it, b in enumerate(np.concatenate([sub[:3], sub])):  # the first three again as warm-up
+        s, e = int(seg[b]), int(seg[b + 1])
+        Xb = gm.X[s:e].cpu().numpy()
+        o = order_h[s:e]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pair = kde.fit_pair_from_rows(Xb, o[:ng], o[e - s - nb:], vts, bwg[b], bwb[b], nlg[b], nlb[b], device=dev)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        l1 = pair.good.logpdf(cands_h[b])
+        g1 = pair.bad.logpdf(cands_h[b])
+        t2 = time.perf_counter()
+        if it >= 3:
+            t_prep.append(t1 - t0)
+            t_lp.append(t2 - t1)
+            agree += int(_same_within(host["default"][0][b], l1, 2e-5) and _same_within(host["default"][1][b], g1, 2e-5))
+    prep_ms, lp_ms, lp_min = 1e3 * float(np.mean(t_prep)), 1e3 * float(np.mean(t_lp)), 1e3 * float(np.min(t_lp))
+    out["loop"] = {"subsample": int(sub.size), "prepare_ms_per_group": prep_ms, "logpdf_ms_per_group": lp_ms,
+                   "logpdf_ms_per_group_fastest": lp_min, "loop_ms_extrapolated": B * (prep_ms + lp_ms),
+                   "loop_ms_extrapolated_without_prepare": B * lp_ms,
+                   "loop_ms_extrapolated_without_prepare_fastest": B * lp_min, "groups_agree": agree}
+    slowest = max(out["default"]["ms_max"], out["fp64_only"]["ms_max"])
+    out["slowest_grouped_vs_fastest_loop_without_prepare"] = B * lp_min / slowest
+    out["default_not_slower_than_fp64_only"] = bool(out["default"]["ms_mean"] <= out["fp64_only"]["ms_mean"])
+    return out, agree == sub.size and out["modes_agree"]
+
+
+def logpdf_bench(a, dev, L):
+    """--logpdf: hbx_kde_logpdf_groups at config #5's shape (24c + 8u, 4 levels) and at a plain unsigned shape (8c),
+    same B, n, C.  Per shape: the grouped call in default and FP64_ONLY mode (device events around each of REPS warmed
+    repetitions: mean, fastest, slowest), the four counters of each mode, and the only route the library offered
+    before -- per bracket gm.pair(b)'s two hbx_kde_prepare calls plus good.logpdf and bad.logpdf, on --sub subsampled
+    brackets (wall clock, synchronised), extrapolated to B with and without the prepare time, its values compared
+    with the grouped call's.  Writes profiles/groups_logpdf/bench_groups_logpdf.json (or --out) and prints it."""
+    a.out = a.out or os.path.join(ROOT, "profiles", "groups_logpdf", "bench_groups_logpdf.json")
+    out = {"workload": "grouped_logpdf_b%d_n%d_c%d" % (a.B, a.n, a.C), "device": torch.cuda.get_device_name(0),
+           "reps": a.reps, "rtol": 1e-5, "shapes": {}}
+    ok = True
+    for name, dc, du in (("config5_24c8u", 24, 8), ("plain_8c", 8, 0)):
+        out["shapes"][name], good = logpdf_shape(a, dev, L, name, dc, du, 4)
+        ok = ok and good
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+    return 0 if ok else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=10000)
@@ -231,9 +359,12 @@ def main(argv=None):
     ap.add_argument("--loop-only", action="store_true",
                     help="time only the S one-request calls (what a library without the batched call offers)")
     ap.add_argument("--topk", type=int, default=0, help="the K best candidates per bracket (topk_bench)")
+    ap.add_argument("--logpdf", action="store_true", help="both KDEs' ln pdf of every pool (logpdf_bench)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     L = N.lib()
+    if a.logpdf:
+        return logpdf_bench(a, dev, L)
     B, n, C, dc, du, lev = a.B, a.n, a.C, 24, 8, 4
     D = dc + du
     vts = S.var_type_string(dc, du)
