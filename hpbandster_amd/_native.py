@@ -69,6 +69,13 @@ SIGNATURES = {
     "hbx_kde_logpdf_groups_stats": (c_i32, [c_vp, c_vp]),
     "hbx_kde_sample_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, ctypes.c_double,
                                       ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp]),
+    "hbx_kde_finish_groups": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, ctypes.c_double,
+                                      ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp]),
+    "hbx_kde_propose_groups_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i32]),
+    "hbx_kde_propose_groups_ws_offsets": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_vp]),
+    "hbx_kde_propose_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
+                                       ctypes.c_uint32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "hbx_philox4x32_10": (c_i32, [c_vp, c_vp, c_vp]),
     "hbx_kde_sample": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_uint64,
                                ctypes.c_uint64, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp, c_vp]),

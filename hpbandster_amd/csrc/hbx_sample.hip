@@ -26,17 +26,7 @@
 #include <string.h>
 #include <stdlib.h>
 
-#define SAMPLE_BLOCK 256
-#define DATUM_WORD 0xFFFFFFFFu  // counter word of the per-candidate datum draw (dims use 0..D-1)
-
-__device__ __forceinline__ HbxU32x4 draw(uint64_t seed, uint64_t i, uint32_t word, uint32_t stream) {
-  HbxU32x4 c;
-  c.x[0] = (uint32_t)i;
-  c.x[1] = (uint32_t)(i >> 32);
-  c.x[2] = word;
-  c.x[3] = stream;
-  return hbx_philox4x32_10_impl(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-}
+#define SAMPLE_BLOCK 256  // (DATUM_WORD and draw(): hbx_philox.h)
 
 // Standardised bounds of a continuous dim around datum m, mirrored so that lo <= 0 side is used
 // (a > 0 -> sample -z from [-b, -a]); false when scipy's a < b check fails.  rh = 1 / h: the bounds are

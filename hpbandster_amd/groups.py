@@ -7,6 +7,9 @@ Config #5's loop on the device from end to end::
     rows, picks = gm.propose(64, seed, levels, requests=S)    # S picks per bracket: hbx_kde_acquire_groups_batch
     rows, top = gm.propose(64, seed, levels, topk=k)          # the k best of each pool: hbx_kde_acquire_groups_topk
     lp = gm.logpdf(cands)                                     # ln l, ln g of every candidate: hbx_kde_logpdf_groups
+    cfg = gm.get_config(64, seed, levels, requests=S)         # a configuration per request, prior draws where the
+                                                              # reference falls back: hbx_kde_propose_groups
+    opt = GroupBOHB(B, var_type, levels)                      # B BOHB runs in lockstep: new_results / get_configs
 
 Bracket b owns the rows ``X[seg_off[b]:seg_off[b+1]]``; its good / bad KDEs are the head ``n_good[b]`` / tail
 ``n_bad[b]`` rows of numpy's argsort of its losses (bohb.py:220-246).  The fit's outputs (order, bandwidths, level
@@ -147,6 +150,94 @@ class GroupTopK(object):
 
     def __repr__(self):
         return "GroupTopK(B=%d, k=%d, returned=%d)" % (len(self), self.k, int(self.count.sum()))
+
+
+class GroupConfigs(object):
+    """One configuration vector per get_config request (hbx_kde_finish_groups / hbx_kde_propose_groups): ``rows``
+    (float64 [B, S, D], or [B, D] when the call had no ``requests``), ``source`` (uint8 [B, S] or [B]: SOURCE_MODEL
+    the winning candidate's row, anything else a prior draw and why -- bohb.py:107-111,154-166), ``model_based``
+    (``source == SOURCE_MODEL``: the reference's info_dict['model_based_pick']) and ``picks`` (the acquisition's
+    records, None when they were not requested).  Host arrays and a GroupPicks after a synchronising call; with
+    ``sync=False`` device tensors, ``picks`` the device tensor of the records (uint8 [B, S, 48] or [B, 48]).
+    ``cands`` / ``domain_err`` hold the pools and the sampler's error bytes when the call kept them.  ``len()`` is B."""
+    SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR = 0, 1, 2, 3, 4  # HBX_CFG_*
+    __slots__ = ("rows", "source", "model_based", "picks", "cands", "domain_err")
+
+    def __init__(self, rows, source, B, S=None, picks=None, cands=None, domain_err=None):
+        lead = (int(B),) if S is None else (int(B), int(S))
+        self.rows = rows.reshape(lead + (int(rows.shape[-1]),))
+        self.source = source.reshape(lead)
+        self.model_based = self.source == self.SOURCE_MODEL
+        self.picks, self.cands, self.domain_err = picks, cands, domain_err
+
+    def __len__(self):
+        return int(self.source.shape[0])
+
+    def __repr__(self):
+        return "GroupConfigs(shape=%s)" % (tuple(self.source.shape),)
+
+
+SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR = 0, 1, 2, 3, 4
+
+
+def _levels_dev(levels, D, device):
+    """``levels`` (D level counts, 0: continuous) as an int32 device tensor; a tensor already there is used as is."""
+    torch = kde._torch()
+    if _is_tensor(levels):
+        if levels.dtype != torch.int32 or tuple(levels.shape) != (D,) or not levels.is_contiguous():
+            raise N.HbxError("levels tensor must be contiguous int32 [%d]" % D)
+        return levels.to(device)
+    lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
+    if lv.shape != (D,):
+        raise N.HbxError("levels must have %d entries" % D)
+    return torch.from_numpy(lv).to(device)
+
+
+def _fraction(random_fraction):
+    rf = float(random_fraction)
+    if not 0.0 <= rf <= 1.0:
+        raise ValueError("random_fraction must be in [0, 1], got %r" % (random_fraction,))
+    return rf
+
+
+def _configs(rows, source, B, S, sync, records=None, cands=None, err=None):
+    """GroupConfigs from the device outputs of one call (inside its on_device context)"""
+    if not sync:
+        if records is not None:
+            records = records.view((B, kde.RESULT_BYTES) if S is None else (B, S, kde.RESULT_BYTES))
+        return GroupConfigs(rows, source, B, S, records, cands, err)
+    picks = None if records is None else GroupPicks.from_bytes(records.cpu().numpy().tobytes(), B, S)
+    return GroupConfigs(rows.cpu().numpy(), source.cpu().numpy(), B, S, picks,
+                        None if cands is None else cands.cpu().numpy(), None if err is None else err.cpu().numpy())
+
+
+def _finish(device, stream, B, S, C, D, records, cands, err, levels, random_fraction, seed, counter_base, stream_id):
+    """one hbx_kde_finish_groups launch over device tensors (records None: NULL); (rows [B * S, D], source [B * S])"""
+    torch = kde._torch()
+    Sn = 1 if S is None else int(S)
+    rows = torch.empty((B * Sn, D), dtype=torch.float64, device=device)
+    source = torch.empty(B * Sn, dtype=torch.uint8, device=device)
+    lvd = _levels_dev(levels, D, device)
+    N.check(N.lib().hbx_kde_finish_groups(
+        N.ptr(records), N.ptr(cands), N.ptr(err), N.ptr(lvd), D, B, Sn, int(C), random_fraction,
+        int(seed) & (2 ** 64 - 1), int(counter_base) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF, N.ptr(rows),
+        N.ptr(source), N.stream_handle(stream, device)))
+    return rows, source
+
+
+def sample_prior(B, S, levels, seed, counter_base=0, C=1, stream=None, stream_id=0, device=None, sync=True):
+    """What B runs without any model answer S get_config requests each with (bohb.py:109-110): one prior draw per
+    request (hbx_kde_finish_groups without records), request (b, s) on the Philox counter
+    ``counter_base + (b * S + s) * C`` -- ``C`` is the counter stride, the pool size the same requests would use
+    with a model.  ``S`` None: one request per run, rows [B, D].  Returns GroupConfigs, every source
+    SOURCE_NO_MODEL."""
+    D = len(levels) if not _is_tensor(levels) else int(levels.shape[0])
+    if device is None:
+        device = levels.device if _is_tensor(levels) else kde.default_device()
+    with N.on_device(device, stream):
+        rows, source = _finish(device, stream, int(B), S, C, D, None, None, None, levels, 0.0, seed, counter_base,
+                               stream_id)
+        return _configs(rows, source, int(B), S, sync)
 
 
 GRP_EXACT_L, GRP_EXACT_G = 64, 128  # include/hbx.h HBX_GRP_EXACT_*
@@ -405,6 +496,88 @@ class GroupModel(object):
             return GroupLogPdf(None if ll is None else ll.cpu().numpy(), None if lg is None else lg.cpu().numpy(),
                                status.cpu().numpy(), stats, lead)
 
+    def workspace_bytes_get_config(self, C, requests=1):
+        return int(N.lib().hbx_kde_propose_groups_workspace_bytes(self.B, int(requests), int(C), self.D))
+
+    def get_config(self, C, seed, levels, requests=None, random_fraction=1.0 / 3, bandwidth_factor=3, counter_base=0,
+                   stream=None, stream_id=0, workspace=None, sync=True, keep_pools=False, records=True):
+        """The reference's get_config (bohb.py:104-169) for ``requests`` requests of every group in one call
+        (hbx_kde_propose_groups: ``sample`` with pool size S * C, ``acquire_requests`` and ``finish`` on one stream):
+        always a configuration -- the best of the request's C candidates, or a prior draw where the group has no
+        model, where the random fraction takes the request, where the sampler met a domain error and where no
+        candidate has a score.  ``levels`` may be an int32 device tensor (no upload).  Returns GroupConfigs: rows
+        [B, S, D] (``requests`` None: one request, [B, D]); with ``sync=False`` everything stays on the device and
+        nothing synchronises.  ``records=False`` leaves ``picks`` None; ``keep_pools`` also returns the pools and
+        the sampler's error bytes (``cands`` [B, S, C, D], ``domain_err`` [B, S, C])."""
+        torch = kde._torch()
+        S = 1 if requests is None else int(requests)
+        C = int(C)
+        rf = _fraction(random_fraction)
+        wsb = self.workspace_bytes_get_config(C, S)
+        if wsb < 0:
+            raise N.HbxError("get_config: B=%d S=%d C=%d out of range (C >= 1, B * S * C within int32)" % (self.B, S, C))
+        with N.on_device(self.device, stream):
+            lvd = _levels_dev(levels, self.D, self.device)
+            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
+            if ws.numel() < wsb:
+                raise N.HbxError("workspace too small")
+            rows = torch.empty((self.B * S, self.D), dtype=torch.float64, device=self.device)
+            source = torch.empty(self.B * S, dtype=torch.uint8, device=self.device)
+            rec = torch.empty((self.B * S, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device) if records else None
+            cands = torch.empty((self.B, S, C, self.D), dtype=torch.float64, device=self.device) if keep_pools else None
+            N.check(N.lib().hbx_kde_propose_groups(
+                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
+                N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
+                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(lvd), float(bandwidth_factor), rf,
+                int(seed) & (2 ** 64 - 1), int(counter_base) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF, S, C,
+                N.ptr(rows), N.ptr(source), N.ptr(rec), N.ptr(cands), N.ptr(ws), ws.numel(),
+                N.stream_handle(stream, self.device)))
+            err = None
+            if keep_pools:
+                off = np.zeros(4, dtype=np.int64)
+                N.check(N.lib().hbx_kde_propose_groups_ws_offsets(self.B, S, C, self.D, off.ctypes.data))
+                err = ws[int(off[1]):int(off[1]) + self.B * S * C].clone().view(self.B, S, C)
+                if requests is None:
+                    cands, err = cands.view(self.B, C, self.D), err.view(self.B, C)
+            return _configs(rows, source, self.B, None if requests is None else S, sync, rec, cands, err)
+
+    def finish(self, cands, records, domain_err, levels, random_fraction=1.0 / 3, seed=0, counter_base=0, stream=None,
+               stream_id=0, sync=True):
+        """The finish step alone (hbx_kde_finish_groups) over caller-made pools: ``cands`` [B, S, C, D] (or [B, C, D])
+        float64, ``records`` the ``sync=False`` output of ``acquire_requests`` (or ``acquire``) over them, or None
+        (every request SOURCE_NO_MODEL), ``domain_err`` the sampler's error bytes [B, S, C] (or [B, C]), or None.
+        ``seed``, ``counter_base`` and ``stream_id`` are the sampler's.  Returns GroupConfigs without picks."""
+        torch = kde._torch()
+        rf = _fraction(random_fraction)
+        with N.on_device(self.device, stream):
+            if _is_tensor(cands):
+                cd = cands
+                if cd.dtype != torch.float64 or not cd.is_contiguous():
+                    raise N.HbxError("candidate tensor must be contiguous float64 [B, S, C, D] or [B, C, D]")
+            else:
+                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
+            if cd.dim() not in (3, 4) or int(cd.shape[0]) != self.B or int(cd.shape[-1]) != self.D:
+                raise N.HbxError("candidates must be [%d, S, C, %d] or [%d, C, %d], got %s" %
+                                 (self.B, self.D, self.B, self.D, tuple(cd.shape)))
+            S = None if cd.dim() == 3 else int(cd.shape[1])
+            C = int(cd.shape[-2])
+            Q = self.B * (1 if S is None else S)
+            if C < 1:
+                raise N.HbxError("finish: a pool needs at least one candidate")
+            if records is not None:
+                if not _is_tensor(records) or records.dtype != torch.uint8 or not records.is_contiguous() or \
+                        records.numel() != Q * kde.RESULT_BYTES:
+                    raise N.HbxError("records must be the contiguous uint8 device tensor of %d records" % Q)
+            ed = domain_err
+            if ed is not None:
+                if not _is_tensor(ed):
+                    ed = torch.from_numpy(np.ascontiguousarray(ed, dtype=np.uint8)).to(self.device)
+                if ed.dtype != torch.uint8 or not ed.is_contiguous() or ed.numel() != Q * C:
+                    raise N.HbxError("domain_err must be contiguous uint8 with one byte per candidate")
+            rows, source = _finish(self.device, stream, self.B, S, C, self.D, records, cd, ed, levels, rf, seed,
+                                   counter_base, stream_id)
+            return _configs(rows, source, self.B, S, sync)
+
     def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, requests=None, topk=None):
         """sample + acquire: (rows [B, D] host float64 -- NaN where a group has no pick --, GroupPicks).
         With ``requests=S``: sample + acquire_requests, (rows [B, S, D], GroupPicks of shape [B, S]).
@@ -496,3 +669,88 @@ def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, 
                       order=order, n_good=ng, n_bad=nb, has_model=(ng > 0), n_good_dev=ngd, n_bad_dev=nbd,
                       fac_good_dev=fgd, fac_bad_dev=fbd, vt_dev=vtd, bw_good=bwg, bw_bad=bwb, nlev_good=nlg,
                       nlev_bad=nlb)
+
+
+class GroupBOHB(object):
+    """B independent BOHB optimisers advancing in lockstep (config #5's workload): what stands in for the reference's
+    ``BOHB`` config generator when every run reports the same number of results per step.  ``new_results`` is
+    bohb.py:171-251 for all runs at once (one batched refit), ``get_configs`` bohb.py:104-169 for S requests of
+    every run (one call, every row on the device).  Run b's observations of a budget are the rows ``[b, :, :]`` of
+    that budget's device store; ``kde_models`` maps budget -> GroupModel.  ``var_type``: the KDE's kinds ('c' / 'u'
+    per dim), ``levels``: D level counts (0: continuous)."""
+
+    def __init__(self, B, var_type, levels, min_points_in_model=None, top_n_percent=15, num_samples=64,
+                 random_fraction=1.0 / 3, bandwidth_factor=3, seed=0, device=None):
+        self.B, self.var_type, self.D = int(B), var_type, len(var_type)
+        self.levels = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
+        if self.levels.shape != (self.D,):
+            raise N.HbxError("levels must have %d entries" % self.D)
+        mp = self.D + 1 if min_points_in_model is None else int(min_points_in_model)
+        self.min_points_in_model = max(mp, self.D + 1)  # bohb.py:55-57
+        self.top_n_percent = top_n_percent
+        self.num_samples = int(num_samples)
+        self.random_fraction = _fraction(random_fraction)
+        self.bandwidth_factor = bandwidth_factor
+        self.seed = int(seed)
+        self.device = kde.default_device() if device is None else device
+        self.configs, self.losses = {}, {}  # budget -> device store [B, n, D] / [B, n]
+        self.kde_models = {}
+        self.counter = 0  # the next call's Philox counter base
+        self._lvd = None
+
+    def _dev(self, a, shape_tail):
+        torch = kde._torch()
+        t = a if _is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+        t = t.to(device=self.device, dtype=torch.float64)
+        if t.dim() != 1 + len(shape_tail) + 1 or int(t.shape[0]) != self.B or tuple(t.shape[2:]) != shape_tail:
+            raise N.HbxError("expected [%d, m%s], got %s" % (self.B, "".join(", %d" % v for v in shape_tail),
+                                                             tuple(t.shape)))
+        return t
+
+    def new_results(self, budget, X, losses):
+        """m finished runs per optimiser on ``budget``: ``X`` [B, m, D] (the configurations' vectors) and ``losses``
+        [B, m], host arrays or device tensors; a crashed run's loss is +inf (bohb.py:189-194).  Returns True when
+        the budget's model was refit."""
+        torch = kde._torch()
+        Xd, ld = self._dev(X, (self.D,)), self._dev(losses, ())
+        if int(Xd.shape[1]) != int(ld.shape[1]):
+            raise N.HbxError("new_results: %d rows and %d losses per run" % (Xd.shape[1], ld.shape[1]))
+        if budget not in self.configs:  # bohb.py:198-200
+            self.configs[budget] = torch.empty((self.B, 0, self.D), dtype=torch.float64, device=self.device)
+            self.losses[budget] = torch.empty((self.B, 0), dtype=torch.float64, device=self.device)
+        if max(list(self.kde_models.keys()) + [-np.inf]) > budget:  # bohb.py:204-205: a bigger model exists
+            return False
+        self.configs[budget] = torch.cat((self.configs[budget], Xd), dim=1)
+        self.losses[budget] = torch.cat((self.losses[budget], ld), dim=1)
+        n = int(self.configs[budget].shape[1])
+        if n <= self.min_points_in_model + 1:  # bohb.py:216-217
+            return False
+        gm = fit_groups(self.configs[budget].reshape(self.B * n, self.D), self.losses[budget].reshape(-1),
+                        np.arange(self.B + 1, dtype=np.int64) * n, self.var_type, self.min_points_in_model,
+                        self.top_n_percent, device=self.device)
+        if not np.all(gm.has_model):  # bohb.py:234-237: the previous model, if any, stays
+            return False
+        self.kde_models[budget] = gm
+        return True
+
+    def _levels(self):
+        if self._lvd is None:
+            self._lvd = kde._torch().from_numpy(self.levels).to(self.device)
+        return self._lvd
+
+    def get_configs(self, budget, S=1, counter_base=None, sync=True):
+        """S configurations for every optimiser (``budget`` is the budget they are scheduled for; as in the
+        reference, the model of the largest modelled budget answers, bohb.py:124): GroupConfigs with rows
+        [B, S, D].  Prior draws while there is no model.  ``counter_base`` None: the internal counter, which
+        advances by B * S * num_samples per call."""
+        S = int(S)
+        if counter_base is None:
+            counter_base = self.counter
+            self.counter += self.B * S * self.num_samples
+        if not self.kde_models:  # bohb.py:109
+            return sample_prior(self.B, S, self._levels(), self.seed, counter_base, C=self.num_samples,
+                                device=self.device, sync=sync)
+        gm = self.kde_models[max(self.kde_models.keys())]
+        return gm.get_config(self.num_samples, self.seed, self._levels(), requests=S,
+                             random_fraction=self.random_fraction, bandwidth_factor=self.bandwidth_factor,
+                             counter_base=counter_base, sync=sync)

@@ -27,6 +27,10 @@
  *   hbx_kde_acquire_groups_topk     <- bohb.py:124-169 per bracket, the scores ranked: the k best candidates of
  *                                      every bracket's pool by (score, index), one call
  *   hbx_kde_sample_groups           <- bohb.py:133-147 per bracket (the candidates of B brackets in one call)
+ *   hbx_kde_finish_groups           <- bohb.py:107-111,154-166 per request (the prior draw where get_config does not
+ *                                      return a model-based pick; the winning row otherwise), B x S requests
+ *   hbx_kde_propose_groups          <- bohb.py:104-169 (get_config whole: sample, score, pick, fall back) for S
+ *                                      requests of each of B brackets, one call
  *   hbx_kde_logpdf_groups           <- KDEMultivariate.pdf (kernel_density.py:162-196) of both KDEs of every bracket
  *                                      at every candidate of its pool, as ln pdf within a relative tolerance, one call
  *   hbx_kde_logpdf                  <- KDEMultivariate.pdf (kernel_density.py:162-196), fp32 log domain
@@ -362,6 +366,55 @@ int hbx_kde_sample_groups(const double* X, int32_t D, const int64_t* seg_off, in
                           const int64_t* n_good, const double* bw_good, const int32_t* levels,
                           double bw_factor, uint64_t seed, uint64_t counter_base, uint32_t stream_id,
                           int64_t C, double* cands, uint8_t* domain_err, void* stream);
+/* Grouped get_config, the finish step: the configuration vector of every one of B x S requests after a grouped
+ * acquisition (bohb.py:107-111,154-166).  Request q = b * S + s has its record records[q]
+ * (hbx_kde_acquire_groups_batch's layout; S = 1: hbx_kde_acquire_groups'), its pool cands[q][C][D] and its sampler
+ * flags domain_err[q][C].  source_out[q], by the first rule that matches, and rows_out[q][0..D):
+ *   2 HBX_CFG_NO_MODEL         the record's flags carry HBX_ACQ_NO_MODEL or HBX_ACQ_UNSUPPORTED, or records == NULL
+ *                              (bohb.py:109: no model for the run)                                       prior draw
+ *   1 HBX_CFG_RANDOM_FRACTION  u_q < random_fraction (bohb.py:109)                                       prior draw
+ *   4 HBX_CFG_DOMAIN_ERR       a byte of domain_err[q][0..C) is not zero (bohb.py:163-166: the sampler raised)
+ *                                                                                                        prior draw
+ *   3 HBX_CFG_NO_SCORE         the record's index < 0 (bohb.py:154-157: best_vector is None)             prior draw
+ *   0 HBX_CFG_MODEL            otherwise                                       cands[q][index][:], copied bit for bit
+ * The request's draws use its first candidate counter ctr_q = counter_base + q * C with hbx_kde_sample_groups' seed
+ * and stream_id and counter words the sampler never uses, so they never meet a candidate's draws and do not depend on
+ * the other groups of the call: u_q = u01(bits64(philox(ctr_q, 0xFFFFFFFE), 0)); the prior of dims 2p and 2p + 1
+ * from philox(ctr_q, 0xFFFE0000 + p), u = u01(bits64(r, 0)) and u01(bits64(r, 1)) (u01: ((bits >> 11) + 0.5) 2^-53,
+ * open): levels[d] == 0 gives u (configspace.py:62), levels[d] = t > 0 gives (double)min(t - 1, floor(t u))
+ * (configspace.py:97,113).  numpy's interval is half-open, this one open: parity with the reference's prior is
+ * distributional, as for the sampler.
+ * records may be NULL (every request HBX_CFG_NO_MODEL; cands and domain_err are then not read); domain_err may be NULL
+ * (no HBX_CFG_DOMAIN_ERR).  C >= 1.  An index not below C, which no acquisition writes, is treated as HBX_CFG_NO_SCORE
+ * and never used as an offset.  rows_out: f64[B][S][D]; source_out: u8[B][S].  One launch on `stream`, no host
+ * synchronisation; the records are not written.  B == 0 or S == 0: nothing to do.  Null pointers, B * S * C beyond
+ * int32, D outside [1, hbx_max_dims()], random_fraction outside [0, 1] or NaN: HBX_ERR_ARG. */
+#define HBX_CFG_MODEL 0
+#define HBX_CFG_RANDOM_FRACTION 1
+#define HBX_CFG_NO_MODEL 2
+#define HBX_CFG_NO_SCORE 3
+#define HBX_CFG_DOMAIN_ERR 4
+int hbx_kde_finish_groups(const void* records, const double* cands, const uint8_t* domain_err, const int32_t* levels,
+                          int32_t D, int64_t B, int64_t S, int64_t C, double random_fraction, uint64_t seed,
+                          uint64_t counter_base, uint32_t stream_id, double* rows_out, uint8_t* source_out, void* stream);
+/* Grouped get_config whole (bohb.py:104-169 for S requests of each of B brackets): hbx_kde_sample_groups (pool S * C
+ * per group) + hbx_kde_acquire_groups_batch + hbx_kde_finish_groups with the same seed, counter_base and stream_id,
+ * on one stream, no host synchronisation -- by definition that composition, byte for byte.  The model arguments are
+ * hbx_kde_acquire_groups_batch's.  The pools and error bytes live in the workspace (hbx_kde_propose_groups_ws_offsets:
+ * byte offsets of [pools f64[B][S][C][D], error bytes u8[B][S][C], records, end]); records_out (B * S records,
+ * 8-byte aligned) and cands_out (f64[B][S][C][D]) -- either may be NULL -- receive the records and a copy of the
+ * pools.  Requests that end up random are still sampled and scored.  workspace:
+ * hbx_kde_propose_groups_workspace_bytes(B, S, C, D) bytes, 16-byte aligned (-1 for arguments out of range, C < 1
+ * included).  Argument errors as hbx_kde_finish_groups', plus a short or misaligned workspace. */
+int64_t hbx_kde_propose_groups_workspace_bytes(int64_t B, int64_t S, int64_t C, int32_t D);
+int hbx_kde_propose_groups_ws_offsets(int64_t B, int64_t S, int64_t C, int32_t D, int64_t* out4);
+int hbx_kde_propose_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                           const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                           const double* bw_good, const double* bw_bad,
+                           const int32_t* nlev_good, const int32_t* nlev_bad, const int32_t* levels,
+                           double bandwidth_factor, double random_fraction, uint64_t seed, uint64_t counter_base,
+                           uint32_t stream_id, int64_t S, int64_t C, double* rows_out, uint8_t* source_out,
+                           void* records_out, double* cands_out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Optional timing: `events` of hbx_kde_acquire is NULL or an array of three hipEvent_t recorded on
  * `stream` before the l scoring launch, between l and g, and after g -- or, when l and g are scored by

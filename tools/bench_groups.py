@@ -27,6 +27,11 @@ S = K pools and the per-bracket acquire_topk loop; prints one JSON line and writ
 
 times hbx_kde_logpdf_groups (logpdf_bench below) in default and FP64_ONLY mode at config #5's shape and at a plain
 unsigned shape (8c) against the per-bracket prepare + logpdf loop; writes profiles/groups_logpdf/bench_groups_logpdf.json.
+
+    python tools/bench_groups.py --get-config [--requests S] [--out FILE]
+
+times the grouped get_config (get_config_bench below): hbx_kde_propose_groups against its parts and against
+propose(requests=S) plus a host prior fill; writes profiles/groups_get_config/bench_groups_get_config.json.
 """
 import argparse
 import json
@@ -347,6 +352,109 @@ def logpdf_bench(a, dev, L):
     return 0 if ok else 1
 
 
+def each_timed(fn, reps, warm=3):
+    """{mean, min, max} ms of fn, every warmed repetition between its own pair of device events"""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for e0, e1 in ev:
+        e0.record()
+        fn()
+        e1.record()
+    torch.cuda.synchronize()
+    ms = [e0.elapsed_time(e1) for e0, e1 in ev]
+    return {"ms_mean": float(np.mean(ms)), "ms_min": float(np.min(ms)), "ms_max": float(np.max(ms))}
+
+
+def get_config_bench(a, gm, L, sh, lvd, levels):
+    """--get-config: S = --requests get_config requests per bracket, every one answered with a configuration.
+      fused      hbx_kde_propose_groups (records kept, pools left in the workspace)
+      two_calls  hbx_kde_sample_groups (pool S C) + hbx_kde_acquire_groups_batch: the composition's first two calls
+      finish     hbx_kde_finish_groups alone, over the pools and records the two calls left
+      parent     what the library offered before for the same answer: propose(requests=S) -- the same two calls, the
+                 records fetched, the winning rows gathered through the host -- plus a numpy prior fill of the rows
+                 the random fraction takes and of the NaN rows (wall clock, synchronised)
+    The fused call's rows and sources are compared with finish's over the two calls' outputs (byte equality)."""
+    dev = gm.device
+    B, R, C, D = gm.B, a.requests, a.C, gm.D
+    rf, seed = 1.0 / 3, S.SEED_CAND
+    a.out = a.out or os.path.join(ROOT, "profiles", "groups_get_config", "bench_groups_get_config.json")
+    model = (N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
+             N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad))
+    wsf = int(L.hbx_kde_propose_groups_workspace_bytes(B, R, C, D))
+    wsb = int(L.hbx_kde_groups_batch_workspace_bytes(B, R, C, D))
+    ws = torch.empty(wsf, dtype=torch.uint8, device=dev)
+    pool = torch.empty((B, R, C, D), dtype=torch.float64, device=dev)
+    derr = torch.empty((B, R, C), dtype=torch.uint8, device=dev)
+    rec = torch.empty((B, R, kde.RESULT_BYTES), dtype=torch.uint8, device=dev)
+    rec_f = torch.empty_like(rec)
+    rows, src = (torch.empty((B, R, D), dtype=torch.float64, device=dev),
+                 torch.empty((B, R), dtype=torch.uint8, device=dev))
+    rows_f, src_f = torch.empty_like(rows), torch.empty_like(src)
+
+    def fused():
+        N.check(L.hbx_kde_propose_groups(*model, N.ptr(lvd), 3.0, rf, seed, 0, 0, R, C, N.ptr(rows_f), N.ptr(src_f),
+                                         N.ptr(rec_f), None, N.ptr(ws), wsf, sh))
+
+    def two_calls():
+        N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
+                                        N.ptr(gm.bw_good), N.ptr(lvd), 3.0, seed, 0, 0, R * C, N.ptr(pool),
+                                        N.ptr(derr), sh))
+        N.check(L.hbx_kde_acquire_groups_batch(*model, N.ptr(pool), R, C, N.ptr(rec), N.ptr(ws), wsb, sh))
+
+    def finish():
+        N.check(L.hbx_kde_finish_groups(N.ptr(rec), N.ptr(pool), N.ptr(derr), N.ptr(lvd), D, B, R, C, rf, seed, 0, 0,
+                                        N.ptr(rows), N.ptr(src), sh))
+
+    lv = np.asarray(levels)
+
+    def parent():
+        got, picks = gm.propose(C, seed, levels, requests=R)
+        rs = np.random.RandomState(0)
+        fill = (rs.rand(B, R) < rf) | np.isnan(got).any(axis=2)
+        draw = rs.rand(int(fill.sum()), D)
+        cat = lv > 0
+        draw[:, cat] = np.floor(draw[:, cat] * lv[cat])
+        got[fill] = draw
+        return got
+
+    out = {"workload": "grouped_get_config_b%d_n%d_d32_24c8u_s%d_c%d" % (B, a.n, R, C),
+           "device": torch.cuda.get_device_name(0), "reps": a.reps, "requests": R, "random_fraction": rf,
+           "workspace_bytes": wsf}
+    two_calls()
+    out["two_calls"] = each_timed(two_calls, a.reps)
+    out["finish"] = each_timed(finish, a.reps)
+    out["fused"] = each_timed(fused, a.reps)
+    out["two_calls_then_finish"] = each_timed(lambda: (two_calls(), finish()), a.reps)
+    t = []
+    for it in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        parent()
+        t.append(1e3 * (time.perf_counter() - t0))
+    out["parent_propose_plus_host_fill"] = {"ms_mean": float(np.mean(t[2:])), "ms_min": float(np.min(t[2:])),
+                                            "ms_max": float(np.max(t[2:]))}
+    same = bool(torch.equal(rows.view(torch.int64), rows_f.view(torch.int64)) and torch.equal(src, src_f) and
+                torch.equal(rec, rec_f))
+    sh_ = src_f.cpu().numpy()
+    out.update({"fused_equals_composition": same,
+                "sources": {str(k): int((sh_ == k).sum()) for k in range(5)},
+                "finish_bytes_read": B * R * (48 + C), "finish_bytes_written": B * R * (8 * D + 1),
+                "fused_slowest_minus_parts_fastest_ms": out["fused"]["ms_max"] - out["two_calls"]["ms_min"] -
+                out["finish"]["ms_min"],
+                "fused_mean_minus_parts_mean_ms": out["fused"]["ms_mean"] - out["two_calls"]["ms_mean"] -
+                out["finish"]["ms_mean"],
+                "parent_fastest_over_fused_slowest": out["parent_propose_plus_host_fill"]["ms_min"] /
+                out["fused"]["ms_max"]})
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+    return 0 if same else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=10000)
@@ -360,6 +468,8 @@ def main(argv=None):
                     help="time only the S one-request calls (what a library without the batched call offers)")
     ap.add_argument("--topk", type=int, default=0, help="the K best candidates per bracket (topk_bench)")
     ap.add_argument("--logpdf", action="store_true", help="both KDEs' ln pdf of every pool (logpdf_bench)")
+    ap.add_argument("--get-config", action="store_true",
+                    help="a configuration per request with the reference's fall-backs (get_config_bench)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     L = N.lib()
@@ -379,6 +489,8 @@ def main(argv=None):
     seg = np.arange(B + 1, dtype=np.int64) * n
     gm = groups.fit_groups(X, losses, seg, vts, device=dev)
     sh = N.stream_handle(None, dev)
+    if a.get_config:
+        return get_config_bench(a, gm, L, sh, torch.tensor(levels, dtype=torch.int32, device=dev), levels)
     if a.topk:
         return topk_bench(a, gm, L, sh, torch.tensor(levels, dtype=torch.int32, device=dev))
     if a.requests > 1 or a.loop_only:
