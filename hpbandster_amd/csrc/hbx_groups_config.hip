@@ -28,6 +28,7 @@
 // hbx_kde_propose_groups is the composition hbx_kde_sample_groups (pool S C) -> hbx_kde_acquire_groups_batch ->
 // the finish launch on one stream; it calls the two existing entry points as they are.
 #include "hbx_common.h"
+#include "hbx_groups_impl.h"  // grp_counts_ok
 #include "hbx_philox.h"
 
 #define FIN_WAVES 4  // requests per block
@@ -84,20 +85,13 @@ __global__ __launch_bounds__(64 * FIN_WAVES) void groups_finish_kernel(
   if (lane == 0) source_out[q] = (uint8_t)src;
 }
 
-// B * S * C within int32 (hbx_groups.hip's rule: what the grids and the slot indices of the composition rely on)
-static bool cfg_counts_ok(int64_t B, int64_t S, int64_t C) {
-  if (B < 0 || S < 0 || C < 0 || B > INT32_MAX || S > INT32_MAX) return false;
-  if (S > 0 && B > (int64_t)INT32_MAX / S) return false;
-  return !(C > 0 && B * S > (int64_t)INT32_MAX / C);
-}
-
 // the checks the finish step and the fused call share; 1: nothing to do
 static int cfg_check(const char* who, int32_t D, int64_t B, int64_t S, int64_t C, double random_fraction,
                      const int32_t* levels, const double* rows_out, const uint8_t* source_out) {
   if (D < 1 || D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "%s: D=%d outside [1, %d]", who, D, HBX_MAX_D);
   if (B < 0 || S < 0 || C < 1)
     return hbx_fail(HBX_ERR_ARG, "%s: B=%lld S=%lld C=%lld", who, (long long)B, (long long)S, (long long)C);
-  if (!cfg_counts_ok(B, S, C))
+  if (!grp_counts_ok(B, S, C))  // (what the grids and the slot indices of the composition rely on)
     return hbx_fail(HBX_ERR_ARG, "%s: B * S * C = %lld * %lld * %lld exceeds int32", who, (long long)B, (long long)S,
                     (long long)C);
   if (!(random_fraction >= 0.0 && random_fraction <= 1.0))

@@ -23,7 +23,9 @@
 // (hbx_groups.hip's buckets: D <= 8, 16, 32 any mix; D <= 96 up to 64 continuous + 32 categorical).  Its values are
 // ln of the reference's own fp64 pdf: NaN where that is negative or NaN, -inf where it underflows to 0.
 //
-// The fp32 pass, glp_dd_kernel<DCP, DUP, NW, DT>: groups_screen_kernel's structure for one KDE -- lane = candidate
+// The fp32 pass, glp_dd_kernel<DCP, DUP, NW, DT>: built from hbx_groups_impl.h's pieces for one KDE (the slots, the
+// row layout, the per-slot constants, grp_stage, grp_load_cand, the pair exponent grp_pair_t and its dispatch -- the
+// acquisition's screens use the same ones; this pass keeps its own sums and its own bound) -- lane = candidate
 // (its scaled coordinates in registers), the block's NW waves take the KDE's 64-observation chunks in turn, each
 // gathered through `order`, centred, scaled and staged as fp32 in the wave's LDS rows, read back as broadcasts.  Per
 // pair, in log2 units, direct differences (no expansion, so no cancellation):
@@ -70,9 +72,7 @@
 // splitting the KDE's 32-row chunks as in the fp32 pass and merging their (m, S) with fp64 exp2.  Categorical codes
 // are compared as fp32 (cand_code): exact for observed codes (integers in [0, 1024)), and a candidate value that is
 // no such integer matches nothing, in the reference as here.
-#include <math.h>
-
-#include "hbx_exact_impl.h"
+#include "hbx_groups_impl.h"
 
 #define GLP_HEAD 256  // workspace header: the four counters (u64) in its first 32 bytes
 #define GLP_G 4       // terms per fp32 group
@@ -80,20 +80,10 @@
 #define GLP_BAD (HBX_ACQ_NO_MODEL | HBX_ACQ_UNSUPPORTED)
 
 struct GlpArgs {
-  const double* X;
-  const int64_t* seg_off;
-  const int64_t* order;
-  const int64_t* n_good;
-  const int64_t* n_bad;
-  const int32_t* vartype;
-  const double* bw_good;
-  const double* bw_bad;
-  const int32_t* nlev_good;
-  const int32_t* nlev_bad;
+  GrpModel M;
   const double* cand;
-  int64_t B, C;
-  int32_t D, tiles;  // tiles = ceil(C / 64)
-  int32_t dcp, dup;  // the slot bucket (from D alone)
+  int64_t C;
+  int32_t tiles;     // ceil(C / 64)
   int32_t kd0;       // first KDE of the launch's grid.y (0: good / ln_l, 1: bad / ln_g)
   int32_t fp64_only;
   double rtol;
@@ -104,78 +94,28 @@ struct GlpArgs {
   int32_t* list;             // [B][2][C]
 };
 
-// the per-group parameter view the exact functions read (hbx_exact_impl.h)
-struct GlpView {
-  int32_t n;
-  const double* bw;
-  const int32_t* vartype;
-  const int32_t* nlev;
-  double prod_bw_c;
-};
-
-// status[b]: hbx_kde_fit's skip rule and hbx_kde_prepare's per-dim rules as hbx_kde_acquire_groups applies them
-// (grp_status, hbx_groups.hip), with the exact-only conditions kept per KDE.  One wave per group.
+// status[b] from grp_classify's bits (hbx_groups_impl.h), one wave per group.  The ln-pdf's reading of them, stated
+// here and nowhere else: HBX_GRP_EXACT_L / _G per KDE where it cannot be screened (GRP_EXACT(kd)) -- and also where a
+// match factor is negative (h > 1, GRP_NEG(kd)): the fp32 and fp64 passes sum positive terms only, so a signed KDE
+// goes through the exact pdf (the acquisition screens it as a signed sum).  UNSUPPORTED comes alone.
 __global__ __launch_bounds__(256) void glp_status_kernel(GlpArgs A) {
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= A.B) return;  // whole wave
-  const int64_t n = A.seg_off[b + 1] - A.seg_off[b], ng = A.n_good[b], nb = A.n_bad[b];
-  if (ng <= 0 || ng > n || nb <= 0 || nb > n) {
-    if (lane == 0) A.status[b] = HBX_ACQ_NO_MODEL;
-    return;
-  }
-  int st = 0, dc = 0, du = 0;
-  for (int d0 = 0; d0 < A.D; d0 += 64) {
-    const int d = d0 + lane;
-    const bool live = d < A.D;
-    const bool cont = live && A.vartype[d] == 0;
-    dc += __popcll(__ballot(cont));
-    du += __popcll(__ballot(live && !cont));
-    if (!live) continue;
-#pragma unroll
-    for (int kd = 0; kd < 2; ++kd) {
-      const int ex = kd ? HBX_GRP_EXACT_G : HBX_GRP_EXACT_L;
-      const double h = (kd ? A.bw_bad : A.bw_good)[b * A.D + d];
-      if (cont) {
-        if (!(h > 0.0 && h < INFINITY)) st |= ex;  // pdf NaN (or 0) everywhere: the exact path says which
-      } else {
-        const int c = (kd ? A.nlev_bad : A.nlev_good)[b * A.D + d];
-        if (c == 1 && h == 0.0)
-          st |= ex;  // one observed level: match -> 1, mismatch -> 0 / 0
-        else if (c < 2 || !(h > 0.0) || h != h)
-          st |= HBX_ACQ_UNSUPPORTED;  // (c == -1: codes not integers in [0, 1024))
-        else if (!(h < INFINITY) || 1.0 - h < 0.0)
-          st |= ex;  // (h > 1: a negative match factor, signed sums)
-      }
-    }
-  }
-  st = (int)wave_reduce_dpp((uint32_t)st, OpOr());
-  if (dc > A.dcp || du > A.dup) st |= HBX_GRP_EXACT_L | HBX_GRP_EXACT_G;
-  if (st & HBX_ACQ_UNSUPPORTED) st = HBX_ACQ_UNSUPPORTED;
+  if (b >= A.M.B) return;  // whole wave
+  int dc, du;
+  const int c = grp_classify(A.M, b, &dc, &du);
+  int st = 0;
+  if (c & GRP_NO_MODEL)
+    st = HBX_ACQ_NO_MODEL;
+  else if (c & GRP_UNSUPPORTED)
+    st = HBX_ACQ_UNSUPPORTED;
+  else
+    st = ((c & (GRP_EXACT(0) | GRP_NEG(0))) ? HBX_GRP_EXACT_L : 0) | ((c & (GRP_EXACT(1) | GRP_NEG(1))) ? HBX_GRP_EXACT_G : 0);
   if (lane == 0) A.status[b] = st;
 }
 
-// The dims of a usable KDE sorted into slots in dim order by one wave: continuous dims to cdim[0 .. dc), categorical
-// dims to udim[0 .. du); every lane returns the counts (dc <= DCP, du <= DUP: the status kernel checked the bucket).
-__device__ __forceinline__ void glp_slots(const GlpArgs& A, int lane, int32_t* cdim, int32_t* udim, int* dc, int* du) {
-  int kc = 0, ku = 0;
-  for (int d0 = 0; d0 < A.D; d0 += 64) {
-    const int d = d0 + lane;
-    const bool cont = d < A.D && A.vartype[d] == 0, cat = d < A.D && !cont;
-    const uint64_t mc = __ballot(cont), mu = __ballot(cat), below = (1ull << lane) - 1ull;
-    if (cont) cdim[kc + __popcll(mc & below)] = d;
-    if (cat) udim[ku + __popcll(mu & below)] = d;
-    kc += __popcll(mc);
-    ku += __popcll(mu);
-  }
-  *dc = kc;
-  *du = ku;
-}
-
-// One staged chunk's pairs for this lane's candidate: rows[0 .. jmax) of the wave's LDS rows (stride rs floats:
-// continuous slots from 0, categorical slots from 4 dcq), GLP_G terms per fp32 group, the groups into S.
-// QC >= 0: QC continuous and QU categorical 4-slot pieces at compile time (every LDS read of a row issued before its
-// first use, grp_pairs_fast's reason); QC < 0: dcq / duq pieces with a uniform branch each.
+// One staged chunk's pairs for this lane's candidate: rows[0 .. jmax) of the wave's LDS rows (grp_pair_t's exponent
+// from t0 = 0, piece counts as there), GLP_G terms per fp32 group, the groups into S.
 template <int DCP, int DUP, int QC, int QU>
 __device__ __forceinline__ void glp_pairs(const float* __restrict__ rows, int rs, int jmax, int dcq, int duq,
                                           const float (&xc)[DCP], const float (&xu)[DUP], const float (&dl)[DUP],
@@ -185,53 +125,8 @@ __device__ __forceinline__ void glp_pairs(const float* __restrict__ rows, int rs
 #pragma unroll
     for (int g = 0; g < GLP_G; ++g) {
       if (j0 + g >= jmax) break;  // uniform
-      const float4* rj = (const float4*)(rows + (j0 + g) * rs);
-      float t = 0.f;
-      if constexpr (QC >= 0) {
-        static_assert(4 * QC <= DCP && 4 * QU <= DUP, "pieces within the slots");
-        float4 vc[QC > 0 ? QC : 1], vu[QU > 0 ? QU : 1];
-#pragma unroll
-        for (int q = 0; q < QC; ++q) vc[q] = rj[q];
-#pragma unroll
-        for (int q = 0; q < QU; ++q) vu[q] = rj[QC + q];
-#pragma unroll
-        for (int q = 0; q < QC; ++q) {
-          const float4 v = vc[q];
-          const float d0 = xc[4 * q] - v.x, d1 = xc[4 * q + 1] - v.y, d2 = xc[4 * q + 2] - v.z, d3 = xc[4 * q + 3] - v.w;
-          t = fmaf(-d0, d0, t);
-          t = fmaf(-d1, d1, t);
-          t = fmaf(-d2, d2, t);
-          t = fmaf(-d3, d3, t);
-        }
-#pragma unroll
-        for (int q = 0; q < QU; ++q) {
-          const float4 v = vu[q];
-          t = fmaf(cat_match(xu[4 * q], v.x), dl[4 * q], t);
-          t = fmaf(cat_match(xu[4 * q + 1], v.y), dl[4 * q + 1], t);
-          t = fmaf(cat_match(xu[4 * q + 2], v.z), dl[4 * q + 2], t);
-          t = fmaf(cat_match(xu[4 * q + 3], v.w), dl[4 * q + 3], t);
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < DCP / 4; ++q)
-          if (q < dcq) {  // uniform
-            const float4 v = rj[q];
-            const float d0 = xc[4 * q] - v.x, d1 = xc[4 * q + 1] - v.y, d2 = xc[4 * q + 2] - v.z, d3 = xc[4 * q + 3] - v.w;
-            t = fmaf(-d0, d0, t);
-            t = fmaf(-d1, d1, t);
-            t = fmaf(-d2, d2, t);
-            t = fmaf(-d3, d3, t);
-          }
-#pragma unroll
-        for (int q = 0; q < DUP / 4; ++q)
-          if (q < duq) {  // uniform
-            const float4 v = rj[dcq + q];
-            t = fmaf(cat_match(xu[4 * q], v.x), dl[4 * q], t);
-            t = fmaf(cat_match(xu[4 * q + 1], v.y), dl[4 * q + 1], t);
-            t = fmaf(cat_match(xu[4 * q + 2], v.z), dl[4 * q + 2], t);
-            t = fmaf(cat_match(xu[4 * q + 3], v.w), dl[4 * q + 3], t);
-          }
-      }
+      const float t = grp_pair_t<DCP, DUP, QC, QU, false>((const float4*)(rows + (j0 + g) * rs), dcq, duq, xc, xu, dl,
+                                                          nullptr, 0.f, nullptr);
       const float tc = ceilf(t);
       if (tc > m) {  // a new reference point (integer): exact rescale of both sums
         const int sh = (int)fmaxf(m - tc, -250.f);
@@ -245,22 +140,21 @@ __device__ __forceinline__ void glp_pairs(const float* __restrict__ rows, int rs
   }
 }
 
+// the dispatch's call: this lane's candidate against jmax staged rows, piece counts (QC, QU)
+#define GLP_PAIRS_CALL(QC, QU) glp_pairs<DCP, DUP, QC, QU>(wrows, lay.rs, jmax, lay.dcq, lay.duq, xc, xu, dl, m, S)
+
 template <int DCP, int DUP, int NW, int DT>
 __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
   constexpr int NT = 64 * NW;
   __shared__ __align__(16) float sobs[NW * 64 * (DT + 4)];
-  __shared__ double s_scale[DCP], s_mu[DCP];
-  __shared__ float s_delta[DUP];
-  __shared__ int32_t s_cdim[DCP], s_udim[DUP];
+  GRP_CONSTS_LDS(K, DCP, DUP, 1);  // the constants of KDE kd alone
   __shared__ uint32_t s_bmax[DCP];
-  __shared__ int32_t s_doff[DCP + DUP];                // dim -> float offset of its slot in a staged row
-  __shared__ double s_dsc[DCP + DUP], s_dmu[DCP + DUP];  // dim -> scale (categorical: 1) and centre (0)
   __shared__ float s_pm[NW][64];
   __shared__ double s_ps[NW][64];
   __shared__ int32_t s_i[2];
   __shared__ double s_norm, s_lbln, s_sdp, s_sad;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int D = A.D;
+  const int D = A.M.D;
   const int kd = A.kd0 + (int)blockIdx.y;
   const int64_t b = (int64_t)blockIdx.x / A.tiles;
   const int tile = (int)((int64_t)blockIdx.x - b * A.tiles);
@@ -270,7 +164,7 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
   const bool valid = i < A.C;
   if (wave == 0) {
     int dc, du;
-    glp_slots(A, lane, s_cdim, s_udim, &dc, &du);
+    grp_slots(A.M, lane, K.cdim, K.udim, &dc, &du);  // (dc <= DCP, du <= DUP: the status kernel checked the bucket)
     if (lane == 0) {
       s_i[0] = dc;
       s_i[1] = du;
@@ -278,65 +172,28 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
   }
   __syncthreads();
   const int dc = s_i[0], du = s_i[1];
-  const int64_t s0 = A.seg_off[b], n = A.seg_off[b + 1] - s0;
-  const int64_t ng = A.n_good[b], nk = kd ? A.n_bad[b] : ng;
-  const double* Xs = A.X + s0 * D;
-  const int64_t* ord = A.order + s0;
-  const int64_t* rows = ord + (kd ? n - nk : 0);
-  const double* bw = (kd ? A.bw_bad : A.bw_good) + b * D;
-  const int32_t* nlev = (kd ? A.nlev_bad : A.nlev_good) + b * D;
-  // the row layout: continuous slots from 0, categorical slots from 4 dcq.  Compile-time piece counts serve dc <= 32
-  // in 2 / 4 / 6 / 8 pieces with du <= 8 in 0 / 2 pieces (config #5's 24c + 8u: 6 + 2); the rest the exact counts
-  const int qcs = dc <= 8 ? 2 : dc <= 16 ? 4 : dc <= 24 ? 6 : 8;
-  const bool fast = dc <= 32 && du <= 8 && 4 * qcs <= DCP && DUP >= 8;
-  const int dcq = fast ? qcs : (dc + 3) >> 2;
-  const int duq = fast ? (du ? 2 : 0) : (du + 3) >> 2;
-  const int dc4 = 4 * dcq, du4 = 4 * duq;
-  const int rs = dc4 + du4 + 4;  // <= DT + 4
-  const int rpp = D <= 64 ? 64 / D : 1;  // rows per staging pass
-  for (int e = tid; e < NT * rs; e += NT) sobs[e] = 0.f;  // (the padding slots stay 0)
-  for (int k = tid; k < DCP; k += NT) {
-    s_bmax[k] = 0u;
-    if (k < dc) {
-      const int d = s_cdim[k];
-      const int nm = (int)(ng < 64 ? ng : 64);
-      double sum = 0.0;
-#pragma unroll 16
-      for (int j = 0; j < nm; ++j) sum += Xs[ord[j] * D + d];
-      double mu = sum / (double)nm;
-      if (!(mu - mu == 0.0)) mu = 0.0;
-      s_mu[k] = mu;
-      s_dmu[d] = mu;
-      s_doff[d] = k;
-      s_scale[k] = sqrt(M_LOG2E / 2.0) / bw[d];
-      s_dsc[d] = s_scale[k];
-    } else {
-      s_mu[k] = 0.0;
-      s_scale[k] = 0.0;
-    }
-  }
-  for (int u = tid; u < DUP; u += NT) {
-    float dl = 0.f;
-    if (u < du) {
-      const int d = s_udim[u];
-      s_doff[d] = dc4 + u;
-      s_dsc[d] = 1.0;
-      s_dmu[d] = 0.0;
-      const double h = bw[d], a = 1.0 - h;  // (a >= 0: a negative factor is an EXACT KDE)
-      dl = (a == 0.0) ? -1e30f : (float)(log2(a) - log2(h / (double)(nlev[d] - 1)));
-    }
-    s_delta[u] = dl;
-  }
+  const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
+  const int64_t nk = kd ? A.M.n_bad[b] : A.M.n_good[b];
+  const double* Xs = A.M.X + s0 * D;
+  const int64_t* rows = A.M.order + s0 + (kd ? n - nk : 0);
+  const double* bw = (kd ? A.M.bw_bad : A.M.bw_good) + b * D;
+  const int32_t* nlev = (kd ? A.M.nlev_bad : A.M.nlev_good) + b * D;
+  const GrpLayout lay = grp_layout<DCP, DUP>(D, dc, du);
+  for (int e = tid; e < NT * lay.rs; e += NT) sobs[e] = 0.f;  // (the padding slots stay 0)
+  for (int k = tid; k < DCP; k += NT) s_bmax[k] = 0u;
+  grp_consts_fill<NT>(K, A.M, b, kd, dc, du, lay.dc4, tid);  // (1 - h >= 0 here: a negative factor is an EXACT KDE)
   __syncthreads();
-  if (tid == 0) {  // the sums in slot order (deterministic)
+  // This pass's own sums, in slot order (deterministic): fp64 and, for lb, in ln units -- the screens' (grp_screen_sums)
+  // are the fp32 chain's start and its bound, other quantities
+  if (tid == 0) {
     double sl = 0.0, lbln = 0.0, sdp = 0.0, sad = 0.0;
-    for (int k = 0; k < dc; ++k) sl += log(bw[s_cdim[k]]);
+    for (int k = 0; k < dc; ++k) sl += log(bw[K.cdim[k]]);
     for (int u = 0; u < du; ++u) {
-      const int d = s_udim[u];
+      const int d = K.udim[u];
       lbln += log(bw[d] / (double)(nlev[d] - 1));
-      if (s_delta[u] > -1e29f) {
-        sdp += fmax((double)s_delta[u], 0.0);
-        sad += fabs((double)s_delta[u]);
+      if (K.delta[0][u] > -1e29f) {
+        sdp += fmax((double)K.delta[0][u], 0.0);
+        sad += fabs((double)K.delta[0][u]);
       }
     }
     s_norm = -log((double)nk) - sl - 0.5 * (double)dc * log(2.0 * M_PI);
@@ -348,86 +205,17 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
   const double* x = A.cand + (b * A.C + (valid ? i : (int64_t)tile * 64)) * D;
   bool certified = true;
   float xc[DCP], xu[DUP], dl[DUP];
-#pragma unroll
-  for (int k = 0; k < DCP; ++k) {
-    xc[k] = 0.f;
-    if (k < dc) {
-      const double xv = x[s_cdim[k]];
-      certified = certified && (xv - xv == 0.0);
-      xc[k] = (float)(s_scale[k] * (xv - s_mu[k]));
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < DUP; ++u) {
-    xu[u] = 0.f;
-    if (u < du) {
-      const double xv = x[s_udim[u]];
-      certified = certified && (xv - xv == 0.0);
-      xu[u] = cand_code(xv);
-    }
-    dl[u] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_delta[u])));
-  }
+  grp_load_cand<DCP, DUP>(x, dc, du, K.cdim, K.udim, K.scale[0], K.mu, K.delta[0], xc, xu, dl, certified);
   float m = -INFINITY;
   double S = 0.0;
-  float* wrows = sobs + (size_t)wave * 64 * rs;
+  float* wrows = sobs + (size_t)wave * 64 * lay.rs;
   for (int64_t c0 = 0; c0 < nk; c0 += (int64_t)NW * 64) {  // uniform trip count: the barriers are block-wide
     __syncthreads();  // (the rows of the previous round are read)
     const int64_t j0 = c0 + (int64_t)wave * 64;
     const int jmax = (int)(nk - j0 < 64 ? (nk - j0 > 0 ? nk - j0 : 0) : 64);
-    if (jmax > 0) {
-      // lane = (row in pass, dim): a row's D doubles are read by consecutive lanes (coalesced), 16 passes of loads in
-      // flight; dims past 64 take further rounds (db).  The chunk's row positions come in one coalesced load and
-      // reach the lanes by a lane exchange (groups_screen_kernel's staging).
-      const int myrow = (int)rows[j0 + (lane < jmax ? lane : 0)];  // (positions local to the segment: < 2^31)
-      for (int db = 0; db < D; db += 64) {
-        const int lr = D <= 64 ? lane / D : 0;
-        const int ld = db + (D <= 64 ? lane - lr * D : lane);
-        const bool act = lr < rpp && ld < D;
-        const int off = act ? s_doff[ld] : 0;
-        const double sc = act ? s_dsc[ld] : 0.0, mu = act ? s_dmu[ld] : 0.0;
-        uint32_t bm = 0u;  // |b| maximum of this lane's dim (non-negative floats order as their bits; NaN above all)
-        for (int p0 = 0; p0 < jmax; p0 += 16 * rpp) {
-          double t[16];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const int r = p0 + q * rpp + lr;
-            const int ri = __shfl(myrow, r < jmax ? r : 0);  // (every lane takes part in the exchange)
-            t[q] = (act && r < jmax) ? Xs[(int64_t)ri * D + ld] : 0.0;
-          }
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const int r = p0 + q * rpp + lr;
-            if (act && r < jmax) {
-              const float v = (float)(sc * (t[q] - mu));
-              wrows[r * rs + off] = v;
-              bm = max(bm, __float_as_uint(fabsf(v)));
-            }
-          }
-        }
-        if (act && off < dc) atomicMax(&s_bmax[off], bm);
-      }
-    }
+    if (jmax > 0) grp_stage<16>(Xs, D, rows, j0, jmax, wrows, lay.rs, lay.rpp, dc, K.doff, K.dsc[0], K.dmu, s_bmax, lane);
     __syncthreads();
-    if (jmax > 0) {
-      if (fast && qcs == 2 && du == 0)
-        glp_pairs<DCP, DUP, 2, 0>(wrows, rs, jmax, dcq, duq, xc, xu, dl, m, S);
-      else if (fast && qcs == 2)
-        glp_pairs<DCP, DUP, 2, DUP >= 8 ? 2 : 0>(wrows, rs, jmax, dcq, duq, xc, xu, dl, m, S);
-      else if (fast && qcs == 4 && du == 0)
-        glp_pairs<DCP, DUP, DCP >= 16 ? 4 : 0, 0>(wrows, rs, jmax, dcq, duq, xc, xu, dl, m, S);
-      else if (fast && qcs == 4)
-        glp_pairs<DCP, DUP, DCP >= 16 ? 4 : 0, DUP >= 8 ? 2 : 0>(wrows, rs, jmax, dcq, duq, xc, xu, dl, m, S);
-      else if (fast && qcs == 6 && du == 0)
-        glp_pairs<DCP, DUP, DCP >= 24 ? 6 : 0, 0>(wrows, rs, jmax, dcq, duq, xc, xu, dl, m, S);
-      else if (fast && qcs == 6)
-        glp_pairs<DCP, DUP, DCP >= 24 ? 6 : 0, DUP >= 8 ? 2 : 0>(wrows, rs, jmax, dcq, duq, xc, xu, dl, m, S);
-      else if (fast && du == 0)
-        glp_pairs<DCP, DUP, DCP >= 32 ? 8 : 0, 0>(wrows, rs, jmax, dcq, duq, xc, xu, dl, m, S);
-      else if (fast)
-        glp_pairs<DCP, DUP, DCP >= 32 ? 8 : 0, DUP >= 8 ? 2 : 0>(wrows, rs, jmax, dcq, duq, xc, xu, dl, m, S);
-      else
-        glp_pairs<DCP, DUP, -1, -1>(wrows, rs, jmax, dcq, duq, xc, xu, dl, m, S);
-    }
+    if (jmax > 0) GRP_PAIRS_DISPATCH_UNSIGNED(DCP, lay, du == 0 ? 0 : 1, GLP_PAIRS_CALL);
   }
   s_pm[wave][lane] = m;
   s_ps[wave][lane] = S;
@@ -460,7 +248,7 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
   const double en = 2.02 * u24 * sqrt(r2) * (1.0 + 0x1p-20);
   const double Q = fmax(0.0, s_sdp - ((double)M - 1.0)) + (double)GLP_K + 2.0;
   const double ein = 2.0 * sqrt(Q) * en + en * en;
-  const double L = (double)(dc4 + du4 + 1);
+  const double L = (double)(lay.dc4 + lay.du4 + 1);
   const double Et = ein + L * u24 * (sad + Q + ein) + u24 * sad + 0x1p-48 * Q + (double)(GLP_K + 3) * u24;
   const double rel = exp2(Et * (1.0 + 0x1p-20)) - 1.0 + 0x1p-22 + (double)(GLP_G - 1) * u24 +
                      (double)(nk + NW) * 0x1p-52 + 4.0 * (double)nk * exp2(-(double)GLP_K);
@@ -494,7 +282,7 @@ __global__ __launch_bounds__(64 * NW) void glp_f64_kernel(GlpArgs A) {
   __shared__ int32_t s_i[2];
   __shared__ double s_lconst;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int D = A.D;
+  const int D = A.M.D;
   const int kd = A.kd0 + (int)blockIdx.y;
   const int64_t b = (int64_t)blockIdx.x / A.tiles;
   const int tile = (int)((int64_t)blockIdx.x - b * A.tiles);
@@ -517,7 +305,7 @@ __global__ __launch_bounds__(64 * NW) void glp_f64_kernel(GlpArgs A) {
   const int64_t p = valid ? (A.fp64_only ? pi : (int64_t)A.list[(b * 2 + kd) * A.C + pi]) : 0;
   if (wave == 0) {
     int dc, du;
-    glp_slots(A, lane, s_cdim, s_udim, &dc, &du);
+    grp_slots(A.M, lane, s_cdim, s_udim, &dc, &du);
     if (lane == 0) {
       s_i[0] = dc;
       s_i[1] = du;
@@ -525,12 +313,12 @@ __global__ __launch_bounds__(64 * NW) void glp_f64_kernel(GlpArgs A) {
   }
   __syncthreads();
   const int dc = s_i[0], du = s_i[1];
-  const int64_t s0 = A.seg_off[b], n = A.seg_off[b + 1] - s0;
-  const int64_t nk = kd ? A.n_bad[b] : A.n_good[b];
-  const double* Xs = A.X + s0 * D;
-  const int64_t* rows = A.order + s0 + (kd ? n - nk : 0);
-  const double* bw = (kd ? A.bw_bad : A.bw_good) + b * D;
-  const int32_t* nlev = (kd ? A.nlev_bad : A.nlev_good) + b * D;
+  const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
+  const int64_t nk = kd ? A.M.n_bad[b] : A.M.n_good[b];
+  const double* Xs = A.M.X + s0 * D;
+  const int64_t* rows = A.M.order + s0 + (kd ? n - nk : 0);
+  const double* bw = (kd ? A.M.bw_bad : A.M.bw_good) + b * D;
+  const int32_t* nlev = (kd ? A.M.nlev_bad : A.M.nlev_good) + b * D;
   // per-slot constants: a_c = 1 / (h sqrt 2); categorical: ln(h / (c - 1)) + [match] (ln(1 - h) - ln(h / (c - 1))),
   // the first part summed into the constant (kde_logpdf_tiled_kernel's)
   for (int k = tid; k < DCP; k += NT) s_sa[k] = k < dc ? 1.0 / (bw[s_cdim[k]] * 1.4142135623730951) : 0.0;
@@ -636,28 +424,18 @@ __global__ __launch_bounds__(64 * NW) void glp_f64_kernel(GlpArgs A) {
 // (groups_select_kernel's use of exact_setup / exact_pdf)
 __global__ __launch_bounds__(EXACT_THREADS) void glp_exact_kernel(GlpArgs A) {
   __shared__ ExactShared sh;
-  __shared__ GlpView vw;
-  const int D = A.D;
+  __shared__ GrpView vw;
+  const int D = A.M.D;
   const int kd = A.kd0 + (int)blockIdx.y;
   const int64_t b = (int64_t)blockIdx.x / A.tiles;
   const int tile = (int)((int64_t)blockIdx.x - b * A.tiles);
   const int st = A.status[b];
   if ((st & GLP_BAD) || !(st & (kd ? HBX_GRP_EXACT_G : HBX_GRP_EXACT_L))) return;  // uniform
-  const int64_t s0 = A.seg_off[b], n = A.seg_off[b + 1] - s0;
-  const int64_t nk = kd ? A.n_bad[b] : A.n_good[b];
-  const double* Xs = A.X + s0 * D;
-  const int64_t* rows = A.order + s0 + (kd ? n - nk : 0);
-  if (threadIdx.x == 0) {  // prod(bw[iscontinuous]) sequentially in dim order: the reference's order
-    GlpView v;
-    v.n = (int32_t)nk;
-    v.bw = (kd ? A.bw_bad : A.bw_good) + b * D;
-    v.nlev = (kd ? A.nlev_bad : A.nlev_good) + b * D;
-    v.vartype = A.vartype;
-    double p = 1.0;
-    for (int d = 0; d < D; ++d) p *= (A.vartype[d] == 0) ? v.bw[d] : 1.0;
-    v.prod_bw_c = p;
-    vw = v;
-  }
+  const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
+  const int64_t nk = kd ? A.M.n_bad[b] : A.M.n_good[b];
+  const double* Xs = A.M.X + s0 * D;
+  const int64_t* rows = A.M.order + s0 + (kd ? n - nk : 0);
+  if (threadIdx.x == 0) vw = grp_view(A.M, b, kd);
   __syncthreads();
   const int64_t i0 = (int64_t)tile * 64, i1 = i0 + 64 < A.C ? i0 + 64 : A.C;
   for (int64_t i = i0; i < i1; ++i) {
@@ -669,30 +447,12 @@ __global__ __launch_bounds__(EXACT_THREADS) void glp_exact_kernel(GlpArgs A) {
   if (threadIdx.x == 0) atomicAdd(&A.stat[2], (unsigned long long)(i1 - i0));
 }
 
-// B * C within int32 (what every grid, list entry and count relies on)
-static bool glp_counts_ok(int64_t B, int64_t C) {
-  if (B < 0 || C < 0 || B > INT32_MAX) return false;
-  return !(C > 0 && B > (int64_t)INT32_MAX / C);
-}
-
 static int64_t glp_cnt_bytes(int64_t B) { return (B * 2 * (int64_t)sizeof(int32_t) + 15) & ~(int64_t)15; }
-
-template <bool E64>
-static void glp_launch_f64(const GlpArgs& A, dim3 grid, hipStream_t s) {
-  if (A.D <= 8)
-    hipLaunchKernelGGL((glp_f64_kernel<8, 8, 4, E64>), grid, dim3(256), 0, s, A);
-  else if (A.D <= 16)
-    hipLaunchKernelGGL((glp_f64_kernel<16, 16, 4, E64>), grid, dim3(256), 0, s, A);
-  else if (A.D <= 32)
-    hipLaunchKernelGGL((glp_f64_kernel<32, 32, 4, E64>), grid, dim3(256), 0, s, A);
-  else
-    hipLaunchKernelGGL((glp_f64_kernel<64, 32, 2, E64>), grid, dim3(128), 0, s, A);
-}
 
 extern "C" {
 
 int64_t hbx_kde_logpdf_groups_workspace_bytes(int64_t B, int64_t C, int32_t D) {
-  if (D < 1 || D > HBX_MAX_D || !glp_counts_ok(B, C)) return -1;
+  if (D < 1 || D > HBX_MAX_D || !grp_counts_ok(B, 1, C)) return -1;
   return GLP_HEAD + glp_cnt_bytes(B) + B * C * 2 * (int64_t)sizeof(int32_t);
 }
 
@@ -702,44 +462,27 @@ int hbx_kde_logpdf_groups(const double* X, int32_t D, const int64_t* seg_off, in
                           int64_t C, double rtol, int32_t flags, double* ln_l, double* ln_g, int32_t* status,
                           void* workspace, int64_t ws_bytes, void* stream) {
   const char* who = "hbx_kde_logpdf_groups";
-  if (D < 1 || D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "%s: D=%d outside [1, %d]", who, D, HBX_MAX_D);
+  if (const int rc = grp_check_dim(who, D)) return rc;
   if (B < 0 || C < 0) return hbx_fail(HBX_ERR_ARG, "%s: B=%lld C=%lld", who, (long long)B, (long long)C);
-  if (!glp_counts_ok(B, C))
+  if (!grp_counts_ok(B, 1, C))  // (what every grid, list entry and count relies on)
     return hbx_fail(HBX_ERR_ARG, "%s: B * C = %lld * %lld exceeds int32", who, (long long)B, (long long)C);
   if (!(rtol > 0.0)) return hbx_fail(HBX_ERR_ARG, "%s: rtol=%g must be positive", who, rtol);
   if (flags & ~HBX_LOGPDF_FP64_ONLY) return hbx_fail(HBX_ERR_ARG, "%s: flags=%d", who, flags);
   if (!ln_l && !ln_g) return hbx_fail(HBX_ERR_ARG, "%s: null pointer (ln_l and ln_g)", who);
   if (B == 0 || C == 0) return HBX_OK;
-  if (!X || !seg_off || !order || !n_good || !n_bad || !vartype || !bw_good || !bw_bad || !nlev_good || !nlev_bad ||
-      !cand || !status || !workspace)
-    return hbx_fail(HBX_ERR_ARG, "%s: null pointer", who);
-  const uintptr_t a8 = (uintptr_t)X | (uintptr_t)seg_off | (uintptr_t)order | (uintptr_t)n_good | (uintptr_t)n_bad |
-                       (uintptr_t)bw_good | (uintptr_t)bw_bad | (uintptr_t)cand | (uintptr_t)ln_l | (uintptr_t)ln_g;
-  const uintptr_t a4 = (uintptr_t)vartype | (uintptr_t)nlev_good | (uintptr_t)nlev_bad | (uintptr_t)status;
-  if ((a8 & 7) || (a4 & 3) || ((uintptr_t)workspace & 15))
+  GlpArgs A;
+  A.M = grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad);
+  if (grp_model_null(A.M) || !cand || !status || !workspace) return hbx_fail(HBX_ERR_ARG, "%s: null pointer", who);
+  if (grp_model_misaligned(A.M) || (((uintptr_t)cand | (uintptr_t)ln_l | (uintptr_t)ln_g) & 7) ||
+      ((uintptr_t)status & 3) || ((uintptr_t)workspace & 15))
     return hbx_fail(HBX_ERR_ARG, "%s: pointers must be aligned (f64 / i64: 8 bytes, i32: 4, workspace: 16)", who);
   const int64_t need = hbx_kde_logpdf_groups_workspace_bytes(B, C, D);
   if (ws_bytes < need)
     return hbx_fail(HBX_ERR_ARG, "%s: workspace too small: %lld < %lld bytes", who, (long long)ws_bytes, (long long)need);
   hipStream_t s = (hipStream_t)stream;
-  GlpArgs A;
-  A.X = X;
-  A.seg_off = seg_off;
-  A.order = order;
-  A.n_good = n_good;
-  A.n_bad = n_bad;
-  A.vartype = vartype;
-  A.bw_good = bw_good;
-  A.bw_bad = bw_bad;
-  A.nlev_good = nlev_good;
-  A.nlev_bad = nlev_bad;
   A.cand = cand;
-  A.B = B;
   A.C = C;
-  A.D = D;
   A.tiles = (int32_t)((C + 63) / 64);
-  A.dcp = D <= 8 ? 8 : D <= 16 ? 16 : D <= 32 ? 32 : 64;  // the slot bucket, from D alone (vartype is device memory)
-  A.dup = D <= 8 ? 8 : D <= 16 ? 16 : 32;
   A.kd0 = ln_l ? 0 : 1;
   A.fp64_only = (flags & HBX_LOGPDF_FP64_ONLY) ? 1 : 0;
   A.rtol = rtol;
@@ -753,22 +496,23 @@ int hbx_kde_logpdf_groups(const double* X, int32_t D, const int64_t* seg_off, in
   hipLaunchKernelGGL(glp_status_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, A);
   HBX_LAUNCH_CHECK();
   const dim3 grid((unsigned)(B * A.tiles), (ln_l && ln_g) ? 2u : 1u);  // B * tiles <= B * C <= INT32_MAX
+#define GLP_LAUNCH_DD(DCP, DUP, NW, DT) hipLaunchKernelGGL((glp_dd_kernel<DCP, DUP, NW, DT>), grid, dim3(64 * NW), 0, s, A)
+#define GLP_LAUNCH_F64(DCP, DUP, NW, DT) \
+  hipLaunchKernelGGL((glp_f64_kernel<DCP, DUP, NW, true>), grid, dim3(64 * NW), 0, s, A)
+#define GLP_LAUNCH_F64_EXP32(DCP, DUP, NW, DT) \
+  hipLaunchKernelGGL((glp_f64_kernel<DCP, DUP, NW, false>), grid, dim3(64 * NW), 0, s, A)
   if (!A.fp64_only) {
-    if (D <= 8)
-      hipLaunchKernelGGL((glp_dd_kernel<8, 8, 4, 16>), grid, dim3(256), 0, s, A);
-    else if (D <= 16)
-      hipLaunchKernelGGL((glp_dd_kernel<16, 16, 4, 24>), grid, dim3(256), 0, s, A);
-    else if (D <= 32)
-      hipLaunchKernelGGL((glp_dd_kernel<32, 32, 4, 40>), grid, dim3(256), 0, s, A);
-    else  // D <= 96 with <= 64 continuous and <= 32 categorical dims; anything larger is EXACT
-      hipLaunchKernelGGL((glp_dd_kernel<64, 32, 2, 104>), grid, dim3(128), 0, s, A);
+    GRP_BUCKET_LAUNCH(D, GLP_LAUNCH_DD);
     HBX_LAUNCH_CHECK();
   }
   if (rtol < 1e-5)
-    glp_launch_f64<true>(A, grid, s);
+    GRP_BUCKET_LAUNCH(D, GLP_LAUNCH_F64);
   else
-    glp_launch_f64<false>(A, grid, s);
+    GRP_BUCKET_LAUNCH(D, GLP_LAUNCH_F64_EXP32);
   HBX_LAUNCH_CHECK();
+#undef GLP_LAUNCH_DD
+#undef GLP_LAUNCH_F64
+#undef GLP_LAUNCH_F64_EXP32
   hipLaunchKernelGGL(glp_exact_kernel, grid, dim3(EXACT_THREADS), 0, s, A);
   HBX_LAUNCH_CHECK();
   return HBX_OK;

@@ -1,7 +1,8 @@
-"""Per-kernel VGPR / scratch / occupancy from a hipcc -S listing: python tools/isa_stats.py file.s [filter]"""
+"""Per-kernel VGPR / AGPR / scratch / LDS / occupancy from a hipcc -S listing: python tools/isa_stats.py file.s [filter]"""
 import re
 import sys
 
+KEYS = ("NumVgprs", "NumAgprs", "ScratchSize", "LDSByteSize", "Occupancy")
 cur = None
 rows = []
 for line in open(sys.argv[1]):
@@ -12,12 +13,13 @@ for line in open(sys.argv[1]):
         continue
     if cur is None:
         continue
-    for key in ("NumVgprs", "ScratchSize", "Occupancy"):
+    for key in KEYS:
         m = re.match(r"^; %s: (\d+)" % key, line)
         if m and key not in cur:
             cur[key] = int(m.group(1))
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 for r in rows:
     if flt in r["name"] and "NumVgprs" in r:
-        print("%-70s vgpr %3d scratch %4d occ %d" % (r["name"][:70], r["NumVgprs"], r.get("ScratchSize", -1),
-                                                   r.get("Occupancy", -1)))
+        print("%-70s vgpr %3d agpr %3d scratch %4d lds %6d occ %d" % (
+            r["name"][:70], r["NumVgprs"], r.get("NumAgprs", -1), r.get("ScratchSize", -1), r.get("LDSByteSize", -1),
+            r.get("Occupancy", -1)))
