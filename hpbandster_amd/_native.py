@@ -92,6 +92,7 @@ SIGNATURES = {
     "hbx_mapped_host_buffers": (c_i64, []),
     "hbx_kde_ws_offsets": (c_i32, [c_i64, c_i64, c_i64, c_vp]),
     "hbx_kde_acquire_stats": (c_i32, [c_vp, c_i64, c_i64, c_vp]),
+    "hbx_kde_acquire_stage1": (c_i32, [c_vp, c_i64, c_i64, c_vp]),
     "hbx_np_exp": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hbx_kde_pdf_scratch_bytes": (c_i64, [c_i64]),
     "hbx_kde_pdf_exact": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),

@@ -31,8 +31,9 @@ struct WsLayout {
       exact_g, part, total;
   // the staged single acquisition (hbx_staged.hip), appended: its state words (in the result slot's padding),
   // the seed list (list_cap entries), the survivor list (Nc), the list launches' split partials
-  // ([OBS_SPLIT_MAX][list_cap] estimates)
-  size_t stage, seeds, surv, lpart;
+  // ([OBS_SPLIT_MAX][list_cap] estimates), stage 1's block maxima (a float per 256 candidates: a block of either
+  // coarse pair kernel covers 256 or 512)
+  size_t stage, seeds, surv, lpart, bmax;
   int32_t list_cap;
 };
 #define STAGED_LIST_CAP 4096  // seeds at most, and listed candidates at most of a split list launch
@@ -52,6 +53,7 @@ struct AcqWs {
   uint32_t* stage;
   int32_t *seeds, *surv;
   KdeEst* lpart;
+  float* bmax;
   int32_t list_cap;
   AcqWs(void* workspace, const WsLayout& w) {
     char* ws = (char*)workspace;
@@ -77,6 +79,7 @@ struct AcqWs {
     seeds = (int32_t*)(ws + w.seeds);
     surv = (int32_t*)(ws + w.surv);
     lpart = (KdeEst*)(ws + w.lpart);
+    bmax = (float*)(ws + w.bmax);
     list_cap = w.list_cap;
   }
   // a single acquisition's state, for the launch that initialises it
@@ -124,7 +127,11 @@ int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* can
 // thresholds between them:
 //   staged_score_l          stage 1: the good KDE's pair kernel, then staged_l_kernel (lhi into a.lo, Lmax into the
 //                           state words).  lkey non-null: also every candidate's ordered key of -llo (+inf: no finite
-//                           llo) and the hist_words words at hist zeroed
+//                           llo) and the hist_words words at hist zeroed.  lhi_blocks non-null (the argmin): where
+//                           the launch runs unsplit and HBX_STAGE1_LHI is not 0, the pair kernel's epilogue leaves
+//                           lhi and one maximum per block in a.bmax instead, staged_l_kernel is not launched, and
+//                           *lhi_blocks is the block count (else 0) -- to be handed to staged_score_seeds, whose
+//                           seed kernel then reduces the maxima itself
 //   staged_score_seeds      stages 2 and 3: the seed list against the threshold in the state words' Lmax, the bad
 //                           KDE's list launch over it, its partials merged and scattered (update_u: U_seed lowered
 //                           to the seeds' smallest upper score bound)
@@ -132,9 +139,10 @@ int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* can
 //                           l-only lower score bound, lhi > 700 raises the overflow flag) and the list launch over it;
 //                           its partials, where it ran split, are left to the caller
 int staged_score_l(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
-                   hipEvent_t* ev, hipStream_t s, uint32_t* lkey, uint32_t* hist, int32_t hist_words);
+                   hipEvent_t* ev, hipStream_t s, uint32_t* lkey, uint32_t* hist, int32_t hist_words,
+                   unsigned* lhi_blocks = nullptr);
 int staged_score_seeds(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
-                       hipStream_t s, bool mark_rest, bool update_u);
+                       hipStream_t s, bool mark_rest, bool update_u, unsigned lhi_blocks = 0);
 int staged_score_survivors(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
                            hipStream_t s, bool lonly);
 // exact-only acquisitions instead of a combine / bounds pass: every candidate joins the re-score

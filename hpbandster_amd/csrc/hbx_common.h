@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #define HBX_MAX_D 256          // largest configuration-space dimension the engine accepts
+#define HBX_LO_TERMS 32        // active categorical dims of a one-hot 32x32 table at most (16 per K-step of 32, two steps)
 #define HBX_WAVE 64            // CDNA wavefront width
 
 #include "hbx.h"  // the public C ABI (include/hbx.h): every definition here must match it
@@ -50,6 +51,9 @@ static inline int hbx_staged_mode() {
 // combine, shortlist, exact, final as launches of their own) instead of the short tail (hbx_staged.hip); for
 // tests and A/B runs
 static inline bool hbx_staged_tail() { return hbx_switch_on("HBX_STAGED_TAIL"); }
+// HBX_STAGE1_LHI=0: stage 1 of a staged argmin leaves lhi and Lmax to staged_l_kernel, a launch of its own,
+// instead of the scoring kernel's epilogue (hbx_staged.hip); for tests and A/B runs
+static inline bool hbx_stage1_lhi() { return hbx_switch_on("HBX_STAGE1_LHI"); }
 
 // ------------------------------------------------------------------------------------------
 // KDE model parameters, one block per KDE (good or bad).  Written on the device by
@@ -107,6 +111,10 @@ struct KdeParams {
   int32_t vartype[HBX_MAX_D];       // 0 = continuous 'c', 1 = unordered categorical 'u'
   int32_t nlev[HBX_MAX_D];
   double bw[HBX_MAX_D];
+  // the coarse 32x32 instances multiply the one-hot deltas' f16 hi parts only: per active categorical dim u the lo
+  // part given up, |d - f16(d)| of the delta clamped to +-60000 (0 at the clamp and past du), which their epilogue
+  // adds to a candidate's bound in u order (the FAST instances compute the same terms themselves)
+  float lo_term[HBX_LO_TERMS];
 };
 
 // A parameter buffer (hbx_kde_param_bytes()) is the KdeParams block followed by a staging area for

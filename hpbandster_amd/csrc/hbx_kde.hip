@@ -565,6 +565,10 @@ WsLayout ws_layout(int64_t Nc, int64_t nmax, int64_t B) {
   w.seeds = take(4 * (size_t)w.list_cap);
   w.surv = take(4 * Nc);
   w.lpart = take(sizeof(KdeEst) * (size_t)OBS_SPLIT_MAX * w.list_cap);
+  // stage 1's block maxima (staged_score_l): an area of its own, 4 bytes per 256 candidates, rather than an alias
+  // of the split partials -- no block count at which the fold would have to be off, nothing to reason about when
+  // another launch starts to use that area
+  w.bmax = take(4 * (size_t)((Nc + 255) / 256));
   w.total = o;
   return w;
 }

@@ -218,6 +218,32 @@ __device__ __forceinline__ KdeEst finish_est_terms(const KdeParams* __restrict__
   o.err = 2.f * (dt * HBX_LN2f + es) + 16.f * u;
   return o;
 }
+// ... the same operations on copies of the four fields it reads, for a kernel that finishes every candidate behind
+// a long loop and loads them once, ahead of it (the coarse 32x32 instances): lnorm = (float)log_norm, dims = dc + du
+struct EstPrm {
+  float lnorm, cmax, sum_abs_delta;
+  int32_t dims;
+};
+__device__ __forceinline__ KdeEst finish_est_terms(const EstPrm q, float S, float Sn, float off, bool nan_c, float ci,
+                                                   float bnd, bool SIGNED, float sum_terms) {
+  KdeEst o;
+  o.pad = 0.f;
+  if (nan_c || S != S) {
+    o.lpos = NAN;
+    o.lneg = -INFINITY;
+    o.err = 0.f;
+    return o;
+  }
+  const float Sp = SIGNED ? (S - Sn) : S;
+  o.lpos = (Sp > 0.f) ? (__log2f(Sp) + off) * HBX_LN2f + q.lnorm : -INFINITY;
+  o.lneg = (SIGNED && Sn > 0.f) ? (__log2f(Sn) + off) * HBX_LN2f + q.lnorm : -INFINITY;
+  const float u = 0x1p-24f;
+  const float Mabs = fabsf(ci) + q.cmax + bnd + q.sum_abs_delta;
+  const float dt = 3.f * (float)(q.dims + 4) * u * Mabs;  // |error of t|, log2 units
+  const float es = sum_terms * u * (SIGNED ? 3.f : 1.f);
+  o.err = 2.f * (dt * HBX_LN2f + es) + 16.f * u;
+  return o;
+}
 
 __device__ __forceinline__ KdeEst finish_est(const KdeParams* __restrict__ P, float S, float Sn, float off,
                                              bool nan_c, float ci, float bnd, bool SIGNED, int chunk) {
@@ -308,6 +334,12 @@ struct KdePairArgs {
   // the coarse 32x32 instances stage their candidate rows through LDS (0: HBX_ROW_STAGE=0, every lane reads its
   // row from global memory; the other instances do not look at it)
   int32_t row_stage = 1;
+  // stage 1 of the staged argmin, unsplit (hbx_staged.hip; both null otherwise): the coarse pair kernels' (two
+  // tiles or one) epilogue also leaves candidate i's ln-pdf interval's upper end in lhi[i] (NaN: l is NaN; +inf: rescue-marked,
+  // the seed kernel re-scores it) and, per block, the largest lower end over its unmarked candidates in
+  // bmax[block] (-inf: none)
+  float* lhi = nullptr;
+  float* bmax = nullptr;
 };
 typedef void (*logpdf_pair_fn)(const double*, int64_t, int32_t, KdePairArgs);
 // the coarse 32x32 instance over one KDE: logpdf_fn's arguments and KdePairArgs::row_stage
@@ -334,7 +366,8 @@ typedef void (*logpdf_list_fn)(const double*, int32_t, KdeListArgs);
 
 // the staged acquisition's state words (hbx_staged.hip), in the result slot's padding right behind the record
 // (WsLayout::stage): whether the call staged, Lmax and U_seed as order-preserving uints, the seed and survivor
-// counts, the length of the short tail's preliminary shortlist.  They stay in the workspace after the call
+// counts, the length of the short tail's preliminary shortlist, whether stage 1's epilogue left lhi.  They stay in the
+// workspace after the call
 // (hbx_kde_acquire_stats).
 enum {
   HBX_ST_FLAG = 0,
@@ -343,6 +376,7 @@ enum {
   HBX_ST_NSEED,
   HBX_ST_NSURV,
   HBX_ST_NPRE,
+  HBX_ST_LHI1,  // 1: the call's lhi and Lmax came from stage 1's epilogue (hbx_kde_acquire_stage1)
   HBX_ST_WORDS
 };
 
@@ -357,6 +391,7 @@ __device__ __forceinline__ void acq_init_state(uint32_t* U, int32_t* count, int3
   st[HBX_ST_NSEED] = 0;
   st[HBX_ST_NSURV] = 0;
   st[HBX_ST_NPRE] = 0;
+  st[HBX_ST_LHI1] = 0;
   *U = hbx_f2ord(INFINITY);
   *first1 = INT32_MAX;
   *count = 0;

@@ -210,6 +210,10 @@ __device__ __forceinline__ void kde_params_body(const PrepArgs& A, KdeParams* P,
       S.cd[ix] = d;
       P->cat_delta[ix] = (a == 0.0) ? -1e30f : (float)(S.t1[d] - S.t0[d]);
       P->cat_negf[ix] = (a < 0.0) ? 1.f : 0.f;
+      if (ix < HBX_LO_TERMS) {  // (the one-hot table's f16 split of the delta, below)
+        const float dl = fminf(fmaxf(P->cat_delta[ix], -60000.f), 60000.f);
+        P->lo_term[ix] = fabsf(dl) < 60000.f ? fabsf(dl - (float)(_Float16)dl) : 0.f;
+      }
       if (a < 0.0) {
         P->has_neg = 1;
         S.neg = 1;

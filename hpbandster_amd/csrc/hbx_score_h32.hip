@@ -32,6 +32,7 @@
 //   MFMAs of T1(c), fragments re-read for T0(c+1) | exp2/sum of T0(c) beside them.
 #include "hbx_common.h"
 #include "hbx_kde_impl.h"
+#include "hbx_acq_impl.h"  // est_interval (the staged argmin's stage 1)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -98,7 +99,9 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
                                                     const unsigned blk, int32_t* __restrict__ rescue_cnt = nullptr,
                                                     const int split = 0, const int nsplit = 1,
                                                     const int32_t* __restrict__ idx = nullptr,
-                                                    const bool scatter = false, const bool row_stage = true) {
+                                                    const bool scatter = false, const bool row_stage = true,
+                                                    float* __restrict__ lhi = nullptr,
+                                                    float* __restrict__ bmax = nullptr) {
   // CO: the coarse pre-screen (hbx_kde_impl.h coarse layout): one product per continuous dim, no lo parts
   constexpr int ND = CO ? h32c_nd(NSC) : h32_nd(NSC);  // dense 16-wide K-steps (C_j / c_i pieces + per dim)
   constexpr int KS = KP;                     // sparse 32-wide K-steps (one-hot positions), hi parts
@@ -128,10 +131,18 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
   // all lie below H32C_ROW_DMIN keeps the ring's size and no staging code (<1, 0>: D = 8)
   constexpr int RDS = !CO ? 0 : ((8 * NSC + 16 * KP) | 1) < H32C_ROW_DS ? ((8 * NSC + 16 * KP) | 1) : H32C_ROW_DS;
   constexpr int RSF = RDS >= (H32C_ROW_DMIN | 1) ? (HW * 32 * RDS * 8 + PRM_BYTES) / 4 : 0;
-  constexpr int LDSF = NBUF * CHF + AUXF > RSF ? NBUF * CHF + AUXF : RSF;
+  // ... and, behind everything else, what their epilogue reads of P (staged with the parameters, below): words 0-5
+  // = (float)log_norm, cmax, sum_abs_delta, dc + du, nconst, nan_all, words 8.. = NLT of KdeParams::lo_term, the
+  // one-hot lo parts given up per active categorical dim (0 past du; du <= 16 KP)
+  constexpr int NLT = CO && KP > 0 ? 16 * KP : 0;
+  static_assert(NLT <= HBX_LO_TERMS, "KdeParams::lo_term");
+  constexpr int EPF = CO ? 8 + NLT : 0;
+  constexpr int LDSB = ((NBUF * CHF + AUXF > RSF ? NBUF * CHF + AUXF : RSF) + 3) & ~3;
+  constexpr int LDSF = LDSB + EPF;
   static_assert(2 * LDSF * 4 <= 160 * 1024, "two blocks per CU");
   __shared__ __align__(16) float lds[LDSF];  // the kernel's only LDS object
   float* aux = lds + NBUF * CHF;
+  float* epi = lds + LDSB;
   if constexpr (CO) table += P->coarse_off;  // the coarse layout follows the precise table
   // observation split: this block's chunk range, its partial estimates at out + split Nc
   int c0 = 0, nchunks = (P->n + OBS_CHUNK - 1) / OBS_CHUNK;
@@ -173,6 +184,19 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
                         act ? P->cont_dim[tid] : 0};
   }
   if (tid < 32 * KP) oprm[tid] = OhPrm{P->oh_val[tid], P->oh_col[tid], 0};  // padding: NaN, never equal
+  if constexpr (CO) {
+    // the epilogue's constants, read here once: the 16 waves of a CU reach the epilogue together, so nothing would
+    // hide loads from P there (the barriers of the main loop lie between this store and its reads)
+    if (tid < EPF)
+      epi[tid] = tid == 0   ? (float)P->log_norm
+                 : tid == 1 ? P->cmax
+                 : tid == 2 ? P->sum_abs_delta
+                 : tid == 3 ? __int_as_float(P->dc + P->du)
+                 : tid == 4 ? __int_as_float(P->nconst)
+                 : tid == 5 ? __int_as_float(P->nan_all)
+                 : tid >= 8 ? P->lo_term[tid - 8]
+                            : 0.f;
+  }
   const bool staged = rows_fit && cbase < Nc;
   const int64_t nv = (Nc - cbase) < 32 * CT ? (Nc - cbase) : 32 * CT;  // valid rows of this wave
   double* xs = (double*)lds + (int64_t)wave * 32 * (tile_fit ? 1 : CT) * DS;
@@ -536,6 +560,7 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
 #pragma unroll
   for (int t = 0; t < CT; ++t) S[t] += __shfl_xor(S[t], 32);
   if constexpr (SG) Sn = 2.f * (Sn + __shfl_xor(Sn, 32));  // the odd-parity terms' sum (exact doubling)
+  if constexpr (!CO) {
 #pragma unroll
   for (int t = 0; t < CT; ++t) {
   if (h == 0) {
@@ -577,6 +602,83 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
     }
   }
   }
+  } else {
+  // Coarse: the same arithmetic per candidate, each thing done once.  Both lane halves hold every column tile's sum
+  // (the shuffle above): with two column tiles lane half h finishes tile h -- its sum, aux slot, index and row --
+  // in one pass; with one, lane half 0 finishes it.  The KDE's constants come from LDS (epi, staged ahead of the
+  // main loop), the one-hot lo parts as KdeParams::lo_term (hbx_prep.hip: the terms the loop above computes), added
+  // behind the candidate's own coarse bound in the same u order: the same sum, bit for bit.
+  const EstPrm eprm{epi[0], epi[1], epi[2], __float_as_int(epi[3])};
+  const int32_t e_nconst = __float_as_int(epi[4]), e_nan = __float_as_int(epi[5]);
+  float lot[NLT > 0 ? NLT : 1];
+#pragma unroll
+  for (int u = 0; u < NLT; ++u) lot[u] = epi[8 + u];
+  float blo = -INFINITY;  // (lhi / bmax) the lower end of this lane's candidate's ln-pdf interval, if it counts
+  auto finish = [&](const int t, const float St) {
+    const int64_t ii = cbase + 32 * t + c;
+    if (ii < Nc) {
+      const float* ax = aux + ((wave * CT + t) * 32 + c) * 4;
+      const float ci_q = ax[0], bnd_q = ax[1], dq = ax[2];
+      const bool big = ax[3] < 0.f;
+      const float cer_q = big ? 0.f : ax[3];
+      int64_t irow = ii;  // the candidate's row, and where its estimate goes
+      if constexpr (LIST) irow = idx[ii];
+      const int64_t iout = LIST && !scatter ? ii : irow;
+      const double* x = cand + irow * (int64_t)D;
+      bool nq = e_nan != 0;
+      for (int k = 0; k < e_nconst; ++k)
+        if (x[P->const_dim[k]] != P->const_level[k]) nq = true;
+      KdeEst o = finish_est_terms(eprm, St, 0.f, -dq, nq, ci_q - dq, bnd_q, false, (float)(nchunks + 6 + 24));
+      if (o.err > 0.f) o.err += (6.f * 0x1p-22f * bnd_q + 0x1p-19f) * HBX_LN2f;
+      float lo_err = cer_q;
+      if constexpr (KP > 0)
+#pragma unroll
+        for (int u = 0; u < NLT; ++u) lo_err += lot[u];
+      if (o.err > 0.f) o.err = (1.f + o.err) * exp2f(lo_err * (1.f + 0x1p-20f)) * (1.f + 0x1p-20f) - 1.f;
+      if (!nq && St == St && (big || St < 0x1p-64f || St > 0x1p100f)) {  // rescue marker
+        o.err = -1.f;
+        if (rescue_cnt) atomicAdd(rescue_cnt, 1);
+      }
+      out[iout] = o;
+      if constexpr (!LIST) {
+        if (lhi) {  // (uniform) stage 1 of the staged argmin: the interval staged_l_kernel would derive from `o`
+          float lo = -INFINITY, hi = NAN, pt;
+          if (o.err == -1.f) {
+            hi = INFINITY;  // marked: re-scored by the seed kernel, and no part of the maximum
+          } else if (o.lpos == o.lpos) {
+            est_interval(o, &lo, &hi, &pt);
+            blo = lo;
+          }
+          lhi[iout] = hi;
+        }
+      }
+    }
+  };
+  if constexpr (CT == 2) {
+    finish(h, h ? S[1] : S[0]);
+  } else {
+    if (h == 0) finish(0, S[0]);
+  }
+  if constexpr (!LIST) {
+    // the block's largest lower end: wave shuffle, then one float per wave in the wave's own aux slots (read
+    // above by this wave alone, and LDS runs a wave's instructions in order), one barrier -- which every wave of
+    // the block reaches: bmax is set for unsplit launches only, so no block has left through the empty-range exit
+    if (bmax) {  // (uniform)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) blo = fmaxf(blo, __shfl_xor(blo, o));
+      if (lane == 0) aux[wave * CT * 32 * 4] = blo;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (threadIdx.x == 0) {
+        float b = aux[0];
+#pragma unroll
+        for (int w = 1; w < HW; ++w) b = fmaxf(b, aux[w * CT * 32 * 4]);
+        bmax[blk] = b;
+      }
+    }
+  }
+  }
 }
 
 // unsigned sums: 128 VGPRs, 4 waves per SIMD (two blocks per CU); the coarse instance: H32C_WAVES-wave
@@ -612,7 +714,7 @@ __global__ __launch_bounds__(64 * (CO ? H32C_WAVES : H16_WAVES)) __attribute__((
   const int split = ns > 1 ? (int)(loc / a.tiles) : 0;
   kde_logpdf_h32_body<NSC, KP, false, FAST, CO, CO ? H32C_CT : 1>(cand, Nc, D, second ? a.P1 : a.P0, second ? a.table1 : a.table0,
                                                 second ? a.out1 : a.out0, tile, a.rescue, split, ns, nullptr, false,
-                                                a.row_stage != 0);
+                                                a.row_stage != 0, a.lhi, a.bmax);
 }
 
 // the coarse pair kernel with ONE candidate column tile per wave (32 candidates, half a block's): for launches
@@ -632,7 +734,7 @@ __global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu
   const int split = ns > 1 ? (int)(loc / a.tiles) : 0;
   kde_logpdf_h32_body<NSC, KP, false, false, true, 1>(cand, Nc, D, second ? a.P1 : a.P0, second ? a.table1 : a.table0,
                                                        second ? a.out1 : a.out0, tile, a.rescue, split, ns, nullptr, false,
-                                                       a.row_stage != 0);
+                                                       a.row_stage != 0, a.lhi, a.bmax);
 }
 
 // the coarse instance over an index list with a device-side count (KdeListArgs, hbx_kde_impl.h): the staged

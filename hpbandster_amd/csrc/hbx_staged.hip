@@ -10,10 +10,27 @@
 // Stages, all on the caller's stream, no host round trip (acq_score_staged):
 //   1 score l      the good KDE's coarse 32x32 pair kernel over all candidates (observation splits as in the
 //                  fused launch), its first workgroup initialising the acquisition's and the stages' state
-//     staged_l     rescue of marked candidates, merge of the splits, [llo, lhi] per candidate (est_interval),
-//                  lhi kept in a.lo until stage 4 / 5 overwrites it, Lmax = max llo (ordered-uint atomic max)
+//                  Unsplit (pair_shape's nsplit = 1; the bench's size): the kernel's epilogue, which holds each
+//                  candidate's finished estimate in a register, also leaves [llo, lhi] (est_interval) -- lhi in
+//                  a.lo, kept until stage 4 / 5 overwrites it, and per block the largest llo in a.bmax, an area
+//                  of its own in the workspace (4 bytes per 256 candidates; not an alias of the split partials,
+//                  so no block count at which this would have to be off).  No atomic, and nothing that races the
+//                  first workgroup's initialisation.  A rescue-marked candidate cannot be re-scored there: its lhi
+//                  is +inf and it contributes nothing to its block's maximum.  KdePairArgs::lhi / bmax.
+//     staged_l     a launch of its own where stage 1 ran split (partials to merge), for the staged top-k (KEYS)
+//                  and under HBX_STAGE1_LHI=0 (tests, A/B): rescue of marked candidates, merge of the splits,
+//                  [llo, lhi] per candidate, lhi into a.lo, Lmax = max llo (ordered-uint atomic max)
 //   2 seed         every candidate with lhi >= Lmax - ln 4 joins the seed list (at most the list capacity;
-//                  the rest fall through to stage 4); NaN-l candidates are never seeded.  (HBX_STAGED_TAIL=0:
+//                  the rest fall through to stage 4); NaN-l candidates are never seeded.  Behind the epilogue's
+//                  lhi, every block of the seed kernel first reduces the block maxima to Lmax itself (1954
+//                  floats on the bench; block 0 stores it in the state words for hbx_kde_acquire_stats and the
+//                  tools), and a candidate whose lhi reads +inf is looked up: a rescue marker is re-scored here
+//                  (kde_rescue_one, staged_l's call), its estimate stored, its interval's upper end taken as lhi
+//                  and tested like any other.  Lmax is then the largest llo over the UNMARKED candidates: lower
+//                  than staged_l's or equal, so the seed set can only grow.  The pick does not depend on which
+//                  candidates are seeds -- only U_seed and the survivor criterion enter the argument below, and
+//                  both hold for any seed set -- so only the seed and survivor counts can differ between the two
+//                  forms, and only where l estimates are marked.  (HBX_STAGED_TAIL=0:
 //                  every other candidate's g estimate becomes the marker "g not evaluated", err =
 //                  HBX_EST_NOT_EVAL, for the combine kernel)
 //   3 score seeds  the bad KDE's list instance (kde_logpdf_h32_list_kernel: candidates through an index list
@@ -70,6 +87,11 @@
 
 #define STAGED_PT 4  // candidates per thread of the selection kernels (1024 per block: few same-address atomics)
 #define HBX_LN4f 1.3862943611198906f
+// blocks at most of the seed kernel behind stage 1's epilogue: every block reads every block maximum (Nc / 512
+// floats), so an unbounded grid would read Nc^2 / 2^19 floats -- 760 MB at 1e7 candidates, more than staged_l_kernel
+// moved; 2048 blocks (two rounds of the chip at 4 blocks per CU) keep it at 160 MB there and change nothing
+// below 2.1e6 candidates
+#define STAGED_SEED_BLOCKS 2048
 
 // Rescue + split merge + interval of l: afterwards el[i] is the final estimate (what the unstaged path's rescue
 // pass and kde_merge_splits_kernel leave), lhi[i] = the interval's upper end (NaN: l is NaN), Lmax raised.
@@ -157,19 +179,57 @@ __device__ __forceinline__ int32_t staged_reserve(int n, int32_t* __restrict__ c
 
 // Seeds: lhi >= Lmax - ln 4, up to cap.  A seeded candidate's lhi becomes NaN (stage 4 skips it); mark_rest (the
 // combine kernel follows): every other candidate's g estimate becomes the marker.
+// bmax (stage 1's epilogue left lhi; null: Lmax is in the state words): Lmax is the largest of the nblk block maxima,
+// which every block reduces for itself (a float per 256 or 512 candidates, from the L2), block 0 storing it and
+// the fold's flag in the state words; and a candidate whose lhi reads +inf is looked up in el: a rescue marker is
+// re-scored here as staged_l_kernel does it, its estimate stored and its interval's upper end taken for lhi.
 __global__ __launch_bounds__(256) void staged_seed_kernel(float* __restrict__ lhi, int64_t Nc,
                                                           KdeEst* __restrict__ eg, int32_t* __restrict__ seeds,
                                                           int32_t cap, uint32_t* __restrict__ stage,
-                                                          int32_t mark_rest) {
-  const float thr = hbx_ord2f(stage[HBX_ST_LMAX]) - HBX_LN4f;
+                                                          int32_t mark_rest, const float* __restrict__ bmax,
+                                                          int32_t nblk, const double* __restrict__ cand, int32_t D,
+                                                          const KdeParams* __restrict__ Pl,
+                                                          KdeEst* __restrict__ el) {
+  float lmax;
+  if (bmax) {  // (uniform)
+    __shared__ float rb[4];
+    float m = -INFINITY;
+    for (int j = threadIdx.x; j < nblk; j += 256) m = fmaxf(m, bmax[j]);
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) rb[threadIdx.x >> 6] = m;
+    __syncthreads();
+    lmax = fmaxf(fmaxf(rb[0], rb[1]), fmaxf(rb[2], rb[3]));
+    if (blockIdx.x == 0 && threadIdx.x == 0) {  // for hbx_kde_acquire_stats / _stage1 and the tools
+      stage[HBX_ST_LMAX] = hbx_f2ord(lmax);
+      stage[HBX_ST_LHI1] = 1;
+    }
+  } else {
+    lmax = hbx_ord2f(stage[HBX_ST_LMAX]);
+  }
+  const float thr = lmax - HBX_LN4f;
+  // a block takes the 1024-candidate tiles blockIdx.x, + gridDim.x, ...: one tile each up to STAGED_SEED_BLOCKS
+  // tiles; the grid stops growing there, so that the blocks' reads of the block maxima do (staged_score_seeds)
+  const int64_t ntile = (Nc + 256 * STAGED_PT - 1) / (256 * STAGED_PT);
+  for (int64_t tb = blockIdx.x; tb < ntile; tb += gridDim.x) {
   bool f[STAGED_PT];
   int n = 0;
 #pragma unroll
   for (int r = 0; r < STAGED_PT; ++r) {
-    const int64_t i = ((int64_t)blockIdx.x * STAGED_PT + r) * 256 + threadIdx.x;
+    const int64_t i = (tb * STAGED_PT + r) * 256 + threadIdx.x;
     f[r] = false;
     if (i < Nc) {
-      const float h = lhi[i];
+      float h = lhi[i];
+      if (bmax && h == INFINITY) {  // rare: stage 1 marked the candidate (or its bound is +inf itself)
+        KdeEst e = el[i];
+        if (e.err == -1.f) {
+          e = kde_rescue_one<0, false, true>(cand, i, D, Pl);
+          el[i] = e;
+          float lo, pt;
+          h = NAN;
+          if (e.lpos == e.lpos) est_interval(e, &lo, &h, &pt);
+          lhi[i] = h;
+        }
+      }
       f[r] = h == h && h >= thr;
     }
     n += f[r] ? 1 : 0;
@@ -178,7 +238,7 @@ __global__ __launch_bounds__(256) void staged_seed_kernel(float* __restrict__ lh
   const KdeEst none = {0.f, -INFINITY, HBX_EST_NOT_EVAL, 0.f};
 #pragma unroll
   for (int r = 0; r < STAGED_PT; ++r) {
-    const int64_t i = ((int64_t)blockIdx.x * STAGED_PT + r) * 256 + threadIdx.x;
+    const int64_t i = (tb * STAGED_PT + r) * 256 + threadIdx.x;
     if (i >= Nc) continue;
     bool seeded = false;
     if (f[r]) {
@@ -190,6 +250,7 @@ __global__ __launch_bounds__(256) void staged_seed_kernel(float* __restrict__ lh
     }
     if (seeded) lhi[i] = NAN;
     else if (mark_rest) eg[i] = none;  // (uniform; the short tail reads no g estimate of an unevaluated candidate)
+  }
   }
 }
 
@@ -501,7 +562,8 @@ static KdeListArgs staged_list_args(const AcqPlan& plan, const KdePairRef& p, co
 }
 
 int staged_score_l(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
-                   hipEvent_t* ev, hipStream_t s, uint32_t* lkey, uint32_t* hist, int32_t hist_words) {
+                   hipEvent_t* ev, hipStream_t s, uint32_t* lkey, uint32_t* hist, int32_t hist_words,
+                   unsigned* lhi_blocks) {
   // stage 1: the good KDE's pair kernel with every block in its first segment; the good KDE has the chip's block
   // slots to itself (pair_shape's kdes = 1)
   const ScoreFns& f = plan.fg;
@@ -512,11 +574,20 @@ int staged_score_l(const AcqPlan& plan, const KdePairRef& p, const double* cand,
   ka.tiles = sh.tiles;
   ka.nsplit0 = ka.nsplit1 = ns;
   ka.row_stage = hbx_row_stage();
+  // the argmin's stage 1, unsplit: lhi and the block maxima from the scoring kernel's epilogue, no staged_l launch.
+  // (A split launch has partials to merge, and the staged top-k wants every candidate's key: staged_l_kernel.)
+  const bool fold = lhi_blocks && !lkey && ns == 1 && hbx_stage1_lhi();
+  if (lhi_blocks) *lhi_blocks = fold ? grid : 0;
+  if (fold) {
+    ka.lhi = a.lo;
+    ka.bmax = a.bmax;  // (one float per block: grid <= ceil(Nc / 256), the area's size)
+  }
   if (ev)  // stamped by the dispatch at the kernel's start
     hipExtLaunchKernelGGL(sh.kernel, dim3(grid), dim3(f.threads), 0, s, ev[0], nullptr, 0, cand, Nc, p.D, ka);
   else
     hipLaunchKernelGGL(sh.kernel, dim3(grid), dim3(f.threads), 0, s, cand, Nc, p.D, ka);
   HBX_LAUNCH_CHECK();
+  if (fold) return HBX_OK;
   if (lkey)
     hipLaunchKernelGGL(staged_l_kernel<true>, staged_gsel(Nc), dim3(256), 0, s, a.el, Nc, (int32_t)ns, cand, p.D,
                        p.Pg(), a.rescue, a.lo, a.stage, lkey, hist, hist_words);
@@ -528,11 +599,14 @@ int staged_score_l(const AcqPlan& plan, const KdePairRef& p, const double* cand,
 }
 
 int staged_score_seeds(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
-                       hipStream_t s, bool mark_rest, bool update_u) {
+                       hipStream_t s, bool mark_rest, bool update_u, unsigned lhi_blocks) {
   // stage 2
   const int32_t cap = a.list_cap;
-  hipLaunchKernelGGL(staged_seed_kernel, staged_gsel(Nc), dim3(256), 0, s, a.lo, Nc, a.eg, a.seeds, cap, a.stage,
-                     (int32_t)(mark_rest ? 1 : 0));
+  dim3 gseed = staged_gsel(Nc);
+  if (lhi_blocks && gseed.x > STAGED_SEED_BLOCKS) gseed.x = STAGED_SEED_BLOCKS;
+  hipLaunchKernelGGL(staged_seed_kernel, gseed, dim3(256), 0, s, a.lo, Nc, a.eg, a.seeds, cap, a.stage,
+                     (int32_t)(mark_rest ? 1 : 0), lhi_blocks ? (const float*)a.bmax : (const float*)nullptr,
+                     (int32_t)lhi_blocks, cand, p.D, p.Pg(), a.el);
   HBX_LAUNCH_CHECK();
   // stage 3
   const ScoreFns& fb = plan.fb;
@@ -565,9 +639,10 @@ int staged_score_survivors(const AcqPlan& plan, const KdePairRef& p, const doubl
 
 int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a,
                      hipEvent_t* ev, hipStream_t s, bool tail) {
-  int rc = staged_score_l(plan, p, cand, Nc, a, ev, s, nullptr, nullptr, 0);
+  unsigned lhi_blocks = 0;
+  int rc = staged_score_l(plan, p, cand, Nc, a, ev, s, nullptr, nullptr, 0, &lhi_blocks);
   if (rc) return rc;
-  rc = staged_score_seeds(plan, p, cand, Nc, a, s, !tail, true);
+  rc = staged_score_seeds(plan, p, cand, Nc, a, s, !tail, true, lhi_blocks);
   if (rc) return rc;
   rc = staged_score_survivors(plan, p, cand, Nc, a, s, tail);
   if (rc) return rc;
@@ -610,6 +685,20 @@ int hbx_kde_acquire_stats(const void* workspace, int64_t Nc, int64_t nmax, int64
   out[1] = seeds;
   out[2] = surv;
   out[3] = staged ? seeds + surv : Nc;
+  return HBX_OK;
+}
+
+// Stage 1 of the last single acquisition on this workspace (device read, synchronises): out[0] = 1 when lhi and
+// Lmax came from the scoring kernel's epilogue (0: from staged_l_kernel, or the call did not stage), out[1] = the
+// state words' Lmax, an order-preserving uint of the float.
+int hbx_kde_acquire_stage1(const void* workspace, int64_t Nc, int64_t nmax, int64_t* out) {
+  if (!workspace || !out || Nc < 0) return hbx_fail(HBX_ERR_ARG, "hbx_kde_acquire_stage1: bad arguments");
+  const WsLayout w = ws_layout(Nc, nmax);
+  uint32_t st[HBX_ST_WORDS];
+  HBX_HIP(hipDeviceSynchronize());
+  HBX_HIP(hipMemcpy(st, (const char*)workspace + w.stage, sizeof(st), hipMemcpyDeviceToHost));
+  out[0] = st[HBX_ST_FLAG] == 1 && st[HBX_ST_LHI1] == 1 ? 1 : 0;
+  out[1] = (int64_t)st[HBX_ST_LMAX];
   return HBX_OK;
 }
 

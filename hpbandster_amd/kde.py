@@ -514,6 +514,16 @@ class KDEPair(object):
         N.check(N.lib().hbx_kde_acquire_stats(workspace.data_ptr(), int(Nc), self.nmax, ctypes.addressof(out)))
         return {"staged": bool(out[0]), "seeds": int(out[1]), "survivors": int(out[2]), "evaluated": int(out[3])}
 
+    def acquire_stage1(self, workspace, Nc):
+        """Stage 1 of the last staged ``acquire`` over ``Nc`` candidates on ``workspace`` (synchronises):
+        dict(lhi_epilogue, lmax_bits) -- ``lhi_epilogue``: the good KDE's scoring launch itself left every
+        candidate's l bound and the largest lower bound (False: a launch of its own did, as with
+        ``HBX_STAGE1_LHI=0`` or a split scoring launch, or the call did not stage); ``lmax_bits``: that largest
+        lower bound as the workspace keeps it, an order-preserving uint32 of the float."""
+        out = (ctypes.c_int64 * 2)()
+        N.check(N.lib().hbx_kde_acquire_stage1(workspace.data_ptr(), int(Nc), self.nmax, ctypes.addressof(out)))
+        return {"lhi_epilogue": bool(out[0]), "lmax_bits": int(out[1])}
+
     def acquire(self, cands, index_base=0, logs=False, stream=None, workspace=None, sync=True, events=None,
                 ties="pinned"):
         """Select the first index minimising max(1e-8, g)/max(l, 1e-8) over the candidates.

@@ -471,6 +471,11 @@ int hbx_kde_ws_offsets(int64_t Nc, int64_t seg, int64_t nmax, int64_t* out);
  * [3] candidates whose g was evaluated (Nc when it did not stage).  Every such call leaves these words valid: an
  * unstaged call on a workspace an earlier staged call used reports 0. */
 int hbx_kde_acquire_stats(const void* workspace, int64_t Nc, int64_t nmax, int64_t* out);
+/* Stage 1 of the last staged single acquisition on `workspace` (a device read, synchronising): out[0] = 1 when
+ * every candidate's l bound and the largest lower l bound came from the good KDE's scoring launch itself (its
+ * unsplit form; environment HBX_STAGE1_LHI=0: never), 0 when a launch of their own derived them or the call did
+ * not stage; out[1] = that largest lower bound as the workspace keeps it, an order-preserving uint32 of the float. */
+int hbx_kde_acquire_stage1(const void* workspace, int64_t Nc, int64_t nmax, int64_t* out);
 
 int64_t hbx_kde_pdf_scratch_bytes(int64_t nmax);
 
