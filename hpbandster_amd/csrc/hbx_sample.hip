@@ -6,15 +6,26 @@
 //     lies in [m - bw_factor*m, m + bw_factor*(1-m)] -- the reference's quirk, kept as is;
 //   categorical (levels[d] = t): keep m with probability 1 - bw, else U{0..t-1} (bohb.py:143-146).
 // The truncated normal is drawn by inversion, z = Phi^-1(p), p = Phi(a) + u (Phi(b) - Phi(a)) (Phi at
-// the bounds in fp64; a > 0 is mirrored), Phi^-1 on the smaller tail min(p, 1 - p) in fp32
-// (-sqrt(2) erfcinv(2 min(p, 1 - p)): ~1e-7 relative in z, far below what a distributional test can see;
-// a branch-free fp32 erfinv polynomial measured 3 % slower in round 5).
-// Random numbers: Philox4x32-10 keyed by the seed; counter = (candidate index, word, stream): word w of lane
-// g's blocks (w = g + 8 i) gives the uniforms u of the lane's pairs g + 16 i and g + 8 + 16 i (32-bit words,
-// u = (w + 1/2) 2^-32).  A categorical dim keeps m when
+// the bounds in fp64; a > 0 is mirrored), Phi^-1 on the smaller tail min(p, 1 - p): in fp32 for
+// min(p, 1 - p) >= 1e-6 (-sqrt(2) erfcinv(2 min(p, 1 - p)) by Giles' erfinv polynomials: within 4e-6 max(1, |z|)
+// of scipy's ndtri there, 3e-7 the worst draw of the tests; a branch-free fp32 erfinv polynomial measured 3 %
+// slower in round 5), and below 1e-6, where those polynomials extrapolate (1e-5 off at 1e-8, 3e-3 at 1e-10, 0.8 at
+// 1e-16), from the fp64 AS 241 tail (norm_ppf_tail), to the same bound.  Data outside [0, 1] is supported: the
+// bounds then both lie on one side of 0 and the whole interval [Phi(lo), Phi(hi)] can sit in a tail (m = -0.3,
+// h = 0.05: z in [6, 26]), which is the fp64 path's case.
+// Random numbers: Philox4x32-10 keyed by the seed (seed & 0xFFFFFFFF, seed >> 32); counter = (ctr & 0xFFFFFFFF,
+// ctr >> 32, word, stream) with ctr = counter_base + i mod 2^64 of candidate i.  The datum index is
+// (bits n) >> 64 of word 0xFFFFFFFF's bits = r[0] << 32 | r[1].  Dim d takes the 32-bit word r[slot] of the
+// block at `word`, u = (r[slot] + 1/2) 2^-32:
+//   pair k = d / 2 belongs to lane g = k % 4 as its q-th pair, q = k / 4:  word = g + 4 (q / 2), slot = 2 (q % 2) + d % 2
+//   (in d alone: word = (d / 2) % 4 + 4 (d / 16), slot = 2 ((d / 8) % 2) + d % 2: period 16 in d, each word
+//   serves 4 dims, words < 64 at HBX_MAX_D).  The 4 lanes per candidate are part of the stream's definition.
+// A categorical dim keeps m when
 // u < 1 - h and otherwise takes level floor(t (u - (1 - h)) / h) -- the conditional uniform of the same draw
-// (h >= 1: always resampled, level floor(t u)) -- the reference draws from numpy's global RNG, so parity is
-// distributional (tests/test_gpu_sample.py).
+// (h >= 1: always resampled, level floor(t u)).  The reference draws from numpy's global RNG, so parity with it
+// is distributional (tests/test_gpu_sample.py); every draw is also checked against a host restatement of this
+// header (tests/sampler_reference.py, tests/test_gpu_sample_draws.py: datum and categorical levels exactly, z to
+// the bound above).
 //
 // One lane per (candidate, pair of dims), 4 lanes per candidate (kde_sample_pair_kernel).  Phi at the
 // bounds comes from a per-model table when many candidates are drawn (hbx_kde_sample_table).
@@ -54,13 +65,10 @@ __device__ __forceinline__ double as241_poly(const double (&c)[8], double x) {
   return r;
 }
 
-__device__ __forceinline__ double norm_ppf(double p) {
-  constexpr double A[8] = {3.3871328727963666080e0, 1.3314166789178437745e+2, 1.9715909503065514427e+3,
-                           1.3731693765509461125e+4, 4.5921953931549871457e+4, 6.7265770927008700853e+4,
-                           3.3430575583588128105e+4, 2.5090809287301226727e+3};
-  constexpr double B[8] = {1.0, 4.2313330701600911252e+1, 6.8718700749205790830e+2, 5.3941960214247511077e+3,
-                           2.1213794301586595867e+4, 3.9307895800092710610e+4, 2.8729085735721942674e+4,
-                           5.2264952788528545610e+3};
+// Phi^-1(r) for a tail probability r = min(p, 1 - p) < 0.075 (the two outer ranges of AS 241): <= 0.  Out of line:
+// the sampler calls it on a branch almost no lane takes, and inlined there it raised the table instance from 44 to
+// 120 VGPRs (8 to 4 waves per SIMD) and a 1e6 x 32 launch from 0.120 to 0.140 ms; as a call, 52 VGPRs and 0.120 ms.
+__device__ __noinline__ double norm_ppf_tail(double r) {
   constexpr double C[8] = {1.42343711074968357734e0, 4.63033784615654529590e0, 5.76949722146069140550e0,
                            3.64784832476320460504e0, 1.27045825245236838258e0, 2.41780725177450611770e-1,
                            2.27238449892691845833e-2, 7.74545014278341407640e-4};
@@ -73,12 +81,6 @@ __device__ __forceinline__ double norm_ppf(double p) {
   constexpr double F[8] = {1.0, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2,
                            7.86869131145613259100e-4, 1.84631831751005468180e-5, 1.42151175831644588870e-7,
                            2.04426310338993978564e-15};
-  const double q = p - 0.5;
-  if (fabs(q) <= 0.425) {
-    const double r = 0.180625 - q * q;
-    return q * as241_poly(A, r) / as241_poly(B, r);
-  }
-  double r = q < 0.0 ? p : 1.0 - p;  // exact for p >= 0.5 (Sterbenz)
   r = sqrt(-log(r));
   double v;
   if (r <= 5.0) {
@@ -88,7 +90,23 @@ __device__ __forceinline__ double norm_ppf(double p) {
     r -= 5.0;
     v = as241_poly(E, r) / as241_poly(F, r);
   }
-  return q < 0.0 ? -v : v;
+  return -v;
+}
+
+__device__ __forceinline__ double norm_ppf(double p) {
+  constexpr double A[8] = {3.3871328727963666080e0, 1.3314166789178437745e+2, 1.9715909503065514427e+3,
+                           1.3731693765509461125e+4, 4.5921953931549871457e+4, 6.7265770927008700853e+4,
+                           3.3430575583588128105e+4, 2.5090809287301226727e+3};
+  constexpr double B[8] = {1.0, 4.2313330701600911252e+1, 6.8718700749205790830e+2, 5.3941960214247511077e+3,
+                           2.1213794301586595867e+4, 3.9307895800092710610e+4, 2.8729085735721942674e+4,
+                           5.2264952788528545610e+3};
+  const double q = p - 0.5;
+  if (fabs(q) <= 0.425) {
+    const double r = 0.180625 - q * q;
+    return q * as241_poly(A, r) / as241_poly(B, r);
+  }
+  const double v = norm_ppf_tail(q < 0.0 ? p : 1.0 - p);  // 1 - p: exact for p >= 0.5 (Sterbenz)
+  return q < 0.0 ? v : -v;
 }
 
 __global__ void norm_ppf_kernel(const double* __restrict__ p, int64_t n, double* __restrict__ z) {
@@ -153,13 +171,23 @@ __device__ __forceinline__ float fast_erfcinvf(float t) {
   return p * (1.0f - t);
 }
 
+// Giles' polynomial is fitted for float erfinv, w <~ 17 (min(p, 1 - p) ~ 1e-8), and extrapolates beyond.  Below
+// TN_TAIL_T = 2e-6f (min(p, 1 - p) < 1e-6, w > 12.4: a margin, the polynomial's error already grows there) z comes
+// from the fp64 AS 241 tail of min(p, 1 - p) itself -- one log and one sqrt on a branch that a draw from data in
+// [0, 1] takes about once in 1e6, and every draw of a datum far outside [0, 1] takes.
+#define TN_TAIL_T 2e-6f
 __device__ __forceinline__ double tn_invert_f32(double plo, double phi, double lo, double hi, double u) {
   const double p = fma(u, phi - plo, plo);
   const bool up = p > 0.5;
-  const float t = (float)(2.0 * (up ? 1.0 - p : p));        // in (0, 1]
-  const float zt = -1.41421356237309505f * fast_erfcinvf(t);  // Phi^-1(min(p, 1 - p)) <= 0
+  const double pm = up ? 1.0 - p : p;  // min(p, 1 - p)
+  const float t = (float)(2.0 * pm);   // in (0, 1]
+  double zt;                           // Phi^-1(min(p, 1 - p)) <= 0
+  if (t < TN_TAIL_T)
+    zt = norm_ppf_tail(pm);
+  else
+    zt = (double)(-1.41421356237309505f * fast_erfcinvf(t));
   // (the library's erfcinvf: the same draws in distribution, 0.126 instead of 0.113 ms per 1e6 x 32 launch)
-  const double z = (double)(up ? -zt : zt);
+  const double z = up ? -zt : zt;
   return fmin(fmax(z, lo), hi);
 }
 

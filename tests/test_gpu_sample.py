@@ -6,6 +6,11 @@ The reference draws from numpy's global RNG; the GPU draws from Philox, so parit
   -- the reference's own distribution object as the CDF    (Kolmogorov-Smirnov)
 * categorical dim | datum m: P(m) = (1-bw) + bw/t, P(other) = bw/t   (chi-square)
 The draws are deterministic (seeded, counter-based), so the p-value thresholds cannot flake.
+
+Parity with the kernel's own definition is per draw: tests/test_gpu_sample_draws.py compares every candidate's datum,
+levels and z with a host reference (tests/sampler_reference.py), data outside [0, 1] and the deep tails of the
+inversion included (z within 4e-6 max(1, |z|) of scipy's ndtri over the whole range).  The distributional tests
+here stay: they tie the rule to the reference's distribution objects, which a restatement of the header cannot.
 """
 import numpy as np
 import pytest
@@ -165,8 +170,10 @@ def test_phi_table_gives_identical_draws(device):
 
 
 def test_norm_ppf_matches_scipy_ndtri(device):
-    """The sampler's inversion routine (fp32 guess + one fp64 Halley step) against scipy's ndtri
-    (the inverse scipy's truncnorm uses), over the whole range the sampler can hit."""
+    """hbx_norm_ppf, the library's fp64 inverse normal CDF (Wichura's AS 241, PPND16), against scipy's ndtri (the
+    inverse scipy's truncnorm uses).  The sampler does not call it for ordinary draws: those go through the fp32
+    erfcinv polynomials, and only draws with min(p, 1 - p) < 1e-6 take this function's tail branches -- both are
+    checked per draw in tests/test_gpu_sample_draws.py."""
     import torch
     from scipy.special import ndtri
     from hpbandster_amd import _native as N
