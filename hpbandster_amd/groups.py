@@ -10,6 +10,8 @@ Config #5's loop on the device from end to end::
     cfg = gm.get_config(64, seed, levels, requests=S)         # a configuration per request, prior draws where the
                                                               # reference falls back: hbx_kde_propose_groups
     opt = GroupBOHB(B, var_type, levels)                      # B BOHB runs in lockstep: new_results / get_configs
+    nxt, src, counts = advance(rows, seg_off, mask, K, fresh) # the next SH stage of every bracket: hbx_sh_advance_groups
+    res = GroupHyperband(opt, eta, min_b, max_b).run(n, f)    # B Hyperband runs: GroupSuccessiveHalving per iteration
 
 Bracket b owns the rows ``X[seg_off[b]:seg_off[b+1]]``; its good / bad KDEs are the head ``n_good[b]`` / tail
 ``n_bad[b]`` rows of numpy's argsort of its losses (bohb.py:220-246).  The fit's outputs (order, bandwidths, level
@@ -754,3 +756,262 @@ class GroupBOHB(object):
         return gm.get_config(self.num_samples, self.seed, self._levels(), requests=S,
                              random_fraction=self.random_fraction, bandwidth_factor=self.bandwidth_factor,
                              counter_base=counter_base, sync=sync)
+
+
+# ---- grouped successive halving ---------------------------------------------------------------------------------
+SRC_NONE = -2 ** 31  # include/hbx.h hbx_sh_advance_groups: an empty slot's src (its row is NaN)
+
+
+def advance(rows, seg_off, mask, K, fresh=None, stream=None, sync=True, device=None, out=None):
+    """The next stage of B brackets from their promotion masks (hbx_sh_advance_groups; HB_iteration.py:184-188,
+    :135-138).  ``rows`` [N, D] float64, ``seg_off`` [B + 1] int64 and ``mask`` [N] uint8 or bool (any non-zero byte
+    is set; what ``promote.promote_segments(..., on_device=True)`` returns), ``fresh`` None or [B, F, D] float64 --
+    host arrays or contiguous device tensors.  Per bracket: the rows of its set positions in ascending position, then
+    ``fresh[b][0 .. f_b)`` while slots are left, then NaN rows.  Returns ``(rows [B, K, D] float64, src [B, K] int32,
+    counts [B, 2] int64)``: ``src`` is the position relative to the bracket's start, ``-1 - i`` for fresh row i and
+    SRC_NONE for a NaN row; ``counts[b]`` is (set bytes -- also where they exceed K --, fresh rows used).  Host arrays,
+    or with ``sync=False`` device tensors and no synchronisation when every input is a device tensor already.
+    ``out``: the three output tensors to write instead of new ones."""
+    torch = kde._torch()
+    K = int(K)
+    if device is None:
+        device = rows.device if _is_tensor(rows) else kde.default_device()
+
+    def dev(a, dtype, what):
+        if _is_tensor(a):
+            t = a.view(torch.uint8) if a.dtype == torch.bool and dtype == torch.uint8 else a
+            if t.dtype != dtype or not t.is_contiguous():
+                raise N.HbxError("advance: %s must be a contiguous %s tensor" % (what, dtype))
+            return t
+        npd = {torch.float64: np.float64, torch.int64: np.int64, torch.uint8: np.uint8}[dtype]
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=npd)).to(device)
+
+    with N.on_device(device, stream):
+        rd, sd, md = dev(rows, torch.float64, "rows"), dev(seg_off, torch.int64, "seg_off"), \
+            dev(mask, torch.uint8, "mask")
+        if rd.dim() != 2 or sd.dim() != 1 or int(sd.shape[0]) < 1 or md.dim() != 1 or \
+                int(md.shape[0]) != int(rd.shape[0]):
+            raise N.HbxError("advance: rows [N, D], seg_off [B + 1] and mask [N] expected, got %s, %s, %s" %
+                             (tuple(rd.shape), tuple(sd.shape), tuple(md.shape)))
+        B, D = int(sd.shape[0]) - 1, int(rd.shape[1])
+        fd, F = None, 0
+        if fresh is not None:
+            fd = dev(fresh, torch.float64, "fresh")
+            if fd.dim() != 3 or int(fd.shape[0]) != B or int(fd.shape[2]) != D:
+                raise N.HbxError("advance: fresh must be [%d, F, %d], got %s" % (B, D, tuple(fd.shape)))
+            F = int(fd.shape[1])
+            if F == 0:
+                fd = None
+        if out is None:
+            ro = torch.empty((B, max(K, 0), D), dtype=torch.float64, device=device)
+            so = torch.empty((B, max(K, 0)), dtype=torch.int32, device=device)
+            co = torch.zeros((B, 2), dtype=torch.int64, device=device)
+        else:
+            ro, so, co = out
+        N.check(N.lib().hbx_sh_advance_groups(N.ptr(rd), D, N.ptr(sd), B, N.ptr(md), N.ptr(fd), F, K, N.ptr(ro),
+                                              N.ptr(so), N.ptr(co), N.stream_handle(stream, device)))
+        if not sync:
+            return ro, so, co
+        if stream is not None:
+            stream.synchronize()
+        return ro.cpu().numpy(), so.cpu().numpy(), co.cpu().numpy()
+
+
+class GroupStage(object):
+    """What GroupSuccessiveHalving.step hands to the next stage, all on the device: ``rows`` [B, K, D], ``src``
+    [B, K] and ``counts`` [B, 2] (``advance``'s), ``fills`` (the GroupConfigs of the reserved fill block, None when
+    no run had a deficit) and ``counter_base`` (the block's first Philox counter)."""
+    __slots__ = ("rows", "src", "counts", "fills", "counter_base")
+
+    def __init__(self, rows, src, counts, fills, counter_base):
+        self.rows, self.src, self.counts, self.fills, self.counter_base = rows, src, counts, fills, counter_base
+
+
+class GroupSuccessiveHalving(object):
+    """One Hyperband bracket of every run of a GroupBOHB, in lockstep (HB_iteration.py:149-190 and, with
+    ``resampling_rate``, :203-250 for all B runs at once).  ``num_configs`` / ``budgets``: the bracket's ladder
+    (HB_master.hb_bracket / hb_budgets).  Lockstep: a stage's requests are all answered by the model as it stands
+    when the stage starts, and its results are reported together -- in the reference the behaviour of a pool with at
+    least ``num_configs[stage]`` workers."""
+
+    def __init__(self, num_configs, budgets, resampling_rate=None, min_samples_advance=1, ties="numpy"):
+        self.num_configs = [int(v) for v in num_configs]
+        self.budgets = [float(v) for v in budgets]
+        if not self.num_configs or len(self.num_configs) != len(self.budgets):
+            raise ValueError("num_configs and budgets must have one entry per stage, got %d and %d" %
+                             (len(self.num_configs), len(self.budgets)))
+        if min(self.num_configs) < 1:
+            raise ValueError("every stage needs at least one configuration, got %r" % (self.num_configs,))
+        if resampling_rate is not None and not 0.0 <= float(resampling_rate) <= 1.0:
+            raise ValueError("resampling_rate must be in [0, 1], got %r" % (resampling_rate,))
+        self.resampling_rate = None if resampling_rate is None else float(resampling_rate)
+        self.min_samples_advance = min_samples_advance
+        N.order_mode(ties)
+        self.ties = ties
+
+    def threshold(self, stage):
+        """k of the promotion after ``stage``: configurations ranked below it advance (HB_iteration.py:180, :242)."""
+        nxt = self.num_configs[stage + 1]
+        if self.resampling_rate is None:
+            return nxt
+        return max(self.min_samples_advance, nxt * (1 - self.resampling_rate))
+
+    def step(self, opt, rows, losses, stage):
+        """The transition behind ``stage``: ``rows`` [B, num_configs[stage], D] (a device tensor) ran on
+        ``budgets[stage]`` and gave ``losses`` [B, num_configs[stage]] (a non-finite loss is a crashed run).
+        Reports them (``opt.new_results``: the reference's new_result per job, before process_results) and, on the
+        last stage, returns None (the reference's cleanup).  Otherwise ranks every run's finite losses
+        (hbx_sh_promote_ex, numpy's tie order by default), reads ONE pair of scalars back -- the smallest and largest
+        advancing count, 16 bytes: the only host read of a transition, it decides whether the fill call is made --,
+        asks ``opt.get_configs(budgets[stage + 1], S=K)`` for the fills when a run has fewer than
+        K = num_configs[stage + 1] survivors, and compacts (``advance``).  Returns a GroupStage.
+
+        Counters: every transition reserves B * K * num_samples Philox counters of ``opt.counter``, whether the fill
+        call runs or not, and fill slot i of run b is request (b, i) of that block: run b's draws depend on (B, b,
+        the ladder) only, never on the other runs' data."""
+        torch = kde._torch()
+        from . import promote
+        stage = int(stage)
+        if not 0 <= stage < len(self.num_configs):
+            raise ValueError("stage %r outside [0, %d)" % (stage, len(self.num_configs)))
+        B, n, D = (int(v) for v in rows.shape)
+        if B != opt.B or n != self.num_configs[stage] or tuple(losses.shape) != (B, n):
+            raise N.HbxError("step: stage %d takes rows [%d, %d, D] and losses [%d, %d], got %s and %s" %
+                             (stage, opt.B, self.num_configs[stage], opt.B, self.num_configs[stage],
+                              tuple(rows.shape), tuple(losses.shape)))
+        opt.new_results(self.budgets[stage], rows, losses)
+        if stage == len(self.num_configs) - 1:
+            return None
+        K = self.num_configs[stage + 1]
+        ld = opt._dev(losses, ())
+        seg = np.arange(B + 1, dtype=np.int64) * n
+        mask, nadv = promote.promote_segments(ld.reshape(-1), seg, np.full(B, self.threshold(stage), dtype=np.float64),
+                                              device=opt.device, ties=self.ties, on_device=True)
+        lo_hi = torch.stack((nadv.min(), nadv.max())).cpu()  # the transition's one host read: 16 bytes
+        base = opt.counter
+        opt.counter += B * K * opt.num_samples
+        fills = None
+        if int(lo_hi[0]) < K:
+            fills = opt.get_configs(self.budgets[stage + 1], S=K, counter_base=base, sync=False)
+        seg_d = torch.from_numpy(seg).to(opt.device)
+        out, src, counts = advance(rows.reshape(B * n, D), seg_d, mask, K, fresh=None if fills is None else fills.rows,
+                                   sync=False, device=opt.device)
+        return GroupStage(out, src, counts, fills, base)
+
+
+class GroupStageRecord(object):
+    """One stage of one Hyperband iteration, for all B runs: ``iteration``, ``stage``, ``budget``, ``rows`` [B, n, D],
+    ``losses`` [B, n], ``src`` [B, n] int32 (``advance``'s map into the previous stage: a position there, or -1 - i
+    for fill request i; at stage 0 every row is request i of the iteration's get_configs call: -1 - i) and
+    ``model_based`` [B, n] bool (the reference's info_dict['model_based_pick'], carried forward with the row)."""
+    __slots__ = ("iteration", "stage", "budget", "rows", "losses", "src", "model_based")
+
+    def __init__(self, iteration, stage, budget, rows, losses, src, model_based):
+        self.iteration, self.stage, self.budget = int(iteration), int(stage), float(budget)
+        self.rows, self.losses, self.src, self.model_based = rows, losses, src, model_based
+
+    def _to_host(self):
+        for name in ("rows", "losses", "src", "model_based"):
+            setattr(self, name, getattr(self, name).cpu().numpy())
+
+
+class GroupRunResult(object):
+    """What GroupHyperband.run returns: ``stages`` (the GroupStageRecords in run order; empty with ``keep=None``),
+    ``result[(iteration, stage)]`` and ``incumbent()``."""
+
+    def __init__(self, stages, inc_budget, inc_loss, inc_row):
+        self.stages = stages
+        self._inc = (inc_budget, inc_loss, inc_row)
+
+    def __getitem__(self, key):
+        for r in self.stages:
+            if (r.iteration, r.stage) == tuple(key):
+                return r
+        raise KeyError(key)
+
+    def __len__(self):
+        return len(self.stages)
+
+    def incumbent(self):
+        """Per run ``(budget [B], loss [B], row [B, D])``: the lowest finite loss at the largest budget that has any
+        (the first such row in run order), +inf / -inf budget / a NaN row for a run without a finite loss."""
+        return self._inc
+
+
+class GroupHyperband(object):
+    """B independent BOHB / Hyperband runs from end to end on the device: ``opt`` (a GroupBOHB) proposes, a
+    GroupSuccessiveHalving per iteration promotes.  The ladder is the reference's (HB_master.py:93-94, :161-168).
+    Lockstep: a stage's requests are all answered by the model as it stands when the stage starts -- the reference
+    with at least as many workers as the stage has configurations.  ``sh_kwargs`` go to GroupSuccessiveHalving
+    (``resampling_rate``, ``min_samples_advance``, ``ties``)."""
+
+    def __init__(self, opt, eta=3, min_budget=0.01, max_budget=1, **sh_kwargs):
+        from .HB_master import hb_budgets
+        if not eta > 1 or not 0 < min_budget <= max_budget:
+            raise ValueError("eta > 1 and 0 < min_budget <= max_budget expected, got %r, %r, %r" %
+                             (eta, min_budget, max_budget))
+        self.opt, self.eta = opt, eta
+        self.max_SH_iter, self.budgets = hb_budgets(eta, min_budget, max_budget)
+        self.sh_kwargs = sh_kwargs
+        GroupSuccessiveHalving([1], [max_budget], **sh_kwargs)  # (argument errors now, not at the first iteration)
+        self.iterations = 0  # Hyperband iterations run so far
+
+    def ladder(self, it):
+        """(num_configs, budgets) of iteration ``it``."""
+        from .HB_master import hb_bracket
+        s, ns = hb_bracket(it, self.eta, self.max_SH_iter)
+        return ns, [float(b) for b in self.budgets[(-s - 1):]]
+
+    def run(self, n_iterations, objective, keep="host"):
+        """``n_iterations`` more Hyperband iterations.  Iteration ``it`` starts with ``opt.get_configs(budgets[0],
+        S=ns[0])``; every stage calls ``objective(rows [B, n, D] device float64, budget, info) -> losses [B, n]`` (a
+        device tensor or a host array; a non-finite loss is a crashed run; ``info``: iteration, stage, budget) and
+        GroupSuccessiveHalving.step moves on.  ``keep``: 'host' (records as numpy arrays, copied once at the end of
+        the run), 'device' (tensors) or None (only the incumbents, as host arrays).  Returns a GroupRunResult."""
+        if keep not in ("host", "device", None):
+            raise ValueError("keep must be 'host', 'device' or None, got %r" % (keep,))
+        torch = kde._torch()
+        opt = self.opt
+        dev = opt.device
+        inc_b = torch.full((opt.B,), float("-inf"), dtype=torch.float64, device=dev)
+        inc_l = torch.full((opt.B,), float("inf"), dtype=torch.float64, device=dev)
+        inc_r = torch.full((opt.B, opt.D), float("nan"), dtype=torch.float64, device=dev)
+        stages = []
+        for it in range(self.iterations, self.iterations + int(n_iterations)):
+            ns, bud = self.ladder(it)
+            sh = GroupSuccessiveHalving(ns, bud, **self.sh_kwargs)
+            cfg = opt.get_configs(bud[0], S=ns[0], sync=False)
+            rows, mb = cfg.rows, cfg.model_based
+            src = (-1 - torch.arange(ns[0], dtype=torch.int32, device=dev)).expand(opt.B, ns[0]).contiguous()
+            for stage in range(len(ns)):
+                losses = opt._dev(objective(rows, bud[stage], dict(iteration=it, stage=stage, budget=bud[stage])), ())
+                if tuple(losses.shape) != (opt.B, ns[stage]):
+                    raise N.HbxError("objective returned %s, expected (%d, %d)" % (tuple(losses.shape), opt.B,
+                                                                                   ns[stage]))
+                if keep is not None:
+                    stages.append(GroupStageRecord(it, stage, bud[stage], rows, losses, src, mb))
+                # incumbent: the lowest finite loss at the largest budget that has one, first row on ties
+                fin = torch.isfinite(losses)
+                lf = torch.where(fin, losses, torch.full_like(losses, float("inf")))
+                m = lf.min(dim=1).values
+                first = torch.argmax((lf == m[:, None]).to(torch.uint8), dim=1)
+                better = fin.any(dim=1) & ((inc_b < bud[stage]) | ((inc_b == bud[stage]) & (m < inc_l)))
+                inc_b = torch.where(better, torch.full_like(inc_b, bud[stage]), inc_b)
+                inc_l = torch.where(better, m, inc_l)
+                inc_r = torch.where(better[:, None], rows[torch.arange(opt.B, device=dev), first], inc_r)
+                nxt = sh.step(opt, rows, losses, stage)
+                if nxt is None:
+                    break
+                adv = nxt.src >= 0
+                mbn = torch.gather(mb, 1, nxt.src.clamp(min=0).long())
+                if nxt.fills is not None:
+                    fi = (-1 - nxt.src).clamp(min=0, max=ns[stage + 1] - 1).long()
+                    mbn = torch.where(adv, mbn, torch.gather(nxt.fills.model_based, 1, fi))
+                rows, src, mb = nxt.rows, nxt.src, mbn & (nxt.src != SRC_NONE)
+            self.iterations = it + 1
+        if keep == "host":
+            for r in stages:
+                r._to_host()
+        if keep == "device":
+            return GroupRunResult(stages, inc_b, inc_l, inc_r)
+        return GroupRunResult(stages, inc_b.cpu().numpy(), inc_l.cpu().numpy(), inc_r.cpu().numpy())

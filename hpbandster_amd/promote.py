@@ -19,19 +19,21 @@ from . import _native as N
 from .kde import default_device
 
 
-def promote_segments(loss, seg_off, k, device=None, stream=None, return_order=False, ties="numpy"):
+def promote_segments(loss, seg_off, k, device=None, stream=None, return_order=False, ties="numpy", on_device=False):
     """loss: fp64 [N] (numpy or device tensor); seg_off: int64 [B+1]; k: per-bracket threshold [B].
 
     Returns a bool numpy mask [N]; with ``return_order`` the device tensors (advance u8, sorted
-    positions i64, advancing count per bracket i64).
+    positions i64, advancing count per bracket i64); with ``on_device`` (and no ``return_order``) the
+    device tensors (advance u8 [N], advancing count per bracket i64 [B]) -- brackets <= 1024 still take
+    the O(n) select, and with ``seg_off`` a host array nothing is read back.
     """
     L = N.lib()
     device = device or default_device()
     with N.on_device(device, stream):
-        return _promote_segments(L, loss, seg_off, k, device, stream, return_order, N.order_mode(ties))
+        return _promote_segments(L, loss, seg_off, k, device, stream, return_order, N.order_mode(ties), on_device)
 
 
-def _promote_segments(L, loss, seg_off, k, device, stream, return_order, mode):
+def _promote_segments(L, loss, seg_off, k, device, stream, return_order, mode, on_device=False):
     import torch
 
     def dev(a, dt):
@@ -56,6 +58,8 @@ def _promote_segments(L, loss, seg_off, k, device, stream, return_order, mode):
                                 N.ptr(nadv), N.ptr(scratch), sb, mode, None, N.stream_handle(stream, device)))
     if return_order:
         return adv, order, nadv
+    if on_device:
+        return adv, nadv[:B]
     return adv.cpu().numpy().astype(bool)
 
 

@@ -36,6 +36,8 @@
  *   hbx_kde_logpdf                  <- KDEMultivariate.pdf (kernel_density.py:162-196), fp32 log domain
  *   hbx_kde_pdf_exact               <- KDEMultivariate.pdf, fp64, reference operation order
  *   hbx_sh_promote(_ex)             <- HB_iteration.py:149-190 (SuccessiveHalving.process_results ranks)
+ *   hbx_sh_advance_groups           <- HB_iteration.py:184-188 (the survivors move to the next budget, in config-id
+ *                                      order) and :135-138 (new configurations fill the stage), B brackets, one call
  *   hbx_argmax_allreduce            <- bohb.py:150-152 'if val < best' across candidate shards on many GPUs
  *                                      (the reference has no multi-GPU path)
  */
@@ -622,6 +624,29 @@ int hbx_sh_advance_state(int64_t* state, int64_t n, double k, void* stream);
 /* Pinned, device-mapped, coherent host memory (hipHostMalloc) and its release. */
 int hbx_host_alloc(int64_t bytes, void** out);
 int hbx_host_free(void* p);
+
+/* Grouped successive halving: the next stage of B brackets from their promotion masks (HB_iteration.py:184-188 the
+ * survivors in config-id order, :135-138 new configurations where crashed runs left slots empty).  Bracket b owns the
+ * positions seg_off[b] .. seg_off[b+1] of rows (f64[N][D]) and of advance (u8[N], the mask hbx_sh_promote_ex writes;
+ * any non-zero byte is set); a_b is its number of set bytes.  rows_out[b][j][0..D) and src_out[b][j], slot j of K:
+ *   j < min(a_b, K)                      the row of the j-th set position in ascending position, copied bit for bit;
+ *                                        src = that position relative to seg_off[b]
+ *   the next f_b = min(F, K - min(a_b, K))  fresh[b][i][0..D), i = 0 .. f_b - 1, copied bit for bit; src = -1 - i
+ *                                        (fresh: f64[B][F][D] or NULL, then f_b = 0)
+ *   the rest                             every element the quiet NaN 0x7FF8000000000000; src = INT32_MIN
+ * counts_out (i64[B][2], nullable): {a_b, f_b}, a_b the true count also where it exceeds K.  Values are never
+ * interpreted (NaN payloads, -0.0, infinities and subnormals move as bits).  seg_off: device i64[B+1], non-decreasing;
+ * it is read on the device only.  8-byte alignment of the f64 / i64 pointers suffices (4 for src_out): 16-byte accesses
+ * are used only where the kernel finds D even and rows, fresh and rows_out 16-byte aligned.  Nothing outside
+ * rows_out[B][K][D], src_out[B][K] and counts_out[B][2] is written, and rows_out is also the call's scratch before
+ * its rows are stored.  One launch (brackets up to 8192 positions, or B > 1024: one workgroup per bracket) plus, for
+ * B <= 1024, three launches that cut longer brackets into slices (count, rank, gather), all on `stream`; no host
+ * synchronisation, no workspace.  B == 0 or K == 0: nothing to do, success.  A bracket longer than 2^31 - 1 positions
+ * is undefined.  Null required pointers, D outside [1, hbx_max_dims()], negative B, K or F (or one beyond int32),
+ * F > 0 with fresh == NULL, misaligned pointers: HBX_ERR_ARG (hbx_last_error), before anything is launched. */
+int hbx_sh_advance_groups(const double* rows, int32_t D, const int64_t* seg_off, int64_t B, const uint8_t* advance,
+                          const double* fresh, int64_t F, int64_t K, double* rows_out, int32_t* src_out,
+                          int64_t* counts_out, void* stream);
 
 /* ---- numpy's argsort on the host (hbx_npsort_host.cpp) ------------------------------------------------
  * hbx_np_argsort_host: np.argsort(x) of numpy 1.26.4 on an AVX-512 host (x86-simd-sort avx512_argsort<double>,

@@ -32,6 +32,12 @@ unsigned shape (8c) against the per-bracket prepare + logpdf loop; writes profil
 
 times the grouped get_config (get_config_bench below): hbx_kde_propose_groups against its parts and against
 propose(requests=S) plus a host prior fill; writes profiles/groups_get_config/bench_groups_get_config.json.
+
+    python tools/bench_groups.py --sh [--sh-max-budget 729] [--out FILE]
+
+times the grouped successive-halving transition (sh_bench below): hbx_sh_advance_groups alone against the sync-free
+torch composition (stable argsort of the mask, gather, where), the two taking turns, and one full GroupHyperband
+iteration with a device objective; writes profiles/groups_sh/bench_groups_sh.json.
 """
 import argparse
 import json
@@ -455,8 +461,159 @@ def get_config_bench(a, gm, L, sh, lvd, levels):
     return 0 if same else 1
 
 
+def _torch_advance(X3, m, K, fresh):
+    """The sync-free composition torch offers without hbx_sh_advance_groups: a stable argsort of the cleared mask per
+    run, its first K, a gather, and a where for the fills (NaN rows without ``fresh``).  (rows, src, counts)."""
+    B, n, D = X3.shape
+    order = torch.argsort((m == 0).to(torch.uint8), dim=1, stable=True)[:, :K]
+    got = X3.gather(1, order[:, :, None].expand(B, K, D))
+    cnt = m.ne(0).sum(dim=1)
+    j = torch.arange(K, device=X3.device)[None, :]
+    keep = j < cnt[:, None]
+    fi = (j - cnt[:, None]).clamp(min=0)
+    if fresh is None:
+        rows = torch.where(keep[:, :, None], got, torch.full_like(got, float("nan")))
+        src = torch.where(keep, order, torch.full_like(order, -2 ** 31))
+        nf = torch.zeros_like(cnt)
+    else:
+        rows = torch.where(keep[:, :, None], got, fresh.gather(1, fi[:, :, None].expand(B, K, D)))
+        src = torch.where(keep, order, -1 - fi)
+        nf = (K - cnt).clamp(min=0)
+    return rows, src.to(torch.int32), torch.stack((cnt, nf), dim=1)
+
+
+def _alternate(fns, reps, warm=3):
+    """name -> {ms_mean, ms_min, ms_max}: the functions take turns, every call between its own pair of device events"""
+    for _ in range(warm):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    ev = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, f in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            ev[k].append((e0, e1))
+    torch.cuda.synchronize()
+    out = {}
+    for k, pairs in ev.items():
+        ms = [e0.elapsed_time(e1) for e0, e1 in pairs]
+        out[k] = {"ms_mean": float(np.mean(ms)), "ms_min": float(np.min(ms)), "ms_max": float(np.max(ms))}
+    return out
+
+
+def sh_bench(a, dev, L):
+    """--sh: the stage transition of B runs.  hbx_sh_advance_groups alone at config #5's shape (n configurations per
+    run, K = n // 3 survivors, D = 32) against the torch composition above, the two taking turns: without fills, with
+    1 % crashed runs (and the fills offered), and with 1 % of the runs crashed whole (their stage all fills).  Then one
+    full GroupHyperband iteration (eta = 3, budgets 1 .. --sh-max-budget) with a device objective: the synchronised
+    wall time beside the device time of its calls."""
+    from hpbandster_amd import promote
+    B, n, D = a.B, a.n, 32
+    K = n // 3
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    X = torch.rand((B * n, D), dtype=torch.float64, device=dev, generator=g)
+    fresh = torch.rand((B, K, D), dtype=torch.float64, device=dev, generator=g)
+    seg = np.arange(B + 1, dtype=np.int64) * n
+    seg_d = torch.from_numpy(seg).to(dev)
+    base_losses = torch.from_numpy(S.make_bracket_losses(B, n).reshape(-1)).to(dev)
+    kk = np.full(B, float(K))
+    moved = B * (n + K * 4 + 16) + 2 * B * K * D * 8  # mask in, src and counts out, K rows per run in and out
+    out = {"shape": {"B": B, "n": n, "K": K, "D": D}, "reps": a.reps, "bytes": moved, "cases": {}}
+    ok = True
+    for name in ("no_fills", "crashed_runs_1pct", "crashed_brackets_1pct"):
+        losses = base_losses.clone()
+        if name == "crashed_runs_1pct":
+            losses[torch.rand(B * n, device=dev, generator=g) < 0.01] = float("inf")
+        elif name == "crashed_brackets_1pct":
+            losses.view(B, n)[torch.rand(B, device=dev, generator=g) < 0.01] = float("inf")
+        mask, nadv = promote.promote_segments(losses, seg, kk, device=dev, on_device=True)
+        fr = None if name == "no_fills" else fresh
+        bufs = (torch.empty((B, K, D), dtype=torch.float64, device=dev),
+                torch.empty((B, K), dtype=torch.int32, device=dev), torch.zeros((B, 2), dtype=torch.int64, device=dev))
+        frp, F = (N.ptr(fr), K) if fr is not None else (None, 0)
+
+        def new():
+            N.check(L.hbx_sh_advance_groups(N.ptr(X), D, N.ptr(seg_d), B, N.ptr(mask), frp, F, K, N.ptr(bufs[0]),
+                                            N.ptr(bufs[1]), N.ptr(bufs[2]), N.stream_handle(None, dev)))
+
+        def composition():
+            return _torch_advance(X.view(B, n, D), mask.view(B, n), K, fr)
+
+        new()
+        want = composition()
+        same = all(torch.equal(x.view(torch.int64) if x.dtype == torch.float64 else x,
+                               y.view(torch.int64) if y.dtype == torch.float64 else y) for x, y in zip(bufs, want))
+        del want
+        t = _alternate({"new": new, "torch": composition}, a.reps)
+        gbs = moved / (t["new"]["ms_mean"] * 1e-3) / 1e9
+        out["cases"][name] = {
+            "new": t["new"], "torch": t["torch"], "equal_outputs": bool(same),
+            "deficit_runs": int((nadv < K).sum()), "new_gb_s": gbs, "new_fraction_of_8tb_s": gbs / 8000.0,
+            "new_fraction_of_5p5tb_s": gbs / 5500.0, "speedup_mean": t["torch"]["ms_mean"] / t["new"]["ms_mean"],
+            "new_slowest_below_torch_fastest": bool(t["new"]["ms_max"] < t["torch"]["ms_min"])}
+        ok = ok and same and t["new"]["ms_max"] < t["torch"]["ms_min"]
+    del X, fresh
+
+    # one Hyperband iteration of B runs: ladder [ns], a device objective, every call between device events
+    dc, du, lev = 24, 8, 4
+    opt = groups.GroupBOHB(B, S.var_type_string(dc, du), [0] * dc + [lev] * du, num_samples=a.C, seed=4, device=dev)
+    hb = groups.GroupHyperband(opt, eta=3, min_budget=1, max_budget=a.sh_max_budget)
+    ev = {}
+
+    def stamped(name, fn):
+        def f(*args, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn(*args, **kw)
+            e1.record()
+            ev.setdefault(name, []).append((e0, e1))
+            return r
+        return f
+
+    def objective(rows, budget, info):
+        return ((rows[..., 0] - 0.3) ** 2 + (rows[..., 1] - 0.7) ** 2 + 0.1 * rows[..., -1]) / budget
+
+    opt.new_results = stamped("new_results", opt.new_results)
+    opt.get_configs = stamped("get_configs", opt.get_configs)
+    promote_plain, advance_plain = promote.promote_segments, groups.advance
+    promote.promote_segments = stamped("promote", promote_plain)
+    groups.advance = stamped("advance", advance_plain)
+    runs = []
+    try:
+        for it in range(2):  # iteration 0 twice (the ladder's longest); the first run warms every shape
+            hb.iterations = 0
+            opt.configs, opt.losses, opt.kde_models, opt.counter = {}, {}, {}, 0
+            ev.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            hb.run(1, stamped("objective", objective), keep=None)
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - t0) * 1e3
+            calls = {k: float(sum(e0.elapsed_time(e1) for e0, e1 in v)) for k, v in ev.items()}
+            runs.append({"wall_ms": wall, "calls_ms": calls, "calls_sum_ms": float(sum(calls.values()))})
+    finally:
+        promote.promote_segments, groups.advance = promote_plain, advance_plain
+    out["hyperband_iteration"] = {"ladder": hb.ladder(0)[0], "budgets": hb.ladder(0)[1], "warm": runs[0],
+                                  "timed": runs[1]}
+    out["ok"] = bool(ok)
+    a.out = a.out or os.path.join(ROOT, "profiles", "groups_sh", "bench_groups_sh.json")
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+    return 0 if ok else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sh", action="store_true", help="the grouped successive-halving transition (sh_bench)")
+    ap.add_argument("--sh-max-budget", type=float, default=729.0,
+                    help="--sh: the Hyperband iteration's budgets run from 1 to this (eta = 3)")
     ap.add_argument("--B", type=int, default=10000)
     ap.add_argument("--n", type=int, default=1000)
     ap.add_argument("--C", type=int, default=64)
@@ -475,6 +632,8 @@ def main(argv=None):
     L = N.lib()
     if a.logpdf:
         return logpdf_bench(a, dev, L)
+    if a.sh:
+        return sh_bench(a, dev, L)
     B, n, C, dc, du, lev = a.B, a.n, a.C, 24, 8, 4
     D = dc + du
     vts = S.var_type_string(dc, du)
