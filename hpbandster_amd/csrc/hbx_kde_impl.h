@@ -452,16 +452,28 @@ int refit_fit_colstats(const double* X, int32_t D, const int64_t* seg_off, const
                        ColStats* cs_bad, hipStream_t s);
 #define FIT_TILE_ROWS 16384  // kde_fit_col_kernel's LDS tile (FIT_TILE)
 
-// host-side pickers of the scoring kernel instances (nullptr when the bucket has none)
-logpdf_fn hbx_pick_f32(int dc_pad, int du_pad, bool sg);   // hbx_score_f32.hip
-logpdf_fn hbx_pick_oh(int dc_pad, int kc, bool sg);        // hbx_score_oh.hip
-logpdf_fn hbx_pick_h(int nsc, int kc, bool sg);            // hbx_score_h.hip
-logpdf_pair_fn hbx_pick_h_pair(int nsc, int kc, bool sg);  // hbx_score_h.hip (l + g in one launch)
-logpdf_fn hbx_pick_h32(int nsc, int kp, bool sg, bool fast);  // hbx_score_h32.hip
-logpdf_co_fn hbx_pick_h32_co(int nsc, int kp);                // the coarse instance over one KDE (unsigned sums)
-logpdf_pair_fn hbx_pick_h32_pair(int nsc, int kp, bool sg, bool fast, bool coarse = false);
-logpdf_pair_fn hbx_pick_h32_pair1(int nsc, int kp);  // the coarse pair kernel, one column tile per wave
-logpdf_list_fn hbx_pick_h32_list(int nsc, int kp);   // the coarse instance over an index list (staged acquisition)
+// host-side pickers of the scoring kernel instances (null pointers when the bucket has none), each with the block
+// its file's kernels are compiled for: candidates and threads per block, from the constants of their
+// __launch_bounds__ and tile loops
+struct ScoreInst {
+  logpdf_fn main = nullptr;
+  logpdf_pair_fn pair = nullptr;  // l + g in one launch (hbx_score_h.hip)
+  int cands_per_block = 0, threads = 0;
+};
+ScoreInst hbx_pick_f32(int dc_pad, int du_pad, bool sg);  // hbx_score_f32.hip
+ScoreInst hbx_pick_oh(int dc_pad, int kc, bool sg);       // hbx_score_oh.hip
+ScoreInst hbx_pick_h(int nsc, int kc, bool sg);           // hbx_score_h.hip
+// hbx_score_h32.hip.  coarse (unsigned sums only): pair is the coarse pair kernel, and with it come its twin with
+// one column tile per wave (half the candidates per block), the coarse instance over an index list (staged
+// acquisition) and over one KDE (launched in main's place); the block is theirs
+struct H32Inst {
+  logpdf_fn main = nullptr;
+  logpdf_pair_fn pair = nullptr, pair1 = nullptr;
+  logpdf_list_fn list = nullptr;
+  logpdf_co_fn main_co = nullptr;
+  int cands_per_block = 0, threads = 0;
+};
+H32Inst hbx_pick_h32(int nsc, int kp, bool sg, bool fast, bool coarse);
 
 // what the ln-pdf contract (hbx_logpdf.hip, hbx_kde_logpdf_rtol) launches from other units: hbx_score.hip's
 // precise estimate instance of a bucket (main + rescue into est; HBX_ERR_UNSUPPORTED when it has none) ...

@@ -15,6 +15,7 @@
 
 #include "hbx_common.h"
 #include "hbx_kde_impl.h"
+#include "hbx_pick.h"
 
 // ln pdf within rtol * max(1, |ln p|) of the reference's (the north-star contract), per candidate: the
 // fp32 estimate where its rigorous bound guarantees it, else queued for an fp64 evaluation
@@ -617,10 +618,12 @@ constexpr int dd_cpt(int dc, int du) { return DD_CPT; }
 struct DdFns {
   logpdf_dd_fn lds = nullptr, sg = nullptr;
   dd_stage_fn stage = nullptr;
+  int cpt = 1;  // candidates per thread of lds and sg: a block of theirs covers 256 cpt candidates
 };
 template <int DC, int DU, int CPT, bool LUT>
 static DdFns dd_fns() {
   DdFns f;
+  f.cpt = CPT;
   f.lds = kde_logpdf_dd_kernel<DC, DU, CPT, LUT>;
   if constexpr ((LUT ? DC + 4 : DC + DU) <= 32) {
     f.sg = kde_logpdf_dd_kernel<DC, DU, CPT, LUT, true>;
@@ -629,36 +632,20 @@ static DdFns dd_fns() {
   return f;
 }
 
-template <int DC>
-static DdFns pick_dd_du(int du_pad, int* cpt, bool lut) {
-  if (lut && du_pad == 4) {
-    *cpt = DD_CPT_LUT;
-    return dd_fns<DC, 4, DD_CPT_LUT, true>();
-  }
-  if (lut && du_pad == 8) {
-    *cpt = DD_CPT_LUT;
-    return dd_fns<DC, 8, DD_CPT_LUT, true>();
-  }
-  switch (du_pad) {
-    case 0: *cpt = dd_cpt(DC, 0); return dd_fns<DC, 0, dd_cpt(DC, 0), false>();
-    case 4: *cpt = dd_cpt(DC, 4); return dd_fns<DC, 4, dd_cpt(DC, 4), false>();
-    case 8: *cpt = dd_cpt(DC, 8); return dd_fns<DC, 8, dd_cpt(DC, 8), false>();
-    case 16: *cpt = dd_cpt(DC, 16); return dd_fns<DC, 16, dd_cpt(DC, 16), false>();
-    case 32: *cpt = dd_cpt(DC, 32); return dd_fns<DC, 32, dd_cpt(DC, 32), false>();
-  }
-  return DdFns{};
-}
-
-static DdFns pick_logpdf_dd(int dc_pad, int du_pad, int* cpt, bool lut) {
-  switch (dc_pad) {
-    case 0:
-    case 4: return pick_dd_du<4>(du_pad, cpt, lut);
-    case 8: return pick_dd_du<8>(du_pad, cpt, lut);
-    case 16: return pick_dd_du<16>(du_pad, cpt, lut);
-    case 24: return pick_dd_du<24>(du_pad, cpt, lut);
-    case 32: return pick_dd_du<32>(du_pad, cpt, lut);
-  }
-  return DdFns{};  // 64 continuous slots: the estimate + fp64 path
+// the direct-difference instances of a bucket (lut: the KDE has small codes and the switch allows the tables)
+static DdFns pick_logpdf_dd(int dc_pad, int du_pad, bool lut) {
+  const int dc = dc_pad == 0 ? 4 : dc_pad;               // no continuous slots: the DC = 4 instance, all padding
+  const bool lu = lut && (du_pad == 4 || du_pad == 8);  // the LUT instances: 4 and 8 categorical slots only
+  return hbx_pick<4, 8, 16, 24, 32>(dc, [=](auto c) {  // 64 continuous slots: the estimate + fp64 path
+    return hbx_pick<0, 4, 8, 16, 32>(du_pad, [=](auto u) {
+      return hbx_pick<0, 1>(lu, [](auto l) {
+        constexpr int DC = HBX_PICKED(c), DU = HBX_PICKED(u);
+        constexpr bool LUT = HBX_PICKED(l) != 0;
+        if constexpr (LUT && DU != 4 && DU != 8) return DdFns{};
+        else return dd_fns<DC, DU, LUT ? DD_CPT_LUT : dd_cpt(DC, DU), LUT>();
+      });
+    });
+  });
 }
 
 __global__ __launch_bounds__(256) void kde_logpdf_classify_kernel(const KdeEst* __restrict__ est, int64_t Nc,
@@ -685,34 +672,17 @@ __global__ __launch_bounds__(256) void kde_logpdf_classify_kernel(const KdeEst* 
 typedef void (*logpdf_tiled_fn)(const double*, int64_t, int32_t, const KdeParams*, const double*, const int64_t*,
                                 double*, const int32_t*, const int32_t*);
 
-template <int DC, bool E64>
-static logpdf_tiled_fn pick_tiled_du(int du_pad) {
-  switch (du_pad) {
-    case 0: return kde_logpdf_tiled_kernel<DC, 0, E64>;
-    case 4:
-    case 8: return kde_logpdf_tiled_kernel<DC, 8, E64>;
-    case 16: return kde_logpdf_tiled_kernel<DC, 16, E64>;
-    case 32: return kde_logpdf_tiled_kernel<DC, 32, E64>;
-  }
-  return nullptr;
-}
-
-template <bool E64>
-static logpdf_tiled_fn pick_tiled_e(int dc_pad, int du_pad) {
-  switch (dc_pad) {
-    case 0:
-    case 4:
-    case 8: return pick_tiled_du<8, E64>(du_pad);
-    case 16: return pick_tiled_du<16, E64>(du_pad);
-    case 24: return pick_tiled_du<24, E64>(du_pad);
-    case 32: return pick_tiled_du<32, E64>(du_pad);
-  }
-  return nullptr;  // 64 continuous slots: the per-point kernel
-}
-
 // the tiled fp64 log-space kernel of a bucket (dc_pad, du_pad), fp64 exponentials for rtol < 1e-5
 static logpdf_tiled_fn pick_logpdf_tiled(int dc_pad, int du_pad, bool exp64) {
-  return exp64 ? pick_tiled_e<true>(dc_pad, du_pad) : pick_tiled_e<false>(dc_pad, du_pad);
+  const int dc = dc_pad == 0 || dc_pad == 4 ? 8 : dc_pad;  // up to 8 continuous slots: the DC = 8 instance
+  const int du = du_pad == 4 ? 8 : du_pad;                 // 4 categorical slots: the DU = 8 instance
+  return hbx_pick<8, 16, 24, 32>(dc, [=](auto c) {  // 64 continuous slots: the per-point kernel
+    return hbx_pick<0, 8, 16, 32>(du, [=](auto u) {
+      return hbx_pick<0, 1>(exp64, [](auto e) -> logpdf_tiled_fn {
+        return kde_logpdf_tiled_kernel<HBX_PICKED(c), HBX_PICKED(u), HBX_PICKED(e) != 0>;
+      });
+    });
+  });
 }
 
 extern "C" {
@@ -737,17 +707,16 @@ int hbx_kde_logpdf_rtol(const double* cand, int64_t Nc, int32_t D, const void* p
   const bool exact_only = v.exact_only;
   // unsigned KDEs of a bucket with <= 32 continuous slots: the direct-difference fp32 pass writes every
   // candidate its bound accepts and lists the rest (its kernel lists all of a KDE it does not model)
-  int cpt = 1;
   // HBX_DD_LUT=0: the packed-match categorical path everywhere (tests)
   const bool lut = v.small_codes && hbx_switch_on("HBX_DD_LUT");
-  const DdFns dd = (!exact_only && !v.has_neg) ? pick_logpdf_dd(dc_pad, du_pad, &cpt, lut) : DdFns{};
+  const DdFns dd = (!exact_only && !v.has_neg) ? pick_logpdf_dd(dc_pad, du_pad, lut) : DdFns{};
   // HBX_DD_SG=0: the LDS-staged dd kernel everywhere (tests)
   // (small calls: the LDS-staged kernel alone -- the staging launch and a second dd launch would cost more than
   // the SG kernel saves, and the scratch of a few thousand candidates rarely holds the rows)
   const bool sg = dd.sg && Nc >= 8192 && hbx_switch_on("HBX_DD_SG");
   HBX_HIP(hipMemsetAsync(count, 0, sizeof(int32_t), s));
   if (dd.lds) {
-    const dim3 g((unsigned)((Nc + 256 * cpt - 1) / (256 * cpt)));
+    const dim3 g((unsigned)((Nc + 256 * dd.cpt - 1) / (256 * dd.cpt)));
     int32_t* flag = sg ? count + 1 : nullptr;
     if (sg) {  // rows staged into the (unused here) estimate area when they fit; the flag picks the kernel
       hipLaunchKernelGGL(dd.stage, dim3(256), dim3(256), 0, s, (const KdeParams*)params, X, rows, D, 16 * Nc,

@@ -1,14 +1,14 @@
 // hbx_score.hip -- scoring dispatch on MI355X (gfx950): which fp32 scoring instance a prepared KDE runs
-// (hbx_score_f32 / _oh / _h / _h32.hip hold them), the launch of one KDE's or a pair's scoring with its rescue
-// pass, and the rescue kernels.  hbx_kde_logpdf scores candidates against one KDE; the acquisitions
+// (hbx_score_f32 / _oh / _h / _h32.hip hold them: each picks its instance for a bucket through the one ladder of
+// hbx_pick.h and hands it back with the block it is compiled for, so no launch shape is restated here), the launch
+// of one KDE's or a pair's scoring with its rescue pass, and the rescue kernels.  hbx_kde_logpdf scores candidates against one KDE; the acquisitions
 // (hbx_kde.hip acq_score, and through it hbx_topk.hip) launch through launch_score2; pair_shape is the one rule for
 // a pair launch's kernel, tiles and splits (the fused launch here, stage 1 of hbx_staged.hip).
 #include "hbx_score.h"
 
 #include <hip/hip_ext.h>
 
-#include <type_traits>
-
+#include "hbx_pick.h"
 #include "hbx_prep.h"
 #include "hbx_rescue_impl.h"
 
@@ -102,32 +102,11 @@ PairShape pair_shape(const ScoreFns& f, bool pair1_ok, int kdes, int64_t Nc, int
   return sh;
 }
 
-// the one ladder over the continuous buckets: f(integral_constant<dc_pad>) for a bucket, else nullptr
-template <class F>
-static auto by_dc_pad(int dc_pad, F f) -> decltype(f(std::integral_constant<int, 0>{})) {
-  switch (dc_pad) {
-    case 0: return f(std::integral_constant<int, 0>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    case 24: return f(std::integral_constant<int, 24>{});
-    case 32: return f(std::integral_constant<int, 32>{});
-    case 64: return f(std::integral_constant<int, 64>{});
-  }
-  return nullptr;
-}
-template <bool SG>
-static logpdf_fn pick_rescue(int dc_pad) {
-  return by_dc_pad(dc_pad, [](auto c) -> logpdf_fn { return kde_rescue_kernel<decltype(c)::value, SG>; });
-}
-template <bool SG>
-static logpdf_pair_fn pick_rescue_pair(int dc_pad) {
-  return by_dc_pad(dc_pad, [](auto c) -> logpdf_pair_fn { return kde_rescue_pair_kernel<decltype(c)::value, SG>; });
-}
-
 static const ScoreFns NO_SCORE_FNS{nullptr, nullptr, 0, 0, nullptr, nullptr};  // no instance for the bucket
 
-// (the variant code and `fast`: hbx_score.h)
+// (the variant code and `fast`: hbx_score.h)  The family's file picks the instance and says what block it is
+// compiled for; here: which family a variant runs, the rescue kernels of its bucket, and what the coarse
+// instances need around them.
 ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast) {
   const KdeVariant v = KdeVariant::decode(variant);
   const bool sg = v.has_neg;
@@ -135,29 +114,32 @@ ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast) {
   int dcp, dup;
   bucket_dims(dc_pad, du_pad, &dcp, &dup);
   if (dcp != dc_pad || dup != du_pad) return NO_SCORE_FNS;  // not a bucket
-  const logpdf_fn r = sg ? pick_rescue<true>(dc_pad) : pick_rescue<false>(dc_pad);
-  const logpdf_pair_fn rp = sg ? pick_rescue_pair<true>(dc_pad) : pick_rescue_pair<false>(dc_pad);
+  struct Rescue {
+    logpdf_fn one;
+    logpdf_pair_fn pair;
+  };
+  const Rescue r = hbx_pick<0, 1>(sg, [=](auto s) {
+    return hbx_pick<0, 4, 8, 16, 24, 32, 64>(dc_pad, [](auto dc) {
+      return Rescue{kde_rescue_kernel<HBX_PICKED(dc), HBX_PICKED(s) != 0>,
+                    kde_rescue_pair_kernel<HBX_PICKED(dc), HBX_PICKED(s) != 0>};
+    });
+  });
+  if (v.hmode && dc_pad < 8) return NO_SCORE_FNS;
   if (v.hmode && v.h32) {
-    if (dc_pad < 8) return NO_SCORE_FNS;
     const int kp = h32_kp(kc);
     const bool co = fast && !sg && v.coarse;  // the acquisition's coarse pre-screen instance
-    const bool fa = fast && kp > 0;
-    const int hw = co ? H32C_WAVES : H16_WAVES;
-    ScoreFns f{hbx_pick_h32(nsc_of(dc_pad), kp, sg, fa), r, 32 * hw * (co ? H32C_CT : 1), 64 * hw,
-               hbx_pick_h32_pair(nsc_of(dc_pad), kp, sg, fa, co), rp, true};
-    if (co && H32C_CT > 1) f.pair1 = hbx_pick_h32_pair1(nsc_of(dc_pad), kp);
-    if (co) f.list = hbx_pick_h32_list(nsc_of(dc_pad), kp);
-    if (co) f.main_co = hbx_pick_h32_co(nsc_of(dc_pad), kp);
+    const H32Inst h = hbx_pick_h32(nsc_of(dc_pad), kp, sg, fast && kp > 0, co);
+    ScoreFns f{h.main, r.one, h.cands_per_block, h.threads, h.pair, r.pair, true};
+    if (co && H32C_CT > 1) f.pair1 = h.pair1;
+    if (co) f.list = h.list;
+    if (co) f.main_co = h.main_co;
     if (co && !f.main_co) return NO_SCORE_FNS;
     return f;
   }
-  if (v.hmode) {
-    if (dc_pad < 8) return NO_SCORE_FNS;
-    return {hbx_pick_h(nsc_of(dc_pad), kc, sg), r, 16 * H16_WAVES * H_ROW_TILES, 64 * H16_WAVES,
-            hbx_pick_h_pair(nsc_of(dc_pad), kc, sg), rp};
-  }
-  if (kc == 0) return {hbx_pick_f32(dc_pad, du_pad, sg), r, 16 * MFMA_WAVES, 64 * MFMA_WAVES, nullptr, nullptr};
-  return {hbx_pick_oh(dc_pad, kc, sg), r, 16 * MFMA_WAVES, 64 * MFMA_WAVES, nullptr, nullptr};
+  // the 16x16 hmode family; else the f32 families (no pair launch): categorical match on the VALU, or one-hot
+  const ScoreInst k = v.hmode ? hbx_pick_h(nsc_of(dc_pad), kc, sg)
+                              : kc == 0 ? hbx_pick_f32(dc_pad, du_pad, sg) : hbx_pick_oh(dc_pad, kc, sg);
+  return {k.main, r.one, k.cands_per_block, k.threads, k.pair, v.hmode ? r.pair : nullptr};
 }
 
 int launch_score(ScoreFns f, const double* cand, int64_t Nc, int32_t D, const void* params, const float* table,

@@ -2,9 +2,13 @@
 // (buckets with fewer than 16 continuous dims or non-integer categorical codes).
 #include "hbx_common.h"
 #include "hbx_kde_impl.h"
+#include "hbx_pick.h"
+
+// the block: MFMA_WAVES waves of 16 candidates each (cbase)
+constexpr int F32_BLOCK_THREADS = 64 * MFMA_WAVES, F32_BLOCK_CANDS = 16 * MFMA_WAVES;
 
 template <int DCP, int DUP, bool SIGNED>
-__global__ __launch_bounds__(64 * MFMA_WAVES) void kde_logpdf_kernel(const double* __restrict__ cand, int64_t Nc,
+__global__ __launch_bounds__(F32_BLOCK_THREADS) void kde_logpdf_kernel(const double* __restrict__ cand, int64_t Nc,
                                                                     int32_t D, const KdeParams* __restrict__ P,
                                                                     const float* __restrict__ table,
                                                                     KdeEst* __restrict__ out) {
@@ -201,32 +205,13 @@ __global__ __launch_bounds__(64 * MFMA_WAVES) void kde_logpdf_kernel(const doubl
   }
 }
 
-template <int DCP, bool SG>
-static logpdf_fn pick_du(int du_pad) {
-  switch (du_pad) {
-    case 0: return kde_logpdf_kernel<DCP, 0, SG>;
-    case 4: return kde_logpdf_kernel<DCP, 4, SG>;
-    case 8: return kde_logpdf_kernel<DCP, 8, SG>;
-    case 16: return kde_logpdf_kernel<DCP, 16, SG>;
-    case 32: return kde_logpdf_kernel<DCP, 32, SG>;
-  }
-  return nullptr;
-}
-
-template <bool SG>
-static logpdf_fn pick_dc(int dc_pad, int du_pad) {
-  switch (dc_pad) {
-    case 0: return pick_du<0, SG>(du_pad);
-    case 4: return pick_du<4, SG>(du_pad);
-    case 8: return pick_du<8, SG>(du_pad);
-    case 16: return pick_du<16, SG>(du_pad);
-    case 24: return pick_du<24, SG>(du_pad);
-    case 32: return pick_du<32, SG>(du_pad);
-    case 64: return pick_du<64, SG>(du_pad);
-  }
-  return nullptr;
-}
-
-logpdf_fn hbx_pick_f32(int dc_pad, int du_pad, bool sg) {
-  return sg ? pick_dc<true>(dc_pad, du_pad) : pick_dc<false>(dc_pad, du_pad);
+ScoreInst hbx_pick_f32(int dc_pad, int du_pad, bool sg) {
+  const logpdf_fn k = hbx_pick<0, 1>(sg, [=](auto s) {
+    return hbx_pick<0, 4, 8, 16, 24, 32, 64>(dc_pad, [=](auto dc) {
+      return hbx_pick<0, 4, 8, 16, 32>(du_pad, [](auto du) -> logpdf_fn {
+        return kde_logpdf_kernel<HBX_PICKED(dc), HBX_PICKED(du), HBX_PICKED(s) != 0>;
+      });
+    });
+  });
+  return {k, nullptr, F32_BLOCK_CANDS, F32_BLOCK_THREADS};
 }

@@ -1,6 +1,7 @@
 // hbx_score_h.hip -- scoring kernel, whole exponent on the f16 matrix cores (hmode).
 #include "hbx_common.h"
 #include "hbx_kde_impl.h"
+#include "hbx_pick.h"
 
 // hmode: the whole exponent is one f16 matrix product.  Continuous coordinates are split into f16
 // hi + lo parts and the cross products are summed (every f16 x f16 product is exact in fp32; the
@@ -42,6 +43,9 @@ struct SgbPrefetch<NM, NM, NV, RT, NDENSE> {
   static __device__ __forceinline__ void run() {}
 };
 
+// the block: H16_WAVES waves of H_ROW_TILES row tiles of 16 candidates each (the body's HW, RT and cbase)
+constexpr int H_BLOCK_THREADS = 64 * H16_WAVES, H_BLOCK_CANDS = 16 * H_ROW_TILES * H16_WAVES;
+
 // The kernel body, for block `blk` of one KDE's grid (the single-KDE kernel and the l+g pair kernel
 // below both run it).
 template <int NSC, int KC, bool SIGNED>
@@ -63,6 +67,7 @@ __device__ __forceinline__ void kde_logpdf_h_body(const double* __restrict__ can
   // LDS ring: 3 buffers (chunk c+2 in flight while c is used) when they fit in the 160 KB, else 2
   constexpr int HW = H16_WAVES;             // waves per block (16 candidates x RT each)
   static_assert(HW == 8, "only the 8-wave block is validated");
+  static_assert(H_BLOCK_THREADS == 64 * HW && H_BLOCK_CANDS == HW * 16 * RT, "the shape hbx_pick_h hands out");
   // LDS ring: with 8-wave blocks (two per CU) 3 buffers when they fit, else 2; with 16-wave blocks (one
   // per CU) as many as fit, at most 6 (the staged candidate rows of 16 waves need the room)
   constexpr int NMAX = 160 * 1024 / (CHF * 4);
@@ -517,7 +522,7 @@ __device__ __forceinline__ void kde_logpdf_h_body(const double* __restrict__ can
 }
 
 template <int NSC, int KC, bool SIGNED>
-__global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(H_WAVES_PER_EU))) void kde_logpdf_h_kernel(
+__global__ __launch_bounds__(H_BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(H_WAVES_PER_EU))) void kde_logpdf_h_kernel(
     const double* __restrict__ cand, int64_t Nc, int32_t D, const KdeParams* __restrict__ P,
     const float* __restrict__ table, KdeEst* __restrict__ out) {
   kde_logpdf_h_body<NSC, KC, SIGNED>(cand, Nc, D, P, table, out, blockIdx.x);
@@ -527,63 +532,23 @@ __global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(
 // same candidates.  The launcher puts the larger KDE first, so the short KDE's blocks fill the tail
 // of the long one's last wave of blocks (and one launch gap goes away).
 template <int NSC, int KC, bool SIGNED>
-__global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(H_WAVES_PER_EU))) void kde_logpdf_h_pair_kernel(
+__global__ __launch_bounds__(H_BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(H_WAVES_PER_EU))) void kde_logpdf_h_pair_kernel(
     const double* __restrict__ cand, int64_t Nc, int32_t D, KdePairArgs a) {
   const bool second = blockIdx.x >= a.nblk0;  // uniform per block: scalar selects
   kde_logpdf_h_body<NSC, KC, SIGNED>(cand, Nc, D, second ? a.P1 : a.P0, second ? a.table1 : a.table0,
                                      second ? a.out1 : a.out0, second ? blockIdx.x - a.nblk0 : blockIdx.x, a.rescue);
 }
 
-template <int NSC, bool SG>
-static logpdf_pair_fn pick_pair_kc(int kc) {
-  switch (kc) {
-    case 0: return kde_logpdf_h_pair_kernel<NSC, 0, SG>;
-    case 1: return kde_logpdf_h_pair_kernel<NSC, 1, SG>;
-    case 2: return kde_logpdf_h_pair_kernel<NSC, 2, SG>;
-    case 3: return kde_logpdf_h_pair_kernel<NSC, 3, SG>;
-    case 4: return kde_logpdf_h_pair_kernel<NSC, 4, SG>;
-  }
-  return nullptr;
+ScoreInst hbx_pick_h(int nsc, int kc, bool sg) {
+  ScoreInst r = hbx_pick<0, 1>(sg, [=](auto s) {
+    return hbx_pick<1, 2, 3, 4, 8>(nsc, [=](auto n) {  // nsc_of(dc_pad) for dc_pad in {8, 16, 24, 32, 64}
+      return hbx_pick<0, 1, 2, 3, 4>(kc, [](auto c) {
+        return ScoreInst{kde_logpdf_h_kernel<HBX_PICKED(n), HBX_PICKED(c), HBX_PICKED(s) != 0>,
+                         kde_logpdf_h_pair_kernel<HBX_PICKED(n), HBX_PICKED(c), HBX_PICKED(s) != 0>};
+      });
+    });
+  });
+  r.cands_per_block = H_BLOCK_CANDS;
+  r.threads = H_BLOCK_THREADS;
+  return r;
 }
-
-template <bool SG>
-static logpdf_pair_fn pick_pair_nsc(int nsc, int kc) {
-  switch (nsc) {
-    case 1: return pick_pair_kc<1, SG>(kc);
-    case 2: return pick_pair_kc<2, SG>(kc);
-    case 3: return pick_pair_kc<3, SG>(kc);
-    case 4: return pick_pair_kc<4, SG>(kc);
-    case 8: return pick_pair_kc<8, SG>(kc);
-  }
-  return nullptr;
-}
-
-logpdf_pair_fn hbx_pick_h_pair(int nsc, int kc, bool sg) {
-  return sg ? pick_pair_nsc<true>(nsc, kc) : pick_pair_nsc<false>(nsc, kc);
-}
-
-template <int NSC, bool SG>
-static logpdf_fn pick_kc(int kc) {
-  switch (kc) {
-    case 0: return kde_logpdf_h_kernel<NSC, 0, SG>;
-    case 1: return kde_logpdf_h_kernel<NSC, 1, SG>;
-    case 2: return kde_logpdf_h_kernel<NSC, 2, SG>;
-    case 3: return kde_logpdf_h_kernel<NSC, 3, SG>;
-    case 4: return kde_logpdf_h_kernel<NSC, 4, SG>;
-  }
-  return nullptr;
-}
-
-template <bool SG>
-static logpdf_fn pick_nsc(int nsc, int kc) {
-  switch (nsc) {  // nsc_of(dc_pad) for dc_pad in {8, 16, 24, 32, 64}
-    case 1: return pick_kc<1, SG>(kc);
-    case 2: return pick_kc<2, SG>(kc);
-    case 3: return pick_kc<3, SG>(kc);
-    case 4: return pick_kc<4, SG>(kc);
-    case 8: return pick_kc<8, SG>(kc);
-  }
-  return nullptr;
-}
-
-logpdf_fn hbx_pick_h(int nsc, int kc, bool sg) { return sg ? pick_nsc<true>(nsc, kc) : pick_nsc<false>(nsc, kc); }

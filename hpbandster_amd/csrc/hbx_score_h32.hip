@@ -33,12 +33,18 @@
 #include "hbx_common.h"
 #include "hbx_kde_impl.h"
 #include "hbx_acq_impl.h"  // est_interval (the staged argmin's stage 1)
+#include "hbx_pick.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 #define H32_CMAX 30000.f    // |shifted c_i| limit of the three-piece split (else: rescue pass)
+
+// the block of an instance (CO: coarse, CT column tiles per wave): its waves, and its candidates -- 32 per wave
+// and column tile.  The kernels' __launch_bounds__, the body's HW and cbase, and the shape hbx_pick_h32 hands out
+constexpr int h32_waves(bool co) { return co ? H32C_WAVES : H16_WAVES; }
+constexpr int h32_cands(bool co, int ct) { return 32 * ct * h32_waves(co); }
 
 // sparse index words of one tile: KS dwords (one ds_read).  KS = 1: both lane halves read the row's two
 // dwords and take theirs (ds_read_b64 banks over 64 dwords, b32 over 32: 4-way on these rows)
@@ -114,7 +120,8 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
   static_assert(!FAST || KP > 0, "the fast instance drops the one-hot lo parts");
   static_assert(!CO || !SG, "the coarse instance is built for unsigned sums");
   static_assert(CT == 1 || (CT == 2 && CO), "two candidate column tiles per wave: the coarse instance");
-  constexpr int HW = CO ? H32C_WAVES : H16_WAVES;  // waves per block, 32 CT candidates each
+  constexpr int HW = h32_waves(CO);  // waves per block, 32 CT candidates each
+  static_assert(h32_cands(CO, CT) == HW * 32 * CT, "the block's candidates (cb, cbase)");
   constexpr int AUXF = HW * 32 * CT * 4;  // per candidate: c_i, bound term, shift, rescue flag
   // LDS ring: 4 buffers (3 chunks in flight) when two blocks' rings fit in the 160 KB, else 3
   constexpr int NBUF = 2 * (4 * CHF + AUXF) * 4 <= 160 * 1024 ? 4 : 3;
@@ -684,7 +691,7 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
 // unsigned sums: 128 VGPRs, 4 waves per SIMD (two blocks per CU); the coarse instance: H32C_WAVES-wave
 // blocks at >= H32C_EU waves per SIMD
 template <int NSC, int KP, bool FAST>
-__global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(4))) void kde_logpdf_h32_kernel(
+__global__ __launch_bounds__(64 * h32_waves(false)) __attribute__((amdgpu_waves_per_eu(4))) void kde_logpdf_h32_kernel(
     const double* __restrict__ cand, int64_t Nc, int32_t D, const KdeParams* __restrict__ P,
     const float* __restrict__ table, KdeEst* __restrict__ out) {
   kde_logpdf_h32_body<NSC, KP, false, FAST>(cand, Nc, D, P, table, out, blockIdx.x);
@@ -692,7 +699,7 @@ __global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(
 
 // ... and the coarse instance over one KDE (logpdf_co_fn: row_stage as in KdePairArgs)
 template <int NSC, int KP>
-__global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu(H32C_EU))) void kde_logpdf_h32_co_kernel(
+__global__ __launch_bounds__(64 * h32_waves(true)) __attribute__((amdgpu_waves_per_eu(H32C_EU))) void kde_logpdf_h32_co_kernel(
     const double* __restrict__ cand, int64_t Nc, int32_t D, const KdeParams* __restrict__ P,
     const float* __restrict__ table, KdeEst* __restrict__ out, int32_t row_stage) {
   kde_logpdf_h32_body<NSC, KP, false, false, true, H32C_CT>(cand, Nc, D, P, table, out, blockIdx.x, nullptr, 0, 1, nullptr,
@@ -700,8 +707,10 @@ __global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu
 }
 
 // both KDEs of an acquisition in one grid (see kde_logpdf_h_pair_kernel)
+// (the three pair kernels here spell the same prologue out: through a shared __forceinline__ helper returning the
+// block's segment every instance came out with its scalar prologue in another order, so the text stays)
 template <int NSC, int KP, bool FAST, bool CO>
-__global__ __launch_bounds__(64 * (CO ? H32C_WAVES : H16_WAVES)) __attribute__((amdgpu_waves_per_eu(CO ? H32C_EU : 4))) void kde_logpdf_h32_pair_kernel(
+__global__ __launch_bounds__(64 * h32_waves(CO)) __attribute__((amdgpu_waves_per_eu(CO ? H32C_EU : 4))) void kde_logpdf_h32_pair_kernel(
     const double* __restrict__ cand, int64_t Nc, int32_t D, KdePairArgs a) {
 #if HBX_PAIR_INIT
   if (a.init.U && blockIdx.x == 0 && threadIdx.x == 0)  // a single acquisition's state (acq_init's work)
@@ -721,7 +730,7 @@ __global__ __launch_bounds__(64 * (CO ? H32C_WAVES : H16_WAVES)) __attribute__((
 // whose two KDEs' H32C_CT-tile blocks fit one round of the chip's block slots (config #2: 2 x 196 blocks), twice
 // the waves, each walking its chunks with half the matrix work -- more waves per SIMD to hide the ring refills
 template <int NSC, int KP>
-__global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu(H32C_EU))) void kde_logpdf_h32_pair1_kernel(
+__global__ __launch_bounds__(64 * h32_waves(true)) __attribute__((amdgpu_waves_per_eu(H32C_EU))) void kde_logpdf_h32_pair1_kernel(
     const double* __restrict__ cand, int64_t Nc, int32_t D, KdePairArgs a) {
 #if HBX_PAIR_INIT
   if (a.init.U && blockIdx.x == 0 && threadIdx.x == 0)
@@ -741,11 +750,11 @@ __global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu
 // acquisition's bad-KDE launches.  Same block shape and scoring body as the pair kernel's, so a candidate's sums
 // are the ones it would get there.
 template <int NSC, int KP>
-__global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu(H32C_EU))) void kde_logpdf_h32_list_kernel(
+__global__ __launch_bounds__(64 * h32_waves(true)) __attribute__((amdgpu_waves_per_eu(H32C_EU))) void kde_logpdf_h32_list_kernel(
     const double* __restrict__ cand, int32_t D, KdeListArgs a) {
   int32_t cnt = *a.count;  // uniform
   if (cnt > a.maxcount) cnt = a.maxcount;
-  constexpr int CPB = 32 * H32C_CT * H32C_WAVES;
+  constexpr int CPB = h32_cands(true, H32C_CT);
   const bool splits = cnt <= a.cap;  // else: unsplit, one block per tile of the whole list, scattering itself
   if (splits && blockIdx.x >= a.tiles_cap * (unsigned)a.nsplit) return;
   const unsigned tile = splits ? blockIdx.x % a.tiles_cap : blockIdx.x;
@@ -759,14 +768,14 @@ __global__ __launch_bounds__(64 * H32C_WAVES) __attribute__((amdgpu_waves_per_eu
 // signed sums (the parity product and its accumulators): one 8-wave block per CU, so 2 waves per SIMD
 // and a 256-register budget
 template <int NSC, int KP, bool FAST>
-__global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(2))) void kde_logpdf_h32s_kernel(
+__global__ __launch_bounds__(64 * h32_waves(false)) __attribute__((amdgpu_waves_per_eu(2))) void kde_logpdf_h32s_kernel(
     const double* __restrict__ cand, int64_t Nc, int32_t D, const KdeParams* __restrict__ P,
     const float* __restrict__ table, KdeEst* __restrict__ out) {
   kde_logpdf_h32_body<NSC, KP, true, FAST>(cand, Nc, D, P, table, out, blockIdx.x);
 }
 
 template <int NSC, int KP, bool FAST>
-__global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(2))) void kde_logpdf_h32s_pair_kernel(
+__global__ __launch_bounds__(64 * h32_waves(false)) __attribute__((amdgpu_waves_per_eu(2))) void kde_logpdf_h32s_pair_kernel(
     const double* __restrict__ cand, int64_t Nc, int32_t D, KdePairArgs a) {
 #if HBX_PAIR_INIT
   if (a.init.U && blockIdx.x == 0 && threadIdx.x == 0)
@@ -781,114 +790,46 @@ __global__ __launch_bounds__(64 * H16_WAVES) __attribute__((amdgpu_waves_per_eu(
                                            second ? a.out1 : a.out0, tile, a.rescue, split, ns);
 }
 
-// instances: h32_ok (hbx_kde_impl.h); FAST where there is a one-hot part; CO (coarse) for unsigned sums (pair
-// launches; one KDE's coarse instance has its own type: hbx_pick_h32_co)
-template <int NSC, int KP, bool SG, bool PAIR, bool FAST, bool CO>
-static constexpr auto h32_inst() {
-  if constexpr (PAIR) {
-    if constexpr (SG) return (logpdf_pair_fn)kde_logpdf_h32s_pair_kernel<NSC, KP, FAST>;
-    else return (logpdf_pair_fn)kde_logpdf_h32_pair_kernel<NSC, KP, FAST, CO>;
+// instances: h32_ok (hbx_kde_impl.h); FAST where there is a one-hot part (else the precise instance stands in);
+// CO (coarse) for unsigned sums: the pair kernel with H32C_CT column tiles, and with it the one-tile pair kernel,
+// the list kernel and the coarse instance over one KDE.  A combination that is not built: all null.
+template <int NSC, int KP, bool SG, bool FAST, bool CO>
+static H32Inst h32_inst() {
+  H32Inst h;
+  constexpr bool FA = FAST && KP > 0;
+  if constexpr (!h32_ok(NSC, KP, SG)) {
+    return h;
+  } else if constexpr (SG) {
+    h.main = kde_logpdf_h32s_kernel<NSC, KP, FA>;
+    h.pair = kde_logpdf_h32s_pair_kernel<NSC, KP, FA>;
   } else {
-    static_assert(!CO, "hbx_pick_h32_co");
-    if constexpr (SG) return (logpdf_fn)kde_logpdf_h32s_kernel<NSC, KP, FAST>;
-    else return (logpdf_fn)kde_logpdf_h32_kernel<NSC, KP, FAST>;
+    h.main = kde_logpdf_h32_kernel<NSC, KP, FA>;
+    if constexpr (CO) {
+      h.pair = kde_logpdf_h32_pair_kernel<NSC, KP, false, true>;
+      h.pair1 = kde_logpdf_h32_pair1_kernel<NSC, KP>;
+      h.list = kde_logpdf_h32_list_kernel<NSC, KP>;
+      h.main_co = kde_logpdf_h32_co_kernel<NSC, KP>;
+    } else {
+      h.pair = kde_logpdf_h32_pair_kernel<NSC, KP, FA, false>;
+    }
   }
+  return h;
 }
 
-template <int NSC, int KP, bool SG, bool PAIR>
-static auto pick32_fast(bool fast, bool coarse) {
-  if constexpr (!SG && PAIR)
-    if (coarse) return h32_inst<NSC, KP, SG, PAIR, false, true>();
-  if constexpr (KP > 0)
-    if (fast) return h32_inst<NSC, KP, SG, PAIR, true, false>();
-  return h32_inst<NSC, KP, SG, PAIR, false, false>();
-}
-
-template <int NSC, bool SG, bool PAIR>
-static auto pick32_kp(int kp, bool fast, bool coarse) {
-  switch (kp) {
-    case 0: if constexpr (h32_ok(NSC, 0, SG)) return pick32_fast<NSC, 0, SG, PAIR>(fast, coarse); break;
-    case 1: if constexpr (h32_ok(NSC, 1, SG)) return pick32_fast<NSC, 1, SG, PAIR>(fast, coarse); break;
-    case 2: if constexpr (h32_ok(NSC, 2, SG)) return pick32_fast<NSC, 2, SG, PAIR>(fast, coarse); break;
-  }
-  return decltype(h32_inst<NSC, 1, SG, PAIR, false, false>())(nullptr);
-}
-
-template <bool SG, bool PAIR>
-static auto pick32(int nsc, int kp, bool fast, bool coarse) {
-  switch (nsc) {  // nsc_of(dc_pad) for dc_pad in {8, 16, 24, 32}
-    case 1: return pick32_kp<1, SG, PAIR>(kp, fast, coarse);
-    case 2: return pick32_kp<2, SG, PAIR>(kp, fast, coarse);
-    case 3: return pick32_kp<3, SG, PAIR>(kp, fast, coarse);
-    case 4: return pick32_kp<4, SG, PAIR>(kp, fast, coarse);
-  }
-  return decltype(pick32_kp<1, SG, PAIR>(0, false, false))(nullptr);
-}
-
-logpdf_fn hbx_pick_h32(int nsc, int kp, bool sg, bool fast) {
-  return sg ? pick32<true, false>(nsc, kp, fast, false) : pick32<false, false>(nsc, kp, fast, false);
-}
-
-logpdf_pair_fn hbx_pick_h32_pair(int nsc, int kp, bool sg, bool fast, bool coarse) {
-  return sg ? pick32<true, true>(nsc, kp, fast, false) : pick32<false, true>(nsc, kp, fast, coarse);
-}
-
-template <int NSC>
-static logpdf_pair_fn pick32_pair1_kp(int kp) {
-  switch (kp) {
-    case 0: if constexpr (h32_ok(NSC, 0, false)) return kde_logpdf_h32_pair1_kernel<NSC, 0>; break;
-    case 1: if constexpr (h32_ok(NSC, 1, false)) return kde_logpdf_h32_pair1_kernel<NSC, 1>; break;
-    case 2: if constexpr (h32_ok(NSC, 2, false)) return kde_logpdf_h32_pair1_kernel<NSC, 2>; break;
-  }
-  return nullptr;
-}
-
-template <int NSC>
-static logpdf_list_fn pick32_list_kp(int kp) {
-  switch (kp) {
-    case 0: if constexpr (h32_ok(NSC, 0, false)) return kde_logpdf_h32_list_kernel<NSC, 0>; break;
-    case 1: if constexpr (h32_ok(NSC, 1, false)) return kde_logpdf_h32_list_kernel<NSC, 1>; break;
-    case 2: if constexpr (h32_ok(NSC, 2, false)) return kde_logpdf_h32_list_kernel<NSC, 2>; break;
-  }
-  return nullptr;
-}
-
-logpdf_list_fn hbx_pick_h32_list(int nsc, int kp) {
-  switch (nsc) {
-    case 1: return pick32_list_kp<1>(kp);
-    case 2: return pick32_list_kp<2>(kp);
-    case 3: return pick32_list_kp<3>(kp);
-    case 4: return pick32_list_kp<4>(kp);
-  }
-  return nullptr;
-}
-
-template <int NSC>
-static logpdf_co_fn pick32_co_kp(int kp) {
-  switch (kp) {
-    case 0: if constexpr (h32_ok(NSC, 0, false)) return kde_logpdf_h32_co_kernel<NSC, 0>; break;
-    case 1: if constexpr (h32_ok(NSC, 1, false)) return kde_logpdf_h32_co_kernel<NSC, 1>; break;
-    case 2: if constexpr (h32_ok(NSC, 2, false)) return kde_logpdf_h32_co_kernel<NSC, 2>; break;
-  }
-  return nullptr;
-}
-
-logpdf_co_fn hbx_pick_h32_co(int nsc, int kp) {
-  switch (nsc) {
-    case 1: return pick32_co_kp<1>(kp);
-    case 2: return pick32_co_kp<2>(kp);
-    case 3: return pick32_co_kp<3>(kp);
-    case 4: return pick32_co_kp<4>(kp);
-  }
-  return nullptr;
-}
-
-logpdf_pair_fn hbx_pick_h32_pair1(int nsc, int kp) {
-  switch (nsc) {
-    case 1: return pick32_pair1_kp<1>(kp);
-    case 2: return pick32_pair1_kp<2>(kp);
-    case 3: return pick32_pair1_kp<3>(kp);
-    case 4: return pick32_pair1_kp<4>(kp);
-  }
-  return nullptr;
+H32Inst hbx_pick_h32(int nsc, int kp, bool sg, bool fast, bool coarse) {
+  coarse = coarse && !sg;
+  H32Inst h = hbx_pick<1, 2, 3, 4>(nsc, [=](auto n) {  // nsc_of(dc_pad) for dc_pad in {8, 16, 24, 32}
+    return hbx_pick<0, 1, 2>(kp, [=](auto k) {
+      return hbx_pick<0, 1>(sg, [=](auto s) {
+        return hbx_pick<0, 1>(fast, [=](auto f) {
+          return hbx_pick<0, 1>(coarse, [](auto c) {
+            return h32_inst<HBX_PICKED(n), HBX_PICKED(k), HBX_PICKED(s) != 0, HBX_PICKED(f) != 0, HBX_PICKED(c) != 0>();
+          });
+        });
+      });
+    });
+  });
+  h.cands_per_block = h32_cands(coarse, coarse ? H32C_CT : 1);  // the blocks that pair, list and main_co are built for
+  h.threads = 64 * h32_waves(coarse);
+  return h;
 }

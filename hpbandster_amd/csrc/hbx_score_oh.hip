@@ -1,6 +1,7 @@
 // hbx_score_oh.hip -- scoring kernel, f32 matrix-core continuous product + f16 one-hot categorical product.
 #include "hbx_common.h"
 #include "hbx_kde_impl.h"
+#include "hbx_pick.h"
 
 // One-hot mode: the categorical sum  sum_u delta_u [x_u == X_u]  is a second matrix product,
 // (candidate one-hot) x (delta-weighted observation one-hot), on the f16 matrix cores: operands are
@@ -9,8 +10,11 @@
 // exp2 and the running sums.  Signed KDEs add one more f16 product that counts matches in dims with
 // a negative match weight (the sign of the term is (-1)^count).
 
+// the block: MFMA_WAVES waves of 16 candidates each (cbase; NT)
+constexpr int OH_BLOCK_THREADS = 64 * MFMA_WAVES, OH_BLOCK_CANDS = 16 * MFMA_WAVES;
+
 template <int DCP, int KC, bool SIGNED>
-__global__ __launch_bounds__(64 * MFMA_WAVES) void kde_logpdf_oh_kernel(const double* __restrict__ cand,
+__global__ __launch_bounds__(OH_BLOCK_THREADS) void kde_logpdf_oh_kernel(const double* __restrict__ cand,
                                                                        int64_t Nc, int32_t D,
                                                                        const KdeParams* __restrict__ P,
                                                                        const float* __restrict__ table,
@@ -193,29 +197,13 @@ __global__ __launch_bounds__(64 * MFMA_WAVES) void kde_logpdf_oh_kernel(const do
   }
 }
 
-template <int DCP, bool SG>
-static logpdf_fn pick_kc(int kc) {
-  switch (kc) {
-    case 1: return kde_logpdf_oh_kernel<DCP, 1, SG>;
-    case 2: return kde_logpdf_oh_kernel<DCP, 2, SG>;
-    case 3: return kde_logpdf_oh_kernel<DCP, 3, SG>;
-    case 4: return kde_logpdf_oh_kernel<DCP, 4, SG>;
-  }
-  return nullptr;
+ScoreInst hbx_pick_oh(int dc_pad, int kc, bool sg) {
+  const logpdf_fn k = hbx_pick<0, 1>(sg, [=](auto s) {
+    return hbx_pick<0, 4, 8, 16, 24, 32, 64>(dc_pad, [=](auto dc) {
+      return hbx_pick<1, 2, 3, 4>(kc, [](auto c) -> logpdf_fn {
+        return kde_logpdf_oh_kernel<HBX_PICKED(dc), HBX_PICKED(c), HBX_PICKED(s) != 0>;
+      });
+    });
+  });
+  return {k, nullptr, OH_BLOCK_CANDS, OH_BLOCK_THREADS};
 }
-
-template <bool SG>
-static logpdf_fn pick_dc(int dc_pad, int kc) {
-  switch (dc_pad) {
-    case 0: return pick_kc<0, SG>(kc);
-    case 4: return pick_kc<4, SG>(kc);
-    case 8: return pick_kc<8, SG>(kc);
-    case 16: return pick_kc<16, SG>(kc);
-    case 24: return pick_kc<24, SG>(kc);
-    case 32: return pick_kc<32, SG>(kc);
-    case 64: return pick_kc<64, SG>(kc);
-  }
-  return nullptr;
-}
-
-logpdf_fn hbx_pick_oh(int dc_pad, int kc, bool sg) { return sg ? pick_dc<true>(dc_pad, kc) : pick_dc<false>(dc_pad, kc); }

@@ -498,6 +498,58 @@ def test_h32_every_instance_matches_oracle(device, dc, du):
     assert (fast.score, fast.pdf_l, fast.pdf_g) == (res.score, res.pdf_l, res.pdf_g)
 
 
+@pytest.mark.parametrize("dc,du,lev,kc", [
+    (0, 4, 20, 0),   # VALU matching (more than the 64 one-hot positions the matrix cores take): dc_pad 0, du_pad 4
+    (33, 8, 12, 0),  # ... dc_pad 64, du_pad 8
+    (3, 17, 3, 0),   # ... dc_pad 4, du_pad 32
+    (12, 16, 3, 4),  # one-hot: dc_pad 16, kc 4
+    (32, 4, 3, 1),   # ... dc_pad 32, kc 1
+    (33, 8, 3, 2),   # ... dc_pad 64, kc 2
+])
+def test_f32_families_remaining_buckets_match_oracle(device, dc, du, lev, kc, monkeypatch):
+    """The f32-MFMA fallback families (HBX_HMODE=0: VALU categorical matching, kc = 0, or the one-hot product)
+    in the buckets no other test selects, modelled on test_h32_every_instance_matches_oracle: 200 observations
+    (the good set under one 64-observation chunk, the bad set two chunks and a partial one) and 600 candidates
+    (a full and a partial block).  The ln-pdf estimates within 1e-5 of the oracle's log-space restatement, the
+    oracle's winner, the same record with and without estimates requested, and the ln-pdf contract through
+    DeviceKDE.logpdf (its direct-difference and tiled fp64 kernels at 16 and 32 categorical slots)."""
+    from hpbandster_amd import kde
+    from hpbandster_amd import synthetic as S
+    _kernel_env(monkeypatch, "f32")
+    n = 200
+    X = S.make_observations(n, dc, du, lev, seed=71)
+    L = S.make_losses(n, seed=72)
+    C = S.make_candidates(600, dc, du, lev, seed=73)
+    vt = S.var_type_string(dc, du)
+    # the reference's split and bandwidths; over 12 and 20 levels the normal-reference rule gives categorical
+    # bandwidths above 1 (signed sums): those dims get bandwidths below 1 instead
+    g_idx, b_idx = O.bohb_split(X, L, dc + du + 1)
+    bwg, bwb = O.normal_reference_bw(X[g_idx]), O.normal_reference_bw(X[b_idx])
+    if lev > 3:
+        bwg[dc:], bwb[dc:] = np.linspace(0.2, 0.5, du), np.linspace(0.6, 0.3, du)
+    pair = kde.fit_pair_from_rows(X, g_idx, b_idx, vt, bwg, bwb, O.num_levels(X[g_idx], vt),
+                                  O.num_levels(X[b_idx], vt), device=device)
+    for k in (pair.good, pair.bad):
+        assert not k.has_neg
+        assert (k.variant >> 4) & 1 == 0 and k.kc == kc  # not the f16 matrix-core kernels; the family
+    res, logl, logg = pair.acquire(C, logs=True)
+    for est, k in ((logl, pair.good), (logg, pair.bad)):
+        lref = O.log_pdf_many(k.data, k.bw, vt, C, k.nlev)
+        fin = np.isfinite(lref)
+        assert np.array_equal(np.isfinite(est), fin)
+        err = np.abs(est[fin] - lref[fin]) / np.maximum(1.0, np.abs(lref[fin]))
+        assert err.max() <= 1e-5, err.max()
+        lp = k.logpdf(C)
+        errc = np.abs(lp[fin] - lref[fin]) / np.maximum(1.0, np.abs(lref[fin]))
+        assert errc.max() <= 1e-5, errc.max()
+    l = O.pdf_many(pair.good.data, pair.good.bw, vt, C, pair.good.nlev)
+    g = O.pdf_many(pair.bad.data, pair.bad.bw, vt, C, pair.bad.nlev)
+    assert res.index == O.select(l, g)[0]
+    fast = pair.acquire(C)
+    assert fast.index == res.index
+    assert (fast.score, fast.pdf_l, fast.pdf_g) == (res.score, res.pdf_l, res.pdf_g)
+
+
 def test_fast_instance_extreme_categorical_bandwidths(device):
     """The acquisition's FAST instance (one-hot lo parts in the bound) where the categorical deltas are
     large and far from f16 values: bandwidths from 1e-3 to 0.7 on 8 four-level dims (|delta| up to
