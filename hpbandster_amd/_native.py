@@ -31,6 +31,8 @@ SIGNATURES = {
     "hbx_seg_argsort": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "hbx_kde_fit": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                             c_vp, c_vp]),
+    "hbx_kde_fit_r": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                              c_vp, c_vp, c_vp]),
     "hbx_kde_bucket": (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp]),
     "hbx_kde_table_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "hbx_kde_prepare": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
@@ -41,6 +43,11 @@ SIGNATURES = {
     "hbx_kde_refit_sync": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, ctypes.c_double,
                                    ctypes.c_double, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
                                    c_vp, c_vp]),
+    "hbx_kde_refit_r": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, ctypes.c_double,
+                                ctypes.c_double, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "hbx_kde_refit_sync_r": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, ctypes.c_double,
+                                     ctypes.c_double, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                     c_vp, c_vp, c_vp]),
     "hbx_stream_order": (c_i32, [c_vp, c_vp]),
     "hbx_kde_logpdf": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "hbx_kde_workspace_bytes": (c_i64, [c_i64, c_i64]),
@@ -49,6 +56,7 @@ SIGNATURES = {
                                  c_i64]),
     "hbx_kde_acquire_bound": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "hbx_kde_pair_free": (None, [c_vp]),
+    "hbx_kde_pair_set_rules": (c_i32, [c_vp, c_vp]),
     "hbx_kde_batch_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "hbx_kde_acquire_batch": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "hbx_kde_topk_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64]),
@@ -60,9 +68,13 @@ SIGNATURES = {
     "hbx_kde_groups_batch_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i32]),
     "hbx_kde_acquire_groups_batch": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                              c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_kde_acquire_groups_batch_r": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "hbx_kde_groups_topk_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "hbx_kde_acquire_groups_topk": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_kde_acquire_groups_topk_r": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "hbx_kde_logpdf_groups_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
     "hbx_kde_logpdf_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_i64, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
@@ -76,6 +88,10 @@ SIGNATURES = {
     "hbx_kde_propose_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
                                        ctypes.c_uint32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_kde_propose_groups_r": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
+                                         ctypes.c_uint32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                         c_vp]),
     "hbx_philox4x32_10": (c_i32, [c_vp, c_vp, c_vp]),
     "hbx_kde_sample": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_uint64,
                                ctypes.c_uint64, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp, c_vp]),
@@ -127,6 +143,37 @@ SIGNATURES = {
     "hbx_bohb_draw": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, ctypes.c_double, c_i64, c_vp, c_vp, c_vp, c_vp,
                               c_vp, c_vp, c_vp]),
 }
+
+# the acquisition rules (hbx_rules, include/hbx.h): the reference snapshot's values, and their accepted ranges
+PDF_FLOOR_DEFAULT = 1e-8
+PDF_FLOOR_MIN = 1e-100
+
+
+class Rules(ctypes.Structure):
+    _fields_ = [("pdf_floor", ctypes.c_double), ("min_bandwidth", ctypes.c_double)]
+
+
+def check_pdf_floor(f):
+    """``pdf_floor`` as a float; ValueError unless finite and in [1e-100, 1]."""
+    f = float(f)
+    if not (PDF_FLOOR_MIN <= f <= 1.0):  # (NaN and inf fail both comparisons)
+        raise ValueError("pdf_floor must be finite and in [1e-100, 1], got %r" % (f,))
+    return f
+
+
+def check_min_bandwidth(m):
+    """``min_bandwidth`` as a float (None -> 0.0, the no-op); ValueError unless finite and >= 0."""
+    m = 0.0 if m is None else float(m)
+    if not (0.0 <= m < float("inf")):
+        raise ValueError("min_bandwidth must be finite and >= 0 (or None), got %r" % (m,))
+    return m
+
+
+def rules(pdf_floor=PDF_FLOOR_DEFAULT, min_bandwidth=None):
+    """An hbx_rules block for a rules-taking entry point (pass ``ctypes.addressof`` of it, and keep it alive
+    over the call); the ranges are checked here, as the library checks them."""
+    return Rules(check_pdf_floor(pdf_floor), check_min_bandwidth(min_bandwidth))
+
 
 # tie order of the sorts (include/hbx.h): numpy's unstable argsort (the reference's) or by position
 ORDER_NUMPY = 0

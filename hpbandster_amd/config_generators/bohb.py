@@ -7,7 +7,7 @@ reference's order), so a seeded run proposes the same configurations.  What move
 * ``new_result``: the per-budget refit (argsort of the losses, good/bad split, normal-reference
   bandwidths, observed level counts -- bohb.py:220-246) runs in libhbx.so (``kde.fit_pair``);
 * ``get_config``: the ``num_samples`` candidates are scored against l (good) and g (bad) and the
-  first index of min max(1e-8, g)/max(l, 1e-8) is selected exactly (bohb.py:124-161) by
+  first index of min max(f, g)/max(l, f) (f = ``pdf_floor``, 1e-8 by default) is selected exactly (bohb.py:124-161) by
   ``KDEPair.acquire`` -- fp32 matrix-core scoring of every candidate, fp64 re-score of the ones that
   can still be the minimum.
 
@@ -75,8 +75,15 @@ class SpeculativeBatch(object):
 class BOHB(base_config_generator):
     def __init__(self, configspace, min_points_in_model=None, top_n_percent=15, num_samples=64,
                  random_fraction=1 / 3, bandwidth_factor=3, device=None, sampler="host", sampler_seed=None,
-                 speculative="auto", **kwargs):
+                 speculative="auto", min_bandwidth=None, pdf_floor=_native.PDF_FLOOR_DEFAULT, **kwargs):
         super().__init__(**kwargs)
+        # the two acquisition rules that releases of the package changed after the reference snapshot (include/hbx.h,
+        # hbx_rules): min_bandwidth -- every fitted bandwidth becomes np.clip(bw, min_bandwidth, None) (None: no
+        # clip, the snapshot's; the releases' constructor default is 1e-3) -- and pdf_floor, the f of the score
+        # max(f, g) / max(l, f) (1e-8: the snapshot's; the releases use 1e-32).  Every model this generator fits
+        # carries both: its samplers read the clipped bandwidths, its acquisitions form their scores under the floor.
+        self.min_bandwidth = _native.check_min_bandwidth(min_bandwidth)
+        self.pdf_floor = _native.check_pdf_floor(pdf_floor)
         # speculative batches (SuccessiveHalving serving a stage's back-to-back requests from one batched
         # acquisition): 'auto' = with the GPU sampler only (the host sampler's scipy draws cost ~100x the
         # acquisition, so batching them gains nothing and risks drawing for calls never served),
@@ -430,7 +437,8 @@ class BOHB(base_config_generator):
         if len(self.configs[budget]) <= self.min_points_in_model + 1:
             return
         # one refit call: the new row to the device, argsort, split, bandwidths, both KDEs prepared
-        pair = store.refit(self.min_points_in_model, self.top_n_percent)
+        pair = store.refit(self.min_points_in_model, self.top_n_percent, min_bandwidth=self.min_bandwidth,
+                           pdf_floor=self.pdf_floor)
         if pair is None:  # bohb.py:234-237: too few rows for a KDE
             return
         self.kde_models[budget] = pair  # atomic swap: a concurrent get_config keeps its snapshot

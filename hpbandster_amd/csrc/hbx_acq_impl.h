@@ -19,17 +19,17 @@ __device__ __forceinline__ void est_interval(const KdeEst e, float* lo, float* h
   *lo = (S - E) > 0.f ? m + __logf(S - E) - 1e-6f * fabsf(m) - 1e-5f : -INFINITY;
 }
 
-// Interval [slo, shi] of ln(max(1e-8, g) / max(l, 1e-8)) (bohb.py:129) of one candidate from its two
-// estimates a (l) and b (g), with the ln-pdf point estimates.
-//   lnan: l is NaN -> max(l, 1e-8) is NaN -> the score is NaN (never selected); slo = shi = NaN
+// Interval [slo, shi] of ln(max(f, g) / max(l, f)) (bohb.py:129; f: the score floor F, 1e-8 in the reference
+// snapshot) of one candidate from its two estimates a (l) and b (g), with the ln-pdf point estimates.
+//   lnan: l is NaN -> max(l, f) is NaN -> the score is NaN (never selected); slo = shi = NaN
 //   of:   a pdf's upper bound is past fp64's exp range: the intervals of this call cannot be trusted
-//   one:  both factors are certainly clamped: the score is exactly 1e-8 / 1e-8 = 1, slo = shi = 0
+//   one:  both factors are certainly clamped: the score is exactly f / f = 1 for every f, slo = shi = 0
 struct ScoreIv {
   float slo, shi, lpt, gpt;
   bool lnan, of, one;
 };
-__device__ __forceinline__ ScoreIv score_interval(const KdeEst a, const KdeEst b) {
-  const float C = (float)HBX_LN_CLAMP;
+__device__ __forceinline__ ScoreIv score_interval(const KdeEst a, const KdeEst b, const ScoreFloor F) {
+  const float C = F.C;
   ScoreIv v;
   v.of = false;
   v.one = false;
@@ -44,7 +44,7 @@ __device__ __forceinline__ ScoreIv score_interval(const KdeEst a, const KdeEst b
   }
   est_interval(a, &llo, &lhi, &v.lpt);
   float Glo, Ghi;
-  if (b.lpos != b.lpos) {  // g NaN -> max(1e-8, g) == 1e-8
+  if (b.lpos != b.lpos) {  // g NaN -> max(f, g) == f
     Glo = Ghi = C;
     v.gpt = NAN;
   } else {
@@ -54,9 +54,9 @@ __device__ __forceinline__ ScoreIv score_interval(const KdeEst a, const KdeEst b
     v.of = ghi > 700.f;
   }
   v.of = v.of || lhi > 700.f;
-  v.slo = Glo - fmaxf(lhi, C);
-  v.shi = Ghi - fmaxf(llo, C);
-  const float C1 = C - 1e-4f;  // margin for the rounding of ln(1e-8) to float
+  v.slo = Glo - fmaxf(lhi, C) - F.w;
+  v.shi = Ghi - fmaxf(llo, C) + F.w;
+  const float C1 = F.C1;  // C less the margin for the rounding of ln f to float (ScoreFloor)
   if (lhi < C1 && (b.lpos != b.lpos || ghi < C1)) {  // both clamped: score exactly 1 (ln 0)
     v.one = true;
     v.slo = v.shi = 0.f;
@@ -66,11 +66,11 @@ __device__ __forceinline__ ScoreIv score_interval(const KdeEst a, const KdeEst b
 
 // The staged acquisition (hbx_staged.hip) did not evaluate g for this candidate: err of its a.eg entry (distinct
 // from the rescue marker -1 and exact-only's -2).  Its score interval from l alone: whatever g is,
-// max(1e-8, g) >= 1e-8, so slo = C - max(lhi, C); no upper end (shi = +inf never lowers U), never a certain
+// max(f, g) >= f, so slo = C - max(lhi, C) (less F.w); no upper end (shi = +inf never lowers U), never a certain
 // tie.  lnan and of come from l as in score_interval.
 #define HBX_EST_NOT_EVAL (-3.f)
-__device__ __forceinline__ ScoreIv score_interval_l_only(const KdeEst a) {
-  const float C = (float)HBX_LN_CLAMP;
+__device__ __forceinline__ ScoreIv score_interval_l_only(const KdeEst a, const ScoreFloor F) {
+  const float C = F.C;
   ScoreIv v;
   v.of = false;
   v.one = false;
@@ -84,7 +84,7 @@ __device__ __forceinline__ ScoreIv score_interval_l_only(const KdeEst a) {
   float llo, lhi;
   est_interval(a, &llo, &lhi, &v.lpt);
   v.of = lhi > 700.f;
-  v.slo = C - fmaxf(lhi, C);
+  v.slo = C - fmaxf(lhi, C) - F.w;
   v.shi = INFINITY;
   return v;
 }
@@ -121,11 +121,11 @@ __device__ __forceinline__ KdeEst merge_splits(const KdeEst* __restrict__ e, int
   return a;
 }
 
-// bohb.py:129 with Python max(): max(1e-8, g) keeps 1e-8 unless g > 1e-8 (NaN -> 1e-8); max(l, 1e-8)
-// keeps l unless 1e-8 > l (NaN -> NaN).  Scores are > 0 or NaN (both factors are clamped to >= 1e-8), so
-// the bits of a non-NaN score order like the score.
-__device__ __forceinline__ double bohb_score(double g, double l) {
-  return ((g > 1e-8) ? g : 1e-8) / ((1e-8 > l) ? 1e-8 : l);
+// bohb.py:129 with Python max() and the score floor f: max(f, g) keeps f unless g > f (NaN -> f); max(l, f)
+// keeps l unless f > l (NaN -> NaN).  Scores are >= 0 or NaN (the numerator is >= f > 0; an l of +inf gives +0,
+// g = l = inf gives NaN), so the bits of a non-NaN score order like the score.
+__device__ __forceinline__ double bohb_score(double g, double l, double f) {
+  return ((g > f) ? g : f) / ((f > l) ? f : l);
 }
 
 // Bound of |exact pdf here - pdf in numpy's arithmetic| / pdf for one KDE at one candidate.  Both run

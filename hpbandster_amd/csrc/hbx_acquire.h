@@ -19,6 +19,7 @@ struct KdePairRef {
   const int64_t* rows_bad;
   int32_t variant_bad, dc_pad, du_pad;
   int64_t nmax;
+  ScoreFloor floor;  // the score floor of every acquisition on the handle (hbx_kde_pair_set_rules)
   const KdeParams* Pg() const { return (const KdeParams*)params_good; }
   const KdeParams* Pb() const { return (const KdeParams*)params_bad; }
 };

@@ -64,15 +64,15 @@ struct KdeParams {
   int32_t D;          // total dims
   int32_t dc;         // continuous dims
   int32_t du;         // active categorical dims (num_levels > 1)
-  int32_t nconst;     // categorical dims with a single observed level (bw == 0)
+  int32_t nconst;     // categorical dims with a single observed level (bw == 0; or bw > 0 and finite: exact_only)
   int32_t nan_all;    // a continuous bandwidth is 0 -> reference pdf is NaN everywhere
   int32_t has_neg;    // some active categorical dim has 1 - h < 0 (signed sums needed)
   int32_t unsupported;// bandwidth/level combination the engine does not model (error)
   int32_t stride;     // floats per observation row of the fp32 table
   int32_t dc_pad;     // continuous slots in the table (template bucket)
   int32_t du_pad;     // categorical slots in the table (template bucket)
-  int32_t exact_only; // no fp32 scoring bucket fits (> 64 continuous / > 32 categorical dims): every
-                      // candidate is re-scored in fp64 (variant bit 5)
+  int32_t exact_only; // no fp32 scoring bucket fits (> 64 continuous / > 32 categorical dims), or a single-level
+                      // categorical dim has bw > 0: every candidate is re-scored in fp64 (variant bit 5)
   double log_norm;    // ln pdf = ln(S) + log_norm  (S = sum of 2^(t - M0))
   double m0_log2;     // M0: upper bound of the per-pair log2 kernel product
   double lb_sum;      // sum over active categorical dims of log2(h/(c-1))
@@ -141,7 +141,7 @@ struct KdeEst {
 // multi-GPU winner exchange needs.
 struct AcqResult {
   int64_t index;     // winning candidate (global index), -1 when no finite score exists
-  double score;      // its exact fp64 score max(1e-8, g) / max(l, 1e-8)
+  double score;      // its exact fp64 score max(f, g) / max(l, f), f the score floor
   float rel;         // bound of |score - score in numpy's arithmetic| / score (exp may differ by ulps)
   int32_t flags;     // HBX_ACQ_* bits
   int32_t shortlist; // candidates re-scored in fp64

@@ -1,7 +1,7 @@
 // hbx_dist.hip -- the multi-GPU winner exchange of a candidate-sharded acquisition.
 //
 // Reference loop being sharded: bohb.py:133-152 (one get_config scores num_samples candidates and
-// keeps the first index of the smallest max(1e-8, g)/max(l, 1e-8)).  Candidates are independent, so
+// keeps the first index of the smallest max(f, g)/max(l, f), every rank under the same score floor f).  Candidates are independent, so
 // each GPU scores a contiguous shard with global indices (hbx_kde_acquire's index_base) and the only
 // collective is here: one RCCL all-gather over xGMI of every rank's 48-byte result record, reduced on
 // the device by (score, index) -- the smallest score, ties to the smallest global index, which is the

@@ -460,13 +460,18 @@ int refit_sort_small(double* X, double* loss, const double* staged, const double
   return HBX_OK;
 }
 
+// hbx_rules.min_bandwidth m on the value a fit kernel is about to store: np.clip(bw, m, None) -- NaN stays NaN, and
+// m = 0 changes nothing (a fitted bandwidth is never negative).  Everything downstream (the refit's output block, the
+// parameter block and tables, the samplers, the exact re-score) reads the stored, clipped value.
+__device__ __forceinline__ double fit_clip(double bw, double m) { return bw < m ? m : bw; }
+
 // one thread per (segment, set in {good, bad}, dim): bandwidth and observed level count
 __global__ __launch_bounds__(128) void kde_fit_stats_kernel(
     const double* __restrict__ X, int32_t D, const int64_t* __restrict__ seg_off, int64_t B,
     const int64_t* __restrict__ order, const int64_t* __restrict__ n_good, const int64_t* __restrict__ n_bad,
     const double* __restrict__ fac_good, const double* __restrict__ fac_bad, const int32_t* __restrict__ vartype,
     double* __restrict__ bw_good, double* __restrict__ bw_bad, int32_t* __restrict__ nlev_good,
-    int32_t* __restrict__ nlev_bad) {
+    int32_t* __restrict__ nlev_bad, double min_bw) {
   __shared__ uint32_t bits[128][33];  // 1024-level bitmap per thread (+1 pad: bank spread)
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t total = B * 2 * D;
@@ -491,7 +496,7 @@ __global__ __launch_bounds__(128) void kde_fit_stats_kernel(
   const double mean = np_sum_column(Xs, D, d, ord, ns, 0.0, false) / (double)ns;
   const double var = np_sum_column(Xs, D, d, ord, ns, mean, true) / (double)ns;
   const double sd = sqrt(var);
-  *bwo = (1.06 * sd) * (good ? fac_good[b] : fac_bad[b]);
+  *bwo = fit_clip((1.06 * sd) * (good ? fac_good[b] : fac_bad[b]), min_bw);
   if (vartype[d] == 0) {
     *nlo = 0;
     return;
@@ -570,7 +575,7 @@ __global__ __launch_bounds__(256) void kde_fit_col_kernel(
     const int64_t* __restrict__ order, const int64_t* __restrict__ n_good, const int64_t* __restrict__ n_bad,
     const double* __restrict__ fac_good, const double* __restrict__ fac_bad, const int32_t* __restrict__ vartype,
     double* __restrict__ bw_good, double* __restrict__ bw_bad, int32_t* __restrict__ nlev_good,
-    int32_t* __restrict__ nlev_bad, ColStats* __restrict__ cs_good, ColStats* __restrict__ cs_bad) {
+    int32_t* __restrict__ nlev_bad, ColStats* __restrict__ cs_good, ColStats* __restrict__ cs_bad, double min_bw) {
   __shared__ double v[FIT_TILE];
   __shared__ uint32_t bits[32];
   __shared__ double red;
@@ -665,7 +670,7 @@ __global__ __launch_bounds__(256) void kde_fit_col_kernel(
   }
   if (threadIdx.x == 0) {
     const double var = acc / (double)ns;
-    *bwo = (1.06 * sqrt(var)) * (good ? fac_good[b] : fac_bad[b]);
+    *bwo = fit_clip((1.06 * sqrt(var)) * (good ? fac_good[b] : fac_bad[b]), min_bw);
     int cnt = 0;
     if (cat) {
       for (int w = 0; w < 32; ++w) cnt += __popc(bits[w]);
@@ -692,7 +697,7 @@ __global__ __launch_bounds__(256) void kde_fit_wave_kernel(
     const int64_t* __restrict__ order, const int64_t* __restrict__ n_good, const int64_t* __restrict__ n_bad,
     const double* __restrict__ fac_good, const double* __restrict__ fac_bad, const int32_t* __restrict__ vartype,
     double* __restrict__ bw_good, double* __restrict__ bw_bad, int32_t* __restrict__ nlev_good,
-    int32_t* __restrict__ nlev_bad) {
+    int32_t* __restrict__ nlev_bad, double min_bw) {
   constexpr int U = FIT_WAVE_U;
   const int64_t per_set = B * (int64_t)D;
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -771,7 +776,7 @@ __global__ __launch_bounds__(256) void kde_fit_wave_kernel(
   };
   const double mean = pass(std::false_type{}, 0.0) / (double)ns;
   const double var = pass(std::true_type{}, mean) / (double)ns;
-  *bwo = (1.06 * sqrt(var)) * (set ? fac_bad[b] : fac_good[b]);
+  *bwo = fit_clip((1.06 * sqrt(var)) * (set ? fac_bad[b] : fac_good[b]), min_bw);
   int32_t cnt = 0;
   if (cat) {
     cnt = __popcll(m0) + __popcll(m1);
@@ -886,6 +891,17 @@ int hbx_kde_fit(const double* X, int32_t D, const int64_t* seg_off, int64_t B, c
                 const int64_t* n_good, const int64_t* n_bad, const double* fac_good, const double* fac_bad,
                 const int32_t* vartype, double* bw_good, double* bw_bad, int32_t* nlev_good, int32_t* nlev_bad,
                 void* stream) {
+  return hbx_kde_fit_r(X, D, seg_off, B, order, n_good, n_bad, fac_good, fac_bad, vartype, bw_good, bw_bad, nlev_good,
+                       nlev_bad, stream, nullptr);
+}
+
+// hbx_kde_fit with every bandwidth clipped from below at rules->min_bandwidth (NULL: no clip)
+int hbx_kde_fit_r(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                  const int64_t* n_good, const int64_t* n_bad, const double* fac_good, const double* fac_bad,
+                  const int32_t* vartype, double* bw_good, double* bw_bad, int32_t* nlev_good, int32_t* nlev_bad,
+                  void* stream, const hbx_rules* rules) {
+  if (const int rc = hbx_rules_check("hbx_kde_fit", rules)) return rc;
+  const double min_bw = rules ? rules->min_bandwidth : 0.0;
   if (!X || !seg_off || !order || !n_good || !n_bad || !fac_good || !fac_bad || !vartype || !bw_good ||
       !bw_bad || !nlev_good || !nlev_bad)
     return hbx_fail(HBX_ERR_ARG, "hbx_kde_fit: null pointer");
@@ -896,15 +912,15 @@ int hbx_kde_fit(const double* X, int32_t D, const int64_t* seg_off, int64_t B, c
     if ((total + 255) / 256 > 0x7fffffffLL) return hbx_fail(HBX_ERR_ARG, "hbx_kde_fit: too many segments");
     hipLaunchKernelGGL(kde_fit_wave_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        X, D, seg_off, B, order, n_good, n_bad, fac_good, fac_bad, vartype, bw_good, bw_bad,
-                       nlev_good, nlev_bad);
+                       nlev_good, nlev_bad, min_bw);
   } else if (D > 1 && total < 16384) {  // few columns: one workgroup each (LDS-staged gathers)
     hipLaunchKernelGGL(kde_fit_col_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, X, D, seg_off,
                        order, n_good, n_bad, fac_good, fac_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad,
-                       (ColStats*)nullptr, (ColStats*)nullptr);
+                       (ColStats*)nullptr, (ColStats*)nullptr, min_bw);
   } else {
     hipLaunchKernelGGL(kde_fit_stats_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0,
                        (hipStream_t)stream, X, D, seg_off, B, order, n_good, n_bad, fac_good, fac_bad, vartype,
-                       bw_good, bw_bad, nlev_good, nlev_bad);
+                       bw_good, bw_bad, nlev_good, nlev_bad, min_bw);
   }
   HBX_LAUNCH_CHECK();
   return HBX_OK;
@@ -917,9 +933,9 @@ int hbx_kde_fit(const double* X, int32_t D, const int64_t* seg_off, int64_t B, c
 int refit_fit_colstats(const double* X, int32_t D, const int64_t* seg_off, const int64_t* order, const int64_t* n_good,
                        const int64_t* n_bad, const double* fac_good, const double* fac_bad, const int32_t* vartype,
                        double* bw_good, double* bw_bad, int32_t* nlev_good, int32_t* nlev_bad, ColStats* cs_good,
-                       ColStats* cs_bad, hipStream_t s) {
+                       ColStats* cs_bad, double min_bw, hipStream_t s) {
   hipLaunchKernelGGL(kde_fit_col_kernel, dim3((unsigned)(2 * D)), dim3(256), 0, s, X, D, seg_off, order, n_good, n_bad,
-                     fac_good, fac_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad, cs_good, cs_bad);
+                     fac_good, fac_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad, cs_good, cs_bad, min_bw);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }

@@ -33,12 +33,12 @@
 //
 // Launch 2, groups_select_kernel: one block per group (per request, below).  U = min shi over the certified candidates; the shortlist
 //   is {slo <= U} plus the uncertified ones, and of the candidates whose score is certainly exactly 1 (both pdfs
-//   certainly below the 1e-8 clamps) only the first index.  Every shortlisted candidate gets both exact fp64 pdfs
+//   certainly below the score floor, GrpArgs.F) only the first index.  Every shortlisted candidate gets both exact fp64 pdfs
 //   in the reference's arithmetic (hbx_exact_impl.h: the single path's functions, fed a per-group parameter view),
 //   then bohb_score, the strict argmin by (score, index), near_best and the record.  A group is exact-only (every
 //   candidate re-scored, HBX_ACQ_OVERFLOW) when a continuous bandwidth is not a positive finite number, a
-//   categorical dim has a single level (c == 1, h == 0), the dims exceed the bucket, or a pdf bound leaves fp64's
-//   exp range.  Correctness never rests on the screen: it only decides what is re-scored.
+//   categorical dim has a single level (c == 1; h == 0, or h > 0 and finite), the dims exceed the bucket, or a pdf bound
+//   leaves fp64's exp range.  Correctness never rests on the screen: it only decides what is re-scored.
 //   The exact scores are kept in the candidates' GScreen slots for the near-tie count (no second buffer).
 //
 // S requests per group (hbx_kde_acquire_groups_batch; bohb.py:124-169 once per get_config call of a stage,
@@ -103,13 +103,26 @@ struct GrpArgs {
   int32_t slabs;     // tile screen: blocks per group, one tile per wave
   GScreen* scr;
   AcqResult* res;
+  ScoreFloor F;      // the call's score floor (hbx_rules.pdf_floor), read by the kernels' <.., DEFF = false> instances
 };
+
+// The call's score floor in a kernel.  DEFF: the reference snapshot's 1e-8 as compile-time constants
+// (hbx_score_floor(1e-8)'s values) -- the default path's kernels are then instruction for instruction what they were
+// before the floor became a parameter (read from the arguments, the same arithmetic measured 0.5 % slower on the
+// grouped benchmark: another register allocation of the screen, profiles/rules/README.md); else the launch argument.
+template <bool DEFF>
+__device__ __forceinline__ ScoreFloor grp_floor(const GrpArgs& A) {
+  if constexpr (DEFF)
+    return ScoreFloor{HBX_PDF_FLOOR_DEFAULT, (float)HBX_LN_CLAMP, (float)HBX_LN_CLAMP - 1e-4f, 0.f};
+  else
+    return A.F;
+}
 
 // the dispatch's call: this lane's candidate against jmax staged rows, piece counts (QC, QU), signed or not
 #define GRP_PAIRS_CALL(QC, QU, SG) \
   grp_pairs<DCP, DUP, QC, QU, SG>(srows, L.rs, jmax, L.dcq, L.duq, xc, xu, dl, nf, lbs, m, sp, sn)
 
-template <int DCP, int DUP, int NW, int DT>
+template <int DCP, int DUP, int NW, int DT, bool DEFF>
 __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
   constexpr int NT = 64 * NW;
   __shared__ __align__(16) float sobs[NW * 64 * (DT + 4)];
@@ -222,7 +235,7 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
       est_g = e;
     __syncthreads();  // (s_pm, s_bmax are rewritten for the bad KDE)
   }
-  if (wave == 0 && valid) *out = grp_emit(D, st, certified, est_l, est_g);
+  if (wave == 0 && valid) *out = grp_emit(D, st, certified, est_l, est_g, grp_floor<DEFF>(A));
 }
 
 // The tile screen (header: "The tile screen"): the block is a slab of NW tiles of one group, wave w owns tile
@@ -237,7 +250,7 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
 // for groups_screen_kernel (before: 165 / 196 / 255 / 256) and 190 / 219 / 235 / 256 for this kernel (180 / 209 / 224 /
 // 256), every one at the waves per SIMD it had (3 / 2 / 2 / 1 and 2 / 2 / 2 / 1), no scratch.  The one step that
 // groups_screen_kernel does not take from the header is the candidate's load (the comment there has the numbers).
-template <int DCP, int DUP, int NW, int DT>
+template <int DCP, int DUP, int NW, int DT, bool DEFF>
 __global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kernel(GrpArgs A) {
   constexpr int NT = 64 * NW;
   __shared__ __align__(16) float sobs[NW * 64 * (DT + 4)];
@@ -326,7 +339,7 @@ __global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kerne
     if (kd == 0)
       est_l = e;
     else if (vw)
-      A.scr[b * A.P + iw] = grp_emit(D, st, certified, est_l, e);
+      A.scr[b * A.P + iw] = grp_emit(D, st, certified, est_l, e, grp_floor<DEFF>(A));
   }
 }
 #undef GRP_PAIRS_CALL
@@ -342,6 +355,7 @@ __device__ __forceinline__ AcqResult grp_empty_record(int32_t flags) {
   return r;
 }
 
+template <bool DEFF>
 __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs A) {
   __shared__ ExactShared sh;
   __shared__ GrpView vw[2];
@@ -420,7 +434,7 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
       double l, g;
       grp_exact_both(vw, D, cand + ip * D, Xs, rows_g, rows_b, &sh, &l, &g);
       if (tid == 0) {
-        const double s = bohb_score(g, l);
+        const double s = bohb_score(g, l, grp_floor<DEFF>(A).f);
         scr[ip].score = s;
         scr[ip].fl |= GS_DONE;
         if (s < best) {  // index order: strict '<' keeps the first index (bohb.py:149-152; NaN never wins)
@@ -525,6 +539,7 @@ static int grp_topk_cap(int32_t k) {
 }
 static_assert(HBX_TOPK_MAX_K + 1 + GRP_SEL_THREADS <= 2048, "a chunk fits behind the kept entries after a merge");
 
+template <bool DEFF>
 __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_topk_kernel(GrpArgs A, GrpTopk K) {
   constexpr int T = GRP_SEL_THREADS;
   extern __shared__ __align__(16) unsigned char s_dyn[];  // the ranking's arrays: cap x (u64, i32, i32)
@@ -681,7 +696,7 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_topk_kernel(GrpArgs A,
       const double l = s_l[tid], gd = s_g[tid];
       idx = (int32_t)(c0 + slist[tid]);
       pdf[idx] = make_double2(l, gd);
-      const double s = bohb_score(gd, l);
+      const double s = bohb_score(gd, l, grp_floor<DEFF>(A).f);
       if (s == s) {  // NaN scores are never returned
         key = (uint64_t)__double_as_longlong(s);
         acc = rank.enters(key, idx);
@@ -746,27 +761,40 @@ static bool grp_tile_screen(int64_t S, int64_t tiles) {
   return tiles >= GRP_TILES_MIN;
 }
 
+// the snapshot's floor: the kernels' constant instances (grp_floor)
+static bool grp_floor_default(const ScoreFloor& F) { return F.f == HBX_PDF_FLOOR_DEFAULT; }
+
 // One screen launch: the bucket's instance (grp_model picked the bucket from D alone)
 template <bool TILES>
 static void grp_launch_screen(GrpArgs& A, hipStream_t s) {
   const int nw = A.M.D <= 32 ? 4 : 2;  // waves of the bucket's instance
   A.slabs = (A.tiles + nw - 1) / nw;  // the tile screen: one tile per wave
   const dim3 grid((unsigned)(A.M.B * (TILES ? A.slabs : A.tiles)));  // <= B * S * C <= INT32_MAX
-#define GRP_LAUNCH(DCP, DUP, NW, DT)                                                              \
-  do {                                                                                            \
-    if (TILES)                                                                                    \
-      hipLaunchKernelGGL((groups_tiles_kernel<DCP, DUP, NW, DT>), grid, dim3(64 * NW), 0, s, A);  \
-    else                                                                                          \
-      hipLaunchKernelGGL((groups_screen_kernel<DCP, DUP, NW, DT>), grid, dim3(64 * NW), 0, s, A); \
+#define GRP_LAUNCH_F(DCP, DUP, NW, DT, DEFF)                                                            \
+  do {                                                                                                  \
+    if (TILES)                                                                                          \
+      hipLaunchKernelGGL((groups_tiles_kernel<DCP, DUP, NW, DT, DEFF>), grid, dim3(64 * NW), 0, s, A);  \
+    else                                                                                                \
+      hipLaunchKernelGGL((groups_screen_kernel<DCP, DUP, NW, DT, DEFF>), grid, dim3(64 * NW), 0, s, A); \
+  } while (0)
+#define GRP_LAUNCH(DCP, DUP, NW, DT)       \
+  do {                                     \
+    if (grp_floor_default(A.F))            \
+      GRP_LAUNCH_F(DCP, DUP, NW, DT, true); \
+    else                                   \
+      GRP_LAUNCH_F(DCP, DUP, NW, DT, false); \
   } while (0)
   GRP_BUCKET_LAUNCH(A.M.D, GRP_LAUNCH);
 #undef GRP_LAUNCH
+#undef GRP_LAUNCH_F
 }
 
 // the argument block of one call: the model, the pools, the screen slots behind the workspace's head
-static GrpArgs grp_args(const GrpModel& M, const double* cand, int64_t S, int64_t C, void* results, void* workspace) {
+static GrpArgs grp_args(const GrpModel& M, const ScoreFloor& F, const double* cand, int64_t S, int64_t C, void* results,
+                        void* workspace) {
   GrpArgs A;
   A.M = M;
+  A.F = F;
   A.cand = cand;
   A.S = S;
   A.C = C;
@@ -779,8 +807,18 @@ static GrpArgs grp_args(const GrpModel& M, const double* cand, int64_t S, int64_
 }
 
 // hbx_kde_acquire_groups (S = 1) and hbx_kde_acquire_groups_batch: the checks, the screen, the select
-static int grp_acquire(const char* who, const GrpModel& M, const double* cand, int64_t S, int64_t C, void* results,
-                       void* workspace, int64_t ws_bytes, void* stream) {
+// the score floor of an entry point's rules (NULL: the reference snapshot's); HBX_ERR_ARG out of range
+static int grp_rules_floor(const char* who, const hbx_rules* rules, ScoreFloor* F) {
+  const int rc = hbx_rules_check(who, rules);
+  if (rc) return rc;
+  *F = hbx_score_floor(rules ? rules->pdf_floor : HBX_PDF_FLOOR_DEFAULT);
+  return HBX_OK;
+}
+
+static int grp_acquire(const char* who, const GrpModel& M, const hbx_rules* rules, const double* cand, int64_t S,
+                       int64_t C, void* results, void* workspace, int64_t ws_bytes, void* stream) {
+  ScoreFloor F;
+  if (const int rc = grp_rules_floor(who, rules, &F)) return rc;
   const int64_t B = M.B;
   if (const int rc = grp_check_dim(who, M.D)) return rc;
   if (B < 0 || S < 0 || C < 0)
@@ -803,20 +841,23 @@ static int grp_acquire(const char* who, const GrpModel& M, const double* cand, i
     return hbx_fail(HBX_ERR_ARG, "%s: workspace too small: %lld < %lld bytes", who, (long long)ws_bytes, (long long)need);
   if (((uintptr_t)workspace & 15) || ((uintptr_t)results & 7))
     return hbx_fail(HBX_ERR_ARG, "%s: workspace must be 16-byte, results 8-byte aligned", who);
-  GrpArgs A = grp_args(M, cand, S, C, results, workspace);
+  GrpArgs A = grp_args(M, F, cand, S, C, results, workspace);
   if (grp_tile_screen(S, A.tiles))
     grp_launch_screen<true>(A, s);
   else
     grp_launch_screen<false>(A, s);
   HBX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(groups_select_kernel, dim3((unsigned)(B * S)), dim3(GRP_SEL_THREADS), 0, s, A);
+  hipLaunchKernelGGL(grp_floor_default(F) ? groups_select_kernel<true> : groups_select_kernel<false>,
+                     dim3((unsigned)(B * S)), dim3(GRP_SEL_THREADS), 0, s, A);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }
 
 // hbx_kde_acquire_groups_topk: grp_acquire's checks with S = 1, the same screen, groups_topk_kernel as the select
-static int grp_acquire_topk(const char* who, const GrpModel& M, const double* cand, int64_t C, int32_t k,
-                            void* results, void* workspace, int64_t ws_bytes, void* stream) {
+static int grp_acquire_topk(const char* who, const GrpModel& M, const hbx_rules* rules, const double* cand, int64_t C,
+                            int32_t k, void* results, void* workspace, int64_t ws_bytes, void* stream) {
+  ScoreFloor F;
+  if (const int rc = grp_rules_floor(who, rules, &F)) return rc;
   const int64_t B = M.B;
   if (const int rc = grp_check_dim(who, M.D)) return rc;
   if (B < 0 || C < 0) return hbx_fail(HBX_ERR_ARG, "%s: B=%lld C=%lld", who, (long long)B, (long long)C);
@@ -838,7 +879,7 @@ static int grp_acquire_topk(const char* who, const GrpModel& M, const double* ca
   if (ws_bytes < need)
     return hbx_fail(HBX_ERR_ARG, "%s: workspace too small: %lld < %lld bytes", who, (long long)ws_bytes, (long long)need);
   if ((uintptr_t)workspace & 15) return hbx_fail(HBX_ERR_ARG, "%s: workspace must be 16-byte aligned", who);
-  GrpArgs A = grp_args(M, cand, 1, C, nullptr, workspace);
+  GrpArgs A = grp_args(M, F, cand, 1, C, nullptr, workspace);
   GrpTopk K;
   K.out = (char*)results;
   K.pdf = (double2*)((char*)workspace + GRP_WS_HEAD + B * C * (int64_t)sizeof(GScreen));  // behind the screen slots
@@ -846,7 +887,8 @@ static int grp_acquire_topk(const char* who, const GrpModel& M, const double* ca
   K.cap = grp_topk_cap(k);
   grp_launch_screen<false>(A, s);
   HBX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(groups_topk_kernel, dim3((unsigned)B), dim3(GRP_SEL_THREADS), (size_t)K.cap * 16, s, A, K);
+  hipLaunchKernelGGL(grp_floor_default(F) ? groups_topk_kernel<true> : groups_topk_kernel<false>, dim3((unsigned)B),
+                     dim3(GRP_SEL_THREADS), (size_t)K.cap * 16, s, A, K);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }
@@ -869,7 +911,7 @@ int hbx_kde_acquire_groups(const double* X, int32_t D, const int64_t* seg_off, i
                            int64_t ws_bytes, void* stream) {
   return grp_acquire("hbx_kde_acquire_groups",
                      grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad),
-                     cand, 1, C, results, workspace, ws_bytes, stream);
+                     nullptr, cand, 1, C, results, workspace, ws_bytes, stream);
 }
 
 int hbx_kde_acquire_groups_batch(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
@@ -879,7 +921,17 @@ int hbx_kde_acquire_groups_batch(const double* X, int32_t D, const int64_t* seg_
                                  void* workspace, int64_t ws_bytes, void* stream) {
   return grp_acquire("hbx_kde_acquire_groups_batch",
                      grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad),
-                     cand, S, C, results, workspace, ws_bytes, stream);
+                     nullptr, cand, S, C, results, workspace, ws_bytes, stream);
+}
+
+int hbx_kde_acquire_groups_batch_r(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                   const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                   const double* bw_good, const double* bw_bad, const int32_t* nlev_good,
+                                   const int32_t* nlev_bad, const double* cand, int64_t S, int64_t C, void* results,
+                                   void* workspace, int64_t ws_bytes, void* stream, const hbx_rules* rules) {
+  return grp_acquire(rules ? "hbx_kde_acquire_groups_batch_r" : "hbx_kde_acquire_groups_batch",
+                     grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad),
+                     rules, cand, S, C, results, workspace, ws_bytes, stream);
 }
 
 // the grouped workspace (the screen slots) followed by the re-scored candidates' pdfs, 16 bytes per candidate: the
@@ -897,7 +949,17 @@ int hbx_kde_acquire_groups_topk(const double* X, int32_t D, const int64_t* seg_o
                                 void* workspace, int64_t ws_bytes, void* stream) {
   return grp_acquire_topk("hbx_kde_acquire_groups_topk",
                           grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad),
-                          cand, C, k, results, workspace, ws_bytes, stream);
+                          nullptr, cand, C, k, results, workspace, ws_bytes, stream);
+}
+
+int hbx_kde_acquire_groups_topk_r(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                  const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                  const double* bw_good, const double* bw_bad, const int32_t* nlev_good,
+                                  const int32_t* nlev_bad, const double* cand, int64_t C, int32_t k, void* results,
+                                  void* workspace, int64_t ws_bytes, void* stream, const hbx_rules* rules) {
+  return grp_acquire_topk("hbx_kde_acquire_groups_topk_r",
+                          grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad),
+                          rules, cand, C, k, results, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -151,7 +151,22 @@ int hbx_kde_propose_groups(const double* X, int32_t D, const int64_t* seg_off, i
                            uint64_t counter_base, uint32_t stream_id, int64_t S, int64_t C, double* rows_out,
                            uint8_t* source_out, void* records_out, double* cands_out, void* workspace,
                            int64_t workspace_bytes, void* stream) {
-  const char* who = "hbx_kde_propose_groups";
+  return hbx_kde_propose_groups_r(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad,
+                                  levels, bandwidth_factor, random_fraction, seed, counter_base, stream_id, S, C,
+                                  rows_out, source_out, records_out, cands_out, workspace, workspace_bytes, stream,
+                                  nullptr);
+}
+
+// the composition with hbx_kde_acquire_groups_batch_r in the middle: the requests' scores under rules->pdf_floor
+int hbx_kde_propose_groups_r(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                             const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype, const double* bw_good,
+                             const double* bw_bad, const int32_t* nlev_good, const int32_t* nlev_bad,
+                             const int32_t* levels, double bandwidth_factor, double random_fraction, uint64_t seed,
+                             uint64_t counter_base, uint32_t stream_id, int64_t S, int64_t C, double* rows_out,
+                             uint8_t* source_out, void* records_out, double* cands_out, void* workspace,
+                             int64_t workspace_bytes, void* stream, const hbx_rules* rules) {
+  const char* who = rules ? "hbx_kde_propose_groups_r" : "hbx_kde_propose_groups";
+  if (const int rrc = hbx_rules_check(who, rules)) return rrc;
   const int rc = cfg_check(who, D, B, S, C, random_fraction, levels, rows_out, source_out);
   if (rc) return rc < 0 ? rc : HBX_OK;
   if (!X || !seg_off || !order || !n_good || !n_bad || !vartype || !bw_good || !bw_bad || !nlev_good || !nlev_bad ||
@@ -172,8 +187,8 @@ int hbx_kde_propose_groups(const double* X, int32_t D, const int64_t* seg_off, i
   int r = hbx_kde_sample_groups(X, D, seg_off, B, order, n_good, bw_good, levels, bandwidth_factor, seed, counter_base,
                                 stream_id, S * C, pool, err, stream);
   if (r != HBX_OK) return r;
-  r = hbx_kde_acquire_groups_batch(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good,
-                                   nlev_bad, pool, S, C, rec, workspace, off[0], stream);
+  r = hbx_kde_acquire_groups_batch_r(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good,
+                                     nlev_bad, pool, S, C, rec, workspace, off[0], stream, rules);
   if (r != HBX_OK) return r;
   r = hbx_kde_finish_groups(rec, pool, err, levels, D, B, S, C, random_fraction, seed, counter_base, stream_id,
                             rows_out, source_out, stream);

@@ -133,8 +133,10 @@ __device__ __forceinline__ int grp_classify(const GrpModel& M, int64_t b, int* d
         if (!(h > 0.0 && h < INFINITY)) st |= GRP_EXACT(kd);  // pdf NaN (or 0) everywhere: the exact path says which
       } else {
         const int c = (kd ? M.nlev_bad : M.nlev_good)[b * M.D + d];
-        if (c == 1 && h == 0.0)
-          st |= GRP_EXACT(kd);  // one observed level: match -> 1, mismatch -> 0 / 0
+        if (c == 1 && (h == 0.0 || (h > 0.0 && h < INFINITY)))
+          // one observed level: match -> 1, mismatch -> 0 / 0; under a finite h > 0 (a fitted 0 clipped to
+          // hbx_rules.min_bandwidth): match -> 1 - h, mismatch -> h / 0 = +inf -- hbx_kde_prepare's rule
+          st |= GRP_EXACT(kd);
         else if (c < 2 || !(h > 0.0) || h != h)
           st |= GRP_UNSUPPORTED;  // (c == -1: codes not integers in [0, 1024))
         else if (!(h < INFINITY))
@@ -589,11 +591,12 @@ __device__ __forceinline__ GScreen grp_uncertified(int D, int st) {
   return g;
 }
 
-// both estimates -> score_interval() (hbx_acq_impl.h) unchanged -> the candidate's slot
-__device__ __forceinline__ GScreen grp_emit(int D, int st, bool certified, const KdeEst& est_l, const KdeEst& est_g) {
+// both estimates -> score_interval() (hbx_acq_impl.h) unchanged, under the call's score floor -> the candidate's slot
+__device__ __forceinline__ GScreen grp_emit(int D, int st, bool certified, const KdeEst& est_l, const KdeEst& est_g,
+                                            const ScoreFloor F) {
   if (!certified) return grp_uncertified(D, st);
   GScreen g;
-  const ScoreIv v = score_interval(est_l, est_g);
+  const ScoreIv v = score_interval(est_l, est_g, F);
   g.slo = v.slo;
   g.shi = v.shi;
   g.rel = (float)((grp_exact_rel(D, st & GRP_NEG(0), &est_l) + grp_exact_rel(D, st & GRP_NEG(1), &est_g) + 0x1p-51) *

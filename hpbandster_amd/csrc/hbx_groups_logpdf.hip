@@ -19,7 +19,8 @@
 // Correctness never rests on the fp32 pass: it only decides which values the fp64 pass need not compute.
 //
 // A KDE is EXACT when a categorical match factor is negative (h > 1), a categorical dim has a single observed level
-// (c == 1, h == 0), a bandwidth is not a positive finite number, or the dims exceed the slot bucket picked from D
+// (c == 1; h == 0, or h > 0 and finite), a bandwidth is not a positive finite number, or the dims exceed the slot bucket
+// picked from D
 // (hbx_groups.hip's buckets: D <= 8, 16, 32 any mix; D <= 96 up to 64 continuous + 32 categorical).  Its values are
 // ln of the reference's own fp64 pdf: NaN where that is negative or NaN, -inf where it underflows to 0.
 //

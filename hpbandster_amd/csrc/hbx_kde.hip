@@ -3,7 +3,8 @@
 //
 // Reference path: bohb.py:124-152 calls statsmodels KDEMultivariate.pdf
 // (SM:kernel_density.py:162-196 -> SM:_kernel_base.py:456-518 gpke -> SM:kernels.py:23-65,108-125)
-// twice per candidate and keeps the first candidate with the smallest max(1e-8,g)/max(l,1e-8).
+// twice per candidate and keeps the first candidate with the smallest max(f,g)/max(l,f), f = the pair's score floor
+// (hbx_kde_pair_set_rules; 1e-8, the reference's, unless set).
 //
 // Engine structure (one acquisition, all on one HIP stream, no host round trip until the result):
 //   acq_init         U = +inf, counters = 0
@@ -57,7 +58,8 @@ __global__ void acq_init_batch_kernel(int64_t B, uint32_t* __restrict__ U, int32
 
 // Candidates [b*seg, (b+1)*seg) form acquisition b (seg = Nc: one acquisition).  U[b] = min over the
 // segment of the upper score bound, flags[b] bit 0 = overflow risk (re-score the whole segment).
-// Candidates whose l and g are both certainly below 1e-8 score exactly 1e-8/1e-8 = 1 (bohb.py:129):
+// Candidates whose l and g are both certainly below the score floor f (1e-8 by default) score exactly f/f = 1
+// (bohb.py:129):
 // they tie, so only the first of them per segment (first1[b]) can win and needs the exact re-score
 // (BOHB's own sampler puts most candidates there at D = 32: the truncnorm scale is 3 bw).
 // (OBS_SPLIT_MAX, the observation splits of one scoring launch at most: hbx_score.h)
@@ -96,7 +98,8 @@ __global__ __launch_bounds__(256) void kde_combine_kernel(KdeEst* __restrict__ e
                                                           int64_t Nc, uint32_t seg, float* __restrict__ logl,
                                                           float* __restrict__ logg, float* __restrict__ lo,
                                                           uint32_t* __restrict__ U, int32_t* __restrict__ flags,
-                                                          int32_t* __restrict__ first1, CombineRescue rs) {
+                                                          int32_t* __restrict__ first1, CombineRescue rs,
+                                                          ScoreFloor F) {
   // COMBINE_SUB consecutive 256-candidate sub-blocks per block: every sub-block's loads are issued first
   // (the kernel is latency-bound with one candidate per thread), then each runs as its own block would
   // the marker count, final since the scoring launch ended: a plain (scalar) load, like the estimates'
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(256) void kde_combine_kernel(KdeEst* __restrict__ e
     if (i < Nc) {
       // (score_interval: hbx_acq_impl.h, shared with the top-k bounds pass)
       // (a staged acquisition's candidates without g: the interval l alone gives)
-      const ScoreIv v = eb[r].err == HBX_EST_NOT_EVAL ? score_interval_l_only(ea[r]) : score_interval(ea[r], eb[r]);
+      const ScoreIv v = eb[r].err == HBX_EST_NOT_EVAL ? score_interval_l_only(ea[r], F) : score_interval(ea[r], eb[r], F);
       const float lpt = v.lpt, gpt = v.gpt;
       const bool of = v.of;
       // an exact tie at 1 is excluded from the shortlist unless it is the segment's first (first1)
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(256) void kde_combine_kernel(KdeEst* __restrict__ e
 }
 
 typedef void (*combine_fn)(KdeEst*, KdeEst*, int64_t, uint32_t, float*, float*, float*, uint32_t*, int32_t*,
-                           int32_t*, CombineRescue);
+                           int32_t*, CombineRescue, ScoreFloor);
 
 __global__ __launch_bounds__(256) void kde_shortlist_kernel(const float* __restrict__ lo, int64_t Nc, uint32_t seg,
                                                             const uint32_t* __restrict__ U,
@@ -265,7 +268,7 @@ __global__ __launch_bounds__(256) void kde_final_kernel(const int32_t* __restric
                                                         int32_t* __restrict__ near_list, AcqResult* __restrict__ res,
                                                         int32_t nbuf, const double* __restrict__ part,
                                                         double* exact_lw, double* exact_gw, AcqResult* host_res,
-                                                        int32_t seq, PickOut pick) {
+                                                        int32_t seq, PickOut pick, double pfloor) {
   __shared__ double bs[256];
   __shared__ AcqResult rec_sh;
   __shared__ int64_t bi[256];
@@ -316,7 +319,7 @@ __global__ __launch_bounds__(256) void kde_final_kernel(const int32_t* __restric
   int32_t bpos = -1;
   if (threadIdx.x == 0) nnear = 0;
   for (int p = threadIdx.x; p < cnt; p += 256) {
-    const double s = bohb_score(small ? exg[p] : exact_g[p], small ? exl[p] : exact_l[p]);
+    const double s = bohb_score(small ? exg[p] : exact_g[p], small ? exl[p] : exact_l[p], pfloor);
     const int64_t idx = small ? my_idx : list[p];
     // valid iff s < +inf (bohb.py:150 'val < best' with best = inf); strict '<', first index wins
     if (s < INFINITY && (s < best || (s == best && idx < bidx))) {
@@ -353,7 +356,7 @@ __global__ __launch_bounds__(256) void kde_final_kernel(const int32_t* __restric
     const double sb = bs[0];
     if (!small) rb = score_rel(Pg, Pb, el, eg, list[wp]);
     for (int p = threadIdx.x; p < cnt; p += 256) {
-      const double s = bohb_score(small ? exg[p] : exact_g[p], small ? exl[p] : exact_l[p]);
+      const double s = bohb_score(small ? exg[p] : exact_g[p], small ? exl[p] : exact_l[p], pfloor);
       const int64_t ip = small ? my_idx : list[p];
       if (p == wp || near_best(s, small ? my_rel : score_rel(Pg, Pb, el, eg, ip), sb, rb))
         near_list[atomicAdd(&nnear, 1)] = (int32_t)ip;
@@ -400,17 +403,17 @@ __global__ __launch_bounds__(256) void kde_final_kernel(const int32_t* __restric
 // Batched argmin, three passes over the shortlist: (1) per-segment minimum of the exact score,
 // (2) among the entries reaching it the smallest index (strict '<', first index -- bohb.py:149-152),
 // (3) one thread per segment writes its record.  Scores are > 0 or NaN (both factors are clamped
-// to >= 1e-8), so the bits of a finite score order like the score.
+// to >= the score floor; 0 where l is +inf), so the bits of a finite score order like the score.
 // (bohb_score: hbx_acq_impl.h)
 
 __global__ __launch_bounds__(256) void kde_batch_min_kernel(const int32_t* __restrict__ list,
                                                             const int32_t* __restrict__ count, uint32_t seg,
                                                             const double* __restrict__ exact_l,
                                                             const double* __restrict__ exact_g,
-                                                            uint64_t* __restrict__ best) {
+                                                            uint64_t* __restrict__ best, double pfloor) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= *count) return;
-  const double s = bohb_score(exact_g[p], exact_l[p]);
+  const double s = bohb_score(exact_g[p], exact_l[p], pfloor);
   if (s < INFINITY) atomicMin((unsigned long long*)best + (uint32_t)list[p] / seg,
                               (unsigned long long)__double_as_longlong(s));
 }
@@ -420,10 +423,10 @@ __global__ __launch_bounds__(256) void kde_batch_key_kernel(const int32_t* __res
                                                             const double* __restrict__ exact_l,
                                                             const double* __restrict__ exact_g,
                                                             const uint64_t* __restrict__ best,
-                                                            uint64_t* __restrict__ key) {
+                                                            uint64_t* __restrict__ key, double pfloor) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= *count) return;
-  const double s = bohb_score(exact_g[p], exact_l[p]);
+  const double s = bohb_score(exact_g[p], exact_l[p], pfloor);
   const uint32_t i = (uint32_t)list[p], sg = i / seg;
   if (s < INFINITY && (uint64_t)__double_as_longlong(s) == best[sg])
     atomicMin((unsigned long long*)key + sg, ((unsigned long long)(i - sg * seg) << 32) | (uint32_t)p);
@@ -441,7 +444,7 @@ __global__ __launch_bounds__(256) void kde_batch_near_kernel(const int32_t* __re
                                                              const KdeEst* __restrict__ el,
                                                              const KdeEst* __restrict__ eg,
                                                              int32_t* __restrict__ near_flag,
-                                                             int32_t* __restrict__ segnear) {
+                                                             int32_t* __restrict__ segnear, double pfloor) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= *count) return;
   const uint32_t i = (uint32_t)list[p], sg = i / seg;
@@ -449,9 +452,9 @@ __global__ __launch_bounds__(256) void kde_batch_near_kernel(const int32_t* __re
   int f = 0;
   if (k != ~0ull) {
     const int wp = (int)(uint32_t)k;
-    const double sb = bohb_score(exact_g[wp], exact_l[wp]);
+    const double sb = bohb_score(exact_g[wp], exact_l[wp], pfloor);
     const double rb = score_rel(Pg, Pb, el, eg, list[wp]);
-    const double s = bohb_score(exact_g[p], exact_l[p]);
+    const double s = bohb_score(exact_g[p], exact_l[p], pfloor);
     f = (p == wp || near_best(s, score_rel(Pg, Pb, el, eg, i), sb, rb)) ? 1 : 0;
   }
   near_flag[p] = f;
@@ -469,7 +472,8 @@ __global__ __launch_bounds__(256) void kde_batch_final_kernel(int64_t B, const u
                                                               const KdeParams* __restrict__ Pb,
                                                               const KdeEst* __restrict__ el,
                                                               const KdeEst* __restrict__ eg,
-                                                              int64_t index_base, AcqResult* __restrict__ res) {
+                                                              int64_t index_base, AcqResult* __restrict__ res,
+                                                              double pfloor) {
   const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   AcqResult r;
@@ -488,7 +492,7 @@ __global__ __launch_bounds__(256) void kde_batch_final_kernel(int64_t B, const u
     r.index = (int64_t)(k >> 32) + index_base;
     r.pdf_l = exact_l[p];
     r.pdf_g = exact_g[p];
-    r.score = bohb_score(r.pdf_g, r.pdf_l);
+    r.score = bohb_score(r.pdf_g, r.pdf_l, pfloor);
     r.rel = (float)score_rel(Pg, Pb, el, eg, list[p]);
   }
   res[b] = r;
@@ -711,7 +715,7 @@ static int acquire_impl(const void* pair, const AcqCall& c) {
                             : sgn          ? kde_combine_kernel<true, true>
                                            : kde_combine_kernel<false, true>;
       hipLaunchKernelGGL(cf, dim3((unsigned)((Nc + 256 * COMBINE_SUB - 1) / (256 * COMBINE_SUB))), dim3(256), 0, s,
-                         a.el, a.eg, Nc, sg, logl_out, logg_out, a.lo, a.U, a.flags, a.first1, rs);
+                         a.el, a.eg, Nc, sg, logl_out, logg_out, a.lo, a.U, a.flags, a.first1, rs, p.floor);
       HBX_LAUNCH_CHECK();
     }
     // a single acquisition of few candidates: the exact re-score's blocks shortlist for themselves
@@ -736,22 +740,23 @@ static int acquire_impl(const void* pair, const AcqCall& c) {
     hipLaunchKernelGGL(kde_final_kernel, dim3(1), dim3(256), 0, s, a.list, a.count, a.exact_l, a.exact_g, a.flags,
                        c.index_base, p.Pg(), p.Pb(), a.el, a.eg, a.near, a.res,
                        (int32_t)((p.nmax + PW_BUF - 1) / PW_BUF), fuse_combine ? a.part : (const double*)nullptr,
-                       a.exact_l, a.exact_g, c.host_res, c.seq, c.pick);
+                       a.exact_l, a.exact_g, c.host_res, c.seq, c.pick, p.floor.f);
     HBX_LAUNCH_CHECK();
     return HBX_OK;
   }
   if (Nc > 0) {
-    hipLaunchKernelGGL(kde_batch_min_kernel, grid, dim3(256), 0, s, a.list, a.count, sg, a.exact_l, a.exact_g, a.best);
+    hipLaunchKernelGGL(kde_batch_min_kernel, grid, dim3(256), 0, s, a.list, a.count, sg, a.exact_l, a.exact_g, a.best,
+                       p.floor.f);
     HBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(kde_batch_key_kernel, grid, dim3(256), 0, s, a.list, a.count, sg, a.exact_l, a.exact_g, a.best,
-                       a.key);
+                       a.key, p.floor.f);
     HBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(kde_batch_near_kernel, grid, dim3(256), 0, s, a.list, a.count, sg, a.exact_l, a.exact_g, a.key,
-                       p.Pg(), p.Pb(), a.el, a.eg, a.near, a.segnear);
+                       p.Pg(), p.Pb(), a.el, a.eg, a.near, a.segnear, p.floor.f);
     HBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(kde_batch_final_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, a.key, a.segcnt,
                        a.flags, a.segnear, a.list, a.exact_l, a.exact_g, p.Pg(), p.Pb(), a.el, a.eg, c.index_base,
-                       batch_res);
+                       batch_res, p.floor.f);
     HBX_LAUNCH_CHECK();
   }
   return HBX_OK;
@@ -798,12 +803,22 @@ void* hbx_kde_pair_bind(int32_t D, const void* params_good, const float* table_g
   }
   KdePairRef* b = new (std::nothrow) KdePairRef{D, params_good, table_good, X_good, rows_good, variant_good,
                                                 params_bad, table_bad, X_bad, rows_bad, variant_bad, dc_pad,
-                                                du_pad, nmax};
+                                                du_pad, nmax, hbx_score_floor(HBX_PDF_FLOOR_DEFAULT)};
   if (!b) hbx_fail(HBX_ERR_ARG, "hbx_kde_pair_bind: out of host memory");
   return b;
 }
 
 void hbx_kde_pair_free(void* pair) { delete (KdePairRef*)pair; }
+
+// The pair's selection rules: every later acquisition on the handle forms its scores with rules->pdf_floor
+// (min_bandwidth belongs to the fits and is only range-checked here).  NULL: the reference snapshot's.
+int hbx_kde_pair_set_rules(void* pair, const hbx_rules* rules) {
+  if (!pair) return hbx_fail(HBX_ERR_ARG, "hbx_kde_pair_set_rules: null pair");
+  const int rc = hbx_rules_check("hbx_kde_pair_set_rules", rules);
+  if (rc) return rc;
+  ((KdePairRef*)pair)->floor = hbx_score_floor(rules ? rules->pdf_floor : HBX_PDF_FLOOR_DEFAULT);
+  return HBX_OK;
+}
 
 // The drop-in's synchronous acquisition on a bound pair: the final kernel stores the 48-byte record into this
 // thread's mapped host buffer as tagged words; the call spins until they carry its sequence number and copies the

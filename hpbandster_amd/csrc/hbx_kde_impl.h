@@ -11,6 +11,42 @@
 
 #define HBX_LN2f 0.69314718055994531f
 #define HBX_LN_CLAMP (-18.420680743952367)   // ln(1e-8), bohb.py:129
+// The score floor f of max(f, g) / max(l, f) (hbx_rules.pdf_floor; the reference snapshot's 1e-8) as the
+// selection kernels take it: a launch argument, so kernel scalars, never a load.
+//   C   (float)ln f.  For the default it is (float)HBX_LN_CLAMP bit for bit (the default is taken by value, not
+//       through log(), so the default path cannot depend on the host's libm).
+//   C1  C - margin: a ln-pdf upper bound below it is certainly under the floor.  The margin covers the rounding of
+//       ln f to float (half an ulp of C) and log()'s own error: max(1e-4, 2 ulp_f32(C)) -- 1e-4 at the default and
+//       over the whole accepted range (2 ulp = 3.1e-5 at |C| = 230, f = 1e-100), two ulps should the range ever grow.
+//   w   what a score interval's ends are widened by where only one factor is clamped (both clamped: the score is
+//       f / f = 1 exactly): the distance of C from ln f, one ulp of C.  0 for the default, whose 1e-6 the ln-pdf
+//       intervals' own slack (1e-5 + 1e-6 |ln pdf|, est_interval) has always covered -- its intervals keep their bits.
+struct ScoreFloor {
+  double f;
+  float C, C1, w;
+};
+#define HBX_PDF_FLOOR_DEFAULT 1e-8
+#define HBX_PDF_FLOOR_MIN 1e-100
+static inline bool hbx_pdf_floor_ok(double f) { return f >= HBX_PDF_FLOOR_MIN && f <= 1.0; }  // NaN, inf: false
+static inline ScoreFloor hbx_score_floor(double f) {
+  ScoreFloor r;
+  r.f = f;
+  r.C = f == HBX_PDF_FLOOR_DEFAULT ? (float)HBX_LN_CLAMP : (float)log(f);
+  const float ulp = nextafterf(fabsf(r.C), INFINITY) - fabsf(r.C);
+  const float margin = 2.f * ulp > 1e-4f ? 2.f * ulp : 1e-4f;
+  r.C1 = r.C - margin;
+  r.w = f == HBX_PDF_FLOOR_DEFAULT ? 0.f : ulp;
+  return r;
+}
+// An entry point's hbx_rules (NULL: the reference snapshot's): HBX_ERR_ARG outside the accepted ranges
+static inline int hbx_rules_check(const char* who, const hbx_rules* r) {
+  if (!r) return HBX_OK;
+  if (!hbx_pdf_floor_ok(r->pdf_floor))
+    return hbx_fail(HBX_ERR_ARG, "%s: pdf_floor=%g outside [1e-100, 1]", who, r->pdf_floor);
+  if (!(r->min_bandwidth >= 0.0) || isinf(r->min_bandwidth))
+    return hbx_fail(HBX_ERR_ARG, "%s: min_bandwidth=%g is not finite and >= 0", who, r->min_bandwidth);
+  return HBX_OK;
+}
 #define HBX_INV_SQRT_2PI 0.3989422804014327  // 1. / np.sqrt(2 * np.pi), SM:kernels.py:125
 #ifndef EXACT_GRID
 #define EXACT_GRID 2048  // blocks of the exact re-score (grid-stride over its work items)
@@ -449,7 +485,7 @@ int refit_sort_small(double* X, double* loss, const double* staged, const double
 int refit_fit_colstats(const double* X, int32_t D, const int64_t* seg_off, const int64_t* order, const int64_t* n_good,
                        const int64_t* n_bad, const double* fac_good, const double* fac_bad, const int32_t* vartype,
                        double* bw_good, double* bw_bad, int32_t* nlev_good, int32_t* nlev_bad, ColStats* cs_good,
-                       ColStats* cs_bad, hipStream_t s);
+                       ColStats* cs_bad, double min_bw, hipStream_t s);
 #define FIT_TILE_ROWS 16384  // kde_fit_col_kernel's LDS tile (FIT_TILE)
 
 // host-side pickers of the scoring kernel instances (null pointers when the bucket has none), each with the block

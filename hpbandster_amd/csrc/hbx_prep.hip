@@ -121,7 +121,8 @@ struct ParamsScratch {
   double t0[HBX_MAX_D], t1[HBX_MAX_D], h[HBX_MAX_D], mean[HBX_MAX_D];
   int32_t c[HBX_MAX_D], maxc[HBX_MAX_D], cm[HBX_MAX_D], cd[HBX_MAX_D];
   int32_t ix[HBX_MAX_D];   // index of dim d within its class (continuous slot k, categorical slot u, constant dim)
-  uint8_t kind[HBX_MAX_D]; // 0 continuous, 1 active categorical, 2 constant (one level, h = 0), 3 unsupported
+  uint8_t kind[HBX_MAX_D]; // 0 continuous, 1 active categorical, 2 constant (one level; h = 0, or h > 0 and finite:
+                           // the KDE is then exact-only), 3 unsupported
   int32_t ohs[HBX_MAX_D];  // first one-hot position of each active categorical dim's block
   int32_t du, dcp, dup, exo, neg, dc_tot, du_tot, dc, nconst, kc, tot;
 };
@@ -150,9 +151,13 @@ __device__ __forceinline__ void kde_params_body(const PrepArgs& A, KdeParams* P,
       S.t0[d] = (h > 0.0) ? log(h) : 0.0;
       S.t1[d] = (h > 0.0) ? sqrt(LOG2E / 2.0) / h : 0.0;
     } else {
-      // single observed level: match -> 1, mismatch -> 0/0 = NaN (a constant dim); c < 2 otherwise, h <= 0 or
-      // NaN (c == -1: codes not integers in [0, 1024)): not modelled
-      S.kind[d] = (c == 1 && h == 0.0) ? 2 : ((c < 2 || !(h > 0.0) || h != h) ? 3 : 1);
+      // single observed level: match -> 1, mismatch -> 0/0 = NaN (a constant dim).  The same level count under a
+      // finite h > 0 (a fitted 0 clipped to hbx_rules.min_bandwidth, or an explicit bandwidth): match -> 1 - h,
+      // mismatch -> h / 0 = +inf in the reference's arithmetic, so the pdf is finite, +inf or NaN (an inf beside
+      // an underflowed 0 in the dim-ordered product) -- also a constant dim, and the KDE exact-only (below): the
+      // fp64 evaluation decides every candidate.  c < 2 otherwise, h <= 0 or NaN (c == -1: codes not integers in
+      // [0, 1024)): not modelled
+      S.kind[d] = (c == 1 && (h == 0.0 || (h > 0.0 && h < INFINITY))) ? 2 : ((c < 2 || !(h > 0.0) || h != h) ? 3 : 1);
       const double a = 1.0 - h, b = h / (double)(c - 1);
       S.t0[d] = log2(b);
       S.t1[d] = (a == 0.0) ? -INFINITY : log2(fabs(a));
@@ -223,6 +228,7 @@ __device__ __forceinline__ void kde_params_body(const PrepArgs& A, KdeParams* P,
   if (tid == 0) {  // the sums in dim order (np.prod(bw[iscontinuous]) sequential: the reference's order)
     double sum_ln_h = 0.0, m0 = 0.0, lb_sum = 0.0, prod_bw_c = 1.0;
     float sad = 0.f;
+    bool one_pos = false;  // a single-level categorical dim with h > 0
     // branch-free (a factor 1 or a term +0.0 where a dim does not count: exact), so the loads of several dims
     // are in flight at once
 #pragma unroll 4
@@ -234,6 +240,7 @@ __device__ __forceinline__ void kde_params_body(const PrepArgs& A, KdeParams* P,
       m0 += (kd == 1) ? ((la > lb) ? la : lb) : 0.0;
       lb_sum += (kd == 1) ? lb : 0.0;
       sad += (kd == 1 && 1.0 - h != 0.0) ? fabsf((float)(la - lb)) : 0.f;
+      one_pos = one_pos || (kd == 2 && h > 0.0);
     }
     int dcp, dup;
     bucket_dims(S.dc_tot, S.du_tot, &dcp, &dup);
@@ -241,9 +248,11 @@ __device__ __forceinline__ void kde_params_body(const PrepArgs& A, KdeParams* P,
     P->D = D;
     P->dc_pad = dcp;
     P->du_pad = dup;
-    const int exo = (dcp < 0 || dup < 0) ? 1 : 0;
+    // exact-only: outside every bucket (the host knows: no table launch), or a single-level dim with h > 0 (the
+    // table launch runs: the f32 layout, which no acquisition reads)
+    const int exo = (dcp < 0 || dup < 0 || one_pos) ? 1 : 0;
     P->exact_only = exo;
-    P->stride = exo ? 0 : table_stride(dcp, dup);
+    P->stride = (dcp < 0 || dup < 0) ? 0 : table_stride(dcp, dup);
     const int dc = S.dc_tot;
     P->dc = dc;
     P->du = S.du;
@@ -306,10 +315,11 @@ __device__ __forceinline__ void kde_params_body(const PrepArgs& A, KdeParams* P,
   if (threadIdx.x != 0) return;
   // (read back from LDS, not from the P just written: see above)
   const int dcp = S.dcp, dup = S.dup, has_neg = S.neg;
-  if (S.exo) {  // no table, no fp32 scoring: the acquisition re-scores every candidate
+  if (S.exo) {  // no fp32 scoring: the acquisition re-scores every candidate
     P->hmode = 0;
     P->nsc = 0;
-    P->chunk_floats = 0;
+    // (within a bucket -- a single-level dim with h > 0 -- the table launch still runs: a well-formed f32 layout)
+    P->chunk_floats = (dcp < 0 || dup < 0) ? 0 : chunk_floats(dcp, dup, 0, 0);
     return;
   }
   if (kc > 0) {

@@ -67,7 +67,8 @@ static int refit_impl(double* X, double* loss, int64_t n, int32_t D, const int32
                       bool staged_host, int64_t n_new, int64_t n_good, int64_t n_bad, double fac_good, double fac_bad,
                       void* params_good, float* table_good, int64_t table_good_floats, void* params_bad,
                       float* table_bad, int64_t table_bad_floats, void* out, void* scratch, int64_t scratch_bytes,
-                      void* stream, const PrepPub* pub = nullptr) {
+                      void* stream, const hbx_rules* rules, const PrepPub* pub = nullptr) {
+  if (const int rrc = hbx_rules_check("hbx_kde_refit", rules)) return rrc;
   if (!X || !loss || !vartype || !params_good || !table_good || !params_bad || !table_bad || !out || !scratch ||
       (n_new > 0 && !staged))
     return hbx_fail(HBX_ERR_ARG, "hbx_kde_refit: null pointer");
@@ -143,12 +144,14 @@ static int refit_impl(double* X, double* loss, int64_t n, int32_t D, const int32
   }
   // both sets within one LDS tile: the fit also writes the preparation's column statistics (one launch less)
   const bool fused = D > 1 && n_good <= FIT_TILE_ROWS && n_bad <= FIT_TILE_ROWS;
+  // (the bandwidths are clipped where the fit stores them: the preparation below reads the clipped ones)
   if (fused)
     rc = refit_fit_colstats(X, D, m->seg, order, &m->n_good, &m->n_bad, &m->fac_good, &m->fac_bad, m->vt, bw_g, bw_b,
-                            nl_g, nl_b, col_stats((KdeParams*)params_good), col_stats((KdeParams*)params_bad), s);
+                            nl_g, nl_b, col_stats((KdeParams*)params_good), col_stats((KdeParams*)params_bad),
+                            rules ? rules->min_bandwidth : 0.0, s);
   else
-    rc = hbx_kde_fit(X, D, m->seg, 1, order, &m->n_good, &m->n_bad, &m->fac_good, &m->fac_bad, m->vt, bw_g, bw_b,
-                     nl_g, nl_b, stream);
+    rc = hbx_kde_fit_r(X, D, m->seg, 1, order, &m->n_good, &m->n_bad, &m->fac_good, &m->fac_bad, m->vt, bw_g, bw_b,
+                       nl_g, nl_b, stream, rules);
   if (rc) return rc;
   return prep_launch(ps, table_good, table_bad, s, fused);
 }
@@ -163,9 +166,20 @@ int hbx_kde_refit(double* X, double* loss, int64_t n, int32_t D, const int32_t* 
                   int64_t n_new, int64_t n_good, int64_t n_bad, double fac_good, double fac_bad, void* params_good,
                   float* table_good, int64_t table_good_floats, void* params_bad, float* table_bad,
                   int64_t table_bad_floats, void* out, void* scratch, int64_t scratch_bytes, void* stream) {
+  return hbx_kde_refit_r(X, loss, n, D, vartype, staged, n_new, n_good, n_bad, fac_good, fac_bad, params_good,
+                         table_good, table_good_floats, params_bad, table_bad, table_bad_floats, out, scratch,
+                         scratch_bytes, stream, nullptr);
+}
+
+// hbx_kde_refit with both KDEs' bandwidths clipped from below at rules->min_bandwidth (NULL: no clip)
+int hbx_kde_refit_r(double* X, double* loss, int64_t n, int32_t D, const int32_t* vartype, const double* staged,
+                    int64_t n_new, int64_t n_good, int64_t n_bad, double fac_good, double fac_bad, void* params_good,
+                    float* table_good, int64_t table_good_floats, void* params_bad, float* table_bad,
+                    int64_t table_bad_floats, void* out, void* scratch, int64_t scratch_bytes, void* stream,
+                    const hbx_rules* rules) {
   return refit_impl(X, loss, n, D, vartype, staged, false, n_new, n_good, n_bad, fac_good, fac_bad, params_good,
                     table_good, table_good_floats, params_bad, table_bad, table_bad_floats, out, scratch, scratch_bytes,
-                    stream);
+                    stream, rules);
 }
 
 // hbx_kde_refit with the appended rows in HOST memory (rows then losses, n_new (D + 1) doubles: up to 256
@@ -183,6 +197,18 @@ int hbx_kde_refit_sync(double* X, double* loss, int64_t n, int32_t D, const int3
                        double fac_bad, void* params_good, float* table_good, int64_t table_good_floats,
                        void* params_bad, float* table_bad, int64_t table_bad_floats, void* out, void* scratch,
                        int64_t scratch_bytes, void* stream, void* out_host) {
+  return hbx_kde_refit_sync_r(X, loss, n, D, vartype, staged_host, n_new, n_good, n_bad, fac_good, fac_bad, params_good,
+                              table_good, table_good_floats, params_bad, table_bad, table_bad_floats, out, scratch,
+                              scratch_bytes, stream, out_host, nullptr);
+}
+
+// hbx_kde_refit_sync with both KDEs' bandwidths clipped from below at rules->min_bandwidth (NULL: no clip)
+int hbx_kde_refit_sync_r(double* X, double* loss, int64_t n, int32_t D, const int32_t* vartype,
+                         const double* staged_host, int64_t n_new, int64_t n_good, int64_t n_bad, double fac_good,
+                         double fac_bad, void* params_good, float* table_good, int64_t table_good_floats,
+                         void* params_bad, float* table_bad, int64_t table_bad_floats, void* out, void* scratch,
+                         int64_t scratch_bytes, void* stream, void* out_host, const hbx_rules* rules) {
+  if (const int rrc = hbx_rules_check("hbx_kde_refit_sync", rules)) return rrc;  // (before the mapped buffer is taken)
   if (!out_host) return hbx_fail(HBX_ERR_ARG, "hbx_kde_refit_sync: null host output");
   if (n < 1 || n > INT32_MAX || D < 1 || D > HBX_MAX_D) return hbx_fail(HBX_ERR_ARG, "hbx_kde_refit_sync: n, D");
   const int64_t words = n + 6 * (int64_t)D;  // flagged words before the info records
@@ -200,7 +226,7 @@ int hbx_kde_refit_sync(double* X, double* loss, int64_t n, int32_t D, const int3
   mb->pending = true;
   rc = refit_impl(X, loss, n, D, vartype, staged_host, true, n_new, n_good, n_bad, fac_good, fac_bad, params_good,
                   table_good, table_good_floats, params_bad, table_bad, table_bad_floats, out, scratch, scratch_bytes,
-                  stream, &pub);
+                  stream, rules, &pub);
   if (rc) return rc;
   // the info records come last: spin on them, then every other word (each wait bounded: ~0.1 s, then the
   // stream is synchronised and the words looked at once more)

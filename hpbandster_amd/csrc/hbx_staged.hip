@@ -1,11 +1,12 @@
 // hbx_staged.hip -- staged scoring of the single argmin acquisition: the good KDE (l) for every candidate, the
 // bad KDE (g) only for the candidates that can still win.
 //
-// BOHB's score is max(1e-8, g) / max(l, 1e-8) (bohb.py:129), so whatever g is, score_i >= 1e-8 / max(l_i, 1e-8):
+// BOHB's score is max(f, g) / max(l, f) (bohb.py:129; f: the pair's score floor, the reference's 1e-8 unless set: every
+// argument below is stated in C = ln f and holds for any f), so whatever g is, score_i >= f / max(l_i, f):
 // l alone bounds a candidate's score from below, and any candidate with both sums bounds the best score from
 // above.  A candidate whose l-only lower bound lies above that upper bound cannot win or tie; its walk over the
 // bad KDE's observations (85 % of the pairs at BOHB's 15 % split) is work the pick does not need.  Where pdfs are
-// near or below 1e-8 -- the normal case at D = 32 -- that is all but a few tens of candidates.
+// near or below f -- at the reference's 1e-8 the normal case at D = 32 -- that is all but a few tens of candidates.
 //
 // Stages, all on the caller's stream, no host round trip (acq_score_staged):
 //   1 score l      the good KDE's coarse 32x32 pair kernel over all candidates (observation splits as in the
@@ -37,7 +38,7 @@
 //                  with a device-side count, observation splits into a compact [split][capacity] area), then
 //                  staged_merge: splits merged, scattered to a.eg, U_seed = min over seeds of the score
 //                  interval's upper end
-//   4 survivors    every unseeded candidate with C - max(lhi, C) <= U_seed (C = ln 1e-8; the shortlist's own
+//   4 survivors    every unseeded candidate with C - max(lhi, C) <= U_seed (C = ln f; the shortlist's own
 //                  '<=', so ties survive) joins the survivor list and is scored like the seeds (more
 //                  survivors than the split capacity: one unsplit launch over the list, scattering itself).
 //                  The same pass turns every unseeded candidate's a.lo entry from lhi into its l-only lower
@@ -65,7 +66,7 @@
 // partial sums merge in another order and the merged bound grows per merge), so U and the intervals move
 // within their bounds.
 // What can differ in the record, all of it about the screen and none about the pick:
-//   * the unstaged path always shortlists the segment's first certain 1e-8/1e-8 tie (first1); a pruned
+//   * the unstaged path always shortlists the segment's first certain f/f tie (first1); a pruned
 //     candidate's tie status is unknown, so when the best score is below 1 `shortlist` is lower by that one
 //     candidate, which cannot win;
 //   * a candidate at the very edge of the shortlist (slo within the estimates' rounding of U) can fall on
@@ -262,7 +263,8 @@ __global__ __launch_bounds__(256) void staged_merge_kernel(const KdeEst* __restr
                                                            const int32_t* __restrict__ count, int32_t maxcount,
                                                            const KdeEst* __restrict__ el, KdeEst* __restrict__ eg,
                                                            const KdeParams* __restrict__ Pb,
-                                                           uint32_t* __restrict__ stage, int32_t update_u) {
+                                                           uint32_t* __restrict__ stage, int32_t update_u,
+                                                           ScoreFloor F) {
   int32_t cnt = *count;
   if (cnt > maxcount) cnt = maxcount;
   if (cnt > cap) return;
@@ -276,7 +278,7 @@ __global__ __launch_bounds__(256) void staged_merge_kernel(const KdeEst* __restr
     if (!mark) e = merge_splits(part, cap, k, ns);
     eg[i] = e;
     if (update_u && !mark) {
-      const ScoreIv v = score_interval(el[i], e);
+      const ScoreIv v = score_interval(el[i], e, F);
       if (!v.lnan) h = v.shi;
     }
   }
@@ -294,14 +296,14 @@ __global__ __launch_bounds__(256) void staged_merge_kernel(const KdeEst* __restr
 
 // Survivors: unseeded, l not NaN, l-only lower score bound <= U_seed.
 // flags (the short tail; null: the combine kernel follows): lhi[i], which is a.lo, becomes the l-only interval's
-// lower end C - max(lhi, C) in place -- score_interval_l_only's slo from the same lhi -- NaN staying NaN (l is NaN,
+// lower end C - max(lhi, C) (less F.w) in place -- score_interval_l_only's slo from the same lhi -- NaN staying NaN (l is NaN,
 // or a seed, whose entry the tail kernel writes), and lhi > 700 raises the overflow flag as that interval's `of`.
 __global__ __launch_bounds__(256) void staged_survivor_kernel(float* __restrict__ lhi, int64_t Nc,
                                                               int32_t* __restrict__ surv,
                                                               uint32_t* __restrict__ stage,
-                                                              int32_t* __restrict__ flags) {
+                                                              int32_t* __restrict__ flags, ScoreFloor F) {
   const float U = hbx_ord2f(stage[HBX_ST_USEED]);
-  const float C = (float)HBX_LN_CLAMP;
+  const float C = F.C;
   bool f[STAGED_PT];
   int n = 0;
 #pragma unroll
@@ -310,9 +312,9 @@ __global__ __launch_bounds__(256) void staged_survivor_kernel(float* __restrict_
     f[r] = false;
     if (i < Nc) {
       const float h = lhi[i];
-      f[r] = h == h && (C - fmaxf(h, C)) <= U;
+      f[r] = h == h && (C - fmaxf(h, C) - F.w) <= U;
       if (flags && h == h) {  // (flags: uniform)
-        lhi[i] = C - fmaxf(h, C);
+        lhi[i] = C - fmaxf(h, C) - F.w;
         if (h > 700.f) atomicOr(flags, 1);
       }
     }
@@ -350,6 +352,7 @@ struct StagedTailArgs {
   int32_t* count;
   int32_t* rescue_cnt;
   uint32_t* stage;
+  ScoreFloor F;
 };
 
 // agent-scope loads of words other blocks of the same launch lower (never through the scalar or a stale vector cache)
@@ -430,7 +433,7 @@ __global__ __launch_bounds__(256) void staged_tail_kernel(StagedTailArgs t) {
       store = true;
     }
     if (store) t.eg[i] = eb[r];
-    const ScoreIv v = score_interval(ea[r], eb[r]);
+    const ScoreIv v = score_interval(ea[r], eb[r], t.F);
     slo[r] = v.one ? NAN : v.slo;
     t.lo[i] = slo[r];
     if (!v.lnan) h = fminf(h, v.shi);
@@ -614,7 +617,8 @@ int staged_score_seeds(const AcqPlan& plan, const KdePairRef& p, const double* c
   hipLaunchKernelGGL(fb.list, dim3(la.tiles_cap * (unsigned)la.nsplit), dim3(fb.threads), 0, s, cand, p.D, la);
   HBX_LAUNCH_CHECK();
   hipLaunchKernelGGL(staged_merge_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, a.lpart, cap,
-                     la.nsplit, a.seeds, la.count, cap, a.el, a.eg, p.Pb(), a.stage, (int32_t)(update_u ? 1 : 0));
+                     la.nsplit, a.seeds, la.count, cap, a.el, a.eg, p.Pb(), a.stage, (int32_t)(update_u ? 1 : 0),
+                     p.floor);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }
@@ -624,7 +628,7 @@ int staged_score_survivors(const AcqPlan& plan, const KdePairRef& p, const doubl
   // stage 4
   const ScoreFns& fb = plan.fb;
   hipLaunchKernelGGL(staged_survivor_kernel, staged_gsel(Nc), dim3(256), 0, s, a.lo, Nc, a.surv, a.stage,
-                     lonly ? a.flags : (int32_t*)nullptr);
+                     lonly ? a.flags : (int32_t*)nullptr, p.floor);
   HBX_LAUNCH_CHECK();
   KdeListArgs la = staged_list_args(plan, p, a);
   la.idx = a.surv;
@@ -652,13 +656,14 @@ int acq_score_staged(const AcqPlan& plan, const KdePairRef& p, const double* can
     // a block per 1024 entries if every candidate is evaluated (blocks without entries exit at once), then one block
     const StagedTailArgs ta{a.lpart, cap,     ls,   a.seeds, a.surv,  Nc,       cand,   p.D,     p.Pb(),
                             a.el,    a.eg,    a.lo, a.U,     a.flags, a.first1, a.list, a.count, a.rescue,
-                            a.stage};
+                            a.stage, p.floor};
     hipLaunchKernelGGL(staged_tail_kernel, dim3((unsigned)((Nc + cap + 1023) / 1024)), dim3(256), 0, s, ta);
     HBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(staged_shortlist_kernel, dim3(1), dim3(TAIL_THREADS), 0, s, ta);
   } else {
     hipLaunchKernelGGL(staged_merge_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, a.lpart, cap, ls,
-                       a.surv, (const int32_t*)a.stage + HBX_ST_NSURV, (int32_t)Nc, a.el, a.eg, p.Pb(), a.stage, 0);
+                       a.surv, (const int32_t*)a.stage + HBX_ST_NSURV, (int32_t)Nc, a.el, a.eg, p.Pb(), a.stage, 0,
+                       p.floor);
   }
   HBX_LAUNCH_CHECK();
   if (ev) {  // [0]->[1]: the staged scoring, first launch's start to the last launch's end

@@ -1,6 +1,7 @@
 // hbx_topk.hip -- top-k acquisition on MI355X (gfx950): the k best candidates of ONE pool, ranked exactly.
 //
-// hbx_kde_acquire answers "which candidate minimises s = max(1e-8, g) / max(l, 1e-8)" (bohb.py:149-152);
+// hbx_kde_acquire answers "which candidate minimises s = max(f, g) / max(l, f)" (bohb.py:149-152; f: the pair's
+// score floor, 1e-8 unless set);
 // hbx_kde_acquire_topk (at the end of this file) returns the first min(k, F) entries of the stable ascending order of s
 // over the F candidates whose score is not NaN: ordered by (s[i], i), every value the reference's fp64 bit
 // for bit.  The scoring launch, its rescue pass and split merge, and the exact fp64 re-score are the
@@ -32,7 +33,7 @@
 //
 // Staged scoring (hbx_topk_staged; where acq_staged_supported(plan) holds and HBX_STAGED says so with the argmin's
 // meaning -- 0 never, 2 wherever supported, unset from Nc x nmax >= HBX_STAGED_TOPK_MIN_PAIRS, hbx_acquire.h): g
-// only for the candidates that can still rank.  score_i >= 1e-8 / max(l_i, 1e-8)
+// only for the candidates that can still rank.  score_i >= f / max(l_i, f)
 // whatever g is (hbx_staged.hip), with the k-th place in the role of the best.  All on the caller's stream:
 //   1 score l      hbx_staged.hip's stage 1 as it is (staged_score_l): the good KDE's coarse pair kernel, then
 //                  staged_l_kernel -- rescue, split merge, [llo, lhi], lhi kept in a.lo -- which here also writes
@@ -53,7 +54,7 @@
 //                  finite hi among them, and {lo <= U_k}.  Under the overflow flag the shortlist is every candidate
 //                  whose lo is not NaN, pruned ones included, as in the unstaged call.
 //   then acq_exact and topk_final, unchanged.
-// Why the result is the unstaged one.  A pruned candidate's true score is >= 1e-8 / max(l, 1e-8) >= exp(its
+// Why the result is the unstaged one.  A pruned candidate's true score is >= f / max(l, f) >= exp(its
 // l-only bound) > exp(U_(k+1)_seed).  U_(k+1)_seed is at least the (k+1)-th smallest true score, because k+1
 // seeds have a true score <= it.  So a pruned candidate lies strictly behind k+1 others, ties by index included:
 // it is neither returned nor the best excluded entry the near-tie test reads, and with lo > U_(k+1)_seed >= U_k
@@ -81,13 +82,14 @@
 __global__ __launch_bounds__(256) void topk_bounds_kernel(const KdeEst* __restrict__ el,
                                                           const KdeEst* __restrict__ eg, int64_t Nc,
                                                           float* __restrict__ lo, uint32_t* __restrict__ hik,
-                                                          int32_t* __restrict__ flags, uint32_t* __restrict__ hist) {
+                                                          int32_t* __restrict__ flags, uint32_t* __restrict__ hist,
+                                                          ScoreFloor F) {
   if (blockIdx.x == 0)  // the select's histograms (its passes are later launches)
     for (int j = threadIdx.x; j < TOPK_HIST_WORDS; j += 256) hist[j] = 0;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   bool of = false;
   if (i < Nc) {
-    const ScoreIv v = score_interval(el[i], eg[i]);
+    const ScoreIv v = score_interval(el[i], eg[i], F);
     of = v.of;
     // inf - inf in a bound (both pdf bounds overflowed; the flag is set then): nothing known
     const float l = v.lnan ? NAN : (v.slo == v.slo ? v.slo : -INFINITY);
@@ -245,7 +247,7 @@ __global__ __launch_bounds__(TOPK_USEED_T) void topk_useed_kernel(const int32_t*
                                                                   const KdeEst* __restrict__ el,
                                                                   const KdeEst* __restrict__ eg,
                                                                   const KdeParams* __restrict__ Pb, int32_t k,
-                                                                  uint32_t* __restrict__ stage) {
+                                                                  uint32_t* __restrict__ stage, ScoreFloor F) {
   __shared__ uint32_t hb[256];
   __shared__ uint32_t s_prefix, s_rank;
   const int t = threadIdx.x;
@@ -260,7 +262,7 @@ __global__ __launch_bounds__(TOPK_USEED_T) void topk_useed_kernel(const int32_t*
       const int32_t i = seeds[j];
       const KdeEst b = eg[i];
       if (b.err != -1.f) {
-        const ScoreIv v = score_interval(el[i], b);
+        const ScoreIv v = score_interval(el[i], b, F);
         if (!v.lnan && v.shi == v.shi) key[r] = hbx_f2ord(v.shi);
       }
     }
@@ -330,6 +332,7 @@ struct TopkStagedArgs {
   uint32_t* ekey;
   int32_t* flags;
   const int32_t* rescue_cnt;
+  ScoreFloor F;
 };
 __global__ __launch_bounds__(256) void topk_staged_bounds_kernel(TopkStagedArgs t) {
   int64_t nseed = (int32_t)t.ev.stage[HBX_ST_NSEED], nsurv = (int32_t)t.ev.stage[HBX_ST_NSURV];
@@ -362,7 +365,7 @@ __global__ __launch_bounds__(256) void topk_staged_bounds_kernel(TopkStagedArgs 
       store = true;
     }
     if (store) t.eg[i] = b;
-    const ScoreIv v = score_interval(t.el[i], b);
+    const ScoreIv v = score_interval(t.el[i], b, t.F);
     of = of || v.of;
     t.lo[i] = v.lnan ? NAN : (v.slo == v.slo ? v.slo : -INFINITY);
     t.ekey[e] = hbx_f2ord((v.lnan || v.shi != v.shi) ? INFINITY : v.shi);
@@ -381,7 +384,7 @@ __global__ __launch_bounds__(TOPK_T) void topk_final_kernel(
     const int32_t* __restrict__ list, const int32_t* __restrict__ count, const double* __restrict__ exact_l,
     const double* __restrict__ exact_g, const int32_t* __restrict__ flags, int64_t index_base, int32_t k,
     const KdeParams* __restrict__ Pg, const KdeParams* __restrict__ Pb, const KdeEst* __restrict__ el,
-    const KdeEst* __restrict__ eg, TopkHead* __restrict__ head, TopkRec* __restrict__ rec) {
+    const KdeEst* __restrict__ eg, TopkHead* __restrict__ head, TopkRec* __restrict__ rec, double pfloor) {
   // the running best-(k+1) (hbx_topk_rank.h): entries (score bits, candidate index, shortlist position)
   __shared__ uint64_t sk[TOPK_CAP];
   __shared__ int32_t si[TOPK_CAP];
@@ -397,7 +400,7 @@ __global__ __launch_bounds__(TOPK_T) void topk_final_kernel(
     uint64_t key = 0;
     int32_t idx = 0;
     if (p < cnt) {
-      const double s = bohb_score(exact_g[p], exact_l[p]);
+      const double s = bohb_score(exact_g[p], exact_l[p], pfloor);
       if (s == s) {  // NaN scores are never returned
         key = (uint64_t)__double_as_longlong(s);
         idx = list[p];
@@ -446,9 +449,9 @@ __global__ __launch_bounds__(TOPK_T) void topk_final_kernel(
 // score intervals from the (merged, rescued) estimates: lo[i] as the shortlist predicate reads it, the
 // ordered key of hi into hik[i]; the overflow rule into flags[0]; zeroes the select's histograms
 static int hbx_topk_bounds(const KdeEst* el, const KdeEst* eg, int64_t Nc, float* lo, uint32_t* hik, int32_t* flags,
-                    uint32_t* hist, hipStream_t s) {
+                    uint32_t* hist, const ScoreFloor& F, hipStream_t s) {
   hipLaunchKernelGGL(topk_bounds_kernel, dim3((unsigned)((Nc + 255) / 256)), dim3(256), 0, s, el, eg, Nc, lo, hik,
-                     flags, hist);
+                     flags, hist, F);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }
@@ -475,10 +478,11 @@ static int hbx_topk_shortlist(const float* lo, const uint32_t* hik, int64_t Nc, 
 // the k smallest (score, index) of the re-scored shortlist, ranked, into the result block
 static int hbx_topk_final(const int32_t* list, const int32_t* count, const double* exact_l, const double* exact_g,
                    const int32_t* flags, int64_t index_base, int32_t k, const KdeParams* Pg, const KdeParams* Pb,
-                   const KdeEst* el, const KdeEst* eg, void* results, hipStream_t s) {
+                   const KdeEst* el, const KdeEst* eg, void* results, double pfloor, hipStream_t s) {
   if (k < 1 || k > HBX_TOPK_MAX_K) return hbx_fail(HBX_ERR_ARG, "top-k: k=%d outside [1, %d]", k, HBX_TOPK_MAX_K);
   hipLaunchKernelGGL(topk_final_kernel, dim3(1), dim3(TOPK_T), 0, s, list, count, exact_l, exact_g, flags,
-                     index_base, k, Pg, Pb, el, eg, (TopkHead*)results, (TopkRec*)((char*)results + sizeof(TopkHead)));
+                     index_base, k, Pg, Pb, el, eg, (TopkHead*)results, (TopkRec*)((char*)results + sizeof(TopkHead)),
+                     pfloor);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }
@@ -505,7 +509,7 @@ static int hbx_topk_staged(const AcqPlan& plan, const KdePairRef& p, const doubl
   if (rc) return rc;
   const int32_t cap = a.list_cap;
   hipLaunchKernelGGL(topk_useed_kernel, dim3(1), dim3(TOPK_USEED_T), 0, s, (const int32_t*)a.seeds, cap,
-                     (const KdeEst*)a.el, (const KdeEst*)a.eg, p.Pb(), k, a.stage);
+                     (const KdeEst*)a.el, (const KdeEst*)a.eg, p.Pb(), k, a.stage, p.floor);
   HBX_LAUNCH_CHECK();
   // 4: the survivors and their g; every unseeded candidate's l-only bound into a.lo
   rc = staged_score_survivors(plan, p, cand, Nc, a, s, true);
@@ -513,7 +517,7 @@ static int hbx_topk_staged(const AcqPlan& plan, const KdePairRef& p, const doubl
   // 5: bounds, U_k and the shortlist over the evaluated candidates
   const TopkEval ev{a.stage, a.seeds, a.surv, cap};
   const TopkStagedArgs ta{a.lpart, cap, (int32_t)list_splits(p.nmax), ev, Nc, cand, p.D, p.Pb(), a.el, a.eg, a.lo,
-                          keys, a.flags, a.rescue};
+                          keys, a.flags, a.rescue, p.floor};
   hipLaunchKernelGGL(topk_staged_bounds_kernel, dim3((unsigned)((Nc + 1023) / 1024)), dim3(256), 0, s, ta);
   HBX_LAUNCH_CHECK();
   return hbx_topk_shortlist(a.lo, keys, Nc, k, hist, a.U, a.flags, a.list, a.count, a.rescue, ev, s);
@@ -573,7 +577,7 @@ int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int64_t inde
     rc = acq_exact(p, cand, Nc, a, false, true, s);
     if (rc) return rc;
     return hbx_topk_final(a.list, a.count, a.exact_l, a.exact_g, a.flags, index_base, k, p.Pg(), p.Pb(), a.el, a.eg,
-                          results, s);
+                          results, p.floor.f, s);
   }
   // (no timing events; the rescue pass always a launch of its own: the bounds pass does not rescue)
   const ScoreRequest rq{cand, Nc, p.D, nullptr, a.rescue, a.init(), p.nmax, false, s};
@@ -585,7 +589,7 @@ int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int64_t inde
     if (rc) return rc;
     HBX_HIP(hipMemsetAsync(hist, 0, 4 * TOPK_HIST_WORDS, s));
   } else {
-    rc = hbx_topk_bounds(a.el, a.eg, Nc, a.lo, hik, a.flags, hist, s);
+    rc = hbx_topk_bounds(a.el, a.eg, Nc, a.lo, hik, a.flags, hist, p.floor, s);
     if (rc) return rc;
   }
   rc = hbx_topk_shortlist(a.lo, plan.exact_only ? nullptr : hik, Nc, k, hist, a.U, a.flags, a.list, a.count, a.rescue,
@@ -594,7 +598,7 @@ int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int64_t inde
   rc = acq_exact(p, cand, Nc, a, false, true, s);
   if (rc) return rc;
   return hbx_topk_final(a.list, a.count, a.exact_l, a.exact_g, a.flags, index_base, k, p.Pg(), p.Pb(), a.el, a.eg,
-                        results, s);
+                        results, p.floor.f, s);
 }
 
 }  // extern "C"

@@ -13,6 +13,12 @@ Exactness across ranks: every rank's exact score is the reference's float64 valu
 (score, index) reduction is the reference's pick.  With ties='process' (see KDEPair.acquire), winners
 of different ranks within each other's numpy-build spread (``HBX_ACQ_NEAR_TIE``) are re-scored with
 this process's numpy (``exact_host``) and a second exchange of those scores decides.
+
+The ranks compare scores, so every rank must fit and bind its pair under the SAME acquisition rules
+(``min_bandwidth`` and ``pdf_floor`` of ``fit_pair`` / ``ObservationStore.refit`` / ``KDEPair``): shards scored
+under different floors, or against differently clipped bandwidths, reduce to a winner no single run would pick,
+and ``merge_topk`` would rank entries that are not comparable.  Nothing on the wire says which rules a record
+was formed under; the floor travels with each rank's pair (``pair.pdf_floor``), which the host re-score uses too.
 """
 
 import struct
@@ -55,7 +61,7 @@ def reduce_records_host(recs):
 
 def merge_topk(parts, k):
     """The global top-k of a candidate-sharded pool from the shards' TopK results (KDEPair.acquire_topk on each
-    shard with its ``index_base``, so the indices are global): the first k entries by (score, index) over all
+    shard with its ``index_base``, so the indices are global; every shard's pair under the same rules): the first k entries by (score, index) over all
     parts -- what acquire_topk(k) over the whole pool returns, since every shard returns its own k best and
     each entry of the global top-k is among its shard's.  Pure host code, no collective: any transport may
     gather the blocks.  ``count`` can be below k (parts with few or no rankable candidates); ``shortlist`` adds
@@ -238,7 +244,7 @@ def acquire_sharded(pair, cands_local, index_base, exchange, stream=None, worksp
             idx = np.unique(ws[o[1]:o[1] + 4 * cnt].view(torch.int32).cpu().numpy().astype(np.int64))
             if idx.size == 0:
                 idx = np.array([mine.index - index_base], dtype=np.int64)
-            pick = exact_host.resolve(pair.good, pair.bad, _rows_of(cands_local, idx), idx)
+            pick = exact_host.resolve(pair.good, pair.bad, _rows_of(cands_local, idx), idx, pair.pdf_floor)
         if pick is None:
             raw = struct.pack(RESULT_FMT, -1, np.nan, 0.0, 0, 0, 0, np.nan, np.nan)
         else:

@@ -7,7 +7,7 @@ another numpy; each exact score carries the relative spread that can cause (``Ac
 request, candidates within that spread of the winner (flag ``HBX_ACQ_NEAR_TIE``) are re-ordered here,
 on the host, with the very numpy expressions the reference evaluates -- KDEMultivariate.pdf (statsmodels 0.12.2 kernel_density.py:162-196) -> gpke
 (_kernel_base.py:456-518) -> gaussian / aitchison_aitken (kernels.py:108-125, 23-65) -- and BOHB's
-``max(1e-8, g) / max(l, 1e-8)`` with a strict ``<`` over the candidates in index order
+``max(f, g) / max(l, f)`` (f = 1e-8, or the pair's score floor) with a strict ``<`` over the candidates in index order
 (bohb.py:129, 149-152).  This is part of the engine (a few candidates, a few numpy calls each), not
 a fallback: by default the GPU's pinned-reference pick is final.  The KDEs' rows are in the
 reference's order even where losses tie (the refit's argsort is numpy's, hbx_npsort.h), so these
@@ -47,21 +47,24 @@ def kde_pdf(data, bw, var_type, nlev, x):
         return dens.sum(axis=0) / data.shape[0]
 
 
-def bohb_score(l, g):
-    """bohb.py:129 with Python max() semantics (NaN g -> 1e-8, NaN l -> NaN)."""
-    return max(CLAMP, g) / max(l, CLAMP)
+def bohb_score(l, g, floor=CLAMP):
+    """bohb.py:129 with Python max() semantics (NaN g -> floor, NaN l -> NaN) and the score floor ``floor``
+    (the reference snapshot's 1e-8 unless the pair carries another).  Both operands are positive or NaN, so
+    Python's division is the IEEE one: an l of +inf gives 0, inf / inf NaN."""
+    return max(floor, g) / max(l, floor)
 
 
-def resolve(good, bad, rows, indices):
+def resolve(good, bad, rows, indices, floor=CLAMP):
     """Among candidates ``indices`` (rows[k] = the candidate's coordinates), the reference's pick:
     strict '<' in index order against best = +inf.  good/bad: objects with .data, .bw, .var_type,
-    .nlev (DeviceKDE).  Returns (index, score, pdf_l, pdf_g) or None when no score is finite."""
+    .nlev (DeviceKDE); ``floor``: the pair's score floor.  Returns (index, score, pdf_l, pdf_g) or None when no
+    score is finite."""
     order = np.argsort(np.asarray(indices), kind="stable")
     best, pick = np.inf, None
     for k in order:
         l = float(kde_pdf(good.data, good.bw, good.var_type, good.nlev, rows[k]))
         g = float(kde_pdf(bad.data, bad.bw, bad.var_type, bad.nlev, rows[k]))
-        s = bohb_score(l, g)
+        s = bohb_score(l, g, floor)
         if s < best:
             best, pick = s, (int(indices[k]), s, l, g)
     return pick

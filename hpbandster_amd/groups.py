@@ -20,6 +20,8 @@ steps.  Every pick is the reference's (bohb.py:124-169 on that bracket's pair): 
 for bit.  The drop-in ``BOHB`` class is not involved; this is the batched engine surface.
 """
 
+import ctypes
+
 import numpy as np
 
 from . import _native as N
@@ -277,8 +279,19 @@ class GroupModel(object):
     ``nlev_good``, ``nlev_bad``)."""
 
     def __init__(self, **kw):
+        self.pdf_floor, self.min_bandwidth = N.PDF_FLOOR_DEFAULT, 0.0  # the rules it was fitted under (fit_groups)
         self.__dict__.update(kw)
         self._host = None
+        # the hbx_rules block of the rules-taking calls; None under the reference snapshot's floor, where the
+        # calls are the ones without it
+        self._rules = None if self.pdf_floor == N.PDF_FLOOR_DEFAULT else N.rules(self.pdf_floor, self.min_bandwidth)
+
+    def _call(self, name, *args):
+        """Entry point ``name``, or under another score floor its rules-taking form with the model's rules."""
+        if self._rules is None:
+            N.check(getattr(N.lib(), name)(*args))
+        else:
+            N.check(getattr(N.lib(), name + "_r")(*(args + (ctypes.addressof(self._rules),))))
 
     # ---- host views (checks and debugging) --------------------------------------------------------------
     def bandwidths(self):
@@ -307,7 +320,7 @@ class GroupModel(object):
         s, e = int(self.seg_host[b]), int(self.seg_host[b + 1])
         g, bd = self.rows_of(b)
         return kde.fit_pair_from_rows(h["X"][s:e], g, bd, self.var_type, h["bw"][0][b], h["bw"][1][b],
-                                      h["nlev"][0][b], h["nlev"][1][b], device=self.device)
+                                      h["nlev"][0][b], h["nlev"][1][b], device=self.device, pdf_floor=self.pdf_floor)
 
     # ---- the grouped calls ------------------------------------------------------------------------------
     def sample(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, stream_id=0, requests=None):
@@ -341,8 +354,8 @@ class GroupModel(object):
         return int(N.lib().hbx_kde_groups_batch_workspace_bytes(self.B, int(requests), int(C), self.D))
 
     def acquire(self, cands, stream=None, workspace=None, sync=True):
-        """Per group the first index minimising max(1e-8, g)/max(l, 1e-8) over its own pool ``cands[b]``
-        (hbx_kde_acquire_groups).  ``cands``: [B, C, D] float64, numpy or a device tensor.  Returns GroupPicks, or
+        """Per group the first index minimising max(f, g)/max(l, f) over its own pool ``cands[b]``, f the model's
+        ``pdf_floor`` (hbx_kde_acquire_groups; under another floor than 1e-8 its S = 1 rules-taking form).  ``cands``: [B, C, D] float64, numpy or a device tensor.  Returns GroupPicks, or
         with ``sync=False`` the device tensor of the B records (uint8 [B, 48])."""
         torch = kde._torch()
         with N.on_device(self.device, stream):
@@ -362,11 +375,15 @@ class GroupModel(object):
             if ws.numel() < wsb:
                 raise N.HbxError("workspace too small")
             res = torch.empty((self.B, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device)
-            N.check(N.lib().hbx_kde_acquire_groups(
+            model = (
                 N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
                 N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
-                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), C, N.ptr(res), N.ptr(ws), ws.numel(),
-                N.stream_handle(stream, self.device)))
+                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd))
+            tail = (N.ptr(res), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device))
+            if self._rules is None:
+                N.check(N.lib().hbx_kde_acquire_groups(*(model + (C,) + tail)))
+            else:  # (the batched call's S = 1 case is this call: include/hbx.h)
+                self._call("hbx_kde_acquire_groups_batch", *(model + (1, C) + tail))
             if not sync:
                 return res
             return GroupPicks.from_bytes(res.cpu().numpy().tobytes(), self.B)
@@ -395,11 +412,12 @@ class GroupModel(object):
             if ws.numel() < wsb:
                 raise N.HbxError("workspace too small")
             res = torch.empty((self.B, S, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device)
-            N.check(N.lib().hbx_kde_acquire_groups_batch(
+            self._call(
+                "hbx_kde_acquire_groups_batch",
                 N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
                 N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
                 N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), S, C, N.ptr(res), N.ptr(ws), ws.numel(),
-                N.stream_handle(stream, self.device)))
+                N.stream_handle(stream, self.device))
             if not sync:
                 return res
             return GroupPicks.from_bytes(res.cpu().numpy().tobytes(), self.B, S)
@@ -434,11 +452,12 @@ class GroupModel(object):
                 raise N.HbxError("workspace too small")
             res = torch.empty((self.B, kde.TOPK_HEAD_BYTES + kde.TOPK_REC.itemsize * k), dtype=torch.uint8,
                               device=self.device)
-            N.check(N.lib().hbx_kde_acquire_groups_topk(
+            self._call(
+                "hbx_kde_acquire_groups_topk",
                 N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
                 N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
                 N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), C, k, N.ptr(res), N.ptr(ws), ws.numel(),
-                N.stream_handle(stream, self.device)))
+                N.stream_handle(stream, self.device))
             if not sync:
                 return res
             return GroupTopK.from_bytes(res.cpu().numpy().tobytes(), self.B, k)
@@ -527,13 +546,14 @@ class GroupModel(object):
             source = torch.empty(self.B * S, dtype=torch.uint8, device=self.device)
             rec = torch.empty((self.B * S, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device) if records else None
             cands = torch.empty((self.B, S, C, self.D), dtype=torch.float64, device=self.device) if keep_pools else None
-            N.check(N.lib().hbx_kde_propose_groups(
+            self._call(
+                "hbx_kde_propose_groups",
                 N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
                 N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
                 N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(lvd), float(bandwidth_factor), rf,
                 int(seed) & (2 ** 64 - 1), int(counter_base) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF, S, C,
                 N.ptr(rows), N.ptr(source), N.ptr(rec), N.ptr(cands), N.ptr(ws), ws.numel(),
-                N.stream_handle(stream, self.device)))
+                N.stream_handle(stream, self.device))
             err = None
             if keep_pools:
                 off = np.zeros(4, dtype=np.int64)
@@ -613,10 +633,15 @@ def group_sizes(lens, D, min_points=None, top_n_percent=15):
     return ng, nb
 
 
-def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, device=None, stream=None):
+def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, device=None, stream=None,
+               min_bandwidth=None, pdf_floor=N.PDF_FLOOR_DEFAULT):
     """Refit every bracket's good / bad KDE in one batched call (hbx_seg_argsort_ex in numpy's order, then
     hbx_kde_fit), everything kept on the device.  ``X`` [N, D], ``losses`` [N] and ``seg_off`` [B + 1] are host
-    arrays or device tensors; ``min_points`` defaults to D + 1 (BOHB's).  Returns a GroupModel."""
+    arrays or device tensors; ``min_points`` defaults to D + 1 (BOHB's).  ``min_bandwidth`` (None = 0: no clip):
+    every fitted bandwidth becomes ``np.clip(bw, min_bandwidth, None)`` where the fit stores it; ``pdf_floor``: the
+    floor f of the score max(f, g)/max(l, f) the model's acquisitions form (default 1e-8, the reference snapshot's).
+    Returns a GroupModel, which carries both."""
+    pdf_floor, min_bandwidth = N.check_pdf_floor(pdf_floor), N.check_min_bandwidth(min_bandwidth)
     torch = kde._torch()
     L = N.lib()
     D = len(var_type)
@@ -665,12 +690,17 @@ def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, 
             scr = torch.empty(sb, dtype=torch.uint8, device=device)
             N.check(L.hbx_seg_argsort_ex(N.ptr(ld), N.ptr(segd), B, int(lens.max()), Ntot, N.ptr(order), N.ptr(scr),
                                          sb, N.ORDER_NUMPY, sh))
-            N.check(L.hbx_kde_fit(N.ptr(Xd), D, N.ptr(segd), B, N.ptr(order), N.ptr(ngd), N.ptr(nbd), N.ptr(fgd),
-                                  N.ptr(fbd), N.ptr(vtd), N.ptr(bwg), N.ptr(bwb), N.ptr(nlg), N.ptr(nlb), sh))
+            fit = (N.ptr(Xd), D, N.ptr(segd), B, N.ptr(order), N.ptr(ngd), N.ptr(nbd), N.ptr(fgd),
+                   N.ptr(fbd), N.ptr(vtd), N.ptr(bwg), N.ptr(bwb), N.ptr(nlg), N.ptr(nlb), sh)
+            if min_bandwidth == 0.0:  # no clip: the call as it has always been
+                N.check(L.hbx_kde_fit(*fit))
+            else:
+                r = N.rules(pdf_floor, min_bandwidth)
+                N.check(L.hbx_kde_fit_r(*(fit + (ctypes.addressof(r),))))
     return GroupModel(B=B, D=D, var_type=var_type, device=device, X=Xd, losses=ld, seg_off=segd, seg_host=seg_h,
                       order=order, n_good=ng, n_bad=nb, has_model=(ng > 0), n_good_dev=ngd, n_bad_dev=nbd,
                       fac_good_dev=fgd, fac_bad_dev=fbd, vt_dev=vtd, bw_good=bwg, bw_bad=bwb, nlev_good=nlg,
-                      nlev_bad=nlb)
+                      nlev_bad=nlb, pdf_floor=pdf_floor, min_bandwidth=min_bandwidth)
 
 
 class GroupBOHB(object):
@@ -682,8 +712,17 @@ class GroupBOHB(object):
     per dim), ``levels``: D level counts (0: continuous)."""
 
     def __init__(self, B, var_type, levels, min_points_in_model=None, top_n_percent=15, num_samples=64,
-                 random_fraction=1.0 / 3, bandwidth_factor=3, seed=0, device=None):
+                 random_fraction=1.0 / 3, bandwidth_factor=3, seed=0, device=None, min_bandwidth=None,
+                 pdf_floor=N.PDF_FLOOR_DEFAULT):
         self.B, self.var_type, self.D = int(B), var_type, len(var_type)
+        # the acquisition rules every refit and get_config of this optimiser uses (fit_groups)
+        self.min_bandwidth, self.pdf_floor = N.check_min_bandwidth(min_bandwidth), N.check_pdf_floor(pdf_floor)
+        # (named only where they differ from the reference snapshot's: the refit call is then the one it always was)
+        self._rules_kw = {}
+        if self.min_bandwidth != 0.0:
+            self._rules_kw["min_bandwidth"] = self.min_bandwidth
+        if self.pdf_floor != N.PDF_FLOOR_DEFAULT:
+            self._rules_kw["pdf_floor"] = self.pdf_floor
         self.levels = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
         if self.levels.shape != (self.D,):
             raise N.HbxError("levels must have %d entries" % self.D)
@@ -729,7 +768,7 @@ class GroupBOHB(object):
             return False
         gm = fit_groups(self.configs[budget].reshape(self.B * n, self.D), self.losses[budget].reshape(-1),
                         np.arange(self.B + 1, dtype=np.int64) * n, self.var_type, self.min_points_in_model,
-                        self.top_n_percent, device=self.device)
+                        self.top_n_percent, device=self.device, **self._rules_kw)
         if not np.all(gm.has_model):  # bohb.py:234-237: the previous model, if any, stays
             return False
         self.kde_models[budget] = gm

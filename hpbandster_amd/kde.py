@@ -6,7 +6,7 @@ The arithmetic mirrors the reference path exactly:
 * bandwidth:  statsmodels 0.12.2 _kernel_base.py:250-265 -- 1.06 * np.std(X, 0) * n**(-1/(4+D))
 * levels:     statsmodels kernels.py:59-60 -- observed np.unique(column).size per categorical dim
 * pdf:        statsmodels kernel_density.py:162-196 / _kernel_base.py:456-518 (gpke)
-* selection:  bohb.py:129,149-152 -- max(1e-8, g)/max(l, 1e-8), strict '<', first index wins
+* selection:  bohb.py:129,149-152 -- max(f, g)/max(l, f) (f = 1e-8, or the pair's pdf_floor), strict '<', first index wins
 
 Everything that touches observations x candidates runs in libhbx.so (HIP, gfx950).  The host
 side does O(D) bookkeeping only: the BOHB size rule, the pow() factor of the bandwidth rule (so it
@@ -418,9 +418,12 @@ class KDEPair(object):
     concurrent ``get_config`` always sees a consistent snapshot.
     """
 
-    def __init__(self, good, bad):
+    def __init__(self, good, bad, pdf_floor=N.PDF_FLOOR_DEFAULT):
+        """``pdf_floor``: the floor f of the score max(f, g)/max(l, f) every acquisition on this pair forms
+        (finite, in [1e-100, 1]; default 1e-8, the reference snapshot's -- released hpbandster uses 1e-32)."""
         self.good = good
         self.bad = bad
+        self.pdf_floor = N.check_pdf_floor(pdf_floor)
         if (good.dc_pad, good.du_pad) != (bad.dc_pad, bad.du_pad):
             raise N.HbxError("good/bad KDEs prepared for different kernel buckets")
         self.nmax = max(good.nobs, bad.nobs)
@@ -445,6 +448,9 @@ class KDEPair(object):
             bad.X_dev.data_ptr(), bad.rows_dev.data_ptr(), bad.variant, good.dc_pad, good.du_pad, self.nmax)
         if not self._bound:
             raise N.HbxError("hbx_kde_pair_bind: %s" % L.hbx_last_error().decode())
+        if self.pdf_floor != N.PDF_FLOOR_DEFAULT:  # the handle carries the floor to every acquisition
+            r = N.rules(self.pdf_floor)
+            N.check(L.hbx_kde_pair_set_rules(self._bound, ctypes.addressof(r)))
 
     def __del__(self):
         b, self._bound = getattr(self, "_bound", None), None
@@ -526,7 +532,7 @@ class KDEPair(object):
 
     def acquire(self, cands, index_base=0, logs=False, stream=None, workspace=None, sync=True, events=None,
                 ties="pinned"):
-        """Select the first index minimising max(1e-8, g)/max(l, 1e-8) over the candidates.
+        """Select the first index minimising max(f, g)/max(l, f) over the candidates (f: the pair's ``pdf_floor``).
 
         ``cands``: [Nc, D] float64 (numpy or a device tensor).  Returns AcqResult (index -1 when no
         candidate has a finite score: the reference then falls back to a random configuration).
@@ -540,10 +546,10 @@ class KDEPair(object):
 
         Without ``logs``, large calls whose KDEs both run the coarse 32x32 kernel are scored in stages: the
         good KDE for every candidate, the bad KDE only where l alone does not rule the candidate out
-        (score >= 1e-8 / max(l, 1e-8) whatever g is).  The pick -- ``index``, ``score``, ``pdf_l``, ``pdf_g``,
+        (score >= f / max(l, f) whatever g is).  The pick -- ``index``, ``score``, ``pdf_l``, ``pdf_g``,
         and with them ``near`` and ``rel`` -- is the unstaged call's, exactly.  ``shortlist`` and
         ``ACQ_OVERFLOW`` describe the screen, which differs: ``shortlist`` is normally equal or lower by one
-        (the first certain 1e-8/1e-8 tie, when it was pruned and cannot win); the evaluated candidates' fp32
+        (the first certain f/f tie, when it was pruned and cannot win); the evaluated candidates' fp32
         estimates come from launches with their own observation splits, valid bounds but not the fused
         launch's bits, so a candidate at the very edge of the shortlist can fall on either side; a pruned
         candidate whose coarse g bound alone would have passed the overflow limit sets ``ACQ_OVERFLOW`` (and
@@ -643,7 +649,8 @@ class KDEPair(object):
 
     def acquire_topk(self, cands, k, index_base=0, stream=None, workspace=None, ties="pinned"):
         """The k best candidates of ONE pool: the first min(k, F) entries of the stable ascending order of
-        max(1e-8, g)/max(l, 1e-8) over the F candidates whose score is not NaN -- ordered by (score, index), so
+        max(f, g)/max(l, f) (f: the pair's ``pdf_floor``) over the F
+        candidates whose score is not NaN -- ordered by (score, index), so
         entry 0 is acquire()'s pick.  ``cands``: [Nc, D] float64 (numpy or a device tensor); 1 <= k <= 1024
         (k > Nc is legal).  Returns a TopK (empty when no candidate has a score: the drop-in then falls back to
         random configurations, as for acquire()'s index -1).  Only ties='pinned' is offered: the GPU's re-score
@@ -651,7 +658,7 @@ class KDEPair(object):
 
         Large calls whose KDEs both run the coarse 32x32 kernel are scored in stages like ``acquire``'s (the
         same ``HBX_STAGED`` switch; unset, from 4e9 candidates x observations): the good KDE for every candidate, the bad KDE only for
-        the seeds around the (k+1)-th largest l and for the candidates whose bound 1e-8 / max(l, 1e-8) does not
+        the seeds around the (k+1)-th largest l and for the candidates whose bound f / max(l, f) does not
         exceed the seeds' (k+1)-th smallest upper score bound.  ``count``, ``flags`` and every entry's
         ``index``, ``score``, ``pdf_l``, ``pdf_g`` and ``rel`` are the unstaged call's, exactly; ``shortlist``
         may differ (the evaluated candidates' fp32 estimates come from launches with other observation
@@ -690,7 +697,7 @@ class KDEPair(object):
         """Record ``res`` re-decided among candidates ``idx``: re-scored in the reference's numpy arithmetic, its
         strict-'<' first-index minimum taken (exact_host.resolve), the index stored with ``shift`` added."""
         from . import exact_host
-        pick = exact_host.resolve(self.good, self.bad, _rows_of(cands, idx), idx)
+        pick = exact_host.resolve(self.good, self.bad, _rows_of(cands, idx), idx, self.pdf_floor)
         if pick is not None:
             res.index, res.score, res.pdf_l, res.pdf_g = pick[0] + shift, pick[1], pick[2], pick[3]
         res.flags |= ACQ_RESOLVED
@@ -912,21 +919,26 @@ class ObservationStore(object):
     def losses_host(self):
         return self._lh[:self.nh]
 
-    def refit(self, min_points, top_n_percent=15, split_rule="bohb", stream=None):
+    def refit(self, min_points, top_n_percent=15, split_rule="bohb", stream=None, min_bandwidth=None,
+              pdf_floor=N.PDF_FLOOR_DEFAULT):
         """Refit on every row added so far (bohb.py:220-251).  Returns a KDEPair, or None where the reference
         builds no model (too few rows for a KDE, bohb.py:234-237).  The row-count gate before it
-        (``len <= min_points + 1``: no refit, bohb.py:216-217) is the caller's, as in new_result."""
+        (``len <= min_points + 1``: no refit, bohb.py:216-217) is the caller's, as in new_result.
+        ``min_bandwidth`` (None = 0: no clip): every fitted bandwidth of both KDEs becomes
+        ``np.clip(bw, min_bandwidth, None)`` where the fit stores it -- the pair's ``bw``, its tables, samplers and
+        exact re-score all hold the clipped values.  ``pdf_floor``: the returned pair's score floor (KDEPair)."""
+        rules = (N.check_pdf_floor(pdf_floor), N.check_min_bandwidth(min_bandwidth))
         n = self.nh
         sizes = split_sizes(n, self.D, min_points, top_n_percent, split_rule)
         if sizes is None:
             return None
         sh = N.home_stream(self.device.index) if stream is None else None
         if sh is not None:
-            return self._refit(self._Xh[:n], self._lh[:n], n, sizes, sh)  # (already current: no context)
+            return self._refit(self._Xh[:n], self._lh[:n], n, sizes, sh, rules)  # (already current: no context)
         with N.on_device(self.device, stream):
-            return self._refit(self._Xh[:n], self._lh[:n], n, sizes, N.stream_handle(stream, self.device))
+            return self._refit(self._Xh[:n], self._lh[:n], n, sizes, N.stream_handle(stream, self.device), rules)
 
-    def _refit(self, X_host, losses, n, sizes, sh):
+    def _refit(self, X_host, losses, n, sizes, sh, rules=(N.PDF_FLOOR_DEFAULT, 0.0)):
         torch = _torch()
         L = N.lib()
         D = self.D
@@ -958,10 +970,15 @@ class ObservationStore(object):
         # the output block lands in a fresh host array when the call returns (published by the preparation's
         # last workgroups through mapped host memory): its pieces are views, no copies
         ah = np.empty(ob, dtype=np.uint8)
-        N.check(L.hbx_kde_refit_sync(N.ptr(self.X_dev), N.ptr(self.loss_dev), n, D, N.ptr(self.vt),
-                                     staged.ctypes.data if staged is not None else None, n_new, n_good, n_bad,
-                                     bandwidth_factor(n_good, D), bandwidth_factor(n_bad, D), pg._ptr,
-                                     tg._ptr, tgf, pbad._ptr, tb._ptr, tbf, p0, p_scr, sb, sh, ah.ctypes.data))
+        args = (N.ptr(self.X_dev), N.ptr(self.loss_dev), n, D, N.ptr(self.vt),
+                staged.ctypes.data if staged is not None else None, n_new, n_good, n_bad,
+                bandwidth_factor(n_good, D), bandwidth_factor(n_bad, D), pg._ptr,
+                tg._ptr, tgf, pbad._ptr, tb._ptr, tbf, p0, p_scr, sb, sh, ah.ctypes.data)
+        if rules[1] == 0.0:  # no clip: the call as it has always been
+            N.check(L.hbx_kde_refit_sync(*args))
+        else:
+            r = N.rules(*rules)
+            N.check(L.hbx_kde_refit_sync_r(*(args + (ctypes.addressof(r),))))
         order_h = ah[:8 * n].view(np.int64)
         o = 8 * n
         bw_gh = ah[o:o + 8 * D].view(np.float64)
@@ -977,29 +994,35 @@ class ObservationStore(object):
                          prepared=(pg, tg, info_g), home=sh)
         bad = DeviceKDE(X_dev, order[n - n_bad:], self.var_type, bw_bh, nl_bh, (X_host, order_h[n - n_bad:]),
                         prepared=(pbad, tb, info_b), home=sh)
-        pair = KDEPair(good, bad)
+        pair = KDEPair(good, bad, pdf_floor=rules[0])
         pair._keep = (blk,)  # the rows tensors are views of the refit's block
         return pair
 
 
 def fit_pair(configs, losses, var_type, min_points, top_n_percent=15, device=None, stream=None,
-             split_rule="bohb"):
+             split_rule="bohb", min_bandwidth=None, pdf_floor=N.PDF_FLOOR_DEFAULT):
     """Refit the good/bad KDEs of one budget on the GPU (BOHB.new_result, bohb.py:220-251) from host
     arrays: all rows staged at once through an ObservationStore.
 
     Returns a KDEPair, or None where the reference returns without building a model.
     ``split_rule`` 'bohb' uses integer floor sizes (bohb.py:224-225) and requires rows > D;
     'kde_ei' uses int(max(top%*N/100., mp)) (kde_ei.py:190-191) and requires rows >= D.
+    ``min_bandwidth`` / ``pdf_floor``: ObservationStore.refit's.
     """
+    N.check_pdf_floor(pdf_floor), N.check_min_bandwidth(min_bandwidth)  # (before anything is moved to the device)
     X = np.ascontiguousarray(np.asarray(configs, dtype=np.float64))
     n, D = X.shape
     store = ObservationStore(D, var_type, device=device, capacity=max(n, 1))
     store.add(X, losses)
-    return store.refit(min_points, top_n_percent, split_rule, stream=stream)
+    return store.refit(min_points, top_n_percent, split_rule, stream=stream, min_bandwidth=min_bandwidth,
+                       pdf_floor=pdf_floor)
 
 
-def fit_pair_from_rows(X, good_rows, bad_rows, var_type, bw_good, bw_bad, nlev_good, nlev_bad, device=None):
-    """Build a KDEPair from an explicit split and bandwidths (tests / externally fitted models)."""
+def fit_pair_from_rows(X, good_rows, bad_rows, var_type, bw_good, bw_bad, nlev_good, nlev_bad, device=None,
+                       pdf_floor=N.PDF_FLOOR_DEFAULT):
+    """Build a KDEPair from an explicit split and bandwidths (tests / externally fitted models); ``pdf_floor``:
+    the pair's score floor (KDEPair)."""
+    pdf_floor = N.check_pdf_floor(pdf_floor)
     torch = _torch()
     device = device or default_device()
     X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
@@ -1009,4 +1032,4 @@ def fit_pair_from_rows(X, good_rows, bad_rows, var_type, bw_good, bw_bad, nlev_g
         rb = torch.from_numpy(np.asarray(bad_rows, dtype=np.int64)).to(device)
         good = DeviceKDE(X_dev, rg, var_type, bw_good, nlev_good, X[np.asarray(good_rows)])
         bad = DeviceKDE(X_dev, rb, var_type, bw_bad, nlev_bad, X[np.asarray(bad_rows)])
-    return KDEPair(good, bad)
+    return KDEPair(good, bad, pdf_floor=pdf_floor)

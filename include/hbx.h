@@ -55,6 +55,25 @@ extern "C" {
 #define HBX_ERR_HIP (-2)
 #define HBX_ERR_UNSUPPORTED (-3)
 
+/* ---- acquisition rules ----------------------------------------------------------------------
+ * Two constants of the reference snapshot that releases of the package changed, as parameters.  Wherever a
+ * `const hbx_rules*` is taken, NULL means {1e-8, 0}: the reference snapshot's numerics, which is also what every
+ * entry point without the argument computes.
+ *   pdf_floor f      the score of a candidate is (g > f ? g : f) / (f > l ? f : l) in fp64 (bohb.py:129 with
+ *                    f = 1e-8; Python max(): a NaN g gives f, a NaN l gives NaN).  Everything else of the selection
+ *                    -- strict '<' and first index, (score, index) for the top-k, rel, the near-tie rule, the
+ *                    flags -- is unchanged, and candidates with both pdfs below f still score exactly f / f = 1.
+ *                    An l of +inf scores 0 (NaN when g is +inf too).  Accepted: finite, 1e-100 <= f <= 1.
+ *   min_bandwidth m  every fitted bandwidth, continuous or categorical, becomes bw < m ? m : bw
+ *                    (np.clip(bw, m, None): NaN stays NaN).  Accepted: finite, m >= 0; 0 changes nothing.
+ *                    Range-checked by every rules-taking entry point; the score-forming ones make no other use
+ *                    of it.
+ * Anything outside the accepted ranges is HBX_ERR_ARG. */
+typedef struct {
+  double pdf_floor;
+  double min_bandwidth;
+} hbx_rules;
+
 /* ---- introspection ---------------------------------------------------------------------- */
 const char* hbx_last_error(void);
 const char* hbx_version(void);
@@ -100,6 +119,13 @@ int hbx_kde_fit(const double* X, int32_t D, const int64_t* seg_off, int64_t B, c
                 const int32_t* vartype, double* bw_good, double* bw_bad, int32_t* nlev_good, int32_t* nlev_bad,
                 void* stream);
 
+/* hbx_kde_fit with every fitted bandwidth, continuous or categorical, clipped from below where it is stored:
+ * bw < rules->min_bandwidth ? rules->min_bandwidth : bw (hbx_rules, above; NULL: hbx_kde_fit itself). */
+int hbx_kde_fit_r(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                  const int64_t* n_good, const int64_t* n_bad, const double* fac_good, const double* fac_bad,
+                  const int32_t* vartype, double* bw_good, double* bw_bad, int32_t* nlev_good, int32_t* nlev_bad,
+                  void* stream, const hbx_rules* rules);
+
 /* One-call refit of one budget's KDE pair (bohb.py:211-251: append the new observation(s), np.argsort
  * of the losses, good = head n_good / bad = tail n_bad rows, KDEMultivariate(.., 'normal_reference') for
  * both), enqueued on `stream` without host synchronisation; the caller reads `out` back once.
@@ -120,6 +146,16 @@ int hbx_kde_refit(double* X, double* loss, int64_t n, int32_t D, const int32_t* 
                   int64_t n_new, int64_t n_good, int64_t n_bad, double fac_good, double fac_bad, void* params_good,
                   float* table_good, int64_t table_good_floats, void* params_bad, float* table_bad,
                   int64_t table_bad_floats, void* out, void* scratch, int64_t scratch_bytes, void* stream);
+/* hbx_kde_refit with the rules' min_bandwidth applied where the fit stores the bandwidths: the output block, both
+ * parameter blocks and tables, and with them the samplers and the exact re-score, hold the clipped values.  A
+ * categorical dim whose set shows ONE level gets h = min_bandwidth > 0 there; it is modelled (hbx_kde_prepare's
+ * variant bit 5: every candidate decided by the fp64 evaluation, match factor 1 - h, mismatch factor the IEEE
+ * h / 0 = +inf).  NULL: hbx_kde_refit itself. */
+int hbx_kde_refit_r(double* X, double* loss, int64_t n, int32_t D, const int32_t* vartype, const double* staged,
+                    int64_t n_new, int64_t n_good, int64_t n_bad, double fac_good, double fac_bad, void* params_good,
+                    float* table_good, int64_t table_good_floats, void* params_bad, float* table_bad,
+                    int64_t table_bad_floats, void* out, void* scratch, int64_t scratch_bytes, void* stream,
+                    const hbx_rules* rules);
 /* hbx_kde_refit with `staged_host` in HOST memory (rows, then losses: n_new*(D+1) doubles; up to 256 staged
  * doubles of a budget of at most 1024 rows ride in the kernel arguments of the refit's first launch, no
  * host-to-device copy; more go through `scratch`), synchronous: when the call returns, `out_host` (host memory,
@@ -134,6 +170,12 @@ int hbx_kde_refit_sync(double* X, double* loss, int64_t n, int32_t D, const int3
                        double fac_bad, void* params_good, float* table_good, int64_t table_good_floats,
                        void* params_bad, float* table_bad, int64_t table_bad_floats, void* out, void* scratch,
                        int64_t scratch_bytes, void* stream, void* out_host);
+/* hbx_kde_refit_sync under rules (as hbx_kde_refit_r; NULL: hbx_kde_refit_sync itself) */
+int hbx_kde_refit_sync_r(double* X, double* loss, int64_t n, int32_t D, const int32_t* vartype,
+                         const double* staged_host, int64_t n_new, int64_t n_good, int64_t n_bad, double fac_good,
+                         double fac_bad, void* params_good, float* table_good, int64_t table_good_floats,
+                         void* params_bad, float* table_bad, int64_t table_bad_floats, void* out, void* scratch,
+                         int64_t scratch_bytes, void* stream, void* out_host, const hbx_rules* rules);
 /* Order stream `waiter` after all work enqueued on `signaller` so far (event record + stream wait, no host
  * wait): a model refit / prepared on one stream, used from another. */
 int hbx_stream_order(void* waiter, void* signaller);
@@ -154,8 +196,9 @@ int64_t hbx_kde_table_floats(int32_t n, int32_t dc_pad, int32_t du_pad);
  *   bits 1-3  kc: 0 = categorical matching on the VALU; >= 1 = categorical one-hot product on the f16 matrix
  *             cores with kc K-steps
  *   bit 4     hmode: the whole exponent on the f16 matrix cores
- *   bit 5     exact_only: outside every fp32 scoring bucket (> 64 continuous / > 32 categorical dims): every
- *             candidate is evaluated in fp64
+ *   bit 5     exact_only: outside every fp32 scoring bucket (> 64 continuous / > 32 categorical dims), or a
+ *             categorical dim with ONE observed level under a finite bandwidth h > 0 (match factor 1 - h, mismatch
+ *             factor h / 0 = +inf: the pdf is finite, +inf or NaN): every candidate is evaluated in fp64
  *   bit 6     h32: the 32x32-tile kernels (with bit 4)
  *   bit 7     coarse: the table also holds the coarse layout of the acquisition's pre-screen instance
  *   bit 8     small_codes: <= 8 categorical slots, every code in [0, 3] (hbx_kde_logpdf_rtol's table look-up) */
@@ -172,7 +215,8 @@ int hbx_kde_logpdf(const double* cand, int64_t Nc, int32_t D, const void* params
 int64_t hbx_kde_workspace_bytes(int64_t Nc, int64_t nmax);
 
 /* One acquisition: l = good KDE, g = bad KDE; selects the first index of the minimum of
- * max(1e-8, g)/max(l, 1e-8) over the candidates, exactly (fp64 re-score of every candidate whose
+ * max(f, g)/max(l, f) over the candidates (f: the pair's pdf_floor, hbx_kde_pair_set_rules; 1e-8 unless set),
+ * exactly (fp64 re-score of every candidate whose
  * fp32 score interval reaches the minimum).  index_base is added to the reported index (GPU
  * sharding).  logl_out/logg_out: nullable device f32[Nc]: the fp32 ln pdf point estimates the
  * selection used (-inf for pdf <= 0, NaN for NaN).  Each lies within its own rigorous bound (what keeps
@@ -208,6 +252,10 @@ void* hbx_kde_pair_bind(int32_t D, const void* params_good, const float* table_g
                         const int64_t* rows_good, int32_t variant_good, const void* params_bad,
                         const float* table_bad, const double* X_bad, const int64_t* rows_bad, int32_t variant_bad,
                         int32_t dc_pad, int32_t du_pad, int64_t nmax);
+/* The rules of every later acquisition on the handle (hbx_kde_acquire, _bound, _batch, _topk, staged or not): their
+ * scores are formed with rules->pdf_floor.  A new handle has the reference snapshot's; NULL restores them.  Not to
+ * be called while another thread runs an acquisition on the same handle. */
+int hbx_kde_pair_set_rules(void* pair, const hbx_rules* rules);
 int hbx_kde_acquire_bound(const void* pair, const double* cand, int64_t Nc, int64_t index_base, void* workspace,
                           int64_t ws_bytes, const uint8_t* err, void* events, void* stream, void* rec_out,
                           double* row_out);
@@ -226,7 +274,7 @@ int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int64_t i
 
 /* Top-k acquisition: the k best candidates of ONE pool, ranked exactly.  Where hbx_kde_acquire keeps the
  * first candidate of the smallest score (bohb.py:149-152: `if val < best`), this returns the first
- * min(k, F) entries of the stable ascending order of the score s = max(1e-8, g)/max(l, 1e-8) over the F
+ * min(k, F) entries of the stable ascending order of the score s = max(f, g)/max(l, f) (f: the pair's pdf_floor) over the F
  * candidates whose score is not NaN: ordered by (s[i], i), so equal scores come out in index order and entry 0
  * is hbx_kde_acquire's pick (index, score and both pdfs bit-identical).  The scoring launch and the exact fp64
  * re-score are hbx_kde_acquire's (fast scoring instances); the shortlist is taken against the k-th smallest
@@ -244,7 +292,7 @@ int hbx_kde_acquire_batch(const double* cand, int64_t Nc, int64_t seg, int64_t i
  * nmax) (-1 for k out of range, as hbx_kde_topk_result_bytes).  Bad arguments: HBX_ERR_ARG (hbx_last_error).
  * Large calls on pairs the staged scoring serves (below, at hbx_kde_acquire_stats; the same HBX_STAGED switch, a
  * size threshold of its own, 4e9 candidates x observations) score g only for the candidates that can still rank: the seeds around the (k+1)-th largest l
- * and the candidates whose l-only bound 1e-8 / max(l, 1e-8) does not exceed the seeds' (k+1)-th smallest upper
+ * and the candidates whose l-only bound f / max(l, f) does not exceed the seeds' (k+1)-th smallest upper
  * score bound.  count, flags and every record's index, score, pdf_l, pdf_g and rel are the unstaged call's,
  * exactly; the header's `shortlist` describes the screen and may differ (the evaluated candidates' fp32 estimates
  * come from launches with other observation splits).  The workspace begins with hbx_kde_acquire's, so
@@ -302,6 +350,14 @@ int hbx_kde_acquire_groups_batch(const double* X, int32_t D, const int64_t* seg_
                                  const int32_t* nlev_good, const int32_t* nlev_bad,
                                  const double* cand, int64_t S, int64_t C, void* results,
                                  void* workspace, int64_t ws_bytes, void* stream);
+/* hbx_kde_acquire_groups_batch with the scores formed under rules->pdf_floor (NULL: the same call); S = 1 is
+ * hbx_kde_acquire_groups under those rules. */
+int hbx_kde_acquire_groups_batch_r(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                   const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                   const double* bw_good, const double* bw_bad,
+                                   const int32_t* nlev_good, const int32_t* nlev_bad,
+                                   const double* cand, int64_t S, int64_t C, void* results,
+                                   void* workspace, int64_t ws_bytes, void* stream, const hbx_rules* rules);
 /* Grouped top-k: the k best candidates of every bracket's own pool in one call -- hbx_kde_acquire_topk's answer for
  * each of hbx_kde_acquire_groups' B groups.  The model arguments are hbx_kde_acquire_groups', unchanged; cand:
  * f64[B][C][D]; 1 <= k <= HBX_TOPK_MAX_K, k > C is legal.  results: B blocks of hbx_kde_topk_result_bytes(k) =
@@ -328,6 +384,13 @@ int hbx_kde_acquire_groups_topk(const double* X, int32_t D, const int64_t* seg_o
                                 const int32_t* nlev_good, const int32_t* nlev_bad,
                                 const double* cand, int64_t C, int32_t k, void* results,
                                 void* workspace, int64_t ws_bytes, void* stream);
+/* hbx_kde_acquire_groups_topk with the scores formed under rules->pdf_floor (NULL: the same call) */
+int hbx_kde_acquire_groups_topk_r(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                  const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                  const double* bw_good, const double* bw_bad,
+                                  const int32_t* nlev_good, const int32_t* nlev_bad,
+                                  const double* cand, int64_t C, int32_t k, void* results,
+                                  void* workspace, int64_t ws_bytes, void* stream, const hbx_rules* rules);
 /* Grouped ln-pdf: ln l(x) and ln g(x) for every candidate of every bracket's pool in one call -- hbx_kde_logpdf_rtol's
  * contract for each of hbx_kde_acquire_groups' B groups.  The model arguments are hbx_kde_acquire_groups', unchanged,
  * read where hbx_kde_fit left them (no KdeParams, no table, no prepare); cand: f64[B][C][D] (S requests per group:
@@ -417,6 +480,15 @@ int hbx_kde_propose_groups(const double* X, int32_t D, const int64_t* seg_off, i
                            double bandwidth_factor, double random_fraction, uint64_t seed, uint64_t counter_base,
                            uint32_t stream_id, int64_t S, int64_t C, double* rows_out, uint8_t* source_out,
                            void* records_out, double* cands_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* hbx_kde_propose_groups with hbx_kde_acquire_groups_batch_r in the middle of the composition (NULL: the same call) */
+int hbx_kde_propose_groups_r(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                             const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                             const double* bw_good, const double* bw_bad,
+                             const int32_t* nlev_good, const int32_t* nlev_bad, const int32_t* levels,
+                             double bandwidth_factor, double random_fraction, uint64_t seed, uint64_t counter_base,
+                             uint32_t stream_id, int64_t S, int64_t C, double* rows_out, uint8_t* source_out,
+                             void* records_out, double* cands_out, void* workspace, int64_t workspace_bytes, void* stream,
+                             const hbx_rules* rules);
 
 /* Optional timing: `events` of hbx_kde_acquire is NULL or an array of three hipEvent_t recorded on
  * `stream` before the l scoring launch, between l and g, and after g -- or, when l and g are scored by
@@ -460,9 +532,9 @@ void* hbx_kde_result_ptr(void* workspace);
 int hbx_kde_ws_offsets(int64_t Nc, int64_t seg, int64_t nmax, int64_t* out);
 /* Staged scoring of hbx_kde_acquire / hbx_kde_acquire_bound without ln-pdf outputs (both KDEs on the coarse
  * 32x32 instance, Nc * nmax large enough; environment HBX_STAGED=0: never, 2: wherever supported): l is scored for
- * every candidate, g only for the candidates l alone does not rule out (score >= 1e-8 / max(l, 1e-8) whatever g
+ * every candidate, g only for the candidates l alone does not rule out (score >= f / max(l, f) whatever g
  * is).  The pick (index, score, pdf_l, pdf_g, and with them near and rel) is the unstaged call's, exactly.  The
- * screen's own figures can differ: `shortlist` is normally equal or lower by one (the first certain 1e-8/1e-8 tie,
+ * screen's own figures can differ: `shortlist` is normally equal or lower by one (the first certain f/f tie,
  * when it was pruned and cannot win); the evaluated candidates' fp32 estimates come from launches with their own
  * observation splits -- valid bounds, not the fused launch's bits -- so a candidate at the very edge of the
  * shortlist can fall on either side; a pruned candidate whose coarse g bound alone would pass the overflow limit
