@@ -92,6 +92,13 @@ SIGNATURES = {
                                          ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
                                          ctypes.c_uint32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
                                          c_vp]),
+    "hbx_kde_impute_groups_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "hbx_kde_impute_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_uint64,
+                                      ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_kde_impute_groups_host": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                           ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp]),
+    "hbx_rows_deactivate": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_rows_deactivate_host": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64]),
     "hbx_philox4x32_10": (c_i32, [c_vp, c_vp, c_vp]),
     "hbx_kde_sample": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_uint64,
                                ctypes.c_uint64, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp, c_vp]),

@@ -75,8 +75,19 @@ class SpeculativeBatch(object):
 class BOHB(base_config_generator):
     def __init__(self, configspace, min_points_in_model=None, top_n_percent=15, num_samples=64,
                  random_fraction=1 / 3, bandwidth_factor=3, device=None, sampler="host", sampler_seed=None,
-                 speculative="auto", min_bandwidth=None, pdf_floor=_native.PDF_FLOOR_DEFAULT, **kwargs):
+                 speculative="auto", min_bandwidth=None, pdf_floor=_native.PDF_FLOOR_DEFAULT, impute_seed=0,
+                 **kwargs):
         super().__init__(**kwargs)
+        # conditional search spaces (the configspace reports conditions): an observation holds NaN where a
+        # hyperparameter is inactive.  Its store accepts such rows, a refit over rows with a NaN imputes them on the
+        # device first (the releases' impute_conditional_data; include/hbx.h hbx_kde_impute_groups) under
+        # impute_seed, on the Philox counters [k * cap, ...): k the store's imputing refits so far, cap twice the
+        # store's row capacity -- never less than the refit's view rows, and it only grows, so no two refits of a
+        # budget share a counter.  Every model-based proposal passes through deactivate_inactive_hyperparameters.
+        # A space without conditions reaches none of this.
+        self.impute_seed = int(impute_seed)
+        self._conditional = bool(getattr(configspace, "get_conditions", lambda: [])())
+        self._impute_refits = dict()  # budget -> refits that imputed
         # the two acquisition rules that releases of the package changed after the reference snapshot (include/hbx.h,
         # hbx_rules): min_bandwidth -- every fitted bandwidth becomes np.clip(bw, min_bandwidth, None) (None: no
         # clip, the snapshot's; the releases' constructor default is 1e-3) -- and pdf_floor, the f of the score
@@ -197,7 +208,7 @@ class BOHB(base_config_generator):
                 else:
                     if self.logger.isEnabledFor(logging.DEBUG):  # (formatting the vector costs ~0.1 ms)
                         self.logger.debug('best_vector: {}, {}'.format(best_vector, res.score))
-                    sample = ConfigSpace.Configuration(self.configspace, vector=best_vector).get_dictionary()
+                    sample = self._to_dict(best_vector)
                     info_dict['model_based_pick'] = True
             except _native.HbxError:
                 raise  # the engine failed: never hide it behind a random configuration
@@ -206,6 +217,14 @@ class BOHB(base_config_generator):
                 sample = self.configspace.sample_configuration().get_dictionary()
                 info_dict['model_based_pick'] = False
         return sample, info_dict
+
+    def _to_dict(self, vector):
+        """A proposed vector as the configuration's dictionary; in a conditional space its inactive hyperparameters
+        are dropped first (the model proposes a value in every dim)."""
+        if self._conditional:
+            return ConfigSpace.util.deactivate_inactive_hyperparameters(
+                configuration=None, configuration_space=self.configspace, vector=vector).get_dictionary()
+        return ConfigSpace.Configuration(self.configspace, vector=vector).get_dictionary()
 
     def _top_pair(self):
         """Always the largest budget's model (bohb.py:124): an immutable snapshot, new_result swaps entries."""
@@ -280,8 +299,8 @@ class BOHB(base_config_generator):
         except Exception:
             self.logger.warning(self._failed("traceback", "No model-based configurations"))
             return []
-        return [(ConfigSpace.Configuration(self.configspace, vector=rows[j]).get_dictionary(),
-                 {'model_based_pick': True, 'score': float(top.score[j])}) for j in range(top.count)]
+        return [(self._to_dict(rows[j]), {'model_based_pick': True, 'score': float(top.score[j])})
+                for j in range(top.count)]
 
     # -- several get_config calls in one GPU pass ----------------------------
     def speculation_enabled(self):
@@ -404,8 +423,7 @@ class BOHB(base_config_generator):
         if e[0] == "model":
             if self.logger.isEnabledFor(logging.DEBUG):
                 self.logger.debug('best_vector: {}, {}'.format(e[1], e[2]))
-            return (ConfigSpace.Configuration(self.configspace, vector=e[1]).get_dictionary(),
-                    {'model_based_pick': True})
+            return self._to_dict(e[1]), {'model_based_pick': True}
         if e[1] == "warning":
             self.logger.warning(e[2])
         elif e[1] == "debug":
@@ -431,14 +449,25 @@ class BOHB(base_config_generator):
         self.losses[budget].append(loss)
         store = self._stores.get(budget)
         if store is None:
-            store = self._stores[budget] = ObservationStore(len(self.kde_vartypes), self.kde_vartypes,
-                                                            device=self.device)
+            if self._conditional:
+                store = ObservationStore(len(self.kde_vartypes), self.kde_vartypes, device=self.device,
+                                         conditional=True)
+            else:
+                store = ObservationStore(len(self.kde_vartypes), self.kde_vartypes, device=self.device)
+            self._stores[budget] = store
         store.add(vec, loss)
         if len(self.configs[budget]) <= self.min_points_in_model + 1:
             return
         # one refit call: the new row to the device, argsort, split, bandwidths, both KDEs prepared
-        pair = store.refit(self.min_points_in_model, self.top_n_percent, min_bandwidth=self.min_bandwidth,
-                           pdf_floor=self.pdf_floor)
+        if self._conditional and store.has_nan:  # the grouped route: rows imputed on the device, then fitted
+            k = self._impute_refits.get(budget, 0)
+            self._impute_refits[budget] = k + 1
+            pair = store.refit(self.min_points_in_model, self.top_n_percent, min_bandwidth=self.min_bandwidth,
+                               pdf_floor=self.pdf_floor, impute_seed=self.impute_seed, levels=self.vartypes,
+                               impute_counter=k * 2 * store._hcap)
+        else:
+            pair = store.refit(self.min_points_in_model, self.top_n_percent, min_bandwidth=self.min_bandwidth,
+                               pdf_floor=self.pdf_floor)
         if pair is None:  # bohb.py:234-237: too few rows for a KDE
             return
         self.kde_models[budget] = pair  # atomic swap: a concurrent get_config keeps its snapshot

@@ -19,7 +19,7 @@ extern "C" {
 
 const char* hbx_last_error(void) { return g_err; }
 
-const char* hbx_version(void) { return "hbx 0.3.0 gfx950"; }
+const char* hbx_version(void) { return "hbx 0.3.1 gfx950"; }
 
 int64_t hbx_kde_param_bytes(void) { return (int64_t)HBX_PARAM_BYTES; }
 int64_t hbx_kde_param_bw_offset(void) { return (int64_t)offsetof(KdeParams, bw); }

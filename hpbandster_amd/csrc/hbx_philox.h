@@ -41,11 +41,12 @@ __host__ __device__ __forceinline__ double hbx_u01_open(uint64_t bits) {
 }
 
 // The counter words of one candidate index i (counter = (i, word, stream), key = seed).  The sampler's dim draws
-// use the small words g + SAMPLE_LPC k (below HBX_MAX_D / 4); the words from 0xFFFE0000 up belong to the draws
+// use the small words g + SAMPLE_LPC k (below HBX_MAX_D / 4); the words from 0xFFFD0000 up belong to the draws
 // named here, so no two of them ever meet on one counter.
 #define DATUM_WORD 0xFFFFFFFFu   // the per-candidate datum draw (hbx_sample.hip)
 #define DECIDE_WORD 0xFFFFFFFEu  // a get_config request's random-fraction decision (hbx_groups_config.hip)
 #define PRIOR_WORD0 0xFFFE0000u  // + p: the prior draw of a request's dims 2p and 2p + 1 (hbx_groups_config.hip)
+#define IMPUTE_WORD0 0xFFFD0000u // + t, t < HBX_MAX_D: iteration t of a view row's imputation (hbx_impute.h)
 
 __host__ __device__ __forceinline__ HbxU32x4 draw(uint64_t seed, uint64_t i, uint32_t word, uint32_t stream) {
   HbxU32x4 c;

@@ -634,14 +634,26 @@ def group_sizes(lens, D, min_points=None, top_n_percent=15):
 
 
 def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, device=None, stream=None,
-               min_bandwidth=None, pdf_floor=N.PDF_FLOOR_DEFAULT):
+               min_bandwidth=None, pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, levels=None, impute_counter=0,
+               impute_stream_id=0):
     """Refit every bracket's good / bad KDE in one batched call (hbx_seg_argsort_ex in numpy's order, then
     hbx_kde_fit), everything kept on the device.  ``X`` [N, D], ``losses`` [N] and ``seg_off`` [B + 1] are host
     arrays or device tensors; ``min_points`` defaults to D + 1 (BOHB's).  ``min_bandwidth`` (None = 0: no clip):
     every fitted bandwidth becomes ``np.clip(bw, min_bandwidth, None)`` where the fit stores it; ``pdf_floor``: the
     floor f of the score max(f, g)/max(l, f) the model's acquisitions form (default 1e-8, the reference snapshot's).
-    Returns a GroupModel, which carries both."""
+    Returns a GroupModel, which carries both.
+
+    Conditional search spaces: with ``impute_seed`` (and ``levels``, D level counts, 0: continuous) the rows may hold
+    NaN at inactive dims.  The argsort is taken on the original losses, then every group's good and bad rows are
+    imputed into a view (hbx_kde_impute_groups; Philox counters ``impute_counter`` + view row under
+    ``impute_stream_id``) and the fit runs on the view.  The model then holds the view in ``X``, ``seg_off``,
+    ``seg_host`` and ``order`` -- a group's segment is its n_good imputed good rows, then its n_bad imputed bad rows
+    -- so every grouped call works as it is; the originals are kept in ``raw_X``, ``raw_seg_off``, ``raw_order``,
+    with ``src_rows`` (int32 [Nv]: the original local row of each view row) and ``impute_counts`` (int32 [B, 2]:
+    entries filled from donors / from the prior).  ``impute_seed`` None: nothing of this happens."""
     pdf_floor, min_bandwidth = N.check_pdf_floor(pdf_floor), N.check_min_bandwidth(min_bandwidth)
+    if impute_seed is not None and levels is None:
+        raise N.HbxError("fit_groups: impute_seed needs levels (D level counts, 0: continuous)")
     torch = kde._torch()
     L = N.lib()
     D = len(var_type)
@@ -690,6 +702,27 @@ def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, 
             scr = torch.empty(sb, dtype=torch.uint8, device=device)
             N.check(L.hbx_seg_argsort_ex(N.ptr(ld), N.ptr(segd), B, int(lens.max()), Ntot, N.ptr(order), N.ptr(scr),
                                          sb, N.ORDER_NUMPY, sh))
+        raw = {}
+        if impute_seed is not None:  # the fit, and everything after it, sees the imputed view
+            raw = dict(raw_X=Xd, raw_seg_off=segd, raw_order=order)
+            view_h = np.concatenate(([0], np.cumsum(np.where(ng > 0, ng + nb, 0)))).astype(np.int64)
+            Nv = int(view_h[-1])
+            Xv = torch.zeros((max(Nv, 1), D), dtype=torch.float64, device=device)
+            order_v = torch.zeros(max(Nv, 1), dtype=torch.int64, device=device)
+            raw["src_rows"] = torch.zeros(max(Nv, 1), dtype=torch.int32, device=device)
+            raw["impute_counts"] = torch.zeros((B, 2), dtype=torch.int32, device=device)
+            viewd = dev(view_h, torch.int64)
+            if B and Nv:
+                wb = int(L.hbx_kde_impute_groups_workspace_bytes(Nv, B, D))
+                iws = torch.empty(wb, dtype=torch.uint8, device=device)
+                N.check(L.hbx_kde_impute_groups(
+                    N.ptr(Xd), D, N.ptr(segd), B, N.ptr(order), N.ptr(ngd), N.ptr(nbd),
+                    N.ptr(_levels_dev(levels, D, device)), N.ptr(viewd), Nv, int(impute_seed) & (2 ** 64 - 1),
+                    int(impute_counter) & (2 ** 64 - 1), int(impute_stream_id) & 0xFFFFFFFF, N.ptr(Xv),
+                    N.ptr(order_v), N.ptr(raw["src_rows"]), N.ptr(raw["impute_counts"]), N.ptr(iws), wb, sh))
+            raw["src_rows"] = raw["src_rows"][:Nv]
+            Xd, segd, seg_h, order, Ntot = Xv, viewd, view_h, order_v, Nv
+        if B and Ntot:
             fit = (N.ptr(Xd), D, N.ptr(segd), B, N.ptr(order), N.ptr(ngd), N.ptr(nbd), N.ptr(fgd),
                    N.ptr(fbd), N.ptr(vtd), N.ptr(bwg), N.ptr(bwb), N.ptr(nlg), N.ptr(nlb), sh)
             if min_bandwidth == 0.0:  # no clip: the call as it has always been
@@ -700,7 +733,56 @@ def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, 
     return GroupModel(B=B, D=D, var_type=var_type, device=device, X=Xd, losses=ld, seg_off=segd, seg_host=seg_h,
                       order=order, n_good=ng, n_bad=nb, has_model=(ng > 0), n_good_dev=ngd, n_bad_dev=nbd,
                       fac_good_dev=fgd, fac_bad_dev=fbd, vt_dev=vtd, bw_good=bwg, bw_bad=bwb, nlev_good=nlg,
-                      nlev_bad=nlb, pdf_floor=pdf_floor, min_bandwidth=min_bandwidth)
+                      nlev_bad=nlb, pdf_floor=pdf_floor, min_bandwidth=min_bandwidth, **raw)
+
+
+def sort_conditions(conditions, levels):
+    """The conditions of a conditional space -- ``(child_dim, parent_dim, allowed_levels)`` each; a child with several
+    is active when all hold -- checked and sorted topologically for hbx_rows_deactivate: (child int32[n], parent
+    int32[n], allowed uint64[n]) with every condition of a dim ahead of those the dim is the parent of.  HbxError for
+    a dim out of range, a parent that is not categorical with at most 64 levels, a level outside the parent's, and
+    a cycle."""
+    levels = np.asarray(levels, dtype=np.int64)
+    D = int(levels.shape[0])
+    conds = []
+    for cond in conditions:
+        c, p, allowed = int(cond[0]), int(cond[1]), [int(a) for a in cond[2]]
+        if not (0 <= c < D and 0 <= p < D) or c == p:
+            raise N.HbxError("condition (%d, %d): dims must be two different dims in [0, %d)" % (c, p, D))
+        if not 0 < levels[p] <= 64:
+            raise N.HbxError("condition (%d, %d): a parent must be categorical with at most 64 levels (dim %d has "
+                             "levels=%d; conditions on continuous parents are not supported)" % (c, p, p, levels[p]))
+        if not allowed or min(allowed) < 0 or max(allowed) >= levels[p]:
+            raise N.HbxError("condition (%d, %d): allowed levels %r outside [0, %d)" % (c, p, allowed, levels[p]))
+        conds.append((c, p, sum(1 << a for a in set(allowed))))
+    parents = {}
+    for c, p, _ in conds:
+        parents.setdefault(c, []).append(p)
+    depth, on_path = {}, set()
+
+    def depth_of(d):
+        if d in depth:
+            return depth[d]
+        if d in on_path:
+            raise N.HbxError("conditions form a cycle through dim %d" % d)
+        on_path.add(d)
+        depth[d] = 1 + max(depth_of(p) for p in parents[d]) if d in parents else 0
+        on_path.discard(d)
+        return depth[d]
+
+    conds.sort(key=lambda t: depth_of(t[0]))  # (stable: the given order among equals)
+    return (np.array([c for c, _, _ in conds], dtype=np.int32), np.array([p for _, p, _ in conds], dtype=np.int32),
+            np.array([a for _, _, a in conds], dtype=np.uint64))
+
+
+def deactivate_rows(rows, child, parent, allowed, stream=None):
+    """hbx_rows_deactivate over a contiguous float64 device tensor [..., D], in place; ``child`` / ``parent`` /
+    ``allowed``: device tensors of sort_conditions' arrays (allowed as int64 bit patterns)."""
+    D = int(rows.shape[-1])
+    n = int(rows.numel()) // D
+    N.check(N.lib().hbx_rows_deactivate(N.ptr(rows), n, D, N.ptr(child), N.ptr(parent), N.ptr(allowed),
+                                        int(child.shape[0]), N.stream_handle(stream, rows.device)))
+    return rows
 
 
 class GroupBOHB(object):
@@ -709,11 +791,17 @@ class GroupBOHB(object):
     bohb.py:171-251 for all runs at once (one batched refit), ``get_configs`` bohb.py:104-169 for S requests of
     every run (one call, every row on the device).  Run b's observations of a budget are the rows ``[b, :, :]`` of
     that budget's device store; ``kde_models`` maps budget -> GroupModel.  ``var_type``: the KDE's kinds ('c' / 'u'
-    per dim), ``levels``: D level counts (0: continuous)."""
+    per dim), ``levels``: D level counts (0: continuous).
+
+    Conditional search spaces: with ``impute_seed`` the reported rows may hold NaN at inactive dims, and every refit
+    imputes them (fit_groups) on a counter block of its own -- ``impute_counter``, which advances by the view's row
+    count per refit and is separate from ``counter``.  ``conditions``, a list of ``(child_dim, parent_dim,
+    allowed_levels)``: every row ``get_configs`` returns, prior draws included, passes through hbx_rows_deactivate,
+    so it holds NaN exactly at its inactive dims."""
 
     def __init__(self, B, var_type, levels, min_points_in_model=None, top_n_percent=15, num_samples=64,
                  random_fraction=1.0 / 3, bandwidth_factor=3, seed=0, device=None, min_bandwidth=None,
-                 pdf_floor=N.PDF_FLOOR_DEFAULT):
+                 pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, conditions=None):
         self.B, self.var_type, self.D = int(B), var_type, len(var_type)
         # the acquisition rules every refit and get_config of this optimiser uses (fit_groups)
         self.min_bandwidth, self.pdf_floor = N.check_min_bandwidth(min_bandwidth), N.check_pdf_floor(pdf_floor)
@@ -738,6 +826,10 @@ class GroupBOHB(object):
         self.kde_models = {}
         self.counter = 0  # the next call's Philox counter base
         self._lvd = None
+        self.impute_seed = None if impute_seed is None else int(impute_seed)
+        self.impute_counter = 0  # the next refit's imputation counter base
+        self.conditions = sort_conditions(conditions, self.levels) if conditions else None
+        self._cond_dev = None
 
     def _dev(self, a, shape_tail):
         torch = kde._torch()
@@ -751,8 +843,12 @@ class GroupBOHB(object):
     def new_results(self, budget, X, losses):
         """m finished runs per optimiser on ``budget``: ``X`` [B, m, D] (the configurations' vectors) and ``losses``
         [B, m], host arrays or device tensors; a crashed run's loss is +inf (bohb.py:189-194).  Returns True when
-        the budget's model was refit."""
+        the budget's model was refit.  With an ``impute_seed`` the rows may hold NaN at inactive dims; without one a
+        host array that holds a NaN is refused (a device tensor is not read back to look)."""
         torch = kde._torch()
+        if self.impute_seed is None and not _is_tensor(X) and np.isnan(np.asarray(X, dtype=np.float64)).any():
+            raise N.HbxError("new_results: rows hold NaN (inactive dims of a conditional space?): give the "
+                             "optimiser an impute_seed")
         Xd, ld = self._dev(X, (self.D,)), self._dev(losses, ())
         if int(Xd.shape[1]) != int(ld.shape[1]):
             raise N.HbxError("new_results: %d rows and %d losses per run" % (Xd.shape[1], ld.shape[1]))
@@ -766,9 +862,14 @@ class GroupBOHB(object):
         n = int(self.configs[budget].shape[1])
         if n <= self.min_points_in_model + 1:  # bohb.py:216-217
             return False
+        kw = dict(self._rules_kw)
+        if self.impute_seed is not None:
+            kw.update(impute_seed=self.impute_seed, levels=self._levels(), impute_counter=self.impute_counter)
         gm = fit_groups(self.configs[budget].reshape(self.B * n, self.D), self.losses[budget].reshape(-1),
                         np.arange(self.B + 1, dtype=np.int64) * n, self.var_type, self.min_points_in_model,
-                        self.top_n_percent, device=self.device, **self._rules_kw)
+                        self.top_n_percent, device=self.device, **kw)
+        if self.impute_seed is not None:  # a fresh counter block per refit: one counter per view row
+            self.impute_counter += int(gm.seg_host[-1])
         if not np.all(gm.has_model):  # bohb.py:234-237: the previous model, if any, stays
             return False
         self.kde_models[budget] = gm
@@ -788,13 +889,27 @@ class GroupBOHB(object):
         if counter_base is None:
             counter_base = self.counter
             self.counter += self.B * S * self.num_samples
+        dsync = sync and self.conditions is None  # with conditions the rows are deactivated before they leave
         if not self.kde_models:  # bohb.py:109
-            return sample_prior(self.B, S, self._levels(), self.seed, counter_base, C=self.num_samples,
-                                device=self.device, sync=sync)
-        gm = self.kde_models[max(self.kde_models.keys())]
-        return gm.get_config(self.num_samples, self.seed, self._levels(), requests=S,
-                             random_fraction=self.random_fraction, bandwidth_factor=self.bandwidth_factor,
-                             counter_base=counter_base, sync=sync)
+            cfg = sample_prior(self.B, S, self._levels(), self.seed, counter_base, C=self.num_samples,
+                               device=self.device, sync=dsync)
+        else:
+            gm = self.kde_models[max(self.kde_models.keys())]
+            cfg = gm.get_config(self.num_samples, self.seed, self._levels(), requests=S,
+                                random_fraction=self.random_fraction, bandwidth_factor=self.bandwidth_factor,
+                                counter_base=counter_base, sync=dsync)
+        if self.conditions is None:
+            return cfg
+        if self._cond_dev is None:
+            torch = kde._torch()
+            self._cond_dev = tuple(torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device)
+                                   for a in self.conditions)
+        with N.on_device(self.device):
+            deactivate_rows(cfg.rows, *self._cond_dev)
+            if not sync:
+                return cfg
+            return _configs(cfg.rows.reshape(-1, self.D), cfg.source.reshape(-1), self.B, S, True,
+                            None if cfg.picks is None else cfg.picks.reshape(-1, kde.RESULT_BYTES))
 
 
 # ---- grouped successive halving ---------------------------------------------------------------------------------

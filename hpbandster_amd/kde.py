@@ -857,7 +857,11 @@ class ObservationStore(object):
     models handed out earlier stay valid while later rows are appended (growth reallocates).
     """
 
-    def __init__(self, D, var_type, device=None, capacity=256):
+    def __init__(self, D, var_type, device=None, capacity=256, conditional=False):
+        # conditional: rows may hold NaN at inactive dims (a conditional search space); a refit over such rows
+        # imputes them first (refit's impute_seed / levels)
+        self.conditional = bool(conditional)
+        self.has_nan = False  # a row added so far holds a NaN
         self.D = int(D)
         self.var_type = var_type
         self.vt = np.ascontiguousarray(var_type_codes(var_type))
@@ -892,10 +896,17 @@ class ObservationStore(object):
         if losses.shape[0] != rows.shape[0]:
             raise N.HbxError("observation store: %d rows, %d losses" % (rows.shape[0], losses.shape[0]))
         cat = self.vt != 0
+        nan = np.isnan(rows) if self.conditional else None
+        if nan is not None and not nan.any():
+            nan = None
         if cat.any():  # checked before the rows enter the store: a bad row would fail every later refit
             codes = rows[:, cat]
+            if nan is not None:  # an inactive entry is no code: the others are still checked
+                codes = codes[~nan[:, cat]]
             if not (np.all((codes >= 0) & (codes < 1024)) and np.all(codes == np.floor(codes))):
-                raise N.HbxError("categorical codes must be integers in [0, 1024)")
+                raise N.HbxError("categorical codes must be integers in [0, 1024)" + (
+                    "" if self.conditional else " (NaN entries of a conditional space need conditional=True)"))
+        self.has_nan = self.has_nan or nan is not None
         m = self.nh + rows.shape[0]
         if m > self._hcap:
             cap = max(self._init_cap, self._hcap)
@@ -920,18 +931,32 @@ class ObservationStore(object):
         return self._lh[:self.nh]
 
     def refit(self, min_points, top_n_percent=15, split_rule="bohb", stream=None, min_bandwidth=None,
-              pdf_floor=N.PDF_FLOOR_DEFAULT):
+              pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, levels=None, impute_counter=0):
         """Refit on every row added so far (bohb.py:220-251).  Returns a KDEPair, or None where the reference
         builds no model (too few rows for a KDE, bohb.py:234-237).  The row-count gate before it
         (``len <= min_points + 1``: no refit, bohb.py:216-217) is the caller's, as in new_result.
         ``min_bandwidth`` (None = 0: no clip): every fitted bandwidth of both KDEs becomes
         ``np.clip(bw, min_bandwidth, None)`` where the fit stores it -- the pair's ``bw``, its tables, samplers and
-        exact re-score all hold the clipped values.  ``pdf_floor``: the returned pair's score floor (KDEPair)."""
+        exact re-score all hold the clipped values.  ``pdf_floor``: the returned pair's score floor (KDEPair).
+        A conditional store whose rows hold a NaN refits through the grouped route instead
+        (``groups.fit_groups(B=1, impute_seed=, levels=, impute_counter=)`` and ``.pair(0)``: the rows imputed on the
+        device, then fitted); it needs ``impute_seed`` and ``levels``.  Rows without NaN never take that route."""
         rules = (N.check_pdf_floor(pdf_floor), N.check_min_bandwidth(min_bandwidth))
         n = self.nh
         sizes = split_sizes(n, self.D, min_points, top_n_percent, split_rule)
         if sizes is None:
             return None
+        if self.has_nan:
+            if impute_seed is None or levels is None:
+                raise N.HbxError("observation store: rows hold NaN entries; refit needs impute_seed and levels")
+            if split_rule != "bohb":
+                raise N.HbxError("observation store: rows with NaN entries are refit under the 'bohb' split only")
+            from . import groups
+            gm = groups.fit_groups(self._Xh[:n], self._lh[:n], np.array([0, n], dtype=np.int64), self.var_type,
+                                   min_points, top_n_percent, device=self.device, stream=stream,
+                                   min_bandwidth=min_bandwidth, pdf_floor=pdf_floor, impute_seed=impute_seed,
+                                   levels=levels, impute_counter=impute_counter)
+            return gm.pair(0)
         sh = N.home_stream(self.device.index) if stream is None else None
         if sh is not None:
             return self._refit(self._Xh[:n], self._lh[:n], n, sizes, sh, rules)  # (already current: no context)
@@ -1000,22 +1025,23 @@ class ObservationStore(object):
 
 
 def fit_pair(configs, losses, var_type, min_points, top_n_percent=15, device=None, stream=None,
-             split_rule="bohb", min_bandwidth=None, pdf_floor=N.PDF_FLOOR_DEFAULT):
+             split_rule="bohb", min_bandwidth=None, pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, levels=None):
     """Refit the good/bad KDEs of one budget on the GPU (BOHB.new_result, bohb.py:220-251) from host
     arrays: all rows staged at once through an ObservationStore.
 
     Returns a KDEPair, or None where the reference returns without building a model.
     ``split_rule`` 'bohb' uses integer floor sizes (bohb.py:224-225) and requires rows > D;
     'kde_ei' uses int(max(top%*N/100., mp)) (kde_ei.py:190-191) and requires rows >= D.
-    ``min_bandwidth`` / ``pdf_floor``: ObservationStore.refit's.
+    ``min_bandwidth`` / ``pdf_floor`` / ``impute_seed`` / ``levels``: ObservationStore.refit's (with an
+    ``impute_seed`` the rows may hold NaN at inactive dims).
     """
     N.check_pdf_floor(pdf_floor), N.check_min_bandwidth(min_bandwidth)  # (before anything is moved to the device)
     X = np.ascontiguousarray(np.asarray(configs, dtype=np.float64))
     n, D = X.shape
-    store = ObservationStore(D, var_type, device=device, capacity=max(n, 1))
+    store = ObservationStore(D, var_type, device=device, capacity=max(n, 1), conditional=impute_seed is not None)
     store.add(X, losses)
     return store.refit(min_points, top_n_percent, split_rule, stream=stream, min_bandwidth=min_bandwidth,
-                       pdf_floor=pdf_floor)
+                       pdf_floor=pdf_floor, impute_seed=impute_seed, levels=levels)
 
 
 def fit_pair_from_rows(X, good_rows, bad_rows, var_type, bw_good, bw_bad, nlev_good, nlev_bad, device=None,

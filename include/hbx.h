@@ -490,6 +490,56 @@ int hbx_kde_propose_groups_r(const double* X, int32_t D, const int64_t* seg_off,
                              void* records_out, double* cands_out, void* workspace, int64_t workspace_bytes, void* stream,
                              const hbx_rules* rules);
 
+/* ---- conditional search spaces ---------------------------------------------------------------
+ * An observation of a conditional space holds NaN where a hyperparameter is inactive.  Released hpbandster imputes
+ * such entries before the KDEs are fitted (impute_conditional_data, a rule added after the reference snapshot);
+ * hbx_kde_impute_groups is that rule for B groups, with Philox draws instead of numpy's global stream and with every
+ * NaN filled (a NaN in dim 0 alone included).
+ *
+ * The good and the bad set of a group are imputed independently, each from its own ORIGINAL rows.  A set is the ns
+ * rows j = 0 .. ns - 1 in split order (hbx_kde_fit's convention: good order[seg_off[b] + j], j < n_good[b]; bad
+ * order[seg_off[b+1] - n_bad[b] + j], j < n_bad[b]).  A row of the set is copied to its view row v; then, for
+ * t = 0, 1, ... while it holds a NaN, with d0 its lowest NaN dim and m the set rows whose original value at d0 is
+ * not NaN (+-inf is a value):
+ *   m > 0    the donor is the k-th such row in ascending j, k = min(m - 1, floor(u_a m)); EVERY NaN dim of the row
+ *            takes the donor's original value, which may be NaN again
+ *   m == 0   dim d0 takes the prior: u_b where levels[d0] == 0, else (double)min(L - 1, floor(L u_b)), L = levels[d0]
+ * r = philox(counter_base + v, 0xFFFD0000 + t) under seed / stream_id as in hbx_kde_sample_groups,
+ * u_a = u01(bits64(r, 0)), u_b = u01(bits64(r, 1)).  At most D iterations per row.
+ *
+ * The view.  view_off: device i64[B+1], given by the caller: view_off[b+1] - view_off[b] is n_good[b] + n_bad[b]
+ * for a group hbx_kde_fit would model and 0 for a skipped one.  Group b's view rows are its imputed good rows, then
+ * its imputed bad rows (a row in both sets occurs twice, imputed separately).  Xv: f64[Nv][D]; order_v: i64[Nv], the
+ * identity local positions; src_v: i32[Nv], the original local row of each view row; counts: nullable i32[B][2],
+ * entries filled from donors / from the prior.  (Xv, view_off, order_v, n_good, n_bad) is then a model for every
+ * grouped entry point as it is: head n_good rows and tail n_bad rows of a segment of n_good + n_bad.  Rows without
+ * NaN are byte copies.  A group whose view length does not match its sizes (or leaves [0, Nv]) is left unwritten,
+ * counts -1 -- not an error return.  X, D, seg_off, B, order, n_good, n_bad: hbx_kde_fit's; levels: i32[D].
+ * Stream-ordered, no allocation, no host synchronisation.  workspace: hbx_kde_impute_groups_workspace_bytes(Nv, B, D)
+ * bytes, 16-byte aligned (-1 for arguments out of range); the per-dim masks of a set live in LDS where they fit and
+ * there otherwise (environment HBX_IMPUTE_LDS=0: always there).  Null or misaligned pointers, D outside
+ * [1, hbx_max_dims()], negative sizes, a short workspace: HBX_ERR_ARG before any launch.  B == 0 or Nv == 0: nothing
+ * to do.  hbx_kde_impute_groups_host: the same rule in plain loops over host memory, byte for byte. */
+int64_t hbx_kde_impute_groups_workspace_bytes(int64_t Nv, int64_t B, int32_t D);
+int hbx_kde_impute_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                          const int64_t* n_good, const int64_t* n_bad, const int32_t* levels, const int64_t* view_off,
+                          int64_t Nv, uint64_t seed, uint64_t counter_base, uint32_t stream_id, double* Xv,
+                          int64_t* order_v, int32_t* src_v, int32_t* counts, void* workspace, int64_t ws_bytes,
+                          void* stream);
+int hbx_kde_impute_groups_host(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                               const int64_t* n_good, const int64_t* n_bad, const int32_t* levels,
+                               const int64_t* view_off, int64_t Nv, uint64_t seed, uint64_t counter_base,
+                               uint32_t stream_id, double* Xv, int64_t* order_v, int32_t* src_v, int32_t* counts);
+/* Deactivate the inactive dims of N rows in place (what makes a proposed vector a valid configuration of a
+ * conditional space; ConfigSpace's deactivate_inactive_hyperparameters).  Conditions i = 0 .. n_cond - 1, in
+ * topological order: rows[r][child[i]] becomes NaN when rows[r][parent[i]] is NaN or is not an integer level in
+ * [0, 64) whose bit is set in allowed[i].  child / parent: device i32[n_cond]; allowed: device u64[n_cond].  One
+ * thread per row, one launch on `stream`.  hbx_rows_deactivate_host: the same over host memory. */
+int hbx_rows_deactivate(double* rows, int64_t N, int32_t D, const int32_t* child, const int32_t* parent,
+                        const uint64_t* allowed, int64_t n_cond, void* stream);
+int hbx_rows_deactivate_host(double* rows, int64_t N, int32_t D, const int32_t* child, const int32_t* parent,
+                             const uint64_t* allowed, int64_t n_cond);
+
 /* Optional timing: `events` of hbx_kde_acquire is NULL or an array of three hipEvent_t recorded on
  * `stream` before the l scoring launch, between l and g, and after g -- or, when l and g are scored by
  * one pair launch (both KDEs on the same hmode kernel, HBX_SCORE_PAIR not 0), only [0] before and [1]

@@ -38,6 +38,12 @@ propose(requests=S) plus a host prior fill; writes profiles/groups_get_config/be
 times the grouped successive-halving transition (sh_bench below): hbx_sh_advance_groups alone against the sync-free
 torch composition (stable argsort of the mask, gather, where), the two taking turns, and one full GroupHyperband
 iteration with a device objective; writes profiles/groups_sh/bench_groups_sh.json.
+
+    python tools/bench_groups.py --impute [--out FILE]
+
+times the imputation of a conditional space's NaN entries (impute_bench below): hbx_kde_impute_groups, the fit on the
+view and the whole refit against the plain refit on NaN-free data and against a plain gather of the same rows; writes
+profiles/impute/bench_impute.json.
 """
 import argparse
 import json
@@ -609,8 +615,95 @@ def sh_bench(a, dev, L):
     return 0 if ok else 1
 
 
+def impute_bench(a, dev, L):
+    """--impute: conditional search spaces at config #5's shape.  8 of the 32 dims conditional (6 continuous, 2
+    categorical, spread over the row), ~30 % of their entries NaN.  Times hbx_kde_impute_groups alone, the fit on the
+    view, and argsort + impute + fit, against argsort + fit on NaN-free data of the same shape (the plain
+    fit_groups) -- and a plain device gather of the same rows (torch.index_select), the rate the impute call is
+    measured against: both read every view row's source once and write the view once."""
+    B, n, dc, du, lev = a.B, a.n, 24, 8, 4
+    D = dc + du
+    vts = S.var_type_string(dc, du)
+    levels = np.array([0] * dc + [lev] * du, dtype=np.int32)
+    cond_dims = [1, 5, 9, 13, 17, 21, 25, 29]
+    losses = torch.from_numpy(S.make_bracket_losses(B, n).reshape(-1)).to(dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    X = torch.empty((B * n, D), dtype=torch.float64, device=dev)
+    X[:, :dc] = torch.rand((B * n, dc), dtype=torch.float64, device=dev, generator=g)
+    X[:, dc:] = torch.randint(0, lev, (B * n, du), device=dev, generator=g).to(torch.float64)
+    seg = np.arange(B + 1, dtype=np.int64) * n
+    plain = groups.fit_groups(X, losses, seg, vts, device=dev)
+    Xn = X.clone()
+    for d in cond_dims:
+        Xn[torch.rand(B * n, device=dev, generator=g) < 0.3, d] = float("nan")
+    gm = groups.fit_groups(Xn, losses, seg, vts, device=dev, impute_seed=1, levels=levels)
+    sh = N.stream_handle(None, dev)
+    Nv = int(gm.seg_host[-1])
+    lvd = torch.from_numpy(levels).to(dev)
+    wb = int(L.hbx_kde_impute_groups_workspace_bytes(Nv, B, D))
+    iws = torch.empty(wb, dtype=torch.uint8, device=dev)
+    sb = int(L.hbx_sort_scratch_bytes(B * n))
+    scr = torch.empty(sb, dtype=torch.uint8, device=dev)
+
+    def argsort(m, order):
+        N.check(L.hbx_seg_argsort_ex(N.ptr(m.losses), N.ptr(order_seg(m)), B, n, B * n, N.ptr(order), N.ptr(scr), sb,
+                                     N.ORDER_NUMPY, sh))
+
+    def order_seg(m):
+        return getattr(m, "raw_seg_off", m.seg_off)
+
+    def fit(m):
+        N.check(L.hbx_kde_fit(N.ptr(m.X), D, N.ptr(m.seg_off), B, N.ptr(m.order), N.ptr(m.n_good_dev),
+                              N.ptr(m.n_bad_dev), N.ptr(m.fac_good_dev), N.ptr(m.fac_bad_dev), N.ptr(m.vt_dev),
+                              N.ptr(m.bw_good), N.ptr(m.bw_bad), N.ptr(m.nlev_good), N.ptr(m.nlev_bad), sh))
+
+    def impute(m=gm):
+        N.check(L.hbx_kde_impute_groups(N.ptr(m.raw_X), D, N.ptr(m.raw_seg_off), B, N.ptr(m.raw_order),
+                                        N.ptr(m.n_good_dev), N.ptr(m.n_bad_dev), N.ptr(lvd), N.ptr(m.seg_off), Nv, 1,
+                                        0, 0, N.ptr(m.X), N.ptr(m.order), N.ptr(m.src_rows),
+                                        N.ptr(m.impute_counts), N.ptr(iws), wb, sh))
+
+    # the same rows through a plain gather: global source row of every view row
+    seg_d = torch.from_numpy(seg[:-1]).to(dev)
+    rows = (gm.src_rows[:Nv].long() + seg_d.repeat_interleave(torch.from_numpy(np.diff(gm.seg_host)).to(dev)))
+    out = torch.empty_like(gm.X)
+    ms_impute = timed(impute, a.reps)
+    ms_gather = timed(lambda: torch.index_select(gm.raw_X, 0, rows, out=out), a.reps)
+    ms_fit_view = timed(lambda: fit(gm), a.reps)
+    ms_chain = timed(lambda: (argsort(gm, gm.raw_order), impute(), fit(gm)), a.reps)
+    ms_plain = timed(lambda: (argsort(plain, plain.order), fit(plain)), a.reps)
+    ms_plain_fit = timed(lambda: fit(plain), a.reps)
+    del out
+    clean = groups.fit_groups(X, losses, seg, vts, device=dev, impute_seed=1, levels=levels)  # nothing to fill
+    ms_clean = timed(lambda: impute(clean), a.reps)
+    counts = gm.impute_counts.cpu().numpy()
+    moved = 2.0 * Nv * D * 8
+    res = {
+        "workload": "impute_groups_b%d_n%d_d32_24c8u_8cond_30pct" % (B, n),
+        "device": torch.cuda.get_device_name(0), "reps": a.reps, "view_rows": Nv,
+        "n_good": int(gm.n_good[0]), "n_bad": int(gm.n_bad[0]),
+        "nan_entries_filled": int(counts[:, 0].sum()), "prior_entries_filled": int(counts[:, 1].sum()),
+        "impute_ms": ms_impute, "impute_nan_free_ms": ms_clean, "gather_ms": ms_gather, "bytes_moved": moved,
+        "impute_gb_per_s": moved / ms_impute / 1e6, "gather_gb_per_s": moved / ms_gather / 1e6,
+        "fraction_of_gather_rate": ms_gather / ms_impute,
+        "fit_on_view_ms": ms_fit_view, "argsort_impute_fit_ms": ms_chain,
+        "plain_fit_ms": ms_plain_fit, "plain_argsort_fit_ms": ms_plain,
+        "workspace_bytes": wb,
+    }
+    a.out = a.out or os.path.join(ROOT, "profiles", "impute", "bench_impute.json")
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(res, sort_keys=True))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--impute", action="store_true",
+                    help="conditional spaces: the impute call and the fit on the view (impute_bench)")
     ap.add_argument("--sh", action="store_true", help="the grouped successive-halving transition (sh_bench)")
     ap.add_argument("--sh-max-budget", type=float, default=729.0,
                     help="--sh: the Hyperband iteration's budgets run from 1 to this (eta = 3)")
@@ -632,6 +725,8 @@ def main(argv=None):
     L = N.lib()
     if a.logpdf:
         return logpdf_bench(a, dev, L)
+    if a.impute:
+        return impute_bench(a, dev, L)
     if a.sh:
         return sh_bench(a, dev, L)
     B, n, C, dc, du, lev = a.B, a.n, a.C, 24, 8, 4
