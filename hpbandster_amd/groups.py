@@ -39,6 +39,37 @@ def _is_tensor(a):
     return hasattr(a, "data_ptr")
 
 
+def _to_device(a, dtype, device, strict=False, what=None):
+    """Host array or tensor ``a`` as a contiguous device tensor of ``dtype``.  Lenient: a tensor is converted, moved
+    and made contiguous where it is not.  ``strict``: a tensor is used where it lies and must be contiguous and of
+    ``dtype`` already (bool counts as uint8) -- HbxError naming ``what`` otherwise."""
+    torch = kde._torch()
+    if not _is_tensor(a):
+        npd = {torch.float64: np.float64, torch.int64: np.int64, torch.int32: np.int32, torch.uint8: np.uint8}[dtype]
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=npd)).to(device)
+    if not strict:
+        return a.to(device=device, dtype=dtype).contiguous()
+    t = a.view(torch.uint8) if a.dtype == torch.bool and dtype == torch.uint8 else a
+    if t.dtype != dtype or not t.is_contiguous():
+        raise N.HbxError("%s must be a contiguous %s tensor" % (what, dtype))
+    return t
+
+
+def _philox(seed, counter_base, stream_id):
+    """(seed, counter_base, stream_id) as the calls take them: u64, u64, u32"""
+    return int(seed) & (2 ** 64 - 1), int(counter_base) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF
+
+
+def _gather_rows(cands, group_index, candidate_index):
+    """``cands[group_index, candidate_index]`` on the host: ``cands`` [G, C, D], numpy or a device tensor (only the
+    indexed rows are fetched); the indices are host int64 arrays."""
+    if _is_tensor(cands):
+        torch = kde._torch()
+        return cands[torch.from_numpy(group_index).to(cands.device),
+                     torch.from_numpy(candidate_index).to(cands.device)].cpu().numpy()
+    return np.asarray(cands, dtype=np.float64)[group_index, candidate_index]
+
+
 class GroupPicks(object):
     """One pick per group (hbx_kde_acquire_groups), from one fetch of the B records: numpy arrays ``index``
     (int64, relative to the group's pool, -1: no pick), ``score``, ``pdf_l``, ``pdf_g`` (float64, the reference's
@@ -73,13 +104,7 @@ class GroupPicks(object):
         out = np.full((index.size, D), np.nan)
         ok = np.nonzero(index >= 0)[0]
         if ok.size:
-            if _is_tensor(cands):
-                torch = kde._torch()
-                bi = torch.from_numpy(ok).to(cands.device)
-                ci = torch.from_numpy(index[ok]).to(cands.device)
-                out[ok] = cands.reshape(-1, C, D)[bi, ci].cpu().numpy()
-            else:
-                out[ok] = np.asarray(cands, dtype=np.float64).reshape(-1, C, D)[ok, index[ok]]
+            out[ok] = _gather_rows(cands.reshape(-1, C, D), ok, index[ok])
         return out.reshape(lead + (D,))
 
     def __repr__(self):
@@ -143,17 +168,14 @@ class GroupTopK(object):
         out = np.full((len(self), self.k, D), np.nan)
         bi, ji = np.nonzero(self.index >= 0)
         if bi.size:
-            ci = self.index[bi, ji]
-            if _is_tensor(cands):
-                torch = kde._torch()
-                out[bi, ji] = cands[torch.from_numpy(bi).to(cands.device), torch.from_numpy(ci).to(cands.device)] \
-                    .cpu().numpy()
-            else:
-                out[bi, ji] = np.asarray(cands, dtype=np.float64)[bi, ci]
+            out[bi, ji] = _gather_rows(cands, bi, self.index[bi, ji])
         return out
 
     def __repr__(self):
         return "GroupTopK(B=%d, k=%d, returned=%d)" % (len(self), self.k, int(self.count.sum()))
+
+
+SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR = 0, 1, 2, 3, 4  # HBX_CFG_*
 
 
 class GroupConfigs(object):
@@ -164,7 +186,8 @@ class GroupConfigs(object):
     records, None when they were not requested).  Host arrays and a GroupPicks after a synchronising call; with
     ``sync=False`` device tensors, ``picks`` the device tensor of the records (uint8 [B, S, 48] or [B, 48]).
     ``cands`` / ``domain_err`` hold the pools and the sampler's error bytes when the call kept them.  ``len()`` is B."""
-    SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR = 0, 1, 2, 3, 4  # HBX_CFG_*
+    SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR = \
+        SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR  # (the module's)
     __slots__ = ("rows", "source", "model_based", "picks", "cands", "domain_err")
 
     def __init__(self, rows, source, B, S=None, picks=None, cands=None, domain_err=None):
@@ -179,9 +202,6 @@ class GroupConfigs(object):
 
     def __repr__(self):
         return "GroupConfigs(shape=%s)" % (tuple(self.source.shape),)
-
-
-SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR = 0, 1, 2, 3, 4
 
 
 def _levels_dev(levels, D, device):
@@ -224,8 +244,7 @@ def _finish(device, stream, B, S, C, D, records, cands, err, levels, random_frac
     lvd = _levels_dev(levels, D, device)
     N.check(N.lib().hbx_kde_finish_groups(
         N.ptr(records), N.ptr(cands), N.ptr(err), N.ptr(lvd), D, B, Sn, int(C), random_fraction,
-        int(seed) & (2 ** 64 - 1), int(counter_base) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF, N.ptr(rows),
-        N.ptr(source), N.stream_handle(stream, device)))
+        *(_philox(seed, counter_base, stream_id) + (N.ptr(rows), N.ptr(source), N.stream_handle(stream, device)))))
     return rows, source
 
 
@@ -272,6 +291,13 @@ class GroupLogPdf(object):
         return "GroupLogPdf(shape=%s, stats=%s)" % (shape, self.stats)
 
 
+# include/hbx.h's names for the model parameters of the grouped entry points, in its order (hbx_kde_acquire_groups),
+# and for those of the sampler, which reads the good side alone (hbx_kde_sample_groups)
+MODEL_ARGS = ("X", "D", "seg_off", "B", "order", "n_good", "n_bad", "vartype", "bw_good", "bw_bad", "nlev_good",
+              "nlev_bad")
+SAMPLE_ARGS = ("X", "D", "seg_off", "B", "order", "n_good", "bw_good")
+
+
 class GroupModel(object):
     """The KDE pairs of B brackets after one batched refit (fit_groups).  ``B``, ``D``, ``n_good`` / ``n_bad``
     (host int64[B], 0 where the reference builds no model) and ``has_model`` (host bool[B]) are host-side facts
@@ -292,6 +318,14 @@ class GroupModel(object):
             N.check(getattr(N.lib(), name)(*args))
         else:
             N.check(getattr(N.lib(), name + "_r")(*(args + (ctypes.addressof(self._rules),))))
+
+    def model_args(self, names=MODEL_ARGS):
+        """The model arguments every grouped entry point takes first, in include/hbx.h's order (MODEL_ARGS)."""
+        arg = dict(X=N.ptr(self.X), D=self.D, seg_off=N.ptr(self.seg_off), B=self.B, order=N.ptr(self.order),
+                   n_good=N.ptr(self.n_good_dev), n_bad=N.ptr(self.n_bad_dev), vartype=N.ptr(self.vt_dev),
+                   bw_good=N.ptr(self.bw_good), bw_bad=N.ptr(self.bw_bad), nlev_good=N.ptr(self.nlev_good),
+                   nlev_bad=N.ptr(self.nlev_bad))
+        return tuple(arg[name] for name in names)
 
     # ---- host views (checks and debugging) --------------------------------------------------------------
     def bandwidths(self):
@@ -336,57 +370,76 @@ class GroupModel(object):
             return cands.view(self.B, S, int(C), self.D), err.view(self.B, S, int(C))
         torch = kde._torch()
         C = int(C)
-        lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
-        if lv.shape != (self.D,):
-            raise N.HbxError("levels must have %d entries" % self.D)
         with N.on_device(self.device, stream):
+            lvd = _levels_dev(levels, self.D, self.device)
             cands = torch.empty((self.B, C, self.D), dtype=torch.float64, device=self.device)
             err = torch.zeros((self.B, C), dtype=torch.uint8, device=self.device)
-            lvd = torch.from_numpy(lv).to(self.device)
             N.check(N.lib().hbx_kde_sample_groups(
-                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
-                N.ptr(self.bw_good), N.ptr(lvd), float(bandwidth_factor), int(seed) & (2 ** 64 - 1),
-                int(counter_base) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF, C, N.ptr(cands), N.ptr(err),
-                N.stream_handle(stream, self.device)))
+                *(self.model_args(SAMPLE_ARGS) + (N.ptr(lvd), float(bandwidth_factor)) +
+                  _philox(seed, counter_base, stream_id) +
+                  (C, N.ptr(cands), N.ptr(err), N.stream_handle(stream, self.device)))))
         return cands, err
 
     def workspace_bytes(self, C, requests=1):
         return int(N.lib().hbx_kde_groups_batch_workspace_bytes(self.B, int(requests), int(C), self.D))
 
+    def _stage_cands(self, cands, ranks):
+        """A caller's pool as the contiguous float64 device tensor the grouped calls read (the grouped twin of
+        KDEPair._stage_cands).  ``ranks``: the legal ones, 3 for [B, C, D] and 4 for [B, S, C, D]."""
+        torch = kde._torch()
+
+        def want():
+            return " or ".join("[%d, %s, %d]" % (self.B, "C" if r == 3 else "S, C", self.D) for r in ranks)
+
+        if _is_tensor(cands):
+            cd = cands
+            if cd.dtype != torch.float64 or not cd.is_contiguous():
+                raise N.HbxError("candidate tensor must be contiguous float64 %s" % want())
+        else:
+            cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
+        if cd.dim() not in ranks or int(cd.shape[0]) != self.B or int(cd.shape[-1]) != self.D:
+            raise N.HbxError("candidates must be %s, got %s" % (want(), tuple(cd.shape)))
+        return cd
+
+    def _workspace(self, workspace, needed_bytes, what):
+        """The caller's workspace, or a new one, of at least ``needed_bytes``; a negative size is the size helper's
+        refusal of the call's sizes, reported in the words ``what``."""
+        if needed_bytes < 0:
+            raise N.HbxError(what)
+        torch = kde._torch()
+        ws = workspace if workspace is not None else torch.empty(needed_bytes, dtype=torch.uint8, device=self.device)
+        if ws.numel() < needed_bytes:
+            raise N.HbxError("workspace too small")
+        return ws
+
+    def _acquire(self, cd, S, C, stream, workspace, sync):
+        """``acquire`` (``S`` None) and ``acquire_requests`` over the staged pool ``cd``, inside the caller's
+        on_device context: the one-request entry point for ``S`` None under the default floor, the batched one
+        otherwise; records [B, 48] or [B, S, 48]."""
+        torch = kde._torch()
+        Sn = 1 if S is None else S
+        sizes = "B * C = %d * %d" % (self.B, C) if S is None else "B * S * C = %d * %d * %d" % (self.B, S, C)
+        ws = self._workspace(workspace, self.workspace_bytes(C, Sn), sizes + " exceeds int32")
+        res = torch.empty((self.B, kde.RESULT_BYTES) if S is None else (self.B, S, kde.RESULT_BYTES),
+                          dtype=torch.uint8, device=self.device)
+        model = self.model_args() + (N.ptr(cd),)
+        tail = (N.ptr(res), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device))
+        if S is None and self._rules is None:
+            N.check(N.lib().hbx_kde_acquire_groups(*(model + (C,) + tail)))
+        else:  # (the batched call's S = 1 case is the one-request call: include/hbx.h)
+            self._call("hbx_kde_acquire_groups_batch", *(model + (Sn, C) + tail))
+        if not sync:
+            return res
+        return GroupPicks.from_bytes(res.cpu().numpy().tobytes(), self.B, S)
+
     def acquire(self, cands, stream=None, workspace=None, sync=True):
         """Per group the first index minimising max(f, g)/max(l, f) over its own pool ``cands[b]``, f the model's
-        ``pdf_floor`` (hbx_kde_acquire_groups; under another floor than 1e-8 its S = 1 rules-taking form).  ``cands``: [B, C, D] float64, numpy or a device tensor.  Returns GroupPicks, or
-        with ``sync=False`` the device tensor of the B records (uint8 [B, 48])."""
-        torch = kde._torch()
+        ``pdf_floor`` (hbx_kde_acquire_groups; under another floor than 1e-8 its S = 1 rules-taking form).
+        ``cands``: [B, C, D] float64, numpy or a device tensor.  Returns GroupPicks, or with ``sync=False`` the device
+        tensor of the B records (uint8 [B, 48])."""
         with N.on_device(self.device, stream):
-            if _is_tensor(cands):
-                cd = cands
-                if cd.dtype != torch.float64 or not cd.is_contiguous():
-                    raise N.HbxError("candidate tensor must be contiguous float64 [B, C, D]")
-            else:
-                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
-            if cd.dim() != 3 or int(cd.shape[0]) != self.B or int(cd.shape[2]) != self.D:
-                raise N.HbxError("candidates must be [%d, C, %d], got %s" % (self.B, self.D, tuple(cd.shape)))
-            C = int(cd.shape[1])
-            wsb = self.workspace_bytes(C)
-            if wsb < 0:
-                raise N.HbxError("B * C = %d * %d exceeds int32" % (self.B, C))
-            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
-            if ws.numel() < wsb:
-                raise N.HbxError("workspace too small")
-            res = torch.empty((self.B, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device)
-            model = (
-                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
-                N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
-                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd))
-            tail = (N.ptr(res), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device))
-            if self._rules is None:
-                N.check(N.lib().hbx_kde_acquire_groups(*(model + (C,) + tail)))
-            else:  # (the batched call's S = 1 case is this call: include/hbx.h)
-                self._call("hbx_kde_acquire_groups_batch", *(model + (1, C) + tail))
-            if not sync:
-                return res
-            return GroupPicks.from_bytes(res.cpu().numpy().tobytes(), self.B)
+            cd = self._stage_cands(cands, (3,))
+            return self._acquire(cd, None, int(cd.shape[1]), stream, workspace, sync)
 
     def acquire_requests(self, cands, stream=None, workspace=None, sync=True):
         """S get_config requests per group in one call (hbx_kde_acquire_groups_batch; HB_iteration.py:136-138 issues
@@ -394,33 +447,9 @@ class GroupModel(object):
         pool ``cands[b, s]`` and sees no other request.  ``cands``: [B, S, C, D] float64, numpy or a device tensor.
         Returns GroupPicks with arrays of shape [B, S], or with ``sync=False`` the device tensor of the records
         (uint8 [B, S, 48])."""
-        torch = kde._torch()
         with N.on_device(self.device, stream):
-            if _is_tensor(cands):
-                cd = cands
-                if cd.dtype != torch.float64 or not cd.is_contiguous():
-                    raise N.HbxError("candidate tensor must be contiguous float64 [B, S, C, D]")
-            else:
-                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
-            if cd.dim() != 4 or int(cd.shape[0]) != self.B or int(cd.shape[3]) != self.D:
-                raise N.HbxError("candidates must be [%d, S, C, %d], got %s" % (self.B, self.D, tuple(cd.shape)))
-            S, C = int(cd.shape[1]), int(cd.shape[2])
-            wsb = self.workspace_bytes(C, S)
-            if wsb < 0:
-                raise N.HbxError("B * S * C = %d * %d * %d exceeds int32" % (self.B, S, C))
-            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
-            if ws.numel() < wsb:
-                raise N.HbxError("workspace too small")
-            res = torch.empty((self.B, S, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device)
-            self._call(
-                "hbx_kde_acquire_groups_batch",
-                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
-                N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
-                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), S, C, N.ptr(res), N.ptr(ws), ws.numel(),
-                N.stream_handle(stream, self.device))
-            if not sync:
-                return res
-            return GroupPicks.from_bytes(res.cpu().numpy().tobytes(), self.B, S)
+            cd = self._stage_cands(cands, (4,))
+            return self._acquire(cd, int(cd.shape[1]), int(cd.shape[2]), stream, workspace, sync)
 
     def workspace_bytes_topk(self, C, k):
         return int(N.lib().hbx_kde_groups_topk_workspace_bytes(self.B, int(C), int(k), self.D))
@@ -435,29 +464,14 @@ class GroupModel(object):
         if k < 1 or k > kde.TOPK_MAX_K:
             raise ValueError("k must be in [1, %d], got %d" % (kde.TOPK_MAX_K, k))
         with N.on_device(self.device, stream):
-            if _is_tensor(cands):
-                cd = cands
-                if cd.dtype != torch.float64 or not cd.is_contiguous():
-                    raise N.HbxError("candidate tensor must be contiguous float64 [B, C, D]")
-            else:
-                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
-            if cd.dim() != 3 or int(cd.shape[0]) != self.B or int(cd.shape[2]) != self.D:
-                raise N.HbxError("candidates must be [%d, C, %d], got %s" % (self.B, self.D, tuple(cd.shape)))
+            cd = self._stage_cands(cands, (3,))
             C = int(cd.shape[1])
-            wsb = self.workspace_bytes_topk(C, k)
-            if wsb < 0:
-                raise N.HbxError("B * C = %d * %d exceeds int32" % (self.B, C))
-            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
-            if ws.numel() < wsb:
-                raise N.HbxError("workspace too small")
+            ws = self._workspace(workspace, self.workspace_bytes_topk(C, k),
+                                 "B * C = %d * %d exceeds int32" % (self.B, C))
             res = torch.empty((self.B, kde.TOPK_HEAD_BYTES + kde.TOPK_REC.itemsize * k), dtype=torch.uint8,
                               device=self.device)
-            self._call(
-                "hbx_kde_acquire_groups_topk",
-                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
-                N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
-                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), C, k, N.ptr(res), N.ptr(ws), ws.numel(),
-                N.stream_handle(stream, self.device))
+            self._call("hbx_kde_acquire_groups_topk", *(self.model_args() + (
+                N.ptr(cd), C, k, N.ptr(res), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device))))
             if not sync:
                 return res
             return GroupTopK.from_bytes(res.cpu().numpy().tobytes(), self.B, k)
@@ -479,34 +493,19 @@ class GroupModel(object):
             raise ValueError("rtol must be positive, got %r" % (rtol,))
         torch = kde._torch()
         with N.on_device(self.device, stream):
-            if _is_tensor(cands):
-                cd = cands
-                if cd.dtype != torch.float64 or not cd.is_contiguous():
-                    raise N.HbxError("candidate tensor must be contiguous float64 [B, C, D] or [B, S, C, D]")
-            else:
-                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
-            if cd.dim() not in (3, 4) or int(cd.shape[0]) != self.B or int(cd.shape[-1]) != self.D:
-                raise N.HbxError("candidates must be [%d, C, %d] or [%d, S, C, %d], got %s" %
-                                 (self.B, self.D, self.B, self.D, tuple(cd.shape)))
+            cd = self._stage_cands(cands, (3, 4))
             lead = tuple(int(v) for v in cd.shape[:-1])
             C = int(np.prod(lead[1:], dtype=np.int64))  # S requests: the flattened pool
-            wsb = self.workspace_bytes_logpdf(C)
-            if wsb < 0:
-                raise N.HbxError("B * C = %d * %d exceeds int32" % (self.B, C))
-            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
-            if ws.numel() < wsb:
-                raise N.HbxError("workspace too small")
+            ws = self._workspace(workspace, self.workspace_bytes_logpdf(C),
+                                 "B * C = %d * %d exceeds int32" % (self.B, C))
             ll = torch.empty((self.B, C), dtype=torch.float64, device=self.device) if which != "bad" else None
             lg = torch.empty((self.B, C), dtype=torch.float64, device=self.device) if which != "good" else None
             status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
             launched = self.B > 0 and C > 0
             if launched:
-                N.check(N.lib().hbx_kde_logpdf_groups(
-                    N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
-                    N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
-                    N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(cd), C, float(rtol),
-                    LOGPDF_FP64_ONLY if fp64_only else 0, N.ptr(ll), N.ptr(lg), N.ptr(status), N.ptr(ws), ws.numel(),
-                    N.stream_handle(stream, self.device)))
+                N.check(N.lib().hbx_kde_logpdf_groups(*(self.model_args() + (
+                    N.ptr(cd), C, float(rtol), LOGPDF_FP64_ONLY if fp64_only else 0, N.ptr(ll), N.ptr(lg),
+                    N.ptr(status), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device)))))
             if not sync:
                 return GroupLogPdf(ll, lg, status, None, lead)
             stats = np.zeros(4, dtype=np.int64)
@@ -534,26 +533,19 @@ class GroupModel(object):
         S = 1 if requests is None else int(requests)
         C = int(C)
         rf = _fraction(random_fraction)
-        wsb = self.workspace_bytes_get_config(C, S)
-        if wsb < 0:
-            raise N.HbxError("get_config: B=%d S=%d C=%d out of range (C >= 1, B * S * C within int32)" % (self.B, S, C))
         with N.on_device(self.device, stream):
+            ws = self._workspace(workspace, self.workspace_bytes_get_config(C, S),
+                                 "get_config: B=%d S=%d C=%d out of range (C >= 1, B * S * C within int32)" %
+                                 (self.B, S, C))
             lvd = _levels_dev(levels, self.D, self.device)
-            ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=self.device)
-            if ws.numel() < wsb:
-                raise N.HbxError("workspace too small")
             rows = torch.empty((self.B * S, self.D), dtype=torch.float64, device=self.device)
             source = torch.empty(self.B * S, dtype=torch.uint8, device=self.device)
             rec = torch.empty((self.B * S, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device) if records else None
             cands = torch.empty((self.B, S, C, self.D), dtype=torch.float64, device=self.device) if keep_pools else None
-            self._call(
-                "hbx_kde_propose_groups",
-                N.ptr(self.X), self.D, N.ptr(self.seg_off), self.B, N.ptr(self.order), N.ptr(self.n_good_dev),
-                N.ptr(self.n_bad_dev), N.ptr(self.vt_dev), N.ptr(self.bw_good), N.ptr(self.bw_bad),
-                N.ptr(self.nlev_good), N.ptr(self.nlev_bad), N.ptr(lvd), float(bandwidth_factor), rf,
-                int(seed) & (2 ** 64 - 1), int(counter_base) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF, S, C,
-                N.ptr(rows), N.ptr(source), N.ptr(rec), N.ptr(cands), N.ptr(ws), ws.numel(),
-                N.stream_handle(stream, self.device))
+            self._call("hbx_kde_propose_groups", *(
+                self.model_args() + (N.ptr(lvd), float(bandwidth_factor), rf) + _philox(seed, counter_base, stream_id) +
+                (S, C, N.ptr(rows), N.ptr(source), N.ptr(rec), N.ptr(cands), N.ptr(ws), ws.numel(),
+                 N.stream_handle(stream, self.device))))
             err = None
             if keep_pools:
                 off = np.zeros(4, dtype=np.int64)
@@ -572,15 +564,7 @@ class GroupModel(object):
         torch = kde._torch()
         rf = _fraction(random_fraction)
         with N.on_device(self.device, stream):
-            if _is_tensor(cands):
-                cd = cands
-                if cd.dtype != torch.float64 or not cd.is_contiguous():
-                    raise N.HbxError("candidate tensor must be contiguous float64 [B, S, C, D] or [B, C, D]")
-            else:
-                cd = torch.from_numpy(np.ascontiguousarray(cands, dtype=np.float64)).to(self.device)
-            if cd.dim() not in (3, 4) or int(cd.shape[0]) != self.B or int(cd.shape[-1]) != self.D:
-                raise N.HbxError("candidates must be [%d, S, C, %d] or [%d, C, %d], got %s" %
-                                 (self.B, self.D, self.B, self.D, tuple(cd.shape)))
+            cd = self._stage_cands(cands, (3, 4))
             S = None if cd.dim() == 3 else int(cd.shape[1])
             C = int(cd.shape[-2])
             Q = self.B * (1 if S is None else S)
@@ -633,6 +617,30 @@ def group_sizes(lens, D, min_points=None, top_n_percent=15):
     return ng, nb
 
 
+def _impute_view(Xd, segd, order, ngd, nbd, ng, nb, B, D, levels, seed, counter, stream_id, device, sh):
+    """fit_groups' imputed view of the raw rows (hbx_kde_impute_groups): every group's n_good good rows, then its
+    n_bad bad rows, NaN entries filled.  Returns the view's (Xd, segd, seg_h, order, Ntot) and the ``raw`` dict of
+    what the model keeps beside it (raw_X, raw_seg_off, raw_order, src_rows, impute_counts)."""
+    torch = kde._torch()
+    L = N.lib()
+    view_h = np.concatenate(([0], np.cumsum(np.where(ng > 0, ng + nb, 0)))).astype(np.int64)
+    Nv = int(view_h[-1])
+    Xv = torch.zeros((max(Nv, 1), D), dtype=torch.float64, device=device)
+    order_v = torch.zeros(max(Nv, 1), dtype=torch.int64, device=device)
+    src = torch.zeros(max(Nv, 1), dtype=torch.int32, device=device)
+    counts = torch.zeros((B, 2), dtype=torch.int32, device=device)
+    viewd = _to_device(view_h, torch.int64, device)
+    if B and Nv:
+        wb = int(L.hbx_kde_impute_groups_workspace_bytes(Nv, B, D))
+        iws = torch.empty(wb, dtype=torch.uint8, device=device)
+        N.check(L.hbx_kde_impute_groups(
+            N.ptr(Xd), D, N.ptr(segd), B, N.ptr(order), N.ptr(ngd), N.ptr(nbd),
+            N.ptr(_levels_dev(levels, D, device)), N.ptr(viewd), Nv, *(_philox(seed, counter, stream_id) + (
+                N.ptr(Xv), N.ptr(order_v), N.ptr(src), N.ptr(counts), N.ptr(iws), wb, sh))))
+    raw = dict(raw_X=Xd, raw_seg_off=segd, raw_order=order, src_rows=src[:Nv], impute_counts=counts)
+    return (Xv, viewd, view_h, order_v, Nv), raw
+
+
 def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, device=None, stream=None,
                min_bandwidth=None, pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, levels=None, impute_counter=0,
                impute_stream_id=0):
@@ -672,25 +680,17 @@ def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, 
     fg = np.array([kde.bandwidth_factor(int(v), D) if v else 0.0 for v in ng], dtype=np.float64)
     fb = np.array([kde.bandwidth_factor(int(v), D) if v else 0.0 for v in nb], dtype=np.float64)
     vt = np.ascontiguousarray(kde.var_type_codes(var_type))
-
-    def dev(a, dtype):
-        if _is_tensor(a):
-            t = a.to(device=device, dtype=dtype)
-            return t if t.is_contiguous() else t.contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a, dtype={torch.float64: np.float64, torch.int64: np.int64,
-                                                               torch.int32: np.int32}[dtype])).to(device)
-
     with N.on_device(device, stream):
-        Xd = dev(X, torch.float64).reshape(-1, D)
-        ld = dev(losses, torch.float64).reshape(-1)
+        Xd = _to_device(X, torch.float64, device).reshape(-1, D)
+        ld = _to_device(losses, torch.float64, device).reshape(-1)
         if int(Xd.shape[0]) < Ntot or int(ld.shape[0]) < Ntot:
             raise N.HbxError("fit_groups: %d rows / %d losses for %d segment entries" % (Xd.shape[0], ld.shape[0], Ntot))
         if int(Xd.shape[0]) == 0:  # every bracket empty: the calls still want non-null pointers (never read)
             Xd = torch.zeros((1, D), dtype=torch.float64, device=device)
             ld = torch.zeros(1, dtype=torch.float64, device=device)
-        segd, ngd, nbd, fgd, fbd = (dev(a, t) for a, t in ((seg_h, torch.int64), (ng, torch.int64), (nb, torch.int64),
-                                                          (fg, torch.float64), (fb, torch.float64)))
-        vtd = dev(vt, torch.int32)
+        segd, ngd, nbd, fgd, fbd, vtd = (_to_device(a, t, device) for a, t in (
+            (seg_h, torch.int64), (ng, torch.int64), (nb, torch.int64), (fg, torch.float64), (fb, torch.float64),
+            (vt, torch.int32)))
         order = torch.empty(max(Ntot, 1), dtype=torch.int64, device=device)
         bwg = torch.full((B, D), float("nan"), dtype=torch.float64, device=device)
         bwb = torch.full((B, D), float("nan"), dtype=torch.float64, device=device)
@@ -704,24 +704,9 @@ def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, 
                                          sb, N.ORDER_NUMPY, sh))
         raw = {}
         if impute_seed is not None:  # the fit, and everything after it, sees the imputed view
-            raw = dict(raw_X=Xd, raw_seg_off=segd, raw_order=order)
-            view_h = np.concatenate(([0], np.cumsum(np.where(ng > 0, ng + nb, 0)))).astype(np.int64)
-            Nv = int(view_h[-1])
-            Xv = torch.zeros((max(Nv, 1), D), dtype=torch.float64, device=device)
-            order_v = torch.zeros(max(Nv, 1), dtype=torch.int64, device=device)
-            raw["src_rows"] = torch.zeros(max(Nv, 1), dtype=torch.int32, device=device)
-            raw["impute_counts"] = torch.zeros((B, 2), dtype=torch.int32, device=device)
-            viewd = dev(view_h, torch.int64)
-            if B and Nv:
-                wb = int(L.hbx_kde_impute_groups_workspace_bytes(Nv, B, D))
-                iws = torch.empty(wb, dtype=torch.uint8, device=device)
-                N.check(L.hbx_kde_impute_groups(
-                    N.ptr(Xd), D, N.ptr(segd), B, N.ptr(order), N.ptr(ngd), N.ptr(nbd),
-                    N.ptr(_levels_dev(levels, D, device)), N.ptr(viewd), Nv, int(impute_seed) & (2 ** 64 - 1),
-                    int(impute_counter) & (2 ** 64 - 1), int(impute_stream_id) & 0xFFFFFFFF, N.ptr(Xv),
-                    N.ptr(order_v), N.ptr(raw["src_rows"]), N.ptr(raw["impute_counts"]), N.ptr(iws), wb, sh))
-            raw["src_rows"] = raw["src_rows"][:Nv]
-            Xd, segd, seg_h, order, Ntot = Xv, viewd, view_h, order_v, Nv
+            (Xd, segd, seg_h, order, Ntot), raw = _impute_view(
+                Xd, segd, order, ngd, nbd, ng, nb, B, D, levels, impute_seed, impute_counter, impute_stream_id,
+                device, sh)
         if B and Ntot:
             fit = (N.ptr(Xd), D, N.ptr(segd), B, N.ptr(order), N.ptr(ngd), N.ptr(nbd), N.ptr(fgd),
                    N.ptr(fbd), N.ptr(vtd), N.ptr(bwg), N.ptr(bwb), N.ptr(nlg), N.ptr(nlb), sh)
@@ -832,9 +817,7 @@ class GroupBOHB(object):
         self._cond_dev = None
 
     def _dev(self, a, shape_tail):
-        torch = kde._torch()
-        t = a if _is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
-        t = t.to(device=self.device, dtype=torch.float64)
+        t = _to_device(a, kde._torch().float64, self.device)
         if t.dim() != 1 + len(shape_tail) + 1 or int(t.shape[0]) != self.B or tuple(t.shape[2:]) != shape_tail:
             raise N.HbxError("expected [%d, m%s], got %s" % (self.B, "".join(", %d" % v for v in shape_tail),
                                                              tuple(t.shape)))
@@ -930,19 +913,10 @@ def advance(rows, seg_off, mask, K, fresh=None, stream=None, sync=True, device=N
     K = int(K)
     if device is None:
         device = rows.device if _is_tensor(rows) else kde.default_device()
-
-    def dev(a, dtype, what):
-        if _is_tensor(a):
-            t = a.view(torch.uint8) if a.dtype == torch.bool and dtype == torch.uint8 else a
-            if t.dtype != dtype or not t.is_contiguous():
-                raise N.HbxError("advance: %s must be a contiguous %s tensor" % (what, dtype))
-            return t
-        npd = {torch.float64: np.float64, torch.int64: np.int64, torch.uint8: np.uint8}[dtype]
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=npd)).to(device)
-
     with N.on_device(device, stream):
-        rd, sd, md = dev(rows, torch.float64, "rows"), dev(seg_off, torch.int64, "seg_off"), \
-            dev(mask, torch.uint8, "mask")
+        rd = _to_device(rows, torch.float64, device, True, "advance: rows")
+        sd = _to_device(seg_off, torch.int64, device, True, "advance: seg_off")
+        md = _to_device(mask, torch.uint8, device, True, "advance: mask")
         if rd.dim() != 2 or sd.dim() != 1 or int(sd.shape[0]) < 1 or md.dim() != 1 or \
                 int(md.shape[0]) != int(rd.shape[0]):
             raise N.HbxError("advance: rows [N, D], seg_off [B + 1] and mask [N] expected, got %s, %s, %s" %
@@ -950,7 +924,7 @@ def advance(rows, seg_off, mask, K, fresh=None, stream=None, sync=True, device=N
         B, D = int(sd.shape[0]) - 1, int(rd.shape[1])
         fd, F = None, 0
         if fresh is not None:
-            fd = dev(fresh, torch.float64, "fresh")
+            fd = _to_device(fresh, torch.float64, device, True, "advance: fresh")
             if fd.dim() != 3 or int(fd.shape[0]) != B or int(fd.shape[2]) != D:
                 raise N.HbxError("advance: fresh must be [%d, F, %d], got %s" % (B, D, tuple(fd.shape)))
             F = int(fd.shape[1])

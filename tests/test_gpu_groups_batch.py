@@ -296,10 +296,8 @@ def test_python_surface_and_edges(device):
     res = torch.empty((5, 4, 48), dtype=torch.uint8, device=device)
 
     def call(B, S, C, wsb):
-        return L.hbx_kde_acquire_groups_batch(
-            N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
-            N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad),
-            N.ptr(cands), S, C, N.ptr(res), N.ptr(ws), wsb, None)
+        model = tuple(B if name == "B" else arg for name, arg in zip(groups.MODEL_ARGS, gm.model_args()))
+        return L.hbx_kde_acquire_groups_batch(*model, N.ptr(cands), S, C, N.ptr(res), N.ptr(ws), wsb, None)
 
     assert call(1 << 12, 1 << 10, 1 << 10, 1 << 12) == -1 and b"int32" in L.hbx_last_error()  # (checked first)
     assert call(5, 4, 32, 1 << 12) == -1 and b"workspace too small" in L.hbx_last_error()

@@ -77,6 +77,16 @@ def timed(fn, reps, warm=3):
     return e0.elapsed_time(e1) / reps
 
 
+def sampler(gm, L, sh, lvd, seed, C, cands, derr):
+    """The hbx_kde_sample_groups call of C candidates per bracket into ``cands`` / ``derr`` (counter base 0, stream
+    id 0), its arguments taken once: the function a timed loop calls."""
+    args = gm.model_args(groups.SAMPLE_ARGS) + (N.ptr(lvd), 3.0, seed, 0, 0, C, N.ptr(cands), N.ptr(derr), sh)
+
+    def call():
+        N.check(L.hbx_kde_sample_groups(*args))
+    return call
+
+
 def requests_bench(a, gm, L, sh, lvd):
     """--requests R: R pools of C candidates per bracket (one hbx_kde_sample_groups call with pool R C), then
       loop         R back-to-back hbx_kde_acquire_groups calls over the R request slices (--loop-only: nothing
@@ -90,12 +100,9 @@ def requests_bench(a, gm, L, sh, lvd):
     B, R, C, D = gm.B, a.requests, a.C, gm.D
     pool = torch.empty((B, R * C, D), dtype=torch.float64, device=dev)
     derr = torch.empty((B, R * C), dtype=torch.uint8, device=dev)
-    N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
-                                    N.ptr(gm.bw_good), N.ptr(lvd), 3.0, S.SEED_CAND, 0, 0, R * C, N.ptr(pool),
-                                    N.ptr(derr), sh))
+    sampler(gm, L, sh, lvd, S.SEED_CAND, R * C, pool, derr)()
     cands = pool.view(B, R, C, D)
-    model = (N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
-             N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad))
+    model = gm.model_args()
     slices = [cands[:, s].contiguous() for s in range(R)]
     wsb1 = int(L.hbx_kde_groups_workspace_bytes(B, C, D))
     ws1 = torch.empty(wsb1, dtype=torch.uint8, device=dev)
@@ -155,13 +162,10 @@ def topk_bench(a, gm, L, sh, lvd):
     and reports the shortlist per group (mean, maximum) and the share of groups flagged NEAR_TIE."""
     dev = gm.device
     B, K, C, D = gm.B, a.topk, a.C, gm.D
-    model = (N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
-             N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad))
+    model = gm.model_args()
     pool = torch.empty((B, K * C, D), dtype=torch.float64, device=dev)
     derr = torch.empty((B, K * C), dtype=torch.uint8, device=dev)
-    N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
-                                    N.ptr(gm.bw_good), N.ptr(lvd), 3.0, S.SEED_CAND, 0, 0, K * C, N.ptr(pool),
-                                    N.ptr(derr), sh))
+    sampler(gm, L, sh, lvd, S.SEED_CAND, K * C, pool, derr)()
     cands_s = pool.view(B, K, C, D)
     cands = cands_s[:, 0].contiguous()  # the top-k's one pool: request 0's
     step = kde.TOPK_HEAD_BYTES + kde.TOPK_REC.itemsize * K
@@ -271,11 +275,8 @@ def logpdf_shape(a, dev, L, name, dc, du, lev):
     lvd = torch.tensor([0] * dc + [lev] * du, dtype=torch.int32, device=dev)
     cands = torch.empty((B, C, D), dtype=torch.float64, device=dev)
     derr = torch.empty((B, C), dtype=torch.uint8, device=dev)
-    N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
-                                    N.ptr(gm.bw_good), N.ptr(lvd), 3.0, S.SEED_CAND, 0, 0, C, N.ptr(cands),
-                                    N.ptr(derr), sh))
-    model = (N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
-             N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad))
+    sampler(gm, L, sh, lvd, S.SEED_CAND, C, cands, derr)()
+    model = gm.model_args()
     wsb = gm.workspace_bytes_logpdf(C)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     ll = torch.empty((B, C), dtype=torch.float64, device=dev)
@@ -392,8 +393,7 @@ def get_config_bench(a, gm, L, sh, lvd, levels):
     B, R, C, D = gm.B, a.requests, a.C, gm.D
     rf, seed = 1.0 / 3, S.SEED_CAND
     a.out = a.out or os.path.join(ROOT, "profiles", "groups_get_config", "bench_groups_get_config.json")
-    model = (N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
-             N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad))
+    model = gm.model_args()
     wsf = int(L.hbx_kde_propose_groups_workspace_bytes(B, R, C, D))
     wsb = int(L.hbx_kde_groups_batch_workspace_bytes(B, R, C, D))
     ws = torch.empty(wsf, dtype=torch.uint8, device=dev)
@@ -409,10 +409,10 @@ def get_config_bench(a, gm, L, sh, lvd, levels):
         N.check(L.hbx_kde_propose_groups(*model, N.ptr(lvd), 3.0, rf, seed, 0, 0, R, C, N.ptr(rows_f), N.ptr(src_f),
                                          N.ptr(rec_f), None, N.ptr(ws), wsf, sh))
 
+    sample = sampler(gm, L, sh, lvd, seed, R * C, pool, derr)
+
     def two_calls():
-        N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
-                                        N.ptr(gm.bw_good), N.ptr(lvd), 3.0, seed, 0, 0, R * C, N.ptr(pool),
-                                        N.ptr(derr), sh))
+        sample()
         N.check(L.hbx_kde_acquire_groups_batch(*model, N.ptr(pool), R, C, N.ptr(rec), N.ptr(ws), wsb, sh))
 
     def finish():
@@ -766,16 +766,11 @@ def main(argv=None):
                               N.ptr(gm.n_bad_dev), N.ptr(gm.fac_good_dev), N.ptr(gm.fac_bad_dev), N.ptr(gm.vt_dev),
                               N.ptr(gm.bw_good), N.ptr(gm.bw_bad), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad), sh))
 
-    def sample():
-        N.check(L.hbx_kde_sample_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
-                                        N.ptr(gm.bw_good), N.ptr(lvd), 3.0, S.SEED_CAND, 0, 0, C, N.ptr(cands),
-                                        N.ptr(derr), sh))
+    sample = sampler(gm, L, sh, lvd, S.SEED_CAND, C, cands, derr)
+    model = gm.model_args()
 
     def acquire():
-        N.check(L.hbx_kde_acquire_groups(N.ptr(gm.X), D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev),
-                                         N.ptr(gm.n_bad_dev), N.ptr(gm.vt_dev), N.ptr(gm.bw_good), N.ptr(gm.bw_bad),
-                                         N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad), N.ptr(cands), C, N.ptr(res),
-                                         N.ptr(ws), wsb, sh))
+        N.check(L.hbx_kde_acquire_groups(*model, N.ptr(cands), C, N.ptr(res), N.ptr(ws), wsb, sh))
 
     sample()
     ms_acq = timed(acquire, a.reps)
