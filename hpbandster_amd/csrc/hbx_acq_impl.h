@@ -93,12 +93,7 @@ __device__ __forceinline__ ScoreIv score_interval_l_only(const KdeEst a, const S
 // e[r stride + i]): the sums add (log domain, fp32); each partial's relative bound holds for the total too (sums
 // of positive terms), plus per merge its own rounding: 2^-18 for the fp32 exp / log / addition, and the rounding
 // of the merged ln S to fp32 (<= |ln S| 2^-23 absolute, counted as 2^-22 |ln S| relative on S)
-__device__ __forceinline__ KdeEst merge_splits(const KdeEst* __restrict__ e, int64_t stride, int64_t i, int nsplit) {
-  // every partial's load issued before the first merge (a load per dependent merge step cost 14 us for 16
-  // splits of 64 candidates); fixed-size and fully unrolled, so the partials stay in registers
-  KdeEst p[OBS_SPLIT_MAX];
-#pragma unroll
-  for (int r = 0; r < OBS_SPLIT_MAX; ++r) p[r] = r < nsplit ? e[(int64_t)r * stride + i] : kde_est_neutral();
+__device__ __forceinline__ KdeEst merge_loaded_splits(const KdeEst (&p)[OBS_SPLIT_MAX], int nsplit) {
   auto lae = [](float x, float y) {
     const float m = fmaxf(x, y);
     return m == -INFINITY ? m : m + __logf(__expf(x - m) + __expf(y - m));
@@ -119,6 +114,31 @@ __device__ __forceinline__ KdeEst merge_splits(const KdeEst* __restrict__ e, int
     }
   }
   return a;
+}
+// every partial's load issued before the first merge (a load per dependent merge step cost 14 us for 16
+// splits of 64 candidates); fixed-size and fully unrolled, so the partials stay in registers
+__device__ __forceinline__ void load_splits(KdeEst (&p)[OBS_SPLIT_MAX], const KdeEst* __restrict__ e, int64_t stride,
+                                            int64_t i, int nsplit) {
+#pragma unroll
+  for (int r = 0; r < OBS_SPLIT_MAX; ++r) p[r] = r < nsplit ? e[(int64_t)r * stride + i] : kde_est_neutral();
+}
+__device__ __forceinline__ KdeEst merge_splits(const KdeEst* __restrict__ e, int64_t stride, int64_t i, int nsplit) {
+  KdeEst p[OBS_SPLIT_MAX];
+  load_splits(p, e, stride, i, nsplit);
+  return merge_loaded_splits(p, nsplit);
+}
+// The same for a list launch's partials, where a rescue marker (err == -1) in any partial makes the merged
+// estimate the marker: the marker test on the partials already loaded, not on a second, one-by-one read of them.
+__device__ __forceinline__ KdeEst merge_splits_or_marker(const KdeEst* __restrict__ e, int64_t stride, int64_t i,
+                                                         int nsplit, bool* mark) {
+  KdeEst p[OBS_SPLIT_MAX];
+  load_splits(p, e, stride, i, nsplit);
+  bool m = false;
+#pragma unroll
+  for (int r = 0; r < OBS_SPLIT_MAX; ++r) m = m || (r < nsplit && p[r].err == -1.f);
+  *mark = m;
+  const KdeEst a = merge_loaded_splits(p, nsplit);
+  return m ? KdeEst{0.f, -INFINITY, -1.f, 0.f} : a;
 }
 
 // bohb.py:129 with Python max() and the score floor f: max(f, g) keeps f unless g > f (NaN -> f); max(l, f)

@@ -150,7 +150,8 @@ int staged_score_survivors(const AcqPlan& plan, const KdePairRef& p, const doubl
 int acq_exact_only_init(int64_t Nc, uint32_t seg, const AcqWs& a, hipStream_t s);
 // (3) the exact fp64 re-score of the shortlist a.list / a.count (scan, a single acquisition of at most
 // EXACT_SCAN_MAX candidates: the blocks shortlist for themselves), then -- combine -- its unit sums into
-// a.exact_l / a.exact_g
+// a.exact_l / a.exact_g; wide: behind the staged acquisition's short tail (short shortlists: the re-score's wide
+// blocks, hbx_exact.hip; never together with scan)
 #define EXACT_SCAN_MAX 1024
 int acq_exact(const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a, bool scan, bool combine,
-              hipStream_t s);
+              hipStream_t s, bool wide = false);

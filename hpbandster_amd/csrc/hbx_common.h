@@ -80,7 +80,7 @@ struct KdeParams {
   float cmax;         // max_j |C_j| over the table (error bound)
   float sum_abs_delta;// sum |delta_u| over finite deltas (error bound)
   float cmax2;        // max_j |C_j| of the f32-layout rebuild (hmode table out of the f16 range)
-  int32_t pad1;
+  int32_t lnpdf_guard;// 1: log_norm + ln max(n, 1) < 600, the staged acquisitions' overflow guard (hbx_staged.hip)
   int32_t kc;         // categorical mode: 0 = VALU match on codes, k >= 1 = one-hot on f16 MFMA,
                       // k steps of K=32 (2 * oh_total <= 32 k)
   int32_t hmode;      // 1: continuous product on f16 matrix cores too (hi/lo split coordinates)

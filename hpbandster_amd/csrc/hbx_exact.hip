@@ -9,11 +9,16 @@
 // Exact re-score of the shortlist.  Small shortlists (<= EXACT_SPLIT_CAP): one work item per
 // (candidate, KDE, 8192-buffer, unit) so one candidate spreads over many CUs; the unit sums go to
 // `part` and kde_final combines them.  Larger: one item per (candidate, KDE), all units in turn.
-// threads per block of the acquisition's exact re-score: one unit (<= 263 observations) per block, one
-// observation per thread (one wave per SIMD; the 32 units of a buffer run on 32 CUs)
-#ifndef EXACT_ACQ_THREADS
+// threads per block of the acquisition's exact re-score: one unit (<= 263 observations) per block; the 32 units of a
+// buffer run on 32 CUs.  LANES = 1: one observation per thread, 256 threads (one wave per SIMD, six blocks per CU) --
+// wherever the shortlist's length is not known to be short: batched and top-k acquisitions, and the unstaged single
+// acquisition (small calls one after the other measured 6 % slower with the wide block: most lanes of short units
+// idle, one block per CU).  LANES = 4: behind the staged acquisition's short tail, which runs at 1e8 pairs and
+// more and shortlists a handful of candidates, so a block or less per CU, where the launch lasts as long as one
+// thread's chain of restated-numpy exps: four adjacent lanes per observation, each with every fourth dim's factor
+// (exact_unit_spread), 1024 threads, and a unit of <= 256 observations still takes one pass.
 #define EXACT_ACQ_THREADS 256
-#endif
+#define EXACT_ACQ_LANES 4
 // SCAN (a single acquisition of <= EXACT_SCAN_MAX candidates): no shortlist launch before this one -- every
 // block restates kde_shortlist_kernel's predicate over the whole candidate set itself, in index order (a
 // ballot prefix per wave), into its own LDS list; block 0 stores the list, its length and the zeroed marker
@@ -30,8 +35,8 @@ struct ExactScan {
   int32_t* count;
   int32_t* rescue_cnt;
 };
-template <bool SCAN>
-__global__ __launch_bounds__(EXACT_ACQ_THREADS) void kde_exact_kernel(
+template <bool SCAN, int LANES>
+__global__ __launch_bounds__(EXACT_ACQ_THREADS * LANES) void kde_exact_kernel(
     const double* __restrict__ cand, int32_t D,
     const KdeParams* __restrict__ Pg, const double* __restrict__ Xg, const int64_t* __restrict__ rows_g,
     const KdeParams* __restrict__ Pb, const double* __restrict__ Xb, const int64_t* __restrict__ rows_b,
@@ -39,7 +44,8 @@ __global__ __launch_bounds__(EXACT_ACQ_THREADS) void kde_exact_kernel(
     double* __restrict__ exact_l, double* __restrict__ exact_g, ExactScan sc) {
   __shared__ ExactShared sh;
   __shared__ int32_t slist[SCAN ? EXACT_SCAN_MAX : 1];
-  __shared__ int32_t swc[EXACT_ACQ_THREADS / 64];
+  constexpr int NT = EXACT_ACQ_THREADS * LANES;
+  __shared__ int32_t swc[NT / 64];
   int cnt;
   const int32_t* list = list_in;
   if constexpr (SCAN) {
@@ -48,7 +54,7 @@ __global__ __launch_bounds__(EXACT_ACQ_THREADS) void kde_exact_kernel(
     const int32_t f1 = sc.first1[0];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int base = 0;
-    for (int64_t c0 = 0; c0 < sc.Nc; c0 += EXACT_ACQ_THREADS) {
+    for (int64_t c0 = 0; c0 < sc.Nc; c0 += NT) {
       const int64_t i = c0 + threadIdx.x;
       bool in = false;
       if (i < sc.Nc) {
@@ -60,7 +66,7 @@ __global__ __launch_bounds__(EXACT_ACQ_THREADS) void kde_exact_kernel(
       __syncthreads();
       int off = base, tot = 0;
 #pragma unroll
-      for (int w = 0; w < EXACT_ACQ_THREADS / 64; ++w) {
+      for (int w = 0; w < NT / 64; ++w) {
         off += w < wv ? swc[w] : 0;
         tot += swc[w];
       }
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(EXACT_ACQ_THREADS) void kde_exact_kernel(
     cnt = base;
     list = slist;
     if (blockIdx.x == 0) {
-      for (int k = threadIdx.x; k < cnt; k += EXACT_ACQ_THREADS) sc.list[k] = slist[k];
+      for (int k = threadIdx.x; k < cnt; k += NT) sc.list[k] = slist[k];
       if (threadIdx.x == 0) {
         *sc.count = cnt;
         if (sc.rescue_cnt) *sc.rescue_cnt = 0;
@@ -98,7 +104,9 @@ __global__ __launch_bounds__(EXACT_ACQ_THREADS) void kde_exact_kernel(
       int off, len;
       if (!pw_unit<PW_SPLIT_CUT>(m, u, &off, &len)) continue;
       exact_setup(P, D, cand + (int64_t)list[p] * D, &sh);
-      const double v = exact_unit<PW_SPLIT_LEVELS>(X, D, rows, P, c + off, len, &sh);
+      double v;
+      if constexpr (LANES > 1) v = exact_unit_spread<PW_SPLIT_LEVELS, LANES>(X, D, rows, P, c + off, len, &sh);
+      else v = exact_unit<PW_SPLIT_LEVELS>(X, D, rows, P, c + off, len, &sh);
       if (threadIdx.x == 0) part[pk * per + r] = v;
     } else {
       exact_setup(P, D, cand + (int64_t)list[p] * D, &sh);
@@ -249,12 +257,16 @@ __global__ __launch_bounds__(256) void kde_logpdf_exact_kernel(const double* __r
 }
 
 int acq_exact(const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a, bool scan, bool combine,
-              hipStream_t s) {
+              hipStream_t s, bool wide) {
+  if (scan && wide) return hbx_fail(HBX_ERR_ARG, "acq_exact: the wide re-score does not scan");
   const int nbuf = (int)((p.nmax + PW_BUF - 1) / PW_BUF);
   const ExactScan esc = scan ? ExactScan{a.lo, Nc, a.U, a.flags, a.first1, a.list, a.count, a.rescue} : ExactScan{};
-  auto ek = scan ? kde_exact_kernel<true> : kde_exact_kernel<false>;
-  hipLaunchKernelGGL(ek, dim3(EXACT_GRID), dim3(EXACT_ACQ_THREADS), 0, s, cand, p.D, p.Pg(), p.X_good, p.rows_good,
-                     p.Pb(), p.X_bad, p.rows_bad, a.list, a.count, nbuf, a.part, a.exact_l, a.exact_g, esc);
+  auto ek = wide   ? kde_exact_kernel<false, EXACT_ACQ_LANES>
+            : scan ? kde_exact_kernel<true, 1>
+                   : kde_exact_kernel<false, 1>;
+  const dim3 threads(EXACT_ACQ_THREADS * (wide ? EXACT_ACQ_LANES : 1));
+  hipLaunchKernelGGL(ek, dim3(EXACT_GRID), threads, 0, s, cand, p.D, p.Pg(), p.X_good, p.rows_good, p.Pb(), p.X_bad,
+                     p.rows_bad, a.list, a.count, nbuf, a.part, a.exact_l, a.exact_g, esc);
   HBX_LAUNCH_CHECK();
   if (combine) {
     hipLaunchKernelGGL(kde_exact_combine_kernel, dim3((2 * EXACT_SPLIT_CAP + 3) / 4), dim3(256), 0, s, p.Pg(), p.Pb(),

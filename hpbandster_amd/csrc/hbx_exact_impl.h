@@ -60,6 +60,67 @@ __device__ double exact_unit(const double* __restrict__ X, int32_t D, const int6
   return np_pairwise_block<LEVELS>(sh->dens, len, sh->nsum);
 }
 
+// The same unit sum with T adjacent lanes per observation (T a power of two <= 64; blockDim.x / T observations
+// a pass): lane t of a group evaluates the factors of the dims t, T + t, ..., so a thread's chain of exps is D / T
+// long instead of D, and every lane of the group multiplies the factors in dim order as they arrive -- the
+// products ((k_0 k_1) k_2) ... of exact_unit, whichever lane evaluated k_d.  Same loads, same exp, same
+// multiplications and division, same pairwise sum: same bits.  Whole block.
+#define EXACT_SPREAD_ROUNDS 2
+template <int LEVELS, int T, typename PV>
+__device__ double exact_unit_spread(const double* __restrict__ X, int32_t D, const int64_t* __restrict__ rows,
+                                    const PV* __restrict__ P, int first, int len, ExactShared* sh) {
+  static_assert(T >= 1 && T <= 64 && (T & (T - 1)) == 0, "a group lies within one wave");
+  const double pbc = P->prod_bw_c;
+  const int t = threadIdx.x & (T - 1), nobs = blockDim.x / T;
+  for (int j0 = 0; j0 < len; j0 += nobs) {  // (uniform trip count: every lane takes part in the shuffles)
+    const int j = j0 + (int)threadIdx.x / T;
+    const bool act = j < len;
+    const double* xr = X + rows[first + (act ? j : 0)] * (int64_t)D;
+    double p = 1.0;
+    // EXACT_SPREAD_ROUNDS rounds of T dims at a time, fixed counts (the shuffles keep the compiler from unrolling a
+    // loop of its own): the next rounds' coordinates are requested before this one's exps (past D: dim D - 1
+    // again, a factor nobody multiplies), and a round past D evaluates nothing
+    double vn[EXACT_SPREAD_ROUNDS];
+#pragma unroll
+    for (int q = 0; q < EXACT_SPREAD_ROUNDS; ++q) vn[q] = xr[q * T + t < D ? q * T + t : D - 1];
+    for (int d0 = 0; d0 < D; d0 += T * EXACT_SPREAD_ROUNDS) {
+      double v[EXACT_SPREAD_ROUNDS], k[EXACT_SPREAD_ROUNDS];
+#pragma unroll
+      for (int q = 0; q < EXACT_SPREAD_ROUNDS; ++q) {
+        const int dn = d0 + (EXACT_SPREAD_ROUNDS + q) * T + t;
+        v[q] = vn[q];
+        vn[q] = xr[dn < D ? dn : D - 1];
+      }
+#pragma unroll
+      for (int q = 0; q < EXACT_SPREAD_ROUNDS; ++q) {
+        const int d = d0 + q * T + t < D ? d0 + q * T + t : D - 1;
+        k[q] = 1.0;
+        if (d0 + q * T < D) {  // (uniform)
+          const double xv = sh->xd[d];
+          if (sh->cont[d]) {
+            const double diff = v[q] - xv;
+            k[q] = HBX_INV_SQRT_2PI * hbx_npexp::exp(-(diff * diff) / sh->c0[d]);  // numpy's exp, bit for bit
+          } else {
+            k[q] = (v[q] == xv) ? sh->c0[d] : sh->c1[d];
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < EXACT_SPREAD_ROUNDS; ++q) {
+#pragma unroll
+        for (int s = 0; s < T; ++s) {
+          const double ks = __shfl(k[q], s, T);
+          const int d = d0 + q * T + s;
+          if (d < D) p = (d == 0) ? ks : p * ks;  // (uniform)
+        }
+      }
+    }
+    if (act && t == 0) sh->dens[j] = p / pbc;
+  }
+  __syncthreads();
+  return np_pairwise_block<LEVELS>(sh->dens, len, sh->nsum);
+}
+
 // exact fp64 pdf of one KDE at the point staged by exact_setup, one block, all units in turn
 template <typename PV>
 __device__ double exact_pdf(const double* __restrict__ X, int32_t D, const int64_t* __restrict__ rows,

@@ -728,7 +728,9 @@ static int acquire_impl(const void* pair, const AcqCall& c) {
     }
     // single acquisition: the final kernel combines the unit sums itself (one launch less)
     fuse_combine = !batch_res && !(plan.exact_only && (logl_out || logg_out));
-    rc = acq_exact(p, cand, Nc, a, scan, !fuse_combine, s);
+    // (behind the short tail the re-score's wide blocks: measured at the bench's shortlist of two or three; a staged
+    // call with a long shortlist -- HBX_STAGED=2 on small pools, ties -- gets them too, and that case is not measured)
+    rc = acq_exact(p, cand, Nc, a, scan, !fuse_combine, s, tail);
     if (rc) return rc;
     if (plan.exact_only && (logl_out || logg_out)) {
       hipLaunchKernelGGL(kde_exact_logs_kernel, grid, dim3(256), 0, s, a.list, a.count, a.exact_l, a.exact_g, logl_out,

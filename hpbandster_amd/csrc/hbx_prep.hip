@@ -264,7 +264,9 @@ __device__ __forceinline__ void kde_params_body(const PrepArgs& A, KdeParams* P,
     P->lb_sum = lb_sum;
     P->prod_bw_c = prod_bw_c;
     P->sum_abs_delta = sad;
-    P->log_norm = -log((double)n) - sum_ln_h - 0.5 * (double)dc * log(2.0 * M_PI) + m0 * M_LN2;
+    const double log_norm = -log((double)n) - sum_ln_h - 0.5 * (double)dc * log(2.0 * M_PI) + m0 * M_LN2;
+    P->log_norm = log_norm;
+    P->lnpdf_guard = log_norm + log((double)(n > 1 ? n : 1)) < 600.0 ? 1 : 0;
     P->X = A.X;
     P->rows = A.rows;
   }

@@ -56,6 +56,14 @@ template <int KS, typename T> __device__ __forceinline__ int h32_idx(const T& v,
   else return (int)v[s];
 }
 
+// max(a, b, c) in one instruction, without the canonicalising v_max_f32 x, x that fmaxf puts in front of an operand
+// whose origin the compiler cannot see (a matrix accumulator)
+__device__ __forceinline__ float h32_max3(float a, float b, float c) {
+  float r;
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+
 // sched_group_barrier pattern of one phase: NM times {1 MFMA, its fragment re-read(s), a share of the
 // NV VALU ops} (the last matrix instruction re-reads its fragment and the index words)
 template <int I, int NM, int NV, int NRL, bool RD = true>
@@ -422,9 +430,15 @@ __device__ __forceinline__ void kde_logpdf_h32_body(const double* __restrict__ c
     mma(a0, t);
     readA(lds, 1);
     mma(a1, t);
-    float mx = fmaxf(a0[0], a1[0]);
+    // the 32 terms' maximum by three-operand maxima, two chains of 8 (the same value: a maximum does not depend on
+    // its association, and v_max3_f32 skips a NaN operand as fmaxf does)
+    float mx = fmaxf(a0[0], a1[0]), my = fmaxf(a0[1], a1[1]);
 #pragma unroll
-    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, fmaxf(a0[r], a1[r]));
+    for (int r = 2; r < 16; r += 2) {
+      mx = h32_max3(mx, a0[r], a1[r]);
+      my = h32_max3(my, a0[r + 1], a1[r + 1]);
+    }
+    mx = fmaxf(mx, my);
     mx = fmaxf(mx, __shfl_xor(mx, 32));
     const float d = rintf(-(ci[t] + mx));
     const float dl = (d > 0.f && d < 1e30f) ? d : 0.f;  // NaN rows: no shift

@@ -195,7 +195,20 @@ __global__ __launch_bounds__(256) void staged_seed_kernel(float* __restrict__ lh
   if (bmax) {  // (uniform)
     __shared__ float rb[4];
     float m = -INFINITY;
-    for (int j = threadIdx.x; j < nblk; j += 256) m = fmaxf(m, bmax[j]);
+    // 16-byte loads, four per thread in flight (4096 maxima a round: one round up to 1e6 candidates), the area being
+    // 256-byte aligned in the workspace like every other (ws_layout); then the last nblk % 4.  The maximum does not
+    // depend on the order it is taken in (no NaN among the block maxima, and no -0: est_interval's lo)
+    const float4* b4 = (const float4*)bmax;
+    const int n4 = nblk >> 2;
+    for (int j = threadIdx.x; j < n4; j += 4 * 256) {
+      float4 v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        v[q] = j + q * 256 < n4 ? b4[j + q * 256] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) m = fmaxf(m, fmaxf(fmaxf(v[q].x, v[q].y), fmaxf(v[q].z, v[q].w)));
+    }
+    for (int j = (n4 << 2) + threadIdx.x; j < nblk; j += 256) m = fmaxf(m, bmax[j]);
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0) rb[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -272,19 +285,20 @@ __global__ __launch_bounds__(256) void staged_merge_kernel(const KdeEst* __restr
   float h = INFINITY;
   if (k < cnt) {
     const int32_t i = idx[k];
-    bool mark = false;
-    for (int q = 0; q < ns; ++q) mark = mark || part[(int64_t)q * cap + k].err == -1.f;
-    KdeEst e = {0.f, -INFINITY, -1.f, 0.f};
-    if (!mark) e = merge_splits(part, cap, k, ns);
+    // the ns partials and the l estimate requested together; the marker test and the merge on the loaded partials
+    const KdeEst a = update_u ? el[i] : kde_est_neutral();
+    bool mark;
+    const KdeEst e = merge_splits_or_marker(part, cap, k, ns, &mark);
     eg[i] = e;
     if (update_u && !mark) {
-      const ScoreIv v = score_interval(el[i], e, F);
+      const ScoreIv v = score_interval(a, e, F);
       if (!v.lnan) h = v.shi;
     }
   }
   if (update_u) {
-    // overflow guard (file header): no pruning when the bad KDE's ln pdf can come near the flag's limit
-    const bool guard = Pb->log_norm + log((double)(Pb->n > 1 ? Pb->n : 1)) < 600.0;
+    // overflow guard (file header): no pruning when the bad KDE's ln pdf can come near the flag's limit; the test
+    // log_norm + ln n < 600 is made once per KDE where its parameters are written (KdeParams::lnpdf_guard)
+    const bool guard = Pb->lnpdf_guard != 0;
     for (int o = 32; o > 0; o >>= 1) h = fminf(h, __shfl_xor(h, o));
     if ((threadIdx.x & 63) == 0 && guard && h < INFINITY) {
       const uint32_t o = hbx_f2ord(h);
@@ -422,10 +436,8 @@ __global__ __launch_bounds__(256) void staged_tail_kernel(StagedTailArgs t) {
     bool store = false;
     if (!(k < nseed || !split)) {
       const int64_t ks = k - nseed;
-      bool mark = false;
-      for (int q = 0; q < t.ns; ++q) mark = mark || t.part[(int64_t)q * t.cap + ks].err == -1.f;
-      eb[r] = {0.f, -INFINITY, -1.f, 0.f};
-      if (!mark) eb[r] = merge_splits(t.part, t.cap, ks, t.ns);
+      bool mark;
+      eb[r] = merge_splits_or_marker(t.part, t.cap, ks, t.ns, &mark);
       store = true;
     }
     if (nres != 0 && eb[r].err == -1.f) {  // rare

@@ -308,7 +308,7 @@ __global__ __launch_bounds__(TOPK_USEED_T) void topk_useed_kernel(const int32_t*
     __syncthreads();
   }
   if (t == 0) {
-    const bool guard = Pb->log_norm + log((double)(Pb->n > 1 ? Pb->n : 1)) < 600.0;
+    const bool guard = Pb->lnpdf_guard != 0;  // log_norm + ln n < 600 (hbx_prep.hip)
     stage[HBX_ST_USEED] = guard && s_rank != 0xffffffffu ? s_prefix : TOPK_KEY_INF;
   }
 }
