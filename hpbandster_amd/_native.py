@@ -92,6 +92,22 @@ SIGNATURES = {
                                          ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
                                          ctypes.c_uint32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
                                          c_vp]),
+    "hbx_kde_sample_groups_m": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, ctypes.c_double,
+                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_i64, c_i64, c_vp, c_vp,
+                                        c_vp, c_vp]),
+    "hbx_kde_acquire_groups_batch_m": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "hbx_kde_groups_request_stats": (c_i32, [c_vp, c_vp]),
+    "hbx_kde_finish_groups_m": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, ctypes.c_double,
+                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp]),
+    "hbx_kde_random_requests_groups": (c_i32, [c_i64, c_i64, c_i64, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
+                                               ctypes.c_uint32, c_vp, c_vp, c_vp]),
+    "hbx_kde_propose_groups_m_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i32]),
+    "hbx_kde_propose_groups_m_ws_offsets": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_vp]),
+    "hbx_kde_propose_groups_m": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
+                                         ctypes.c_uint32, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                         c_i64, c_vp, c_vp]),
     "hbx_kde_impute_groups_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
     "hbx_kde_impute_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_uint64,
                                       ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),

@@ -104,7 +104,53 @@ struct GrpArgs {
   GScreen* scr;
   AcqResult* res;
   ScoreFloor F;      // the call's score floor (hbx_rules.pdf_floor), read by the kernels' <.., DEFF = false> instances
+  // the request mask (hbx_kde_acquire_groups_batch_m), read by the kernels' <.., MASK = true> instances alone:
+  const uint8_t* want;         // u8[B][S], request (b, s) is answered when its byte is not 0; NULL: every request
+  unsigned long long* stats;   // the workspace head's four counters (hbx_kde_groups_request_stats)
 };
+
+// The request mask in a kernel.  MASK follows DEFF's precedent: the <.., MASK = false> instances are, instruction for
+// instruction, the kernels the unmasked entry points have always launched (profiles/request_mask/README.md has the
+// register figures of both); the <.., true> instances serve hbx_kde_acquire_groups_batch_m.  The grid is the dense
+// one either way -- the host never reads the mask -- and blocks and waves decide for themselves:
+//   groups_screen_kernel   a tile of the flattened pool without a wanted candidate returns after its uniform test,
+//                          before classification and staging; in a mixed tile the lanes of unwanted requests are !valid
+//   groups_tiles_kernel    the block lists its group's wanted tiles (grp_wanted_tiles) and slab j takes the wanted
+//                          tiles j NW .. j NW + NW - 1; slabs beyond the list return at once
+//   groups_select_kernel   the block of an unwanted request classifies its group, writes the skipped record, returns
+// A candidate's arithmetic does not change with the mask (the same rows in the same order into the same sums), and
+// the host picks the screen from the dense S and tile count, so a wanted request's record is the dense call's, byte
+// for byte.  Counters, one atomic add per block: [0] requests answered, [1] requests skipped (select), [2] candidates
+// the screen evaluated, [3] candidates re-scored in fp64 (select).
+__device__ __forceinline__ bool grp_wanted(const GrpArgs& A, int64_t b, int64_t i) {  // candidate i of group b's pool
+  return !A.want || A.want[b * A.S + (int64_t)((uint32_t)i / (uint32_t)A.C)] != 0;    // (i < P <= INT32_MAX)
+}
+
+// The wanted tiles of group b in ascending order, ranks r0 .. r0 + NW - 1, into s_tile[0 .. NW) (-1 past the list):
+// one wave, 64 tiles per round -- lane = tile, wanted when a request that owns one of its candidates is, a ballot
+// prefix gives its rank.  Stops once the slab is full.
+template <int NW>
+__device__ __forceinline__ void grp_wanted_tiles(const GrpArgs& A, int64_t b, int r0, int lane, int32_t* s_tile) {
+  if (lane < NW) s_tile[lane] = -1;
+  int cnt = 0;
+  for (int t0 = 0; t0 < A.tiles && cnt < r0 + NW; t0 += 64) {  // (uniform)
+    const int t = t0 + lane;
+    bool w = false;
+    if (t < A.tiles) {
+      const int64_t i0 = (int64_t)t * 64, i1 = i0 + 63 < A.P ? i0 + 63 : A.P - 1;
+      if (!A.want) {
+        w = true;
+      } else {
+        const int s1 = (int)((uint32_t)i1 / (uint32_t)A.C);
+        for (int s = (int)((uint32_t)i0 / (uint32_t)A.C); s <= s1; ++s) w = w || A.want[b * A.S + s] != 0;
+      }
+    }
+    const uint64_t bal = __ballot(w);
+    const int r = cnt + __popcll(bal & ((1ull << lane) - 1ull)) - r0;
+    if (w && r >= 0 && r < NW) s_tile[r] = t;
+    cnt += __popcll(bal);
+  }
+}
 
 // The call's score floor in a kernel.  DEFF: the reference snapshot's 1e-8 as compile-time constants
 // (hbx_score_floor(1e-8)'s values) -- the default path's kernels are then instruction for instruction what they were
@@ -122,7 +168,7 @@ __device__ __forceinline__ ScoreFloor grp_floor(const GrpArgs& A) {
 #define GRP_PAIRS_CALL(QC, QU, SG) \
   grp_pairs<DCP, DUP, QC, QU, SG>(srows, L.rs, jmax, L.dcq, L.duq, xc, xu, dl, nf, lbs, m, sp, sn)
 
-template <int DCP, int DUP, int NW, int DT, bool DEFF>
+template <int DCP, int DUP, int NW, int DT, bool DEFF, bool MASK>
 __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
   constexpr int NT = 64 * NW;
   __shared__ __align__(16) float sobs[NW * 64 * (DT + 4)];
@@ -136,7 +182,13 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
   const int64_t b = (int64_t)blockIdx.x / A.tiles;
   const int tile = (int)((int64_t)blockIdx.x - b * A.tiles);
   const int64_t i = (int64_t)tile * 64 + lane;
-  const bool valid = i < A.P;  // (the group's flattened pool: S requests of C candidates)
+  bool valid = i < A.P;  // (the group's flattened pool: S requests of C candidates)
+  int nvalid = 0;
+  if constexpr (MASK) {  // (every wave sees the same 64 candidates: the test is uniform over the block)
+    valid = valid && grp_wanted(A, b, i);
+    nvalid = __popcll(__ballot(valid));
+    if (nvalid == 0) return;
+  }
   GScreen* out = A.scr + b * A.P + i;
   if (wave == 0) {
     int dc, du;
@@ -154,6 +206,8 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
     if (wave == 0 && valid) *out = grp_uncertified(D, st);
     return;
   }
+  if constexpr (MASK)
+    if (tid == 0) atomicAdd(A.stats + 2, (unsigned long long)nvalid);
   const int64_t s0 = mod.seg_off[b], n = mod.seg_off[b + 1] - s0;
   const int64_t ng = mod.n_good[b], nb = mod.n_bad[b];
   const double* Xs = mod.X + s0 * D;
@@ -250,7 +304,7 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
 // for groups_screen_kernel (before: 165 / 196 / 255 / 256) and 190 / 219 / 235 / 256 for this kernel (180 / 209 / 224 /
 // 256), every one at the waves per SIMD it had (3 / 2 / 2 / 1 and 2 / 2 / 2 / 1), no scratch.  The one step that
 // groups_screen_kernel does not take from the header is the candidate's load (the comment there has the numbers).
-template <int DCP, int DUP, int NW, int DT, bool DEFF>
+template <int DCP, int DUP, int NW, int DT, bool DEFF, bool MASK>
 __global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kernel(GrpArgs A) {
   constexpr int NT = 64 * NW;
   __shared__ __align__(16) float sobs[NW * 64 * (DT + 4)];
@@ -262,6 +316,15 @@ __global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kerne
   const int D = mod.D;
   const int64_t b = (int64_t)blockIdx.x / A.slabs;
   const int tile0 = (int)((int64_t)blockIdx.x - b * A.slabs) * NW;  // the slab's first tile
+  // MASK: wave w's tile is the (tile0 + w)-th WANTED tile of the group (-1: none); a slab past the list returns
+  int32_t* s_tile = nullptr;
+  if constexpr (MASK) {
+    __shared__ int32_t s_wtile[NW];
+    s_tile = s_wtile;
+    if (wave == 0) grp_wanted_tiles<NW>(A, b, tile0, lane, s_tile);
+    __syncthreads();
+    if (s_tile[0] < 0) return;  // (uniform)
+  }
   if (wave == 0) {
     int dc, du;
     const int st = grp_classify(mod, b, &dc, &du);
@@ -275,8 +338,13 @@ __global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kerne
   __syncthreads();
   const int st = s_i[0], dc = s_i[1], du = s_i[2];
   if (st & GRP_NO_SCREEN) {  // no screen: the select kernel re-scores (or skips)
-    const int64_t iw = (int64_t)(tile0 + wave) * 64 + lane;
-    if (iw < A.P) A.scr[b * A.P + iw] = grp_uncertified(D, st);
+    if constexpr (MASK) {
+      const int64_t iw = (int64_t)s_tile[wave] * 64 + lane;
+      if (s_tile[wave] >= 0 && iw < A.P && grp_wanted(A, b, iw)) A.scr[b * A.P + iw] = grp_uncertified(D, st);
+    } else {
+      const int64_t iw = (int64_t)(tile0 + wave) * 64 + lane;
+      if (iw < A.P) A.scr[b * A.P + iw] = grp_uncertified(D, st);
+    }
     return;
   }
   const int64_t s0 = mod.seg_off[b], n = mod.seg_off[b + 1] - s0;
@@ -308,10 +376,24 @@ __global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kerne
   int g = 0;
   bool certified = true;
   KdeEst est_l = kde_est_neutral();
-  const int tw = tile0 + wave;  // this wave's tile
+  int tw = tile0 + wave;  // this wave's tile
+  if constexpr (MASK) tw = s_tile[wave];
   const int64_t iw = (int64_t)tw * 64 + lane;
-  const bool vw = iw < A.P;
-  const bool live = tw < A.tiles;  // (wave-uniform; a wave without a tile still stages its rows)
+  bool vw = iw < A.P;
+  bool live = tw < A.tiles;  // (wave-uniform; a wave without a tile still stages its rows)
+  if constexpr (MASK) {
+    live = tw >= 0;
+    vw = live && vw && grp_wanted(A, b, iw);
+    if (wave == 0) {  // the slab's evaluated candidates, counted by one wave: one atomic add per block
+      int nev = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        const int64_t ie = (int64_t)s_tile[w] * 64 + lane;
+        nev += __popcll(__ballot(s_tile[w] >= 0 && ie < A.P && grp_wanted(A, b, ie)));
+      }
+      if (lane == 0) atomicAdd(A.stats + 2, (unsigned long long)nev);
+    }
+  }
   const double* x = A.cand + (b * A.P + (vw ? iw : live ? (int64_t)tw * 64 : 0)) * D;
 #pragma unroll 1
   for (int kd = 0; kd < 2; ++kd) {
@@ -355,7 +437,7 @@ __device__ __forceinline__ AcqResult grp_empty_record(int32_t flags) {
   return r;
 }
 
-template <bool DEFF>
+template <bool DEFF, bool MASK>
 __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs A) {
   __shared__ ExactShared sh;
   __shared__ GrpView vw[2];
@@ -381,8 +463,22 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
   }
   __syncthreads();
   const int st = s_st;
+  if constexpr (MASK) {
+    if (A.want && A.want[q] == 0) {  // (uniform) the skipped record, with the group's bits as the dense call sets them
+      if (tid == 0) {
+        A.res[q] = grp_empty_record(HBX_ACQ_SKIPPED | ((st & GRP_NO_MODEL)      ? HBX_ACQ_NO_MODEL
+                                                       : (st & GRP_UNSUPPORTED) ? HBX_ACQ_UNSUPPORTED
+                                                                                : 0));
+        atomicAdd(A.stats + 1, 1ull);
+      }
+      return;
+    }
+  }
   if (st & (GRP_NO_MODEL | GRP_UNSUPPORTED)) {
-    if (tid == 0) A.res[q] = grp_empty_record((st & GRP_NO_MODEL) ? HBX_ACQ_NO_MODEL : HBX_ACQ_UNSUPPORTED);
+    if (tid == 0) {
+      A.res[q] = grp_empty_record((st & GRP_NO_MODEL) ? HBX_ACQ_NO_MODEL : HBX_ACQ_UNSUPPORTED);
+      if constexpr (MASK) atomicAdd(A.stats + 0, 1ull);
+    }
     return;
   }
   const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
@@ -487,12 +583,17 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
       r.pdf_g = bg;
     }
     A.res[q] = r;
+    if constexpr (MASK) {
+      atomicAdd(A.stats + 0, 1ull);
+      atomicAdd(A.stats + 3, (unsigned long long)nshort);
+    }
   }
 }
 
-__global__ void groups_empty_kernel(AcqResult* res, int64_t B) {
+// C == 0: every record is the empty one; want (nullable): the skipped record for the unwanted requests
+__global__ void groups_empty_kernel(AcqResult* res, int64_t B, const uint8_t* want) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) res[b] = grp_empty_record(0);
+  if (b < B) res[b] = grp_empty_record(want && want[b] == 0 ? HBX_ACQ_SKIPPED : 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -765,17 +866,17 @@ static bool grp_tile_screen(int64_t S, int64_t tiles) {
 static bool grp_floor_default(const ScoreFloor& F) { return F.f == HBX_PDF_FLOOR_DEFAULT; }
 
 // One screen launch: the bucket's instance (grp_model picked the bucket from D alone)
-template <bool TILES>
+template <bool TILES, bool MASK = false>
 static void grp_launch_screen(GrpArgs& A, hipStream_t s) {
   const int nw = A.M.D <= 32 ? 4 : 2;  // waves of the bucket's instance
   A.slabs = (A.tiles + nw - 1) / nw;  // the tile screen: one tile per wave
   const dim3 grid((unsigned)(A.M.B * (TILES ? A.slabs : A.tiles)));  // <= B * S * C <= INT32_MAX
-#define GRP_LAUNCH_F(DCP, DUP, NW, DT, DEFF)                                                            \
-  do {                                                                                                  \
-    if (TILES)                                                                                          \
-      hipLaunchKernelGGL((groups_tiles_kernel<DCP, DUP, NW, DT, DEFF>), grid, dim3(64 * NW), 0, s, A);  \
-    else                                                                                                \
-      hipLaunchKernelGGL((groups_screen_kernel<DCP, DUP, NW, DT, DEFF>), grid, dim3(64 * NW), 0, s, A); \
+#define GRP_LAUNCH_F(DCP, DUP, NW, DT, DEFF)                                                                  \
+  do {                                                                                                        \
+    if (TILES)                                                                                                \
+      hipLaunchKernelGGL((groups_tiles_kernel<DCP, DUP, NW, DT, DEFF, MASK>), grid, dim3(64 * NW), 0, s, A);  \
+    else                                                                                                      \
+      hipLaunchKernelGGL((groups_screen_kernel<DCP, DUP, NW, DT, DEFF, MASK>), grid, dim3(64 * NW), 0, s, A); \
   } while (0)
 #define GRP_LAUNCH(DCP, DUP, NW, DT)       \
   do {                                     \
@@ -803,6 +904,8 @@ static GrpArgs grp_args(const GrpModel& M, const ScoreFloor& F, const double* ca
   A.slabs = 0;
   A.scr = (GScreen*)((char*)workspace + GRP_WS_HEAD);
   A.res = (AcqResult*)results;
+  A.want = nullptr;
+  A.stats = nullptr;
   return A;
 }
 
@@ -815,8 +918,12 @@ static int grp_rules_floor(const char* who, const hbx_rules* rules, ScoreFloor* 
   return HBX_OK;
 }
 
+// MASK: hbx_kde_acquire_groups_batch_m -- the same checks, the same choice of screen (from the dense S and tile count:
+// the host does not see the mask), the kernels' masked instances, the counters in the workspace's head zeroed first
+template <bool MASK = false>
 static int grp_acquire(const char* who, const GrpModel& M, const hbx_rules* rules, const double* cand, int64_t S,
-                       int64_t C, void* results, void* workspace, int64_t ws_bytes, void* stream) {
+                       int64_t C, void* results, void* workspace, int64_t ws_bytes, void* stream,
+                       const uint8_t* want = nullptr) {
   ScoreFloor F;
   if (const int rc = grp_rules_floor(who, rules, &F)) return rc;
   const int64_t B = M.B;
@@ -831,7 +938,7 @@ static int grp_acquire(const char* who, const GrpModel& M, const hbx_rules* rule
   hipStream_t s = (hipStream_t)stream;
   if (C == 0) {  // nothing to score: every record is the empty one
     hipLaunchKernelGGL(groups_empty_kernel, dim3((unsigned)((B * S + 255) / 256)), dim3(256), 0, s, (AcqResult*)results,
-                       B * S);
+                       B * S, want);
     HBX_LAUNCH_CHECK();
     return HBX_OK;
   }
@@ -842,12 +949,17 @@ static int grp_acquire(const char* who, const GrpModel& M, const hbx_rules* rule
   if (((uintptr_t)workspace & 15) || ((uintptr_t)results & 7))
     return hbx_fail(HBX_ERR_ARG, "%s: workspace must be 16-byte, results 8-byte aligned", who);
   GrpArgs A = grp_args(M, F, cand, S, C, results, workspace);
+  if constexpr (MASK) {
+    A.want = want;
+    A.stats = (unsigned long long*)workspace;
+    HBX_HIP(hipMemsetAsync(workspace, 0, 4 * sizeof(unsigned long long), s));
+  }
   if (grp_tile_screen(S, A.tiles))
-    grp_launch_screen<true>(A, s);
+    grp_launch_screen<true, MASK>(A, s);
   else
-    grp_launch_screen<false>(A, s);
+    grp_launch_screen<false, MASK>(A, s);
   HBX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(grp_floor_default(F) ? groups_select_kernel<true> : groups_select_kernel<false>,
+  hipLaunchKernelGGL((grp_floor_default(F) ? groups_select_kernel<true, MASK> : groups_select_kernel<false, MASK>),
                      dim3((unsigned)(B * S)), dim3(GRP_SEL_THREADS), 0, s, A);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
@@ -932,6 +1044,28 @@ int hbx_kde_acquire_groups_batch_r(const double* X, int32_t D, const int64_t* se
   return grp_acquire(rules ? "hbx_kde_acquire_groups_batch_r" : "hbx_kde_acquire_groups_batch",
                      grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good, nlev_bad),
                      rules, cand, S, C, results, workspace, ws_bytes, stream);
+}
+
+int hbx_kde_acquire_groups_batch_m(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                   const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                   const double* bw_good, const double* bw_bad, const int32_t* nlev_good,
+                                   const int32_t* nlev_bad, const double* cand, int64_t S, int64_t C,
+                                   const uint8_t* want, void* results, void* workspace, int64_t ws_bytes, void* stream,
+                                   const hbx_rules* rules) {
+  return grp_acquire<true>("hbx_kde_acquire_groups_batch_m",
+                           grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good,
+                                     nlev_bad),
+                           rules, cand, S, C, results, workspace, ws_bytes, stream, want);
+}
+
+// the masked acquisition's counters (the workspace's head): synchronises the device
+int hbx_kde_groups_request_stats(const void* workspace, int64_t* out4) {
+  if (!workspace || !out4) return hbx_fail(HBX_ERR_ARG, "hbx_kde_groups_request_stats: null pointer");
+  HBX_HIP(hipDeviceSynchronize());
+  unsigned long long v[4];
+  HBX_HIP(hipMemcpy(v, workspace, sizeof(v), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 4; ++k) out4[k] = (int64_t)v[k];
+  return HBX_OK;
 }
 
 // the grouped workspace (the screen slots) followed by the re-scored candidates' pdfs, 16 bytes per candidate: the

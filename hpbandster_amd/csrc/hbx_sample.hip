@@ -299,23 +299,39 @@ __global__ __launch_bounds__(256) void kde_sample_pair_kernel(
 // counter_base + b C + i: the same draw, sample_dim and stores, so its bytes are hbx_kde_sample's for that group
 // at counter_base + b C.  Blocks: B x ceil(C / CPB), linear in blockIdx.x.  Groups without a model (n_good[b] <= 0
 // or past the segment, hbx_kde_fit's rule) get NaN rows.
+//
+// MASK (hbx_kde_sample_groups_m): the pool is S requests of Cr candidates (C = S Cr) and want[b][s] says which
+// requests are drawn.  The grid is the dense one; a block whose candidates all belong to unwanted requests returns
+// before it reads the model, and in a mixed block the lanes of unwanted requests neither draw nor store -- so a wanted
+// candidate's bytes are the dense call's, and an unwanted request's rows and error bytes are not written.  The
+// <false> instance is the kernel hbx_kde_sample_groups has always launched.
+template <bool MASK>
 __global__ __launch_bounds__(256) void kde_sample_groups_kernel(
     const double* __restrict__ X, int32_t D, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ order,
     const int64_t* __restrict__ n_good, const double* __restrict__ bw_good, const int32_t* __restrict__ levels,
     double bw_factor, uint64_t seed, uint64_t counter_base, uint32_t stream_id, int64_t C, int32_t tiles,
-    double* __restrict__ cands, uint8_t* __restrict__ domain_err) {
+    double* __restrict__ cands, uint8_t* __restrict__ domain_err, int32_t S, int32_t Cr,
+    const uint8_t* __restrict__ want) {
   constexpr int CPB = 256 / SAMPLE_LPC;  // candidates per block
   __shared__ int32_t sdat[CPB];
   __shared__ double srh[HBX_MAX_D];  // 1 / bw per dim
   const int64_t b = (int64_t)blockIdx.x / tiles;
   const int64_t c0 = ((int64_t)blockIdx.x - b * tiles) * CPB;
   const int nc = (int)(C - c0 < CPB ? C - c0 : CPB);
+  bool wdraw = true, wlane = true;  // the datum draw of candidate c0 + threadIdx.x, the dims of candidate c0 + cl
+  if constexpr (MASK) {
+    const uint8_t* wb = want + b * S;
+    wdraw = (int)threadIdx.x < nc && wb[(uint32_t)(c0 + threadIdx.x) / (uint32_t)Cr] != 0;
+    if (!__syncthreads_or(wdraw)) return;  // (uniform) nothing wanted here: the model is not read
+    const int clm = threadIdx.x / SAMPLE_LPC;
+    wlane = clm < nc && wb[(uint32_t)(c0 + clm) / (uint32_t)Cr] != 0;
+  }
   const int64_t s0 = seg_off[b], n = n_good[b];
   const bool model = n > 0 && n <= seg_off[b + 1] - s0;  // (uniform)
   const int cl = threadIdx.x / SAMPLE_LPC, g = threadIdx.x % SAMPLE_LPC;
   const int D2 = (D + 1) >> 1;
   if (!model) {
-    if (cl < nc) {
+    if (cl < nc && wlane) {
       double* out = cands + (b * C + c0 + cl) * (int64_t)D;
       for (int d = g; d < D; d += SAMPLE_LPC) out[d] = NAN;
     }
@@ -325,13 +341,13 @@ __global__ __launch_bounds__(256) void kde_sample_groups_kernel(
   const int64_t* rows = order + s0;
   const double* Xs = X + s0 * (int64_t)D;
   for (int t = threadIdx.x; t < D; t += 256) srh[t] = 1.0 / bw[t];
-  if (threadIdx.x < nc) {
+  if (threadIdx.x < nc && wdraw) {
     const uint64_t ctr = counter_base + (uint64_t)(b * C + c0 + threadIdx.x);
     const uint64_t rb = hbx_bits64(draw(seed, ctr, DATUM_WORD, stream_id), 0);
     sdat[threadIdx.x] = (int32_t)__umul64hi(rb, (uint64_t)n);  // floor(u * n), u = rb / 2^64
   }
   __syncthreads();
-  if (cl >= nc) return;
+  if (cl >= nc || !wlane) return;
   const int64_t i = b * C + c0 + cl;  // the candidate's row in cands and its byte in domain_err
   const uint64_t ctr = counter_base + (uint64_t)i;
   const int32_t idx = sdat[cl];
@@ -379,8 +395,39 @@ int hbx_kde_sample_groups(const double* X, int32_t D, const int64_t* seg_off, in
   if (domain_err) HBX_HIP(hipMemsetAsync(domain_err, 0, (size_t)(B * C), s));
   constexpr int CPB = 256 / SAMPLE_LPC;
   const int64_t tiles = (C + CPB - 1) / CPB;
-  hipLaunchKernelGGL(kde_sample_groups_kernel, dim3((unsigned)(B * tiles)), dim3(256), 0, s, X, D, seg_off, order, n_good,
-                     bw_good, levels, bw_factor, seed, counter_base, stream_id, C, (int32_t)tiles, cands, domain_err);
+  hipLaunchKernelGGL(kde_sample_groups_kernel<false>, dim3((unsigned)(B * tiles)), dim3(256), 0, s, X, D, seg_off, order,
+                     n_good, bw_good, levels, bw_factor, seed, counter_base, stream_id, C, (int32_t)tiles, cands,
+                     domain_err, 1, 1, (const uint8_t*)nullptr);
+  HBX_LAUNCH_CHECK();
+  return HBX_OK;
+}
+
+int hbx_kde_sample_groups_m(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                            const int64_t* n_good, const double* bw_good, const int32_t* levels, double bw_factor,
+                            uint64_t seed, uint64_t counter_base, uint32_t stream_id, int64_t S, int64_t C,
+                            const uint8_t* want, double* cands, uint8_t* domain_err, void* stream) {
+  const char* who = "hbx_kde_sample_groups_m";
+  if (B < 0 || S < 0 || C < 0 || D < 1 || D > HBX_MAX_D)
+    return hbx_fail(HBX_ERR_ARG, "%s: B=%lld S=%lld C=%lld D=%d", who, (long long)B, (long long)S, (long long)C, D);
+  if (B > INT32_MAX || S > INT32_MAX || (S > 0 && B > (int64_t)INT32_MAX / S) ||
+      (C > 0 && B * S > (int64_t)INT32_MAX / C))
+    return hbx_fail(HBX_ERR_ARG, "%s: B * S * C = %lld * %lld * %lld exceeds int32", who, (long long)B, (long long)S,
+                    (long long)C);
+  if (!want)  // every request wanted: the dense call itself
+    return hbx_kde_sample_groups(X, D, seg_off, B, order, n_good, bw_good, levels, bw_factor, seed, counter_base,
+                                 stream_id, S * C, cands, domain_err, stream);
+  if (B == 0 || S == 0 || C == 0) return HBX_OK;
+  if (!X || !seg_off || !order || !n_good || !bw_good || !levels || !cands)
+    return hbx_fail(HBX_ERR_ARG, "%s: null pointer", who);
+  if ((D & 1) == 0 && ((uintptr_t)cands & 15)) return hbx_fail(HBX_ERR_ARG, "%s: cands not 16-byte aligned", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t P = S * C;
+  if (domain_err) HBX_HIP(hipMemsetAsync(domain_err, 0, (size_t)(B * P), s));
+  constexpr int CPB = 256 / SAMPLE_LPC;
+  const int64_t tiles = (P + CPB - 1) / CPB;
+  hipLaunchKernelGGL(kde_sample_groups_kernel<true>, dim3((unsigned)(B * tiles)), dim3(256), 0, s, X, D, seg_off, order,
+                     n_good, bw_good, levels, bw_factor, seed, counter_base, stream_id, P, (int32_t)tiles, cands,
+                     domain_err, (int32_t)S, (int32_t)C, want);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }

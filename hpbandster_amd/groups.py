@@ -176,6 +176,60 @@ class GroupTopK(object):
 
 
 SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR = 0, 1, 2, 3, 4  # HBX_CFG_*
+SOURCE_SKIPPED = 5           # HBX_CFG_SKIPPED: the request mask left the request out (its row is NaN)
+ACQ_SKIPPED = 64             # include/hbx.h HBX_ACQ_SKIPPED: the record of such a request
+PROPOSE_SKIP_RANDOM = 1      # include/hbx.h HBX_PROPOSE_SKIP_RANDOM
+
+
+def counts_to_mask(counts, S):
+    """The request mask of per-run request counts: ``counts`` [B] (an int array, or an int device tensor) ->
+    uint8 [B, S] with request (b, s) wanted iff ``s < counts[b]``; a tensor op where ``counts`` lies, no read-back."""
+    S = int(S)
+    if _is_tensor(counts):
+        torch = kde._torch()
+        if counts.dim() != 1 or counts.dtype not in (torch.int64, torch.int32):
+            raise N.HbxError("counts must be an int32 / int64 tensor [B], got %s %s" % (counts.dtype,
+                                                                                      tuple(counts.shape)))
+        return (torch.arange(S, device=counts.device)[None, :] < counts[:, None]).to(torch.uint8)
+    c = np.asarray(counts)
+    if c.ndim != 1 or c.dtype.kind not in "iu":
+        raise N.HbxError("counts must be an int array [B], got %s %s" % (c.dtype, c.shape))
+    return (np.arange(S)[None, :] < c[:, None]).astype(np.uint8)
+
+
+def request_mask(want, B, S, device):
+    """``want`` as the contiguous uint8 device tensor [B, S] the masked calls read (None stays None: every request).
+    ``want``: a bool / uint8 array or contiguous device tensor [B, S], or per-run counts -- an int array or device
+    tensor [B] (counts_to_mask).  HbxError for another dtype, shape, device or memory order, before any launch."""
+    if want is None:
+        return None
+    torch = kde._torch()
+    B, S = int(B), int(S)
+    if _is_tensor(want):
+        if want.device.type != torch.device(device).type or (
+                torch.device(device).index is not None and want.device.index != torch.device(device).index):
+            raise N.HbxError("the request mask must lie on %s, got a tensor on %s" % (device, want.device))
+        if want.dim() == 1 and want.dtype in (torch.int64, torch.int32):
+            if int(want.shape[0]) != B:
+                raise N.HbxError("counts must have %d entries, got %d" % (B, int(want.shape[0])))
+            return counts_to_mask(want, S)
+        if want.dtype not in (torch.bool, torch.uint8):
+            raise N.HbxError("the request mask must be bool or uint8, got %s" % (want.dtype,))
+        if tuple(want.shape) != (B, S):
+            raise N.HbxError("the request mask must be [%d, %d], got %s" % (B, S, tuple(want.shape)))
+        if not want.is_contiguous():
+            raise N.HbxError("the request mask must be contiguous")
+        return want.view(torch.uint8) if want.dtype == torch.bool else want
+    w = np.asarray(want)
+    if w.ndim == 1 and w.dtype.kind in "iu" and w.dtype != np.uint8:
+        if w.shape[0] != B:
+            raise N.HbxError("counts must have %d entries, got %d" % (B, w.shape[0]))
+        w = counts_to_mask(w, S)
+    if w.dtype not in (np.bool_, np.uint8):
+        raise N.HbxError("the request mask must be bool or uint8, got %s" % (w.dtype,))
+    if w.shape != (B, S):
+        raise N.HbxError("the request mask must be [%d, %d], got %s" % (B, S, w.shape))
+    return torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint8)).to(device)
 
 
 class GroupConfigs(object):
@@ -188,6 +242,7 @@ class GroupConfigs(object):
     ``cands`` / ``domain_err`` hold the pools and the sampler's error bytes when the call kept them.  ``len()`` is B."""
     SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR = \
         SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR  # (the module's)
+    SOURCE_SKIPPED = SOURCE_SKIPPED  # a request the mask left out: a NaN row, not model based
     __slots__ = ("rows", "source", "model_based", "picks", "cands", "domain_err")
 
     def __init__(self, rows, source, B, S=None, picks=None, cands=None, domain_err=None):
@@ -235,31 +290,40 @@ def _configs(rows, source, B, S, sync, records=None, cands=None, err=None):
                         None if cands is None else cands.cpu().numpy(), None if err is None else err.cpu().numpy())
 
 
-def _finish(device, stream, B, S, C, D, records, cands, err, levels, random_fraction, seed, counter_base, stream_id):
-    """one hbx_kde_finish_groups launch over device tensors (records None: NULL); (rows [B * S, D], source [B * S])"""
+def _finish(device, stream, B, S, C, D, records, cands, err, levels, random_fraction, seed, counter_base, stream_id,
+            want=None):
+    """one hbx_kde_finish_groups launch over device tensors (records None: NULL); (rows [B * S, D], source [B * S]).
+    ``want``: the request mask (request_mask's tensor) -- then hbx_kde_finish_groups_m."""
     torch = kde._torch()
     Sn = 1 if S is None else int(S)
     rows = torch.empty((B * Sn, D), dtype=torch.float64, device=device)
     source = torch.empty(B * Sn, dtype=torch.uint8, device=device)
     lvd = _levels_dev(levels, D, device)
-    N.check(N.lib().hbx_kde_finish_groups(
-        N.ptr(records), N.ptr(cands), N.ptr(err), N.ptr(lvd), D, B, Sn, int(C), random_fraction,
-        *(_philox(seed, counter_base, stream_id) + (N.ptr(rows), N.ptr(source), N.stream_handle(stream, device)))))
+    head = (N.ptr(records), N.ptr(cands), N.ptr(err), N.ptr(lvd), D, B, Sn, int(C), random_fraction) + \
+        _philox(seed, counter_base, stream_id)
+    tail = (N.ptr(rows), N.ptr(source), N.stream_handle(stream, device))
+    if want is None:
+        N.check(N.lib().hbx_kde_finish_groups(*(head + tail)))
+    else:
+        N.check(N.lib().hbx_kde_finish_groups_m(*(head + (N.ptr(want),) + tail)))
     return rows, source
 
 
-def sample_prior(B, S, levels, seed, counter_base=0, C=1, stream=None, stream_id=0, device=None, sync=True):
+def sample_prior(B, S, levels, seed, counter_base=0, C=1, stream=None, stream_id=0, device=None, sync=True,
+                 want=None):
     """What B runs without any model answer S get_config requests each with (bohb.py:109-110): one prior draw per
     request (hbx_kde_finish_groups without records), request (b, s) on the Philox counter
     ``counter_base + (b * S + s) * C`` -- ``C`` is the counter stride, the pool size the same requests would use
     with a model.  ``S`` None: one request per run, rows [B, D].  Returns GroupConfigs, every source
-    SOURCE_NO_MODEL."""
+    SOURCE_NO_MODEL -- or, under a request mask ``want`` (request_mask's forms), SOURCE_SKIPPED and a NaN row for the
+    requests it leaves out."""
     D = len(levels) if not _is_tensor(levels) else int(levels.shape[0])
     if device is None:
         device = levels.device if _is_tensor(levels) else kde.default_device()
     with N.on_device(device, stream):
+        wd = request_mask(want, B, 1 if S is None else S, device)
         rows, source = _finish(device, stream, int(B), S, C, D, None, None, None, levels, 0.0, seed, counter_base,
-                               stream_id)
+                               stream_id, wd)
         return _configs(rows, source, int(B), S, sync)
 
 
@@ -357,13 +421,31 @@ class GroupModel(object):
                                       h["nlev"][0][b], h["nlev"][1][b], device=self.device, pdf_floor=self.pdf_floor)
 
     # ---- the grouped calls ------------------------------------------------------------------------------
-    def sample(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, stream_id=0, requests=None):
+    def sample(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, stream_id=0, requests=None,
+               want=None):
         """C candidates per group around its good KDE's rows (bohb.py:133-147; hbx_kde_sample_groups):
         candidate (b, i) draws from the Philox counter ``counter_base + b * C + i``.  Returns device tensors
         (cands [B, C, D] float64, domain_err [B, C] uint8); groups without a model get NaN rows.
         With ``requests=S``: S pools of C candidates per group, (cands [B, S, C, D], domain_err [B, S, C]) -- the
         same call with pool size S * C, so candidate (b, s, i) draws from the Philox counter
-        ``counter_base + (b * S + s) * C + i`` and the bytes equal ``sample(S * C, ...)``'s."""
+        ``counter_base + (b * S + s) * C + i`` and the bytes equal ``sample(S * C, ...)``'s.
+        ``want`` (with ``requests``; request_mask's forms): hbx_kde_sample_groups_m -- only the wanted requests are
+        drawn, with the same bytes; the rows of the others are not written (whatever the new tensor held)."""
+        if want is not None:
+            if requests is None:
+                raise N.HbxError("sample: a request mask needs requests=S")
+            torch = kde._torch()
+            S, C = int(requests), int(C)
+            with N.on_device(self.device, stream):
+                wd = request_mask(want, self.B, S, self.device)
+                lvd = _levels_dev(levels, self.D, self.device)
+                cands = torch.empty((self.B, S, C, self.D), dtype=torch.float64, device=self.device)
+                err = torch.zeros((self.B, S, C), dtype=torch.uint8, device=self.device)
+                N.check(N.lib().hbx_kde_sample_groups_m(
+                    *(self.model_args(SAMPLE_ARGS) + (N.ptr(lvd), float(bandwidth_factor)) +
+                      _philox(seed, counter_base, stream_id) +
+                      (S, C, N.ptr(wd), N.ptr(cands), N.ptr(err), N.stream_handle(stream, self.device)))))
+            return cands, err
         if requests is not None:
             S = int(requests)
             cands, err = self.sample(S * int(C), seed, levels, bandwidth_factor, counter_base, stream, stream_id)
@@ -412,7 +494,7 @@ class GroupModel(object):
             raise N.HbxError("workspace too small")
         return ws
 
-    def _acquire(self, cd, S, C, stream, workspace, sync):
+    def _acquire(self, cd, S, C, stream, workspace, sync, want=None):
         """``acquire`` (``S`` None) and ``acquire_requests`` over the staged pool ``cd``, inside the caller's
         on_device context: the one-request entry point for ``S`` None under the default floor, the batched one
         otherwise; records [B, 48] or [B, S, 48]."""
@@ -424,7 +506,10 @@ class GroupModel(object):
                           dtype=torch.uint8, device=self.device)
         model = self.model_args() + (N.ptr(cd),)
         tail = (N.ptr(res), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device))
-        if S is None and self._rules is None:
+        if want is not None:
+            N.check(N.lib().hbx_kde_acquire_groups_batch_m(*(model + (Sn, C, N.ptr(want)) + tail + (
+                None if self._rules is None else ctypes.addressof(self._rules),))))
+        elif S is None and self._rules is None:
             N.check(N.lib().hbx_kde_acquire_groups(*(model + (C,) + tail)))
         else:  # (the batched call's S = 1 case is the one-request call: include/hbx.h)
             self._call("hbx_kde_acquire_groups_batch", *(model + (Sn, C) + tail))
@@ -441,15 +526,27 @@ class GroupModel(object):
             cd = self._stage_cands(cands, (3,))
             return self._acquire(cd, None, int(cd.shape[1]), stream, workspace, sync)
 
-    def acquire_requests(self, cands, stream=None, workspace=None, sync=True):
+    def acquire_requests(self, cands, stream=None, workspace=None, sync=True, want=None):
         """S get_config requests per group in one call (hbx_kde_acquire_groups_batch; HB_iteration.py:136-138 issues
         a stage's requests back to back against one model): request (b, s) is ``acquire`` for group b over its own
         pool ``cands[b, s]`` and sees no other request.  ``cands``: [B, S, C, D] float64, numpy or a device tensor.
         Returns GroupPicks with arrays of shape [B, S], or with ``sync=False`` the device tensor of the records
-        (uint8 [B, S, 48])."""
+        (uint8 [B, S, 48]).  ``want`` (request_mask's forms): hbx_kde_acquire_groups_batch_m -- the wanted requests'
+        records are the same bytes, the others get the empty record with ACQ_SKIPPED and their pools are not read;
+        ``request_stats(workspace)`` then says what was computed."""
         with N.on_device(self.device, stream):
             cd = self._stage_cands(cands, (4,))
-            return self._acquire(cd, int(cd.shape[1]), int(cd.shape[2]), stream, workspace, sync)
+            wd = request_mask(want, self.B, int(cd.shape[1]), self.device)
+            return self._acquire(cd, int(cd.shape[1]), int(cd.shape[2]), stream, workspace, sync, wd)
+
+    def request_stats(self, workspace):
+        """The counters of the last masked acquisition that used ``workspace`` (``acquire_requests(want=...)``, or
+        ``get_config`` with a mask or ``skip_random``): (requests answered, requests skipped, candidates the screen
+        evaluated, candidates re-scored in fp64).  Synchronises the device (hbx_kde_groups_request_stats)."""
+        out = np.zeros(4, dtype=np.int64)
+        with N.on_device(self.device):
+            N.check(N.lib().hbx_kde_groups_request_stats(N.ptr(workspace), out.ctypes.data))
+        return tuple(int(v) for v in out)
 
     def workspace_bytes_topk(self, C, k):
         return int(N.lib().hbx_kde_groups_topk_workspace_bytes(self.B, int(C), int(k), self.D))
@@ -516,11 +613,45 @@ class GroupModel(object):
             return GroupLogPdf(None if ll is None else ll.cpu().numpy(), None if lg is None else lg.cpu().numpy(),
                                status.cpu().numpy(), stats, lead)
 
-    def workspace_bytes_get_config(self, C, requests=1):
+    def workspace_bytes_get_config(self, C, requests=1, masked=False):
+        """``masked``: of the call with a request mask or ``skip_random`` (hbx_kde_propose_groups_m)"""
+        if masked:
+            return int(N.lib().hbx_kde_propose_groups_m_workspace_bytes(self.B, int(requests), int(C), self.D))
         return int(N.lib().hbx_kde_propose_groups_workspace_bytes(self.B, int(requests), int(C), self.D))
 
+    def _get_config_m(self, C, S, requests, seed, levels, rf, bandwidth_factor, counter_base, stream, stream_id,
+                      workspace, sync, keep_pools, records, want, skip_random):
+        """get_config under a request mask and / or skip_random: one hbx_kde_propose_groups_m call"""
+        torch = kde._torch()
+        with N.on_device(self.device, stream):
+            wd = request_mask(want, self.B, S, self.device)
+            ws = self._workspace(workspace, self.workspace_bytes_get_config(C, S, masked=True),
+                                 "get_config: B=%d S=%d C=%d out of range (C >= 1, B * S * C within int32)" %
+                                 (self.B, S, C))
+            lvd = _levels_dev(levels, self.D, self.device)
+            rows = torch.empty((self.B * S, self.D), dtype=torch.float64, device=self.device)
+            source = torch.empty(self.B * S, dtype=torch.uint8, device=self.device)
+            rec = torch.empty((self.B * S, kde.RESULT_BYTES), dtype=torch.uint8, device=self.device) if records else None
+            # (the pools of unanswered requests are not written: NaN rather than what the allocation held)
+            cands = torch.full((self.B, S, C, self.D), float("nan"), dtype=torch.float64, device=self.device) \
+                if keep_pools else None
+            N.check(N.lib().hbx_kde_propose_groups_m(*(
+                self.model_args() + (N.ptr(lvd), float(bandwidth_factor), rf) + _philox(seed, counter_base, stream_id) +
+                (S, C, N.ptr(wd), PROPOSE_SKIP_RANDOM if skip_random else 0, N.ptr(rows), N.ptr(source), N.ptr(rec),
+                 N.ptr(cands), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device),
+                 None if self._rules is None else ctypes.addressof(self._rules)))))
+            err = None
+            if keep_pools:
+                off = np.zeros(5, dtype=np.int64)
+                N.check(N.lib().hbx_kde_propose_groups_m_ws_offsets(self.B, S, C, self.D, off.ctypes.data))
+                err = ws[int(off[1]):int(off[1]) + self.B * S * C].clone().view(self.B, S, C)
+                if requests is None:
+                    cands, err = cands.view(self.B, C, self.D), err.view(self.B, C)
+            return _configs(rows, source, self.B, None if requests is None else S, sync, rec, cands, err)
+
     def get_config(self, C, seed, levels, requests=None, random_fraction=1.0 / 3, bandwidth_factor=3, counter_base=0,
-                   stream=None, stream_id=0, workspace=None, sync=True, keep_pools=False, records=True):
+                   stream=None, stream_id=0, workspace=None, sync=True, keep_pools=False, records=True, want=None,
+                   skip_random=False):
         """The reference's get_config (bohb.py:104-169) for ``requests`` requests of every group in one call
         (hbx_kde_propose_groups: ``sample`` with pool size S * C, ``acquire_requests`` and ``finish`` on one stream):
         always a configuration -- the best of the request's C candidates, or a prior draw where the group has no
@@ -528,11 +659,21 @@ class GroupModel(object):
         candidate has a score.  ``levels`` may be an int32 device tensor (no upload).  Returns GroupConfigs: rows
         [B, S, D] (``requests`` None: one request, [B, D]); with ``sync=False`` everything stays on the device and
         nothing synchronises.  ``records=False`` leaves ``picks`` None; ``keep_pools`` also returns the pools and
-        the sampler's error bytes (``cands`` [B, S, C, D], ``domain_err`` [B, S, C])."""
+        the sampler's error bytes (``cands`` [B, S, C, D], ``domain_err`` [B, S, C]).
+
+        ``want`` (request_mask's forms: a bool / uint8 mask [B, S], or int counts [B]) and ``skip_random`` make it one
+        hbx_kde_propose_groups_m call: only the wanted requests are sampled, scored and finished, each with exactly
+        the bytes of the call without a mask; the others come back as SOURCE_SKIPPED with a NaN row and an ACQ_SKIPPED
+        record.  ``skip_random``: requests that the random fraction takes are not sampled and scored either -- rows
+        and sources are unchanged, their records are skipped ones and their pools are not written (NaN with
+        ``keep_pools``).  ``request_stats(workspace)`` reports what was computed."""
         torch = kde._torch()
         S = 1 if requests is None else int(requests)
         C = int(C)
         rf = _fraction(random_fraction)
+        if want is not None or skip_random:
+            return self._get_config_m(C, S, requests, seed, levels, rf, bandwidth_factor, counter_base, stream,
+                                      stream_id, workspace, sync, keep_pools, records, want, bool(skip_random))
         with N.on_device(self.device, stream):
             ws = self._workspace(workspace, self.workspace_bytes_get_config(C, S),
                                  "get_config: B=%d S=%d C=%d out of range (C >= 1, B * S * C within int32)" %
@@ -556,11 +697,12 @@ class GroupModel(object):
             return _configs(rows, source, self.B, None if requests is None else S, sync, rec, cands, err)
 
     def finish(self, cands, records, domain_err, levels, random_fraction=1.0 / 3, seed=0, counter_base=0, stream=None,
-               stream_id=0, sync=True):
+               stream_id=0, sync=True, want=None):
         """The finish step alone (hbx_kde_finish_groups) over caller-made pools: ``cands`` [B, S, C, D] (or [B, C, D])
         float64, ``records`` the ``sync=False`` output of ``acquire_requests`` (or ``acquire``) over them, or None
         (every request SOURCE_NO_MODEL), ``domain_err`` the sampler's error bytes [B, S, C] (or [B, C]), or None.
-        ``seed``, ``counter_base`` and ``stream_id`` are the sampler's.  Returns GroupConfigs without picks."""
+        ``seed``, ``counter_base`` and ``stream_id`` are the sampler's.  Returns GroupConfigs without picks.
+        ``want`` (request_mask's forms): hbx_kde_finish_groups_m -- SOURCE_SKIPPED and a NaN row where it is 0."""
         torch = kde._torch()
         rf = _fraction(random_fraction)
         with N.on_device(self.device, stream):
@@ -580,8 +722,9 @@ class GroupModel(object):
                     ed = torch.from_numpy(np.ascontiguousarray(ed, dtype=np.uint8)).to(self.device)
                 if ed.dtype != torch.uint8 or not ed.is_contiguous() or ed.numel() != Q * C:
                     raise N.HbxError("domain_err must be contiguous uint8 with one byte per candidate")
+            wd = request_mask(want, self.B, 1 if S is None else S, self.device)
             rows, source = _finish(self.device, stream, self.B, S, C, self.D, records, cd, ed, levels, rf, seed,
-                                   counter_base, stream_id)
+                                   counter_base, stream_id, wd)
             return _configs(rows, source, self.B, S, sync)
 
     def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, requests=None, topk=None):
@@ -786,8 +929,11 @@ class GroupBOHB(object):
 
     def __init__(self, B, var_type, levels, min_points_in_model=None, top_n_percent=15, num_samples=64,
                  random_fraction=1.0 / 3, bandwidth_factor=3, seed=0, device=None, min_bandwidth=None,
-                 pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, conditions=None):
+                 pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, conditions=None, skip_random=False):
         self.B, self.var_type, self.D = int(B), var_type, len(var_type)
+        if not isinstance(skip_random, (bool, np.bool_)):
+            raise ValueError("skip_random must be a bool, got %r" % (skip_random,))
+        self.skip_random = bool(skip_random)  # get_configs' default: random requests are not sampled and scored
         # the acquisition rules every refit and get_config of this optimiser uses (fit_groups)
         self.min_bandwidth, self.pdf_floor = N.check_min_bandwidth(min_bandwidth), N.check_pdf_floor(pdf_floor)
         # (named only where they differ from the reference snapshot's: the refit call is then the one it always was)
@@ -863,24 +1009,44 @@ class GroupBOHB(object):
             self._lvd = kde._torch().from_numpy(self.levels).to(self.device)
         return self._lvd
 
-    def get_configs(self, budget, S=1, counter_base=None, sync=True):
+    def get_configs(self, budget, S=1, counter_base=None, sync=True, want=None, counts=None, skip_random=None):
         """S configurations for every optimiser (``budget`` is the budget they are scheduled for; as in the
         reference, the model of the largest modelled budget answers, bohb.py:124): GroupConfigs with rows
         [B, S, D].  Prior draws while there is no model.  ``counter_base`` None: the internal counter, which
-        advances by B * S * num_samples per call."""
+        advances by B * S * num_samples per call.
+
+        ``want`` (a bool / uint8 mask [B, S]) or ``counts`` (ints [B]: run b's first counts[b] requests), host arrays
+        or device tensors: only those requests are computed, with the bytes they have without a mask; the others are
+        SOURCE_SKIPPED with NaN rows.  The counters advance as without a mask.  ``skip_random`` (None: the
+        optimiser's): requests the random fraction takes are not sampled and scored; rows and sources do not change."""
         S = int(S)
+        if want is not None and counts is not None:
+            raise ValueError("get_configs: give want or counts, not both")
+        if counts is not None:
+            want = counts
+            if not _is_tensor(counts):
+                want = np.asarray(counts)
+                if want.ndim != 1 or want.dtype.kind not in "iu":
+                    raise N.HbxError("counts must be ints [%d], got %s %s" % (self.B, want.dtype, want.shape))
+                want = want.astype(np.int64)  # (uint8 counts are counts here, not a mask)
+            elif counts.dim() != 1:
+                raise N.HbxError("counts must be ints [%d], got %s" % (self.B, tuple(counts.shape)))
+        if want is not None:
+            with N.on_device(self.device):
+                want = request_mask(want, self.B, S, self.device)  # (refusals before the counter moves)
+        skip = self.skip_random if skip_random is None else bool(skip_random)
         if counter_base is None:
             counter_base = self.counter
             self.counter += self.B * S * self.num_samples
         dsync = sync and self.conditions is None  # with conditions the rows are deactivated before they leave
         if not self.kde_models:  # bohb.py:109
             cfg = sample_prior(self.B, S, self._levels(), self.seed, counter_base, C=self.num_samples,
-                               device=self.device, sync=dsync)
+                               device=self.device, sync=dsync, want=want)
         else:
             gm = self.kde_models[max(self.kde_models.keys())]
             cfg = gm.get_config(self.num_samples, self.seed, self._levels(), requests=S,
                                 random_fraction=self.random_fraction, bandwidth_factor=self.bandwidth_factor,
-                                counter_base=counter_base, sync=dsync)
+                                counter_base=counter_base, sync=dsync, want=want, skip_random=skip)
         if self.conditions is None:
             return cfg
         if self._cond_dev is None:
@@ -962,7 +1128,12 @@ class GroupSuccessiveHalving(object):
     when the stage starts, and its results are reported together -- in the reference the behaviour of a pool with at
     least ``num_configs[stage]`` workers."""
 
-    def __init__(self, num_configs, budgets, resampling_rate=None, min_samples_advance=1, ties="numpy"):
+    FILLS = ("all", "needed")
+
+    def __init__(self, num_configs, budgets, resampling_rate=None, min_samples_advance=1, ties="numpy", fills="all"):
+        if fills not in self.FILLS:
+            raise ValueError("fills must be 'all' or 'needed', got %r" % (fills,))
+        self.fills = fills  # 'needed': the fill call computes run b's first K - survivors_b requests only
         self.num_configs = [int(v) for v in num_configs]
         self.budgets = [float(v) for v in budgets]
         if not self.num_configs or len(self.num_configs) != len(self.budgets):
@@ -1020,7 +1191,10 @@ class GroupSuccessiveHalving(object):
         opt.counter += B * K * opt.num_samples
         fills = None
         if int(lo_hi[0]) < K:
-            fills = opt.get_configs(self.budgets[stage + 1], S=K, counter_base=base, sync=False)
+            # 'needed': run b uses its first K - nadv[b] fill requests and only those are computed (a device tensor of
+            # counts: nothing more is read back); same counters, same bytes at every slot that `advance` reads
+            kw = dict(counts=(K - nadv.to(torch.int64)).clamp(min=0, max=K)) if self.fills == "needed" else {}
+            fills = opt.get_configs(self.budgets[stage + 1], S=K, counter_base=base, sync=False, **kw)
         seg_d = torch.from_numpy(seg).to(opt.device)
         out, src, counts = advance(rows.reshape(B * n, D), seg_d, mask, K, fresh=None if fills is None else fills.rows,
                                    sync=False, device=opt.device)
@@ -1071,7 +1245,7 @@ class GroupHyperband(object):
     GroupSuccessiveHalving per iteration promotes.  The ladder is the reference's (HB_master.py:93-94, :161-168).
     Lockstep: a stage's requests are all answered by the model as it stands when the stage starts -- the reference
     with at least as many workers as the stage has configurations.  ``sh_kwargs`` go to GroupSuccessiveHalving
-    (``resampling_rate``, ``min_samples_advance``, ``ties``)."""
+    (``resampling_rate``, ``min_samples_advance``, ``ties``, ``fills``)."""
 
     def __init__(self, opt, eta=3, min_budget=0.01, max_budget=1, **sh_kwargs):
         from .HB_master import hb_budgets

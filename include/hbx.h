@@ -489,6 +489,67 @@ int hbx_kde_propose_groups_r(const double* X, int32_t D, const int64_t* seg_off,
                              uint32_t stream_id, int64_t S, int64_t C, double* rows_out, uint8_t* source_out,
                              void* records_out, double* cands_out, void* workspace, int64_t workspace_bytes, void* stream,
                              const hbx_rules* rules);
+/* The request mask: the four grouped get_config calls with only the wanted requests computed.  want: device
+ * u8[B][S], request (b, s) is wanted when its byte is not zero; want == NULL: every request is wanted.  The Philox
+ * counter of request q = b * S + s is fixed by its position (counter_base + q * C + i), so: EVERY WANTED REQUEST GETS
+ * EXACTLY THE BYTES THE DENSE CALL GIVES IT, AND AN UNWANTED REQUEST COSTS NOTHING AND IS MARKED AS SKIPPED.  The
+ * grids are the dense calls'; the host never reads the mask and nothing synchronises -- blocks and waves test it.
+ * The model arguments are the dense calls', unchanged; so are the argument checks (before the first launch).
+ *
+ * hbx_kde_sample_groups_m: candidate (b, s, i) of a wanted request is byte-equal to hbx_kde_sample_groups' draw for
+ *   it with pool size S * C.  The rows and error bytes of an unwanted request are not written (the error bytes are
+ *   zeroed first, all of them, as there).
+ * hbx_kde_acquire_groups_batch_m: a wanted request's record is hbx_kde_acquire_groups_batch(_r)'s, all 48 bytes (the
+ *   screen is chosen from S and the dense tile count, and a candidate's sums do not depend on the other candidates).
+ *   An unwanted request gets the empty record -- index -1, NaN score and pdfs, shortlist and near 0 -- with
+ *   HBX_ACQ_SKIPPED and the group's HBX_ACQ_NO_MODEL / HBX_ACQ_UNSUPPORTED bit as the dense call sets it.  rules may be
+ *   NULL.  The workspace (hbx_kde_groups_batch_workspace_bytes) starts with four counters that
+ *   hbx_kde_groups_request_stats reads (it synchronises the device): out4[0] requests answered, [1] requests skipped,
+ *   [2] candidates the screen evaluated, [3] candidates re-scored in fp64.  C == 0: empty records (skipped ones for
+ *   unwanted requests), no counters.
+ * hbx_kde_finish_groups_m: a rule ahead of hbx_kde_finish_groups' five -- an unwanted request gets
+ *   source_out[q] = HBX_CFG_SKIPPED and a NaN row; wanted requests go by the five rules.
+ * hbx_kde_random_requests_groups: want_out[q] = (want_in == NULL or want_in[q] != 0) and not (u_q < random_fraction),
+ *   u_q the finish step's draw -- the requests that a model has to answer.  One launch.
+ * hbx_kde_propose_groups_m: the composition of the three on one stream.  flags & HBX_PROPOSE_SKIP_RANDOM: the sampler
+ *   and the acquisition run under hbx_kde_random_requests_groups' mask (kept in the workspace), the finish step under
+ *   want.  Rule 1 (HBX_CFG_RANDOM_FRACTION) comes before the rules that read the pool, so rows_out and source_out are
+ *   byte-equal to the call without the flag; a random request has a skipped record and its pool is not written.
+ *   Without the flag, requests that end up random are still sampled and scored.  cands_out, when given (16-byte
+ *   aligned), IS the pool: unwanted requests' rows stay as they were.  workspace:
+ *   hbx_kde_propose_groups_m_workspace_bytes bytes; hbx_kde_propose_groups_m_ws_offsets: byte offsets of [pools, error
+ *   bytes, records, mask, end]. */
+#define HBX_ACQ_SKIPPED 64  /* the record of a request the mask left out (the next free bit of the record's flags) */
+#define HBX_CFG_SKIPPED 5
+#define HBX_PROPOSE_SKIP_RANDOM 1
+int hbx_kde_sample_groups_m(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                            const int64_t* n_good, const double* bw_good, const int32_t* levels,
+                            double bw_factor, uint64_t seed, uint64_t counter_base, uint32_t stream_id,
+                            int64_t S, int64_t C, const uint8_t* want, double* cands, uint8_t* domain_err, void* stream);
+int hbx_kde_acquire_groups_batch_m(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                   const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                   const double* bw_good, const double* bw_bad,
+                                   const int32_t* nlev_good, const int32_t* nlev_bad,
+                                   const double* cand, int64_t S, int64_t C, const uint8_t* want, void* results,
+                                   void* workspace, int64_t ws_bytes, void* stream, const hbx_rules* rules);
+int hbx_kde_groups_request_stats(const void* workspace, int64_t* out4);
+int hbx_kde_finish_groups_m(const void* records, const double* cands, const uint8_t* domain_err, const int32_t* levels,
+                            int32_t D, int64_t B, int64_t S, int64_t C, double random_fraction, uint64_t seed,
+                            uint64_t counter_base, uint32_t stream_id, const uint8_t* want, double* rows_out,
+                            uint8_t* source_out, void* stream);
+int hbx_kde_random_requests_groups(int64_t B, int64_t S, int64_t C, double random_fraction, uint64_t seed,
+                                   uint64_t counter_base, uint32_t stream_id, const uint8_t* want_in, uint8_t* want_out,
+                                   void* stream);
+int64_t hbx_kde_propose_groups_m_workspace_bytes(int64_t B, int64_t S, int64_t C, int32_t D);
+int hbx_kde_propose_groups_m_ws_offsets(int64_t B, int64_t S, int64_t C, int32_t D, int64_t* out5);
+int hbx_kde_propose_groups_m(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                             const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                             const double* bw_good, const double* bw_bad,
+                             const int32_t* nlev_good, const int32_t* nlev_bad, const int32_t* levels,
+                             double bandwidth_factor, double random_fraction, uint64_t seed, uint64_t counter_base,
+                             uint32_t stream_id, int64_t S, int64_t C, const uint8_t* want, int32_t flags,
+                             double* rows_out, uint8_t* source_out, void* records_out, double* cands_out,
+                             void* workspace, int64_t workspace_bytes, void* stream, const hbx_rules* rules);
 
 /* ---- conditional search spaces ---------------------------------------------------------------
  * An observation of a conditional space holds NaN where a hyperparameter is inactive.  Released hpbandster imputes

@@ -28,12 +28,12 @@ S = K pools and the per-bracket acquire_topk loop; prints one JSON line and writ
 times hbx_kde_logpdf_groups (logpdf_bench below) in default and FP64_ONLY mode at config #5's shape and at a plain
 unsigned shape (8c) against the per-bracket prepare + logpdf loop; writes profiles/groups_logpdf/bench_groups_logpdf.json.
 
-    python tools/bench_groups.py --get-config [--requests S] [--out FILE]
+    python tools/bench_groups.py --get-config [--requests S] [--skip-random] [--counts K] [--no-parent] [--out FILE]
 
 times the grouped get_config (get_config_bench below): hbx_kde_propose_groups against its parts and against
 propose(requests=S) plus a host prior fill; writes profiles/groups_get_config/bench_groups_get_config.json.
 
-    python tools/bench_groups.py --sh [--sh-max-budget 729] [--out FILE]
+    python tools/bench_groups.py --sh [--sh-max-budget 729] [--fills needed] [--out FILE]
 
 times the grouped successive-halving transition (sh_bench below): hbx_sh_advance_groups alone against the sync-free
 torch composition (stable argsort of the mask, gather, where), the two taking turns, and one full GroupHyperband
@@ -388,7 +388,12 @@ def get_config_bench(a, gm, L, sh, lvd, levels):
       parent     what the library offered before for the same answer: propose(requests=S) -- the same two calls, the
                  records fetched, the winning rows gathered through the host -- plus a numpy prior fill of the rows
                  the random fraction takes and of the NaN rows (wall clock, synchronised)
-    The fused call's rows and sources are compared with finish's over the two calls' outputs (byte equality)."""
+    The fused call's rows and sources are compared with finish's over the two calls' outputs (byte equality).
+    --skip-random adds fused_skip_random: hbx_kde_propose_groups_m with HBX_PROPOSE_SKIP_RANDOM (requests the random
+    fraction takes are not sampled and scored; rows and sources compared with the fused call's, byte for byte).
+    --counts K adds fused_counts: hbx_kde_propose_groups_m under the mask of a deficit of K requests in every 100th
+    run and none elsewhere (a crashed worker's fill call), the wanted rows compared with the fused call's.  Both print
+    their line beside the fused call's, with hbx_kde_groups_request_stats' counters."""
     dev = gm.device
     B, R, C, D = gm.B, a.requests, a.C, gm.D
     rf, seed = 1.0 / 3, S.SEED_CAND
@@ -431,6 +436,22 @@ def get_config_bench(a, gm, L, sh, lvd, levels):
         got[fill] = draw
         return got
 
+    wsm = int(L.hbx_kde_propose_groups_m_workspace_bytes(B, R, C, D))
+    ws_m = torch.empty(wsm, dtype=torch.uint8, device=dev)
+    rows_m, src_m, rec_m = torch.empty_like(rows), torch.empty_like(src), torch.empty_like(rec)
+
+    def masked(want, flags):
+        def call():
+            N.check(L.hbx_kde_propose_groups_m(*model, N.ptr(lvd), 3.0, rf, seed, 0, 0, R, C, N.ptr(want), flags,
+                                               N.ptr(rows_m), N.ptr(src_m), N.ptr(rec_m), None, N.ptr(ws_m), wsm, sh,
+                                               None))
+        return call
+
+    def request_stats():
+        st = np.zeros(4, dtype=np.int64)
+        N.check(L.hbx_kde_groups_request_stats(N.ptr(ws_m), st.ctypes.data))
+        return dict(zip(("answered", "skipped", "screened_candidates", "rescored_candidates"), (int(v) for v in st)))
+
     out = {"workload": "grouped_get_config_b%d_n%d_d32_24c8u_s%d_c%d" % (B, a.n, R, C),
            "device": torch.cuda.get_device_name(0), "reps": a.reps, "requests": R, "random_fraction": rf,
            "workspace_bytes": wsf}
@@ -439,12 +460,35 @@ def get_config_bench(a, gm, L, sh, lvd, levels):
     out["finish"] = each_timed(finish, a.reps)
     out["fused"] = each_timed(fused, a.reps)
     out["two_calls_then_finish"] = each_timed(lambda: (two_calls(), finish()), a.reps)
+    same_m = True
+    if a.skip_random:
+        call = masked(None, groups.PROPOSE_SKIP_RANDOM)
+        out["fused_skip_random"] = each_timed(call, a.reps)
+        out["fused_skip_random"]["stats"] = request_stats()
+        same_m = same_m and bool(torch.equal(rows_m.view(torch.int64), rows_f.view(torch.int64)) and
+                                 torch.equal(src_m, src_f))
+        print("fused             ", json.dumps(out["fused"], sort_keys=True))
+        print("fused_skip_random ", json.dumps(out["fused_skip_random"], sort_keys=True))
+    if a.counts:
+        cnt = torch.zeros(B, dtype=torch.int64, device=dev)
+        cnt[::100] = min(a.counts, R)
+        want = groups.counts_to_mask(cnt, R).contiguous()
+        call = masked(want, 0)
+        out["fused_counts"] = each_timed(call, a.reps)
+        out["fused_counts"].update(stats=request_stats(), counts=int(min(a.counts, R)), every=100)
+        on = want.bool()
+        same_m = same_m and bool(torch.equal(rows_m.view(torch.int64)[on], rows_f.view(torch.int64)[on]) and
+                                 torch.equal(src_m[on], src_f[on]) and bool((src_m[~on] == 5).all()))
+        print("fused             ", json.dumps(out["fused"], sort_keys=True))
+        print("fused_counts      ", json.dumps(out["fused_counts"], sort_keys=True))
+    out["masked_equals_fused"] = same_m
     t = []
-    for it in range(5):
+    for it in range(0 if a.no_parent else 5):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         parent()
         t.append(1e3 * (time.perf_counter() - t0))
+    t = t or [float("nan")] * 5  # (--no-parent)
     out["parent_propose_plus_host_fill"] = {"ms_mean": float(np.mean(t[2:])), "ms_min": float(np.min(t[2:])),
                                             "ms_max": float(np.max(t[2:]))}
     same = bool(torch.equal(rows.view(torch.int64), rows_f.view(torch.int64)) and torch.equal(src, src_f) and
@@ -464,7 +508,7 @@ def get_config_bench(a, gm, L, sh, lvd, levels):
         json.dump(out, f, indent=1, sort_keys=True)
         f.write("\n")
     print(json.dumps(out, sort_keys=True))
-    return 0 if same else 1
+    return 0 if same and same_m else 1
 
 
 def _torch_advance(X3, m, K, fresh):
@@ -567,7 +611,8 @@ def sh_bench(a, dev, L):
     # one Hyperband iteration of B runs: ladder [ns], a device objective, every call between device events
     dc, du, lev = 24, 8, 4
     opt = groups.GroupBOHB(B, S.var_type_string(dc, du), [0] * dc + [lev] * du, num_samples=a.C, seed=4, device=dev)
-    hb = groups.GroupHyperband(opt, eta=3, min_budget=1, max_budget=a.sh_max_budget)
+    kw = dict(fills=a.fills) if a.fills != "all" else {}  # ('needed': only the deficits' fill requests are computed)
+    hb = groups.GroupHyperband(opt, eta=3, min_budget=1, max_budget=a.sh_max_budget, **kw)
     ev = {}
 
     def stamped(name, fn):
@@ -720,6 +765,14 @@ def main(argv=None):
     ap.add_argument("--logpdf", action="store_true", help="both KDEs' ln pdf of every pool (logpdf_bench)")
     ap.add_argument("--get-config", action="store_true",
                     help="a configuration per request with the reference's fall-backs (get_config_bench)")
+    ap.add_argument("--skip-random", action="store_true",
+                    help="--get-config: also the masked call that does not sample and score random requests")
+    ap.add_argument("--counts", type=int, default=0,
+                    help="--get-config: also the masked call with a deficit of K requests in every 100th run")
+    ap.add_argument("--no-parent", action="store_true",
+                    help="--get-config: leave out the host-side 'parent' composition (wall clock, seconds per call)")
+    ap.add_argument("--fills", choices=("all", "needed"), default="all",
+                    help="--sh: GroupSuccessiveHalving's fills option for the driven run")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     L = N.lib()
