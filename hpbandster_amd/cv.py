@@ -152,15 +152,53 @@ class _null(object):
         return False
 
 
-def select_bandwidth(data, var_type, bw="cv_ls", device=None):
+def select_cv_ml_device(data, var_type, device=None, x0=None, max_evals=1000, info=None):
+    """bw='cv_ml' of one data set with the search on the device (hbx_kde_cv_groups: one group whose good KDE is the
+    data set): Nelder-Mead from the normal-reference bandwidths (or ``x0``), then the bounds, in one launch -- one
+    objective per pair exponential, not numpy's operation order, so the selection agrees with statsmodels' to the
+    search's tolerance rather than bit for bit.  ``info``: a dict that receives status, objective and evals."""
+    from . import groups
+    torch = _torch()
+    data = np.ascontiguousarray(np.asarray(data, dtype=np.float64))
+    n, D = data.shape
+    if D != len(var_type) or any(t not in "cu" for t in var_type):
+        raise ValueError("data must be [nobs, len(var_type)] with var_type of 'c' / 'u'")
+    if n <= D:  # SM:kernel_density.py:107-109
+        raise ValueError("The number of observations must be larger than the number of variables.")
+    device = device if device is not None else default_device()
+    h0 = 1.06 * np.std(data, axis=0) * bandwidth_factor(n, D) if x0 is None else np.asarray(x0, dtype=np.float64)
+    nlev = np.array([0 if t == "c" else np.unique(data[:, d]).size for d, t in enumerate(var_type)], dtype=np.int32)
+    with N.on_device(device):
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+        bw = t(h0.reshape(1, D))
+        gm = groups.GroupModel(B=1, D=D, device=device, X=t(data), seg_host=np.array([0, n], dtype=np.int64),
+                               seg_off=t(np.array([0, n], dtype=np.int64)), order=t(np.arange(n, dtype=np.int64)),
+                               n_good_dev=t(np.array([n], dtype=np.int64)), n_bad_dev=t(np.zeros(1, dtype=np.int64)),
+                               vt_dev=t(var_type_codes(var_type)), nlev_good=t(nlev.reshape(1, D)),
+                               nlev_bad=t(nlev.reshape(1, D)))
+        status, objective, evals = groups._cv_groups(gm, groups.CV_ML, bw, torch.zeros_like(bw), None, max_evals)
+        if info is not None:
+            info.update(status=int(status[0, 0]), objective=float(objective[0, 0]), evals=int(evals[0, 0]))
+        return bw[0].cpu().numpy()
+
+
+def select_bandwidth(data, var_type, bw="cv_ls", device=None, search="host"):
     """Bandwidths KDEMultivariate(data, var_type, bw=...) would choose (SM:_kernel_base.py:103-139):
-    'normal_reference', 'cv_ls', 'cv_ml' or an explicit array."""
+    'normal_reference', 'cv_ls', 'cv_ml' or an explicit array.  ``search``: 'host' (scipy's Nelder-Mead around
+    hbx_kde_cv_terms, one launch per evaluation) or, for 'cv_ml' and at most 32 dims, 'device' (select_cv_ml_device:
+    the whole search in one launch)."""
+    if search not in ("host", "device"):
+        raise ValueError("search must be 'host' or 'device', got %r" % (search,))
     if not isinstance(bw, str):
         return np.asarray(bw, dtype=np.float64)
     data = np.asarray(data, dtype=np.float64)
     if bw == "normal_reference":
         return 1.06 * np.std(data, axis=0) * bandwidth_factor(data.shape[0], data.shape[1])
+    if search == "device":
+        if bw != "cv_ml":
+            raise ValueError("search='device' selects 'cv_ml' bandwidths only, got %r" % (bw,))
+        return select_cv_ml_device(data, var_type, device=device)
     return CVObjective(data, var_type, device=device).select(bw)
 
 
-__all__ = ["CVObjective", "select_bandwidth", "level_tables"]
+__all__ = ["CVObjective", "select_bandwidth", "select_cv_ml_device", "level_tables"]

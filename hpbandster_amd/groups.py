@@ -355,6 +355,42 @@ class GroupLogPdf(object):
         return "GroupLogPdf(shape=%s, stats=%s)" % (shape, self.stats)
 
 
+CV_EVAL, CV_ML = 0, 1  # include/hbx.h HBX_CV_*: hbx_kde_cv_groups' modes
+CV_CONVERGED, CV_LIMIT, CV_NOT_SEARCHABLE, CV_NO_MODEL = 0, 1, 2, 3  # ... and its status codes
+BW_RULES = ("normal_reference", "cv_ml")
+CV_MAX_EVALS = 1000  # statsmodels' maxiter = maxfun (SM:_kernel_base.py:326-327)
+
+
+def _bw_rule(bw):
+    if bw not in BW_RULES:
+        raise ValueError("the bandwidth rule must be one of %r, got %r" % (BW_RULES, bw))
+    return bw
+
+
+def _cv_groups(gm, mode, bw_good, bw_bad, stream=None, max_evals=CV_MAX_EVALS):
+    """One hbx_kde_cv_groups launch over GroupModel ``gm`` (inside the caller's on_device context): CV_ML searches
+    from ``bw_good`` / ``bw_bad`` (device float64 [B, D]) and overwrites them, CV_EVAL only evaluates there.  Returns
+    the device tensors (status int32 [B, 2], objective float64 [B, 2], evals int32 [B, 2]); nothing is read back."""
+    torch = kde._torch()
+    B, D = gm.B, gm.D
+    status = torch.full((B, 2), CV_NO_MODEL, dtype=torch.int32, device=gm.device)
+    objective = torch.full((B, 2), float("nan"), dtype=torch.float64, device=gm.device)
+    evals = torch.zeros((B, 2), dtype=torch.int32, device=gm.device)
+    Nrows = int(gm.seg_host[-1]) if B else 0
+    wb = int(N.lib().hbx_kde_cv_groups_workspace_bytes(Nrows, B, D))
+    if wb < 0:
+        raise N.HbxError("cv_ml bandwidths: D=%d is beyond the search's 32 dims" % D)
+    if B and Nrows:
+        ws = torch.empty(wb, dtype=torch.uint8, device=gm.device)
+        r = None if gm.min_bandwidth == 0.0 else N.rules(gm.pdf_floor, gm.min_bandwidth)
+        N.check(N.lib().hbx_kde_cv_groups(
+            N.ptr(gm.X), Nrows, D, N.ptr(gm.seg_off), B, N.ptr(gm.order), N.ptr(gm.n_good_dev), N.ptr(gm.n_bad_dev),
+            N.ptr(gm.vt_dev), N.ptr(gm.nlev_good), N.ptr(gm.nlev_bad), N.ptr(bw_good), N.ptr(bw_bad), int(mode),
+            int(max_evals), N.ptr(status), N.ptr(objective), N.ptr(evals), N.ptr(ws), wb,
+            N.stream_handle(stream, gm.device), None if r is None else ctypes.addressof(r)))
+    return status, objective, evals
+
+
 # include/hbx.h's names for the model parameters of the grouped entry points, in its order (hbx_kde_acquire_groups),
 # and for those of the sampler, which reads the good side alone (hbx_kde_sample_groups)
 MODEL_ARGS = ("X", "D", "seg_off", "B", "order", "n_good", "n_bad", "vartype", "bw_good", "bw_bad", "nlev_good",
@@ -421,6 +457,21 @@ class GroupModel(object):
                                       h["nlev"][0][b], h["nlev"][1][b], device=self.device, pdf_floor=self.pdf_floor)
 
     # ---- the grouped calls ------------------------------------------------------------------------------
+    def cv_objective(self, bw_good=None, bw_bad=None, stream=None):
+        """The cv_ml objective -sum_i ln L_i (leave-one-out likelihood, SM:kernel_density.py:126-160) of every KDE at
+        ``bw_good`` / ``bw_bad`` ([B, D], host arrays or device tensors; None: the model's own) -- hbx_kde_cv_groups
+        in its evaluate-only mode.  Returns a device tensor float64 [B, 2] ([b, 0] the good KDE, [b, 1] the bad
+        one; NaN for groups without a model)."""
+        torch = kde._torch()
+        with N.on_device(self.device, stream):
+            bws = []
+            for given, own in ((bw_good, self.bw_good), (bw_bad, self.bw_bad)):
+                t = own if given is None else _to_device(given, torch.float64, self.device)
+                if tuple(t.shape) != (self.B, self.D):
+                    raise N.HbxError("bandwidths must be [%d, %d], got %s" % (self.B, self.D, tuple(t.shape)))
+                bws.append(t)
+            return _cv_groups(self, CV_EVAL, bws[0], bws[1], stream)[1]
+
     def sample(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, stream_id=0, requests=None,
                want=None):
         """C candidates per group around its good KDE's rows (bohb.py:133-147; hbx_kde_sample_groups):
@@ -786,13 +837,21 @@ def _impute_view(Xd, segd, order, ngd, nbd, ng, nb, B, D, levels, seed, counter,
 
 def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, device=None, stream=None,
                min_bandwidth=None, pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, levels=None, impute_counter=0,
-               impute_stream_id=0):
+               impute_stream_id=0, bw="normal_reference"):
     """Refit every bracket's good / bad KDE in one batched call (hbx_seg_argsort_ex in numpy's order, then
     hbx_kde_fit), everything kept on the device.  ``X`` [N, D], ``losses`` [N] and ``seg_off`` [B + 1] are host
     arrays or device tensors; ``min_points`` defaults to D + 1 (BOHB's).  ``min_bandwidth`` (None = 0: no clip):
     every fitted bandwidth becomes ``np.clip(bw, min_bandwidth, None)`` where the fit stores it; ``pdf_floor``: the
     floor f of the score max(f, g)/max(l, f) the model's acquisitions form (default 1e-8, the reference snapshot's).
     Returns a GroupModel, which carries both.
+
+    ``bw``: the bandwidth rule.  "normal_reference" (the default, the reference's) is the fit's own; "cv_ml" then
+    runs hbx_kde_cv_groups on the same stream: every KDE's bandwidths are replaced in place by the maximisers of its
+    leave-one-out likelihood (statsmodels' bw='cv_ml': Nelder-Mead from the normal-reference start, its bounds, then
+    ``min_bandwidth``), searched on the device in that one launch.  The model then carries ``bw_status`` (int32 [B, 2]:
+    CV_CONVERGED, CV_LIMIT, CV_NOT_SEARCHABLE -- a constant column: the normal-reference bandwidths stay --,
+    CV_NO_MODEL), ``bw_objective`` (float64 [B, 2]) and ``bw_evals`` (int32 [B, 2]) as device tensors ([b, 0] the
+    good KDE, [b, 1] the bad one); nothing is read back.  At most 32 dims.
 
     Conditional search spaces: with ``impute_seed`` (and ``levels``, D level counts, 0: continuous) the rows may hold
     NaN at inactive dims.  The argsort is taken on the original losses, then every group's good and bad rows are
@@ -803,6 +862,8 @@ def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, 
     with ``src_rows`` (int32 [Nv]: the original local row of each view row) and ``impute_counts`` (int32 [B, 2]:
     entries filled from donors / from the prior).  ``impute_seed`` None: nothing of this happens."""
     pdf_floor, min_bandwidth = N.check_pdf_floor(pdf_floor), N.check_min_bandwidth(min_bandwidth)
+    if _bw_rule(bw) == "cv_ml" and len(var_type) > 32:
+        raise N.HbxError("fit_groups: bw='cv_ml' searches at most 32 dims, got %d" % len(var_type))
     if impute_seed is not None and levels is None:
         raise N.HbxError("fit_groups: impute_seed needs levels (D level counts, 0: continuous)")
     torch = kde._torch()
@@ -858,10 +919,14 @@ def fit_groups(X, losses, seg_off, var_type, min_points=None, top_n_percent=15, 
             else:
                 r = N.rules(pdf_floor, min_bandwidth)
                 N.check(L.hbx_kde_fit_r(*(fit + (ctypes.addressof(r),))))
-    return GroupModel(B=B, D=D, var_type=var_type, device=device, X=Xd, losses=ld, seg_off=segd, seg_host=seg_h,
-                      order=order, n_good=ng, n_bad=nb, has_model=(ng > 0), n_good_dev=ngd, n_bad_dev=nbd,
-                      fac_good_dev=fgd, fac_bad_dev=fbd, vt_dev=vtd, bw_good=bwg, bw_bad=bwb, nlev_good=nlg,
-                      nlev_bad=nlb, pdf_floor=pdf_floor, min_bandwidth=min_bandwidth, **raw)
+    gm = GroupModel(B=B, D=D, var_type=var_type, device=device, X=Xd, losses=ld, seg_off=segd, seg_host=seg_h,
+                    order=order, n_good=ng, n_bad=nb, has_model=(ng > 0), n_good_dev=ngd, n_bad_dev=nbd,
+                    fac_good_dev=fgd, fac_bad_dev=fbd, vt_dev=vtd, bw_good=bwg, bw_bad=bwb, nlev_good=nlg,
+                    nlev_bad=nlb, pdf_floor=pdf_floor, min_bandwidth=min_bandwidth, **raw)
+    if bw == "cv_ml":  # right behind the fit on its stream; the search sees what the fit saw (the imputed view)
+        with N.on_device(device, stream):
+            gm.bw_status, gm.bw_objective, gm.bw_evals = _cv_groups(gm, CV_ML, gm.bw_good, gm.bw_bad, stream)
+    return gm
 
 
 def sort_conditions(conditions, levels):
@@ -919,7 +984,8 @@ class GroupBOHB(object):
     bohb.py:171-251 for all runs at once (one batched refit), ``get_configs`` bohb.py:104-169 for S requests of
     every run (one call, every row on the device).  Run b's observations of a budget are the rows ``[b, :, :]`` of
     that budget's device store; ``kde_models`` maps budget -> GroupModel.  ``var_type``: the KDE's kinds ('c' / 'u'
-    per dim), ``levels``: D level counts (0: continuous).
+    per dim), ``levels``: D level counts (0: continuous).  ``bw_estimation``: every refit's bandwidth rule,
+    "normal_reference" (the reference's) or "cv_ml" (fit_groups' ``bw``: searched on the device, at most 32 dims).
 
     Conditional search spaces: with ``impute_seed`` the reported rows may hold NaN at inactive dims, and every refit
     imputes them (fit_groups) on a counter block of its own -- ``impute_counter``, which advances by the view's row
@@ -929,8 +995,10 @@ class GroupBOHB(object):
 
     def __init__(self, B, var_type, levels, min_points_in_model=None, top_n_percent=15, num_samples=64,
                  random_fraction=1.0 / 3, bandwidth_factor=3, seed=0, device=None, min_bandwidth=None,
-                 pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, conditions=None, skip_random=False):
+                 pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, conditions=None, skip_random=False,
+                 bw_estimation="normal_reference"):
         self.B, self.var_type, self.D = int(B), var_type, len(var_type)
+        self.bw_estimation = _bw_rule(bw_estimation)  # every refit's bandwidth rule (fit_groups' ``bw``)
         if not isinstance(skip_random, (bool, np.bool_)):
             raise ValueError("skip_random must be a bool, got %r" % (skip_random,))
         self.skip_random = bool(skip_random)  # get_configs' default: random requests are not sampled and scored
@@ -942,6 +1010,8 @@ class GroupBOHB(object):
             self._rules_kw["min_bandwidth"] = self.min_bandwidth
         if self.pdf_floor != N.PDF_FLOOR_DEFAULT:
             self._rules_kw["pdf_floor"] = self.pdf_floor
+        if self.bw_estimation != "normal_reference":
+            self._rules_kw["bw"] = self.bw_estimation
         self.levels = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
         if self.levels.shape != (self.D,):
             raise N.HbxError("levels must have %d entries" % self.D)

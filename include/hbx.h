@@ -737,6 +737,39 @@ int hbx_kde_cv_terms(const double* X, int64_t n, int32_t D, const int32_t* varty
                      const double* lev, const int32_t* lev_off, const int32_t* loo_levels, double c4, double c2,
                      double bwprod, double* F, double* L, void* stream);
 
+/* Grouped cv_ml bandwidths: KDEMultivariate(bw='cv_ml')'s selection (SM:_kernel_base.py:267-332) for every KDE of a
+ * grouped refit in ONE launch, no host involvement between start and finish.  The model arguments are
+ * hbx_kde_acquire_groups', read where hbx_kde_fit left them, plus N, the rows of X (seg_off[B]).  Per (group, KDE):
+ *   objective  f(h) = -sum_i ln L_i(h), L_i = sum_{j != i} prod_d k_d(X_jd, X_id; h_d): Gaussian kernels on the
+ *              continuous dims, Aitchison-Aitken on the categorical ones with the level count of the column without
+ *              row i (nlev, minus one where row i's level occurs once).  Evaluated as one exponential per pair and
+ *              the continuous normaliser once per row in log space, all fp64: NOT numpy's operation order.
+ *   search     scipy.optimize.fmin as statsmodels calls it (Nelder-Mead, xtol 1e-3, ftol 1e-4, maxiter = maxfun =
+ *              max_evals; statsmodels: 1000), started at the bandwidths bw_good / bw_bad hold on entry, which the
+ *              selection overwrites after the bounds (h < 0 -> 1e-10; categorical min(h, 1)) and then
+ *              rules->min_bandwidth (hbx_rules; NULL: no clip).
+ * mode: HBX_CV_ML searches; HBX_CV_EVAL only evaluates f at the given bandwidths (nothing but objective, status and
+ * evals is written).  status: i32[B][2] ([b][0] the good KDE, [b][1] the bad one): HBX_CV_CONVERGED, HBX_CV_LIMIT
+ * (the evaluation or iteration limit stopped the search: the best vertex so far is the answer),
+ * HBX_CV_NOT_SEARCHABLE (a start bandwidth that is not finite and positive, e.g. a constant column, or an unknown
+ * level count: the bandwidths are kept) and HBX_CV_NO_MODEL (n_good / n_bad <= 0 or past the segment: skipped).
+ * objective: f64[B][2], f at the answer (NaN where nothing was evaluated); evals: i32[B][2], evaluations made.
+ * workspace: hbx_kde_cv_groups_workspace_bytes(N, B, D) bytes (-1 for arguments out of range), 4-byte aligned.
+ * D > 32: HBX_ERR_UNSUPPORTED; null or misaligned pointers, negative sizes, an unknown mode, max_evals < 1, a short
+ * workspace: HBX_ERR_ARG -- all before the launch.  B == 0: nothing to do.  Two runs give the same bytes. */
+#define HBX_CV_EVAL 0
+#define HBX_CV_ML 1
+#define HBX_CV_CONVERGED 0
+#define HBX_CV_LIMIT 1
+#define HBX_CV_NOT_SEARCHABLE 2
+#define HBX_CV_NO_MODEL 3
+int64_t hbx_kde_cv_groups_workspace_bytes(int64_t N, int64_t B, int32_t D);
+int hbx_kde_cv_groups(const double* X, int64_t N, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                      const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype, const int32_t* nlev_good,
+                      const int32_t* nlev_bad, double* bw_good, double* bw_bad, int32_t mode, int32_t max_evals,
+                      int32_t* status, double* objective, int32_t* evals, void* workspace, int64_t ws_bytes,
+                      void* stream, const hbx_rules* rules);
+
 /* ---- multi-GPU winner exchange (candidate sharding; bohb.py:133-152 sharded) ----- */
 /* Each rank runs hbx_kde_acquire on its contiguous shard with index_base = its first global index; the
  * ranks' result records then meet in ONE RCCL all-gather over xGMI and are reduced on the device by

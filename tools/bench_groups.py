@@ -745,8 +745,71 @@ def impute_bench(a, dev, L):
     return 0
 
 
+def cv_bench(a, dev, L):
+    """--cv: cv_ml bandwidths at config #5's row counts (n = 1000: 150 + 850 rows, 24c + 8u) for --B groups.  Times
+    the hbx_kde_cv_groups call of fit_groups(bw='cv_ml') between device events (--reps runs from the same start, each
+    reported), with the evaluations per KDE and the share that stopped at statsmodels' limit of 1000; against it the
+    only way to the same bandwidths without the call: CVObjective.select('cv_ml') per KDE (a launch, a copy and a
+    synchronisation per evaluation, scipy's search on the host), timed on --sub groups and extrapolated to 2 B."""
+    from hpbandster_amd import cv
+    B, n, dc, du, lev = a.B, a.n, 24, 8, 4
+    D = dc + du
+    vts = S.var_type_string(dc, du)
+    losses = torch.from_numpy(S.make_bracket_losses(B, n).reshape(-1)).to(dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    X = torch.empty((B * n, D), dtype=torch.float64, device=dev)
+    X[:, :dc] = torch.rand((B * n, dc), dtype=torch.float64, device=dev, generator=g)
+    X[:, dc:] = torch.randint(0, lev, (B * n, du), device=dev, generator=g).to(torch.float64)
+    seg = np.arange(B + 1, dtype=np.int64) * n
+    gm = groups.fit_groups(X, losses, seg, vts, device=dev)
+    start = gm.bw_good.clone(), gm.bw_bad.clone()
+    ms = []
+    for _ in range(a.reps):
+        bwg, bwb = start[0].clone(), start[1].clone()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        status, objective, evals = groups._cv_groups(gm, groups.CV_ML, bwg, bwb)
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    status, evals = status.cpu().numpy(), evals.cpu().numpy()
+    Xh = X.cpu().numpy()
+    sub = np.unique(np.linspace(0, B - 1, min(a.sub, B)).astype(np.int64))
+    host_s, host_evals, worst = [], [], 0.0
+    for b in sub:
+        for side, rows in enumerate(gm.rows_of(int(b))):
+            obj = cv.CVObjective(Xh[int(b) * n + rows], vts, device=dev)
+            t0 = time.perf_counter()
+            bw = obj.select("cv_ml", x0=start[side][int(b)].cpu().numpy())
+            host_s.append(time.perf_counter() - t0)
+            host_evals.append(obj.evals)
+            got = (bwg, bwb)[side][int(b)].cpu().numpy()
+            worst = max(worst, float(np.max(np.abs(got - bw) / np.abs(bw))))
+    res = {
+        "workload": "cv_groups_b%d_n%d_d32_24c8u" % (B, n), "device": torch.cuda.get_device_name(0),
+        "n_good": int(gm.n_good[0]), "n_bad": int(gm.n_bad[0]), "device_call_ms": ms,
+        "evals_mean_good": float(evals[:, 0].mean()), "evals_mean_bad": float(evals[:, 1].mean()),
+        "share_at_limit_good": float((status[:, 0] == groups.CV_LIMIT).mean()),
+        "share_at_limit_bad": float((status[:, 1] == groups.CV_LIMIT).mean()),
+        "host_loop_kdes_timed": len(host_s), "host_loop_s_per_kde": host_s, "host_loop_evals": host_evals,
+        "host_loop_extrapolated_s_fastest": min(host_s) * 2 * B,
+        "host_loop_extrapolated_s_mean": float(np.mean(host_s)) * 2 * B,
+        "slowest_device_over_fastest_host": max(ms) * 1e-3 / (min(host_s) * 2 * B),
+        "max_rel_diff_device_vs_host_selection": worst,
+    }
+    a.out = a.out or os.path.join(ROOT, "profiles", "groups_cv", "bench_cv.json")
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(res, sort_keys=True))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cv", action="store_true", help="cv_ml bandwidths: the grouped device search (cv_bench)")
     ap.add_argument("--impute", action="store_true",
                     help="conditional spaces: the impute call and the fit on the view (impute_bench)")
     ap.add_argument("--sh", action="store_true", help="the grouped successive-halving transition (sh_bench)")
@@ -778,6 +841,8 @@ def main(argv=None):
     L = N.lib()
     if a.logpdf:
         return logpdf_bench(a, dev, L)
+    if a.cv:
+        return cv_bench(a, dev, L)
     if a.impute:
         return impute_bench(a, dev, L)
     if a.sh:
