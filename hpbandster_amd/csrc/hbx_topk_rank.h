@@ -1,6 +1,9 @@
 // hbx_topk_rank.h -- the running best-(k+1) by (score bits, index) over a stream of any length, one block, LDS.
 // Users: topk_final_kernel (hbx_topk.hip: the single pool's ranking) and groups_topk_kernel (hbx_groups.hip: one
 // block per group).  Both feed it chunks of at most T entries, one per thread, and read the ranked entries back.
+// groups_rank_kernel's k <= 1024 instance (hbx_groups_rank.hip: one block per group or slice) uses the arrays, merge,
+// enters and finish, and stages its entrants itself -- two per thread and step, one LDS atomic per wave -- setting
+// `pend` before it merges; its keys are hbx_d2ord's (any sign, NaN dropped), which order like the values too.
 //
 // Entries are (score bits, candidate index, payload position); what a position refers to (the caller's exact pdfs,
 // its error bound) stays where the caller keeps it.  [0, nb) are the best so far in ascending (score, index) order,

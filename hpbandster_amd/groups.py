@@ -7,6 +7,8 @@ Config #5's loop on the device from end to end::
     rows, picks = gm.propose(64, seed, levels, requests=S)    # S picks per bracket: hbx_kde_acquire_groups_batch
     rows, top = gm.propose(64, seed, levels, topk=k)          # the k best of each pool: hbx_kde_acquire_groups_topk
     lp = gm.logpdf(cands)                                     # ln l, ln g of every candidate: hbx_kde_logpdf_groups
+    rk = gm.rank_logratio(cands, k)                           # the k smallest ln g - ln l of each pool, no floor:
+                                                              # hbx_kde_rank_logratio_groups
     cfg = gm.get_config(64, seed, levels, requests=S)         # a configuration per request, prior draws where the
                                                               # reference falls back: hbx_kde_propose_groups
     opt = GroupBOHB(B, var_type, levels)                      # B BOHB runs in lockstep: new_results / get_configs
@@ -355,6 +357,98 @@ class GroupLogPdf(object):
         return "GroupLogPdf(shape=%s, stats=%s)" % (shape, self.stats)
 
 
+RANK_MAX_K = 1024  # include/hbx.h HBX_RANK_MAX_K
+RANK_HEAD_BYTES = 16
+RANK_REC = np.dtype([("index", "<i4"), ("pad", "<i4"), ("score", "<f8"), ("ln_l", "<f8"), ("ln_g", "<f8")])
+SCORES = ("ratio", "log_ratio")  # propose's rankings: the reference's floored ratio, or ln g - ln l with no floor
+
+
+def _rank_k(k, C):
+    k = int(k)
+    if k < 1 or k > RANK_MAX_K or k > int(C):
+        raise ValueError("k must be in [1, min(%d, C = %d)], got %d" % (RANK_MAX_K, int(C), k))
+    return k
+
+
+class GroupRank(object):
+    """Per group the k candidates with the smallest ``ln g - ln l``, ranked by (score, index) (hbx_kde_rank_groups),
+    from one fetch of the B result blocks: ``count`` (int32 [B]: candidates whose score is not NaN, at most k) and
+    ``status`` (int32 [B], the ln-pdf's words: ACQ_NO_MODEL / ACQ_UNSUPPORTED groups have count 0); ``index`` (int32
+    [B, k], relative to the group's pool, -1 past ``count``); ``score``, ``ln_l``, ``ln_g`` (float64 [B, k], NaN past
+    ``count``).  +inf scores rank behind every other value, NaN scores are never returned.  ``len()`` is B."""
+    __slots__ = ("k", "count", "status", "index", "score", "ln_l", "ln_g")
+
+    @classmethod
+    def from_bytes(cls, b, B, k):
+        """B blocks of 16 + 32 k bytes (include/hbx.h hbx_kde_rank_groups)."""
+        B, k = int(B), int(k)
+        step = RANK_HEAD_BYTES + RANK_REC.itemsize * k
+        raw = np.frombuffer(bytes(b), dtype=np.uint8, count=B * step).reshape(B, step)
+        head = np.ascontiguousarray(raw[:, :RANK_HEAD_BYTES]).view("<i4").reshape(B, 4)
+        rec = np.ascontiguousarray(raw[:, RANK_HEAD_BYTES:]).view(RANK_REC).reshape(B, k)
+        out = cls()
+        out.k = k
+        out.count, out.status = head[:, 0].copy(), head[:, 2].copy()
+        if np.any(out.count < 0) or np.any(out.count > k):
+            raise N.HbxError("rank blocks: a count outside [0, %d]" % k)
+        for name in ("index", "score", "ln_l", "ln_g"):
+            setattr(out, name, np.ascontiguousarray(rec[name]))
+        return out
+
+    def __len__(self):
+        return int(self.count.shape[0])
+
+    def top(self, b):
+        """Group b's ranked entries: (index, score, ln_l, ln_g), each of length ``count[b]``."""
+        c = int(self.count[b])
+        return self.index[b, :c].copy(), self.score[b, :c].copy(), self.ln_l[b, :c].copy(), self.ln_g[b, :c].copy()
+
+    def rows(self, cands):
+        """The ranked candidate rows on the host, float64 [B, k, D]; NaN rows past ``count``.  ``cands``: [B, C, D],
+        numpy or a device tensor."""
+        if len(cands.shape) != 3 or int(cands.shape[0]) != len(self):
+            raise N.HbxError("candidates %s do not match %d groups" % (tuple(cands.shape), len(self)))
+        out = np.full((len(self), self.k, int(cands.shape[2])), np.nan)
+        bi, ji = np.nonzero(self.index >= 0)
+        if bi.size:
+            out[bi, ji] = _gather_rows(cands, bi, self.index[bi, ji].astype(np.int64))
+        return out
+
+    def __repr__(self):
+        return "GroupRank(B=%d, k=%d, returned=%d)" % (len(self), self.k, int(self.count.sum()))
+
+
+def rank_values(ln_l, ln_g, k, status=None, device=None, stream=None, sync=True):
+    """The ranking alone (hbx_kde_rank_groups) over log densities the caller has, such as a GroupLogPdf's: ``ln_l``,
+    ``ln_g`` float64 [B, C] (numpy or contiguous device tensors), ``status`` int32 [B] (None: every group has a
+    model).  Returns GroupRank, or with ``sync=False`` the device tensor of the B result blocks (uint8 [B, 16 + 32 k])."""
+    if tuple(ln_l.shape) != tuple(ln_g.shape) or len(ln_l.shape) != 2:
+        raise ValueError("ln_l and ln_g must both be [B, C], got %s and %s" % (tuple(ln_l.shape), tuple(ln_g.shape)))
+    B, C = int(ln_l.shape[0]), int(ln_l.shape[1])
+    if status is not None and tuple(status.shape) != (B,):
+        raise ValueError("status must be [%d], got %s" % (B, tuple(status.shape)))
+    k = _rank_k(k, C)
+    torch = kde._torch()
+    if device is None:
+        device = ln_l.device if _is_tensor(ln_l) else kde.default_device()
+    with N.on_device(device, stream):
+        ll = _to_device(ln_l, torch.float64, device, strict=True, what="ln_l")
+        lg = _to_device(ln_g, torch.float64, device, strict=True, what="ln_g")
+        st = torch.zeros(B, dtype=torch.int32, device=device) if status is None else \
+            _to_device(status, torch.int32, device, strict=True, what="status")
+        wb = int(N.lib().hbx_kde_rank_groups_workspace_bytes(B, C, k))
+        if wb < 0:
+            raise N.HbxError("B * C = %d * %d exceeds int32" % (B, C))
+        ws = torch.empty(wb, dtype=torch.uint8, device=device)
+        res = torch.empty((B, RANK_HEAD_BYTES + RANK_REC.itemsize * k), dtype=torch.uint8, device=device)
+        if B:
+            N.check(N.lib().hbx_kde_rank_groups(N.ptr(ll), N.ptr(lg), N.ptr(st), B, C, k, N.ptr(res), N.ptr(ws), wb,
+                                                N.stream_handle(stream, device)))
+        if not sync:
+            return res
+        return GroupRank.from_bytes(res.cpu().numpy().tobytes(), B, k)
+
+
 CV_EVAL, CV_ML = 0, 1  # include/hbx.h HBX_CV_*: hbx_kde_cv_groups' modes
 CV_CONVERGED, CV_LIMIT, CV_NOT_SEARCHABLE, CV_NO_MODEL = 0, 1, 2, 3  # ... and its status codes
 BW_RULES = ("normal_reference", "cv_ml")
@@ -664,6 +758,35 @@ class GroupModel(object):
             return GroupLogPdf(None if ll is None else ll.cpu().numpy(), None if lg is None else lg.cpu().numpy(),
                                status.cpu().numpy(), stats, lead)
 
+    def workspace_bytes_rank(self, C, k):
+        return int(N.lib().hbx_kde_rank_logratio_groups_workspace_bytes(self.B, int(C), int(k), self.D))
+
+    def rank_logratio(self, cands, k, rtol=1e-5, fp64_only=True, stream=None, workspace=None, sync=True):
+        """Per group the k candidates of its own pool ``cands[b]`` with the smallest ``ln g(x) - ln l(x)``, ranked by
+        (score, index), with no floor (hbx_kde_rank_logratio_groups: ``logpdf`` for both KDEs, then the ranking, on
+        one stream; the ln arrays stay in the workspace).  Where both densities lie under ``pdf_floor`` the floored
+        score of ``acquire_topk`` is 1 for every candidate; this ranking still orders them.  ``cands``: [B, C, D]
+        float64, numpy or a device tensor; 1 <= k <= min(RANK_MAX_K, C); ``rtol`` and ``fp64_only`` are ``logpdf``'s,
+        and every returned ``ln_l`` / ``ln_g`` is its value for that candidate.  Returns GroupRank, or with
+        ``sync=False`` the device tensor of the B result blocks (uint8 [B, 16 + 32 k])."""
+        if not float(rtol) > 0.0:
+            raise ValueError("rtol must be positive, got %r" % (rtol,))
+        torch = kde._torch()
+        with N.on_device(self.device, stream):
+            cd = self._stage_cands(cands, (3,))
+            C = int(cd.shape[1])
+            k = _rank_k(k, C)
+            ws = self._workspace(workspace, self.workspace_bytes_rank(C, k),
+                                 "B * C = %d * %d exceeds int32" % (self.B, C))
+            res = torch.empty((self.B, RANK_HEAD_BYTES + RANK_REC.itemsize * k), dtype=torch.uint8, device=self.device)
+            if self.B:
+                N.check(N.lib().hbx_kde_rank_logratio_groups(*(self.model_args() + (
+                    N.ptr(cd), C, k, float(rtol), LOGPDF_FP64_ONLY if fp64_only else 0, N.ptr(res), N.ptr(ws),
+                    ws.numel(), N.stream_handle(stream, self.device)))))
+            if not sync:
+                return res
+            return GroupRank.from_bytes(res.cpu().numpy().tobytes(), self.B, k)
+
     def workspace_bytes_get_config(self, C, requests=1, masked=False):
         """``masked``: of the call with a request mask or ``skip_random`` (hbx_kde_propose_groups_m)"""
         if masked:
@@ -778,15 +901,24 @@ class GroupModel(object):
                                    counter_base, stream_id, wd)
             return _configs(rows, source, self.B, S, sync)
 
-    def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, requests=None, topk=None):
+    def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, requests=None, topk=None,
+                score="ratio"):
         """sample + acquire: (rows [B, D] host float64 -- NaN where a group has no pick --, GroupPicks).
         With ``requests=S``: sample + acquire_requests, (rows [B, S, D], GroupPicks of shape [B, S]).
         With ``topk=k``: sample + acquire_topk, (rows [B, k, D] -- NaN rows past a group's count --, GroupTopK);
-        not together with ``requests``."""
+        not together with ``requests``.  ``score="log_ratio"`` (with ``topk``): the same pools ranked by
+        ``rank_logratio`` instead -- ln g - ln l with no floor --, (rows [B, k, D], GroupRank)."""
+        if score not in SCORES:
+            raise ValueError("score must be one of %r, got %r" % (SCORES, score))
+        if score == "log_ratio" and topk is None:
+            raise N.HbxError("propose: score='log_ratio' ranks the k best of a pool and needs topk=k")
         if topk is not None:
             if requests is not None:
                 raise N.HbxError("propose: topk and requests cannot be combined")
             cands, _ = self.sample(C, seed, levels, bandwidth_factor, counter_base, stream=stream)
+            if score == "log_ratio":
+                top = self.rank_logratio(cands, topk, stream=stream)
+                return top.rows(cands), top
             top = self.acquire_topk(cands, topk, stream=stream)
             return top.rows(cands), top
         if requests is None:

@@ -33,6 +33,8 @@
  *                                      requests of each of B brackets, one call
  *   hbx_kde_logpdf_groups           <- KDEMultivariate.pdf (kernel_density.py:162-196) of both KDEs of every bracket
  *                                      at every candidate of its pool, as ln pdf within a relative tolerance, one call
+ *   hbx_kde_rank_logratio_groups    <- bohb.py:124-169's ranking with no floor: the k smallest ln g - ln l per bracket
+ *                                      (hbx_kde_rank_groups: the ranking alone, over ln-pdfs the caller has)
  *   hbx_kde_logpdf                  <- KDEMultivariate.pdf (kernel_density.py:162-196), fp32 log domain
  *   hbx_kde_pdf_exact               <- KDEMultivariate.pdf, fp64, reference operation order
  *   hbx_sh_promote(_ex)             <- HB_iteration.py:149-190 (SuccessiveHalving.process_results ranks)
@@ -422,6 +424,43 @@ int hbx_kde_logpdf_groups(const double* X, int32_t D, const int64_t* seg_off, in
                           double* ln_l, double* ln_g, int32_t* status,
                           void* workspace, int64_t ws_bytes, void* stream);
 int hbx_kde_logpdf_groups_stats(const void* workspace, int64_t* out4);
+/* Grouped log-ratio ranking: per group the k candidates with the smallest s = ln g - ln l, with no floor -- where both
+ * densities lie under the score's floor, max(f, g) / max(l, f) is exactly 1 for every candidate and ranks nothing.
+ * ln_l, ln_g: device f64[B][C], hbx_kde_logpdf_groups' outputs (or any values in that layout); status: device i32[B],
+ * its status words: a group with HBX_ACQ_NO_MODEL or HBX_ACQ_UNSUPPORTED gets count = 0.  1 <= k <= HBX_RANK_MAX_K and
+ * k <= C.  results: B blocks of HBX_RANK_BLOCK_BYTES(k) = 16 + 32 k bytes, block b at b * HBX_RANK_BLOCK_BYTES(k):
+ *   header  {i32 count, i32 k, i32 status (the group's word), i32 0}
+ *   k records {i32 index, i32 0, f64 s, f64 ln_l, f64 ln_g}: the first `count` ranked, ascending by (s, index); the
+ *           rest index -1 and three NaN (0x7FF8000000000000).  index is relative to the group's pool; s is ln_g - ln_l
+ *           as IEEE double subtraction gives it, ln_l and ln_g the inputs' bytes.
+ * The order: finite and -inf s first, by value (-0 and +0 are one value); then +inf (l = 0 with g > 0); a NaN s --
+ * either input NaN, -inf - (-inf), +inf - (+inf) -- comes last and is never ranked or counted.  count = min(k, number
+ * of candidates whose s is not NaN).  Equal s (equal bit patterns after -0 -> +0) rank by lower index.  The order is
+ * total: two runs give the same bytes.
+ * One launch on `stream` (two for pools of 32768 candidates or more, which are ranked in slices first); no host
+ * synchronisation, no allocation.  B == 0: nothing to do.  Null or misaligned pointers (f64 and results: 8 bytes,
+ * i32: 4, workspace: 16), B < 0, k < 1, k > HBX_RANK_MAX_K, k > C, B * C beyond int32 or a short workspace:
+ * HBX_ERR_ARG (hbx_last_error) before any launch.  workspace: hbx_kde_rank_groups_workspace_bytes(B, C, k) bytes
+ * (the slices' index lists; at least 16; -1 for arguments out of range). */
+#define HBX_RANK_MAX_K 1024
+#define HBX_RANK_BLOCK_BYTES(k) (16 + 32 * (int64_t)(k))
+int64_t hbx_kde_rank_groups_workspace_bytes(int64_t B, int64_t C, int32_t k);
+int hbx_kde_rank_groups(const double* ln_l, const double* ln_g, const int32_t* status, int64_t B, int64_t C, int32_t k,
+                        void* results, void* workspace, int64_t ws_bytes, void* stream);
+/* The composite: hbx_kde_logpdf_groups for both KDEs of every group, then hbx_kde_rank_groups over its outputs, on
+ * `stream`.  The model arguments, cand, rtol and flags are hbx_kde_logpdf_groups'; k and results are
+ * hbx_kde_rank_groups'.  Both ln arrays and the status words live in the workspace, which the call lays out itself
+ * (hbx_kde_rank_logratio_groups_workspace_bytes(B, C, k, D) bytes, 16-byte aligned; -1 for arguments out of range):
+ * the caller gets the B result blocks alone, whose ln_l / ln_g are the ln-pdf call's values for that candidate.
+ * Sizes, k, results and the workspace are checked here before any launch, the rest by the ln-pdf call before its
+ * first launch. */
+int64_t hbx_kde_rank_logratio_groups_workspace_bytes(int64_t B, int64_t C, int32_t k, int32_t D);
+int hbx_kde_rank_logratio_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                 const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                 const double* bw_good, const double* bw_bad,
+                                 const int32_t* nlev_good, const int32_t* nlev_bad,
+                                 const double* cand, int64_t C, int32_t k, double rtol, int32_t flags,
+                                 void* results, void* workspace, int64_t ws_bytes, void* stream);
 /* The matching sampler: C candidates per group around its good KDE's rows (hbx_kde_sample's rule).  Candidate
  * (b, i) is byte-equal to what hbx_kde_sample draws for group b's good KDE (tab = NULL) at candidate index i of a
  * call with counter_base + b * C.  cands: f64[B][C][D] (16-byte aligned when D is even); domain_err: nullable

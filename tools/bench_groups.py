@@ -28,6 +28,12 @@ S = K pools and the per-bracket acquire_topk loop; prints one JSON line and writ
 times hbx_kde_logpdf_groups (logpdf_bench below) in default and FP64_ONLY mode at config #5's shape and at a plain
 unsigned shape (8c) against the per-bracket prepare + logpdf loop; writes profiles/groups_logpdf/bench_groups_logpdf.json.
 
+    python tools/bench_groups.py --rank K [--out FILE]
+
+times the grouped log-ratio ranking (rank_bench below): hbx_kde_rank_logratio_groups against the ln-pdf call alone and
+against GroupModel.logpdf plus a torch sort, at config #5's shape and at 64 brackets x 1e5 candidates; writes
+profiles/groups_rank/bench_groups_rank.json.
+
     python tools/bench_groups.py --get-config [--requests S] [--skip-random] [--counts K] [--no-parent] [--out FILE]
 
 times the grouped get_config (get_config_bench below): hbx_kde_propose_groups against its parts and against
@@ -807,8 +813,94 @@ def cv_bench(a, dev, L):
     return 0
 
 
+def rank_shape(a, dev, L, B, C, k, reps):
+    """One shape of --rank: B brackets of a.n rows at config #5's dims, C sampled candidates each, the k best."""
+    dc, du, lev, n = 24, 8, 4, a.n
+    D = dc + du
+    losses = torch.from_numpy(S.make_bracket_losses(B, n).reshape(-1)).to(dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    X = torch.empty((B * n, D), dtype=torch.float64, device=dev)
+    X[:, :dc] = torch.rand((B * n, dc), dtype=torch.float64, device=dev, generator=g)
+    X[:, dc:] = torch.randint(0, lev, (B * n, du), device=dev, generator=g).to(torch.float64)
+    gm = groups.fit_groups(X, losses, np.arange(B + 1, dtype=np.int64) * n, S.var_type_string(dc, du), device=dev)
+    sh = N.stream_handle(None, dev)
+    cands = torch.empty((B, C, D), dtype=torch.float64, device=dev)
+    derr = torch.empty((B, C), dtype=torch.uint8, device=dev)
+    sampler(gm, L, sh, torch.tensor([0] * dc + [lev] * du, dtype=torch.int32, device=dev), S.SEED_CAND, C, cands, derr)()
+    model = gm.model_args()
+    lws = torch.empty(gm.workspace_bytes_logpdf(C), dtype=torch.uint8, device=dev)
+    cws = torch.empty(gm.workspace_bytes_rank(C, k), dtype=torch.uint8, device=dev)
+    rws = torch.empty(int(L.hbx_kde_rank_groups_workspace_bytes(B, C, k)), dtype=torch.uint8, device=dev)
+    ll = torch.empty((B, C), dtype=torch.float64, device=dev)
+    lg = torch.empty((B, C), dtype=torch.float64, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    res = torch.empty((B, groups.RANK_HEAD_BYTES + groups.RANK_REC.itemsize * k), dtype=torch.uint8, device=dev)
+    res2 = torch.empty_like(res)
+    flags = groups.LOGPDF_FP64_ONLY
+    parent = {}
+
+    def logpdf():
+        N.check(L.hbx_kde_logpdf_groups(*model, N.ptr(cands), C, 1e-5, flags, N.ptr(ll), N.ptr(lg), N.ptr(status),
+                                        N.ptr(lws), lws.numel(), sh))
+
+    def rank_alone():  # (over the ln arrays the ln-pdf call left)
+        N.check(L.hbx_kde_rank_groups(N.ptr(ll), N.ptr(lg), N.ptr(status), B, C, k, N.ptr(res2), N.ptr(rws), rws.numel(),
+                                      sh))
+
+    def composite():
+        N.check(L.hbx_kde_rank_logratio_groups(*model, N.ptr(cands), C, k, 1e-5, flags, N.ptr(res), N.ptr(cws),
+                                               cws.numel(), sh))
+
+    def parent_route():  # GroupModel.logpdf, then a stable (index tie-break) torch sort trimmed to k
+        lp = gm.logpdf(cands, sync=False)
+        s, i = torch.sort(lp.ln_g - lp.ln_l, dim=1, stable=True)
+        parent["score"], parent["index"] = s[:, :k], i[:, :k]
+
+    out = {"B": B, "C": C, "k": k, "n": n, "dims": "%dc+%du" % (dc, du), "reps": reps,
+           "workspace_bytes": int(cws.numel())}
+    out.update(_alternate({"logpdf": logpdf, "composite": composite, "parent_logpdf_torch_sort": parent_route}, reps))
+    logpdf()
+    out["rank_alone"] = each_timed(rank_alone, reps)
+    torch.cuda.synchronize()
+    new = groups.GroupRank.from_bytes(res.cpu().numpy().tobytes(), B, k)
+    alone = groups.GroupRank.from_bytes(res2.cpu().numpy().tobytes(), B, k)
+    pi, ps = parent["index"].cpu().numpy(), parent["score"].cpu().numpy()
+    live = np.arange(k)[None, :] < new.count[:, None]
+    ok = bool(np.array_equal(new.index[live], pi[live]) and np.array_equal(new.score[live], ps[live]) and
+              np.array_equal(new.index, alone.index))
+    out["agrees_with_parent_route"] = ok
+    out["groups_ranked"] = int((new.count == k).sum())
+    out["slowest_composite_vs_fastest_parent"] = out["parent_logpdf_torch_sort"]["ms_min"] / out["composite"]["ms_max"]
+    out["rank_share_of_composite"] = out["rank_alone"]["ms_mean"] / out["composite"]["ms_mean"]
+    return out, ok
+
+
+def rank_bench(a, dev, L):
+    """--rank K: hbx_kde_rank_logratio_groups at config #5's shape (a.B brackets x a.C candidates) and at a long-pool
+    shape (64 brackets x 1e5 candidates), the K best of each pool.  Per shape, taking turns, every call between its
+    own pair of device events: the ln-pdf call alone, the composite call, and the only route the library offered
+    before (GroupModel.logpdf, then a stable torch sort of ln_g - ln_l trimmed to K); then the ranking launch alone
+    over the ln arrays.  The composite's indices and scores are compared with the parent route's.  Writes
+    profiles/groups_rank/bench_groups_rank.json (or --out) and prints it."""
+    a.out = a.out or os.path.join(ROOT, "profiles", "groups_rank", "bench_groups_rank.json")
+    out = {"workload": "grouped_rank_k%d" % a.rank, "device": torch.cuda.get_device_name(0), "rtol": 1e-5, "shapes": {}}
+    ok = True
+    for name, B, C, reps in (("config5", a.B, a.C, a.reps), ("long_pool", 64, 100000, max(5, a.reps // 4))):
+        out["shapes"][name], good = rank_shape(a, dev, L, B, C, min(a.rank, C), reps)
+        ok = ok and good
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+    return 0 if ok else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rank", type=int, default=0,
+                    help="the K smallest ln g - ln l per bracket, no floor (rank_bench)")
     ap.add_argument("--cv", action="store_true", help="cv_ml bandwidths: the grouped device search (cv_bench)")
     ap.add_argument("--impute", action="store_true",
                     help="conditional spaces: the impute call and the fit on the view (impute_bench)")
@@ -841,6 +933,8 @@ def main(argv=None):
     L = N.lib()
     if a.logpdf:
         return logpdf_bench(a, dev, L)
+    if a.rank:
+        return rank_bench(a, dev, L)
     if a.cv:
         return cv_bench(a, dev, L)
     if a.impute:
