@@ -46,6 +46,8 @@ EXTRA_FLAGS = {"hbx_score_h.hip": ["-fno-slp-vectorize"], "hbx_score_h32.hip": [
                "hbx_score_f32.hip": ["-fno-slp-vectorize"],
                # all fp64: no packed fp32 arithmetic is wanted from this file
                "hbx_groups_cv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               # fp64 sums; the only fp32 arithmetic is v_exp_f32
+               "hbx_groups_logpdf_signed.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # fp64 subtractions and integer keys only
                "hbx_groups_rank.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 

@@ -13,8 +13,11 @@
 //   glp_dd_kernel        (not with HBX_LOGPDF_FP64_ONLY) the fp32 pass: writes what its bound certifies, lists the rest
 //   glp_f64_kernel       the fp64 log-space pass over the listed candidates (FP64_ONLY: over all); also the NaN fill
 //                        of groups without a usable model
+//   glp_signed_kernel    (HBX_LOGPDF_SIGNED only; hbx_groups_logpdf_signed.hip) KDEs with a SIGNED bit: the signed
+//                        log-space pass, writes what its bound certifies, lists the rest
 //   glp_exact_kernel     KDEs with an EXACT bit: ln of the bit-exact fp64 pdf (hbx_exact_impl.h, the single path's
-//                        functions fed a per-group parameter view), every candidate
+//                        functions fed a per-group parameter view), every candidate; KDEs with a SIGNED bit: the same
+//                        for the candidates the signed pass listed
 // Grids are (B x ceil(C / 64), KDEs requested): a block is one 64-candidate tile of one group and one KDE.
 // Correctness never rests on the fp32 pass: it only decides which values the fp64 pass need not compute.
 //
@@ -22,7 +25,8 @@
 // (c == 1; h == 0, or h > 0 and finite), a bandwidth is not a positive finite number, or the dims exceed the slot bucket
 // picked from D
 // (hbx_groups.hip's buckets: D <= 8, 16, 32 any mix; D <= 96 up to 64 continuous + 32 categorical).  Its values are
-// ln of the reference's own fp64 pdf: NaN where that is negative or NaN, -inf where it underflows to 0.
+// ln of the reference's own fp64 pdf: NaN where that is negative or NaN, -inf where it underflows to 0.  With
+// HBX_LOGPDF_SIGNED a KDE whose only such reason is the negative factor is SIGNED instead.
 //
 // The fp32 pass, glp_dd_kernel<DCP, DUP, NW, DT>: built from hbx_groups_impl.h's pieces for one KDE (the slots, the
 // row layout, the per-slot constants, grp_stage, grp_load_cand, the pair exponent grp_pair_t and its dispatch -- the
@@ -73,32 +77,16 @@
 // splitting the KDE's 32-row chunks as in the fp32 pass and merging their (m, S) with fp64 exp2.  Categorical codes
 // are compared as fp32 (cand_code): exact for observed codes (integers in [0, 1024)), and a candidate value that is
 // no such integer matches nothing, in the reference as here.
-#include "hbx_groups_impl.h"
+#include "hbx_groups_logpdf_impl.h"
 
-#define GLP_HEAD 256  // workspace header: the four counters (u64) in its first 32 bytes
 #define GLP_G 4       // terms per fp32 group
 #define GLP_K 40      // pairs more than K log2 units under the largest are bounded, not tracked
-#define GLP_BAD (HBX_ACQ_NO_MODEL | HBX_ACQ_UNSUPPORTED)
-
-struct GlpArgs {
-  GrpModel M;
-  const double* cand;
-  int64_t C;
-  int32_t tiles;     // ceil(C / 64)
-  int32_t kd0;       // first KDE of the launch's grid.y (0: good / ln_l, 1: bad / ln_g)
-  int32_t fp64_only;
-  double rtol;
-  double* out[2];    // ln_l, ln_g (nullable)
-  int32_t* status;
-  unsigned long long* stat;  // the header's counters
-  int32_t* cnt;              // [B][2] listed candidates per (group, KDE)
-  int32_t* list;             // [B][2][C]
-};
 
 // status[b] from grp_classify's bits (hbx_groups_impl.h), one wave per group.  The ln-pdf's reading of them, stated
 // here and nowhere else: HBX_GRP_EXACT_L / _G per KDE where it cannot be screened (GRP_EXACT(kd)) -- and also where a
 // match factor is negative (h > 1, GRP_NEG(kd)): the fp32 and fp64 passes sum positive terms only, so a signed KDE
-// goes through the exact pdf (the acquisition screens it as a signed sum).  UNSUPPORTED comes alone.
+// goes through the exact pdf (the acquisition screens it as a signed sum) -- or, with HBX_LOGPDF_SIGNED, where that is
+// its only reason, through the signed pass (HBX_GRP_SIGNED_L / _G in place of the EXACT bit).  UNSUPPORTED comes alone.
 __global__ __launch_bounds__(256) void glp_status_kernel(GlpArgs A) {
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -111,7 +99,12 @@ __global__ __launch_bounds__(256) void glp_status_kernel(GlpArgs A) {
   else if (c & GRP_UNSUPPORTED)
     st = HBX_ACQ_UNSUPPORTED;
   else
-    st = ((c & (GRP_EXACT(0) | GRP_NEG(0))) ? HBX_GRP_EXACT_L : 0) | ((c & (GRP_EXACT(1) | GRP_NEG(1))) ? HBX_GRP_EXACT_G : 0);
+    for (int kd = 0; kd < 2; ++kd) {
+      if (c & GRP_EXACT(kd))
+        st |= GLP_EXACT_BIT(kd);
+      else if (c & GRP_NEG(kd))
+        st |= A.signed_route ? GLP_SIGNED_BIT(kd) : GLP_EXACT_BIT(kd);
+    }
   if (lane == 0) A.status[b] = st;
 }
 
@@ -160,7 +153,7 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
   const int64_t b = (int64_t)blockIdx.x / A.tiles;
   const int tile = (int)((int64_t)blockIdx.x - b * A.tiles);
   const int st = A.status[b];
-  if (st & (GLP_BAD | (kd ? HBX_GRP_EXACT_G : HBX_GRP_EXACT_L))) return;  // uniform: the later kernels write these
+  if (st & (GLP_BAD | GLP_EXACT_BIT(kd) | GLP_SIGNED_BIT(kd))) return;  // uniform: the later kernels write these
   const int64_t i = (int64_t)tile * 64 + lane;
   const bool valid = i < A.C;
   if (wave == 0) {
@@ -259,14 +252,8 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
   const bool ok = valid && certified && !bad && St > 0.0 && St - St == 0.0 && M - M == 0.f && lp - lp == 0.0 &&
                   Et < 0.5 && rel < 0.5 && bound <= 0.99 * A.rtol * fmax(1.0, fabs(lp));
   if (ok) A.out[kd][b * A.C + i] = lp;
-  const uint64_t okb = __ballot(ok), bal = __ballot(valid && !ok);
-  if (bal) {  // one atomic per tile; the segment holds C entries and a candidate is listed once
-    const int first = __ffsll((long long)bal) - 1;
-    int32_t base = 0;
-    if (lane == first) base = atomicAdd(&A.cnt[b * 2 + kd], __popcll(bal));
-    base = __shfl(base, first);
-    if (valid && !ok) A.list[(b * 2 + kd) * A.C + base + __popcll(bal & ((1ull << lane) - 1ull))] = (int32_t)i;
-  }
+  const uint64_t okb = __ballot(ok);
+  glp_list_append(A, b, kd, valid && !ok, i, lane);
   if (lane == 0 && okb) atomicAdd(&A.stat[0], (unsigned long long)__popcll(okb));
 }
 
@@ -298,7 +285,7 @@ __global__ __launch_bounds__(64 * NW) void glp_f64_kernel(GlpArgs A) {
     }
     return;
   }
-  if (st & (kd ? HBX_GRP_EXACT_G : HBX_GRP_EXACT_L)) return;  // glp_exact_kernel
+  if (st & (GLP_EXACT_BIT(kd) | GLP_SIGNED_BIT(kd))) return;  // glp_exact_kernel / glp_signed_kernel
   const int64_t cnt = A.fp64_only ? A.C : (int64_t)A.cnt[b * 2 + kd];
   const int64_t pi = (int64_t)tile * 64 + lane;
   if ((int64_t)tile * 64 >= cnt) return;  // uniform
@@ -422,7 +409,9 @@ __global__ __launch_bounds__(64 * NW) void glp_f64_kernel(GlpArgs A) {
 }
 
 // EXACT KDEs: ln of the bit-exact fp64 pdf of every candidate of the tile, each by the whole block
-// (groups_select_kernel's use of exact_setup / exact_pdf)
+// (groups_select_kernel's use of exact_setup / exact_pdf).  SIGNED KDEs, the listed form: the block takes the entries
+// [tile * 64, min(cnt, tile * 64 + 64)) of the (group, KDE)'s list, what the signed pass did not certify, instead of
+// the tile's candidates.  The order of a list may depend on timing (C > 64); a candidate's value does not.
 __global__ __launch_bounds__(EXACT_THREADS) void glp_exact_kernel(GlpArgs A) {
   __shared__ ExactShared sh;
   __shared__ GrpView vw;
@@ -431,15 +420,19 @@ __global__ __launch_bounds__(EXACT_THREADS) void glp_exact_kernel(GlpArgs A) {
   const int64_t b = (int64_t)blockIdx.x / A.tiles;
   const int tile = (int)((int64_t)blockIdx.x - b * A.tiles);
   const int st = A.status[b];
-  if ((st & GLP_BAD) || !(st & (kd ? HBX_GRP_EXACT_G : HBX_GRP_EXACT_L))) return;  // uniform
+  if ((st & GLP_BAD) || !(st & (GLP_EXACT_BIT(kd) | GLP_SIGNED_BIT(kd)))) return;  // uniform
+  const int32_t* list = (st & GLP_SIGNED_BIT(kd)) ? A.list + (b * 2 + kd) * A.C : nullptr;
+  const int64_t lim = list ? (int64_t)A.cnt[b * 2 + kd] : A.C;  // (cnt <= C: a candidate is listed once)
+  if ((int64_t)tile * 64 >= lim) return;  // uniform
   const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
   const int64_t nk = kd ? A.M.n_bad[b] : A.M.n_good[b];
   const double* Xs = A.M.X + s0 * D;
   const int64_t* rows = A.M.order + s0 + (kd ? n - nk : 0);
   if (threadIdx.x == 0) vw = grp_view(A.M, b, kd);
   __syncthreads();
-  const int64_t i0 = (int64_t)tile * 64, i1 = i0 + 64 < A.C ? i0 + 64 : A.C;
-  for (int64_t i = i0; i < i1; ++i) {
+  const int64_t i0 = (int64_t)tile * 64, i1 = i0 + 64 < lim ? i0 + 64 : lim;
+  for (int64_t e = i0; e < i1; ++e) {
+    const int64_t i = list ? (int64_t)list[e] : e;
     exact_setup(&vw, D, A.cand + (b * A.C + i) * D, &sh);
     const double v = exact_pdf(Xs, D, rows, &vw, &sh);
     if (threadIdx.x == 0) A.out[kd][b * A.C + i] = log(v);
@@ -468,7 +461,7 @@ int hbx_kde_logpdf_groups(const double* X, int32_t D, const int64_t* seg_off, in
   if (!grp_counts_ok(B, 1, C))  // (what every grid, list entry and count relies on)
     return hbx_fail(HBX_ERR_ARG, "%s: B * C = %lld * %lld exceeds int32", who, (long long)B, (long long)C);
   if (!(rtol > 0.0)) return hbx_fail(HBX_ERR_ARG, "%s: rtol=%g must be positive", who, rtol);
-  if (flags & ~HBX_LOGPDF_FP64_ONLY) return hbx_fail(HBX_ERR_ARG, "%s: flags=%d", who, flags);
+  if (flags & ~(HBX_LOGPDF_FP64_ONLY | HBX_LOGPDF_SIGNED)) return hbx_fail(HBX_ERR_ARG, "%s: flags=%d", who, flags);
   if (!ln_l && !ln_g) return hbx_fail(HBX_ERR_ARG, "%s: null pointer (ln_l and ln_g)", who);
   if (B == 0 || C == 0) return HBX_OK;
   GlpArgs A;
@@ -486,6 +479,7 @@ int hbx_kde_logpdf_groups(const double* X, int32_t D, const int64_t* seg_off, in
   A.tiles = (int32_t)((C + 63) / 64);
   A.kd0 = ln_l ? 0 : 1;
   A.fp64_only = (flags & HBX_LOGPDF_FP64_ONLY) ? 1 : 0;
+  A.signed_route = (flags & HBX_LOGPDF_SIGNED) ? 1 : 0;
   A.rtol = rtol;
   A.out[0] = ln_l;
   A.out[1] = ln_g;
@@ -514,6 +508,8 @@ int hbx_kde_logpdf_groups(const double* X, int32_t D, const int64_t* seg_off, in
 #undef GLP_LAUNCH_DD
 #undef GLP_LAUNCH_F64
 #undef GLP_LAUNCH_F64_EXP32
+  if (A.signed_route)  // (before the exact pass, which reads the lists it leaves)
+    if (const int rc = glp_signed_launch(A, grid, s)) return rc;
   hipLaunchKernelGGL(glp_exact_kernel, grid, dim3(EXACT_THREADS), 0, s, A);
   HBX_LAUNCH_CHECK();
   return HBX_OK;

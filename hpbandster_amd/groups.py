@@ -329,17 +329,26 @@ def sample_prior(B, S, levels, seed, counter_base=0, C=1, stream=None, stream_id
         return _configs(rows, source, int(B), S, sync)
 
 
-GRP_EXACT_L, GRP_EXACT_G = 64, 128  # include/hbx.h HBX_GRP_EXACT_*
-LOGPDF_FP64_ONLY = 1                 # include/hbx.h HBX_LOGPDF_FP64_ONLY
+GRP_EXACT_L, GRP_EXACT_G = 64, 128    # include/hbx.h HBX_GRP_EXACT_*
+GRP_SIGNED_L, GRP_SIGNED_G = 256, 512  # include/hbx.h HBX_GRP_SIGNED_*
+LOGPDF_FP64_ONLY = 1                   # include/hbx.h HBX_LOGPDF_FP64_ONLY
+LOGPDF_SIGNED = 4                      # include/hbx.h HBX_LOGPDF_SIGNED
+SIGNED_ROUTES = ("exact", "logspace")  # logpdf's routes for KDEs with a negative match factor (h > 1)
+
+
+def _logpdf_flags(fp64_only, signed):
+    if signed not in SIGNED_ROUTES:
+        raise ValueError("signed must be one of %r, got %r" % (SIGNED_ROUTES, signed))
+    return (LOGPDF_FP64_ONLY if fp64_only else 0) | (LOGPDF_SIGNED if signed == "logspace" else 0)
 
 
 class GroupLogPdf(object):
     """Both KDEs' log densities at every candidate of every group's pool (hbx_kde_logpdf_groups): ``ln_l`` and
     ``ln_g`` (float64, shaped like the pool's leading dims -- [B, C] or [B, S, C] --, None when not requested; -inf
     where the pdf is 0, NaN where the reference's is NaN or negative and for groups without a usable model),
-    ``status`` (int32 [B]: ACQ_NO_MODEL / ACQ_UNSUPPORTED, GRP_EXACT_L / GRP_EXACT_G) and ``stats`` (4 ints: values
-    written by the fp32 pass, the fp64 log-space pass, through the exact pdf, NaN-filled; None before a
-    synchronisation).  With ``sync=False`` the arrays are device tensors.  ``len()`` is B."""
+    ``status`` (int32 [B]: ACQ_NO_MODEL / ACQ_UNSUPPORTED, GRP_EXACT_L / GRP_EXACT_G, with ``signed="logspace"``
+    GRP_SIGNED_L / GRP_SIGNED_G) and ``stats`` (4 ints: values written by the fp32 pass, the fp64 log-space passes,
+    through the exact pdf, NaN-filled; None before a synchronisation).  With ``sync=False`` the arrays are device tensors.  ``len()`` is B."""
     __slots__ = ("ln_l", "ln_g", "status", "stats")
 
     def __init__(self, ln_l, ln_g, status, stats=None, lead=None):
@@ -721,14 +730,20 @@ class GroupModel(object):
     def workspace_bytes_logpdf(self, C):
         return int(N.lib().hbx_kde_logpdf_groups_workspace_bytes(self.B, int(C), self.D))
 
-    def logpdf(self, cands, rtol=1e-5, which="both", fp64_only=True, stream=None, workspace=None, sync=True):
+    def logpdf(self, cands, rtol=1e-5, which="both", fp64_only=True, stream=None, workspace=None, sync=True,
+               signed="exact"):
         """ln l(x) and ln g(x) of every candidate of every group's own pool (hbx_kde_logpdf_groups): each value within
         ``rtol * max(1, |ln p|)`` of the reference's KDEMultivariate.pdf.  ``cands``: [B, C, D] or [B, S, C, D]
         float64, numpy or a contiguous device tensor; ``which``: "both", "good" (ln_l only) or "bad" (ln_g only);
         ``fp64_only=False`` runs the fp32 first pass before the fp64 one (the C ABI's flags = 0): the same contract,
         3 % faster at config #5's shape and half as fast at 8 continuous dims (DESIGN section 4 "Grouped ln-pdf"), so
-        the fp64 pass alone is the default here.  Returns GroupLogPdf with host arrays, or with ``sync=False`` with
-        device tensors (and ``stats`` None: reading the counters synchronises)."""
+        the fp64 pass alone is the default here.  ``signed``: what a KDE with a negative match factor (a categorical
+        bandwidth > 1) goes through -- "exact": ln of the bit-exact fp64 pdf for every candidate; "logspace"
+        (HBX_LOGPDF_SIGNED): a signed sum in fp64 log space where its bound certifies the value, the exact pdf only
+        where the sum cancels (status GRP_SIGNED_L / _G; a certified candidate whose pdf underflows to 0 gets its
+        finite value).  Returns GroupLogPdf with host arrays, or with ``sync=False`` with device tensors (and
+        ``stats`` None: reading the counters synchronises)."""
+        flags = _logpdf_flags(fp64_only, signed)
         if which not in ("both", "good", "bad"):
             raise ValueError("which must be 'both', 'good' or 'bad', got %r" % (which,))
         if not float(rtol) > 0.0:
@@ -746,7 +761,7 @@ class GroupModel(object):
             launched = self.B > 0 and C > 0
             if launched:
                 N.check(N.lib().hbx_kde_logpdf_groups(*(self.model_args() + (
-                    N.ptr(cd), C, float(rtol), LOGPDF_FP64_ONLY if fp64_only else 0, N.ptr(ll), N.ptr(lg),
+                    N.ptr(cd), C, float(rtol), flags, N.ptr(ll), N.ptr(lg),
                     N.ptr(status), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device)))))
             if not sync:
                 return GroupLogPdf(ll, lg, status, None, lead)
@@ -761,16 +776,18 @@ class GroupModel(object):
     def workspace_bytes_rank(self, C, k):
         return int(N.lib().hbx_kde_rank_logratio_groups_workspace_bytes(self.B, int(C), int(k), self.D))
 
-    def rank_logratio(self, cands, k, rtol=1e-5, fp64_only=True, stream=None, workspace=None, sync=True):
+    def rank_logratio(self, cands, k, rtol=1e-5, fp64_only=True, stream=None, workspace=None, sync=True,
+                      signed="exact"):
         """Per group the k candidates of its own pool ``cands[b]`` with the smallest ``ln g(x) - ln l(x)``, ranked by
         (score, index), with no floor (hbx_kde_rank_logratio_groups: ``logpdf`` for both KDEs, then the ranking, on
         one stream; the ln arrays stay in the workspace).  Where both densities lie under ``pdf_floor`` the floored
         score of ``acquire_topk`` is 1 for every candidate; this ranking still orders them.  ``cands``: [B, C, D]
-        float64, numpy or a device tensor; 1 <= k <= min(RANK_MAX_K, C); ``rtol`` and ``fp64_only`` are ``logpdf``'s,
-        and every returned ``ln_l`` / ``ln_g`` is its value for that candidate.  Returns GroupRank, or with
-        ``sync=False`` the device tensor of the B result blocks (uint8 [B, 16 + 32 k])."""
+        float64, numpy or a device tensor; 1 <= k <= min(RANK_MAX_K, C); ``rtol``, ``fp64_only`` and ``signed`` are
+        ``logpdf``'s, and every returned ``ln_l`` / ``ln_g`` is its value for that candidate.  Returns GroupRank, or
+        with ``sync=False`` the device tensor of the B result blocks (uint8 [B, 16 + 32 k])."""
         if not float(rtol) > 0.0:
             raise ValueError("rtol must be positive, got %r" % (rtol,))
+        flags = _logpdf_flags(fp64_only, signed)
         torch = kde._torch()
         with N.on_device(self.device, stream):
             cd = self._stage_cands(cands, (3,))
@@ -781,7 +798,7 @@ class GroupModel(object):
             res = torch.empty((self.B, RANK_HEAD_BYTES + RANK_REC.itemsize * k), dtype=torch.uint8, device=self.device)
             if self.B:
                 N.check(N.lib().hbx_kde_rank_logratio_groups(*(self.model_args() + (
-                    N.ptr(cd), C, k, float(rtol), LOGPDF_FP64_ONLY if fp64_only else 0, N.ptr(res), N.ptr(ws),
+                    N.ptr(cd), C, k, float(rtol), flags, N.ptr(res), N.ptr(ws),
                     ws.numel(), N.stream_handle(stream, self.device)))))
             if not sync:
                 return res
@@ -902,12 +919,13 @@ class GroupModel(object):
             return _configs(rows, source, self.B, S, sync)
 
     def propose(self, C, seed, levels, bandwidth_factor=3, counter_base=0, stream=None, requests=None, topk=None,
-                score="ratio"):
+                score="ratio", signed="exact"):
         """sample + acquire: (rows [B, D] host float64 -- NaN where a group has no pick --, GroupPicks).
         With ``requests=S``: sample + acquire_requests, (rows [B, S, D], GroupPicks of shape [B, S]).
         With ``topk=k``: sample + acquire_topk, (rows [B, k, D] -- NaN rows past a group's count --, GroupTopK);
         not together with ``requests``.  ``score="log_ratio"`` (with ``topk``): the same pools ranked by
-        ``rank_logratio`` instead -- ln g - ln l with no floor --, (rows [B, k, D], GroupRank)."""
+        ``rank_logratio`` instead -- ln g - ln l with no floor --, (rows [B, k, D], GroupRank); ``signed`` is
+        ``rank_logratio``'s."""
         if score not in SCORES:
             raise ValueError("score must be one of %r, got %r" % (SCORES, score))
         if score == "log_ratio" and topk is None:
@@ -917,7 +935,7 @@ class GroupModel(object):
                 raise N.HbxError("propose: topk and requests cannot be combined")
             cands, _ = self.sample(C, seed, levels, bandwidth_factor, counter_base, stream=stream)
             if score == "log_ratio":
-                top = self.rank_logratio(cands, topk, stream=stream)
+                top = self.rank_logratio(cands, topk, stream=stream, signed=signed)
                 return top.rows(cands), top
             top = self.acquire_topk(cands, topk, stream=stream)
             return top.rows(cands), top

@@ -405,16 +405,28 @@ int hbx_kde_acquire_groups_topk_r(const double* X, int32_t D, const int64_t* seg
  * dims beyond the slot bucket): NaN where that pdf is negative or NaN, -inf where it underflows to 0.
  * flags: HBX_LOGPDF_FP64_ONLY skips the fp32 first pass (the fp64 pass alone meets the contract; the fp32 pass only
  * writes values its own rigorous bound certifies).  rtol > 0; below 1e-5 the fp64 pass uses fp64 exponentials.
+ * HBX_LOGPDF_SIGNED (may be combined with FP64_ONLY; any other bit is HBX_ERR_ARG) opts into the signed log-space
+ * route: a KDE whose only reason for the exact pdf is a negative match factor (h > 1 in a categorical dim with >= 2
+ * levels) reports HBX_GRP_SIGNED_L / HBX_GRP_SIGNED_G instead of the EXACT bit and is summed as a signed sum S+ - S-
+ * in fp64 log space; a candidate gets that value where a rigorous bound (eps (S+ + S-) / |S+ - S-|, eps the error of
+ * one sum) keeps it within rtol * max(1, |ln p|), and otherwise -- the sum cancels, is <= 0 or NaN -- ln of the
+ * bit-exact fp64 pdf, exactly the value of the call without the flag.  On this route a candidate whose fp64 pdf
+ * underflows to 0 gets its finite log-space value when the bound certifies it (without the flag: -inf).  Without
+ * the flag every status word, value and counter is what it was before the flag existed.
  * Launches on `stream` only: no host synchronisation, no allocation, no per-group host work.  B == 0 or C == 0:
  * nothing to do (status is not written).  B * C beyond int32, D outside [1, hbx_max_dims()], null or misaligned
  * pointers (f64 / i64: 8 bytes, i32: 4, workspace: 16) or a short workspace: HBX_ERR_ARG (hbx_last_error), before the
  * first launch.  workspace: hbx_kde_logpdf_groups_workspace_bytes(B, C, D) bytes (-1 for arguments out of range); its
  * header holds four counters of output values, read by hbx_kde_logpdf_groups_stats (synchronises the device):
- * out4[0] written by the fp32 pass, [1] by the fp64 log-space pass, [2] through the exact pdf, [3] NaN-filled for
- * groups without a usable model; their sum is B * C times the number of non-NULL outputs. */
+ * out4[0] written by the fp32 pass, [1] by the fp64 log-space passes (the signed one included), [2] through the
+ * exact pdf (on the signed route: the candidates it handed over), [3] NaN-filled for groups without a usable model;
+ * their sum is B * C times the number of non-NULL outputs. */
 #define HBX_GRP_EXACT_L 64
 #define HBX_GRP_EXACT_G 128
+#define HBX_GRP_SIGNED_L 256  /* HBX_LOGPDF_SIGNED: the good KDE took the signed log-space route */
+#define HBX_GRP_SIGNED_G 512  /* ... the bad KDE */
 #define HBX_LOGPDF_FP64_ONLY 1
+#define HBX_LOGPDF_SIGNED 4  /* (2 stays refused, as every bit but these two) */
 int64_t hbx_kde_logpdf_groups_workspace_bytes(int64_t B, int64_t C, int32_t D);
 int hbx_kde_logpdf_groups(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
                           const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,

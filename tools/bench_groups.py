@@ -34,6 +34,13 @@ times the grouped log-ratio ranking (rank_bench below): hbx_kde_rank_logratio_gr
 against GroupModel.logpdf plus a torch sort, at config #5's shape and at 64 brackets x 1e5 candidates; writes
 profiles/groups_rank/bench_groups_rank.json.
 
+    python tools/bench_groups.py --logpdf --signed [--out FILE]
+    python tools/bench_groups.py --rank K --signed [--out FILE]
+
+time the two routes for KDEs with a categorical bandwidth > 1 (signed_bench below): the exact pdf for every candidate
+against the signed log-space pass (HBX_LOGPDF_SIGNED), taking turns at config #5's shape; write
+profiles/groups_logpdf_signed/bench_{logpdf,rank}_signed.json.
+
     python tools/bench_groups.py --get-config [--requests S] [--skip-random] [--counts K] [--no-parent] [--out FILE]
 
 times the grouped get_config (get_config_bench below): hbx_kde_propose_groups against its parts and against
@@ -897,8 +904,89 @@ def rank_bench(a, dev, L):
     return 0 if ok else 1
 
 
+def signed_bench(a, dev, L):
+    """--logpdf --signed / --rank K --signed: the two routes for KDEs with a negative match factor at config #5's shape
+    (a.B brackets x a.n rows x a.C candidates, 24c + 8u, 4 levels), FP64_ONLY as GroupModel.logpdf calls it:
+    "exact" (flags without HBX_LOGPDF_SIGNED: every candidate of such a KDE through the exact pdf, the only route
+    before the flag) and "logspace" (with it).  Both run in one session, taking turns, every call between its own pair
+    of device events: hbx_kde_logpdf_groups, and with --rank K hbx_kde_rank_logratio_groups.  Per route the four
+    counters; the new route's certified share is stats[1] and its handed-over share stats[2] over the values of the
+    KDEs with a SIGNED bit.  The routes' values are compared (the same NaNs; finite values within 2e-5 max(1, |ln p|);
+    a finite log-space value against the exact route's -inf is the underflow reading) and, with --rank, the indices.
+    Writes profiles/groups_logpdf_signed/bench_{logpdf,rank}_signed.json (or --out) and prints it."""
+    B, n, C, dc, du, lev = a.B, a.n, a.C, 24, 8, 4
+    D, k = dc + du, min(a.rank, a.C)
+    a.out = a.out or os.path.join(ROOT, "profiles", "groups_logpdf_signed",
+                                  "bench_%s_signed.json" % ("rank" if a.rank else "logpdf"))
+    losses = torch.from_numpy(S.make_bracket_losses(B, n).reshape(-1)).to(dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    X = torch.empty((B * n, D), dtype=torch.float64, device=dev)
+    X[:, :dc] = torch.rand((B * n, dc), dtype=torch.float64, device=dev, generator=g)
+    X[:, dc:] = torch.randint(0, lev, (B * n, du), device=dev, generator=g).to(torch.float64)
+    gm = groups.fit_groups(X, losses, np.arange(B + 1, dtype=np.int64) * n, S.var_type_string(dc, du), device=dev)
+    sh = N.stream_handle(None, dev)
+    cands = torch.empty((B, C, D), dtype=torch.float64, device=dev)
+    derr = torch.empty((B, C), dtype=torch.uint8, device=dev)
+    sampler(gm, L, sh, torch.tensor([0] * dc + [lev] * du, dtype=torch.int32, device=dev), S.SEED_CAND, C, cands, derr)()
+    model = gm.model_args()
+    routes = {"exact": groups.LOGPDF_FP64_ONLY, "logspace": groups.LOGPDF_FP64_ONLY | groups.LOGPDF_SIGNED}
+    buf, fns = {}, {}
+    for key, flags in routes.items():
+        r = buf[key] = {"ws": torch.empty(gm.workspace_bytes_logpdf(C), dtype=torch.uint8, device=dev),
+                        "ll": torch.empty((B, C), dtype=torch.float64, device=dev),
+                        "lg": torch.empty((B, C), dtype=torch.float64, device=dev),
+                        "status": torch.zeros(B, dtype=torch.int32, device=dev)}
+        fns["logpdf_" + key] = lambda r=r, flags=flags: N.check(L.hbx_kde_logpdf_groups(
+            *model, N.ptr(cands), C, 1e-5, flags, N.ptr(r["ll"]), N.ptr(r["lg"]), N.ptr(r["status"]), N.ptr(r["ws"]),
+            r["ws"].numel(), sh))
+        if a.rank:
+            r["cws"] = torch.empty(gm.workspace_bytes_rank(C, k), dtype=torch.uint8, device=dev)
+            r["res"] = torch.empty((B, groups.RANK_HEAD_BYTES + groups.RANK_REC.itemsize * k), dtype=torch.uint8, device=dev)
+            fns["rank_" + key] = lambda r=r, flags=flags: N.check(L.hbx_kde_rank_logratio_groups(
+                *model, N.ptr(cands), C, k, 1e-5, flags, N.ptr(r["res"]), N.ptr(r["cws"]), r["cws"].numel(), sh))
+    out = {"workload": "grouped_logpdf_signed_b%d_n%d_c%d" % (B, n, C), "device": torch.cuda.get_device_name(0),
+           "dims": "%dc+%du" % (dc, du), "reps": a.reps, "rtol": 1e-5, "k": k, "n_good": int(gm.n_good[0]),
+           "n_bad": int(gm.n_bad[0])}
+    out.update(_alternate(fns, a.reps))
+    host = {}
+    for key, r in buf.items():
+        stats = np.zeros(4, dtype=np.int64)
+        N.check(L.hbx_kde_logpdf_groups_stats(N.ptr(r["ws"]), stats.ctypes.data))
+        out["stats_" + key] = [int(v) for v in stats]
+        host[key] = (r["ll"].cpu().numpy(), r["lg"].cpu().numpy(), r["status"].cpu().numpy())
+    st = host["logspace"][2]
+    nsig = int(((st & groups.GRP_SIGNED_L) != 0).sum() + ((st & groups.GRP_SIGNED_G) != 0).sum())
+    out["kdes_signed_l"] = int(((st & groups.GRP_SIGNED_L) != 0).sum())
+    out["kdes_signed_g"] = int(((st & groups.GRP_SIGNED_G) != 0).sum())
+    out["kdes_exact_on_exact_route"] = int(((host["exact"][2] & groups.GRP_EXACT_L) != 0).sum() +
+                                           ((host["exact"][2] & groups.GRP_EXACT_G) != 0).sum())
+    # (the unsigned KDEs' values are counted in stats[1] on both routes: the difference is the signed pass's)
+    cert = out["stats_logspace"][1] - out["stats_exact"][1]
+    out["certified_share"] = cert / float(nsig * C) if nsig else 0.0
+    out["handed_over_share"] = 1.0 - out["certified_share"] if nsig else 0.0
+    ok = all(_same_within(host["logspace"][q], host["exact"][q], 2e-5) for q in (0, 1))
+    out["routes_agree"] = bool(ok)
+    both = [np.isneginf(host["exact"][q]) & np.isfinite(host["logspace"][q]) for q in (0, 1)]
+    out["finite_where_exact_underflows"] = int(both[0].sum() + both[1].sum())
+    for kind in ("logpdf",) + (("rank",) if a.rank else ()):
+        out["slowest_logspace_vs_fastest_exact_" + kind] = out[kind + "_exact"]["ms_min"] / out[kind + "_logspace"]["ms_max"]
+    if a.rank:
+        rk = {key: groups.GroupRank.from_bytes(r["res"].cpu().numpy().tobytes(), B, k) for key, r in buf.items()}
+        out["rank_same_indices_groups"] = int(np.all(rk["exact"].index == rk["logspace"].index, axis=1).sum())
+        out["groups_ranked"] = int((rk["logspace"].count == k).sum())
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+    return 0 if ok else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--signed", action="store_true",
+                    help="--logpdf / --rank K: the exact and the log-space route for signed KDEs, taking turns (signed_bench)")
     ap.add_argument("--rank", type=int, default=0,
                     help="the K smallest ln g - ln l per bracket, no floor (rank_bench)")
     ap.add_argument("--cv", action="store_true", help="cv_ml bandwidths: the grouped device search (cv_bench)")
@@ -931,6 +1019,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     L = N.lib()
+    if a.signed and (a.logpdf or a.rank):
+        return signed_bench(a, dev, L)
     if a.logpdf:
         return logpdf_bench(a, dev, L)
     if a.rank:
