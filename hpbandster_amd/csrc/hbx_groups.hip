@@ -75,6 +75,10 @@
 // hbx_topk_rank.h (shared with hbx_topk.hip).  Its comment, before the kernel, has the steps and the argument why the
 // shortlist holds the whole top-k.
 //
+// The pick by log ratio (hbx_kde_acquire_groups_batch_lr): the screens' <.., LR = true> instances, then
+// groups_select_lr_kernel of hbx_groups_lr.hip in launch 2's place; its header has the route.  The entry point and its
+// checks stand here (grp_acquire<true, true>), with the other grouped acquisitions'.
+//
 // The grouped sampler (hbx_kde_sample_groups) lives in hbx_sample.hip beside the draw functions it shares with
 // hbx_kde_sample, so the byte-equality of the draws holds by construction.
 //
@@ -85,29 +89,8 @@
 //   - the slot bucket comes from D alone, and the kernel sorts the dims into slots itself: vartype is device memory
 //     and reading it on the host would be the synchronisation the call must not make;
 //   - C == 0 launches one small kernel: the B empty records have to be written by something (NaN is not a byte fill).
-#include "hbx_groups_impl.h"
+#include "hbx_groups_acq.h"  // GrpArgs, GRP_NO_SCREEN, grp_empty_record
 #include "hbx_topk_rank.h"
-
-// The acquisition's reading of grp_classify's bits (hbx_groups_impl.h), stated here and nowhere else: a group is
-// exact-only -- re-scored whole, HBX_ACQ_OVERFLOW -- when either of its KDEs cannot be screened (GRP_EXACT(kd)); a
-// negative match factor (h > 1, GRP_NEG(kd)) is screened like any other KDE, as a signed sum.
-#define GRP_EXACT_ONLY GRP_EXACT_ANY
-#define GRP_NO_SCREEN (GRP_NO_MODEL | GRP_UNSUPPORTED | GRP_EXACT_ONLY)
-
-struct GrpArgs {
-  GrpModel M;
-  const double* cand;
-  int64_t S, C;      // requests per group (1: hbx_kde_acquire_groups), candidates per request
-  int64_t P;         // S * C: the group's flattened pool, what the screen sees
-  int32_t tiles;     // ceil(P / 64)
-  int32_t slabs;     // tile screen: blocks per group, one tile per wave
-  GScreen* scr;
-  AcqResult* res;
-  ScoreFloor F;      // the call's score floor (hbx_rules.pdf_floor), read by the kernels' <.., DEFF = false> instances
-  // the request mask (hbx_kde_acquire_groups_batch_m), read by the kernels' <.., MASK = true> instances alone:
-  const uint8_t* want;         // u8[B][S], request (b, s) is answered when its byte is not 0; NULL: every request
-  unsigned long long* stats;   // the workspace head's four counters (hbx_kde_groups_request_stats)
-};
 
 // The request mask in a kernel.  MASK follows DEFF's precedent: the <.., MASK = false> instances are, instruction for
 // instruction, the kernels the unmasked entry points have always launched (profiles/request_mask/README.md has the
@@ -168,7 +151,12 @@ __device__ __forceinline__ ScoreFloor grp_floor(const GrpArgs& A) {
 #define GRP_PAIRS_CALL(QC, QU, SG) \
   grp_pairs<DCP, DUP, QC, QU, SG>(srows, L.rs, jmax, L.dcq, L.duq, xc, xu, dl, nf, lbs, m, sp, sn)
 
-template <int DCP, int DUP, int NW, int DT, bool DEFF, bool MASK>
+// The log-ratio route in a screen.  LR follows DEFF's and MASK's precedent: the <.., LR = false> instances are the
+// kernels they were (same registers, profiles/groups_lr/README.md); the <.., DEFF = true, MASK = true, LR = true>
+// instances serve hbx_kde_acquire_groups_batch_lr.  Only the last step differs: the two KdeEst go through grp_emit_lr
+// (hbx_groups_impl.h) -- the interval of ln g - ln l with no floor -- instead of grp_emit; the loop, the staging and
+// the bound `err` are the same statements.
+template <int DCP, int DUP, int NW, int DT, bool DEFF, bool MASK, bool LR = false>
 __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
   constexpr int NT = 64 * NW;
   __shared__ __align__(16) float sobs[NW * 64 * (DT + 4)];
@@ -289,7 +277,11 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
       est_g = e;
     __syncthreads();  // (s_pm, s_bmax are rewritten for the bad KDE)
   }
-  if (wave == 0 && valid) *out = grp_emit(D, st, certified, est_l, est_g, grp_floor<DEFF>(A));
+  if constexpr (LR) {
+    if (wave == 0 && valid) *out = grp_emit_lr(D, st, certified, est_l, est_g);
+  } else {
+    if (wave == 0 && valid) *out = grp_emit(D, st, certified, est_l, est_g, grp_floor<DEFF>(A));
+  }
 }
 
 // The tile screen (header: "The tile screen"): the block is a slab of NW tiles of one group, wave w owns tile
@@ -304,7 +296,7 @@ __global__ __launch_bounds__(64 * NW) void groups_screen_kernel(GrpArgs A) {
 // for groups_screen_kernel (before: 165 / 196 / 255 / 256) and 190 / 219 / 235 / 256 for this kernel (180 / 209 / 224 /
 // 256), every one at the waves per SIMD it had (3 / 2 / 2 / 1 and 2 / 2 / 2 / 1), no scratch.  The one step that
 // groups_screen_kernel does not take from the header is the candidate's load (the comment there has the numbers).
-template <int DCP, int DUP, int NW, int DT, bool DEFF, bool MASK>
+template <int DCP, int DUP, int NW, int DT, bool DEFF, bool MASK, bool LR = false>
 __global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kernel(GrpArgs A) {
   constexpr int NT = 64 * NW;
   __shared__ __align__(16) float sobs[NW * 64 * (DT + 4)];
@@ -376,6 +368,7 @@ __global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kerne
   int g = 0;
   bool certified = true;
   KdeEst est_l = kde_est_neutral();
+  [[maybe_unused]] KdeEst est_g = kde_est_neutral();  // (LR alone)
   int tw = tile0 + wave;  // this wave's tile
   if constexpr (MASK) tw = s_tile[wave];
   const int64_t iw = (int64_t)tw * 64 + lane;
@@ -420,22 +413,15 @@ __global__ __launch_bounds__(64 * NW, DCP <= 32 ? 2 : 1) void groups_tiles_kerne
     const KdeEst e = grp_estimate(K, kd, dc, du, nk, s_bmax[kd], xc, m, sp, sn, m != m, certified);
     if (kd == 0)
       est_l = e;
+    else if constexpr (LR)
+      est_g = e;  // (emitted past the loop, where the candidate's registers are dead: no scratch in the 32-slot instance)
     else if (vw)
       A.scr[b * A.P + iw] = grp_emit(D, st, certified, est_l, e, grp_floor<DEFF>(A));
   }
+  if constexpr (LR)
+    if (vw) A.scr[b * A.P + iw] = grp_emit_lr(D, st, certified, est_l, est_g);
 }
 #undef GRP_PAIRS_CALL
-
-__device__ __forceinline__ AcqResult grp_empty_record(int32_t flags) {
-  AcqResult r;
-  r.index = -1;
-  r.score = r.pdf_l = r.pdf_g = NAN;
-  r.rel = 0.f;
-  r.flags = flags;
-  r.shortlist = 0;
-  r.near = 0;
-  return r;
-}
 
 template <bool DEFF, bool MASK>
 __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs A) {
@@ -590,10 +576,11 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
   }
 }
 
-// C == 0: every record is the empty one; want (nullable): the skipped record for the unwanted requests
-__global__ void groups_empty_kernel(AcqResult* res, int64_t B, const uint8_t* want) {
+// C == 0: every record is the empty one; want (nullable): the skipped record for the unwanted requests; flags: what an
+// answered record carries (HBX_ACQ_LOG_RATIO on the log-ratio route, 0 otherwise)
+__global__ void groups_empty_kernel(AcqResult* res, int64_t B, const uint8_t* want, int32_t flags) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) res[b] = grp_empty_record(want && want[b] == 0 ? HBX_ACQ_SKIPPED : 0);
+  if (b < B) res[b] = grp_empty_record(want && want[b] == 0 ? HBX_ACQ_SKIPPED : flags);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -844,8 +831,6 @@ __global__ void groups_topk_empty_kernel(char* out, int64_t B, int32_t k) {
   if (b < B) *(TopkHead*)(out + b * (int64_t)(sizeof(TopkHead) + sizeof(TopkRec) * (size_t)k)) = TopkHead{0, 0, 0, k};
 }
 
-#define GRP_WS_HEAD 256
-
 // Which screen a call runs -- the one rule.  One request per group is hbx_kde_acquire_groups' own case: the
 // chunk-splitting screen, always.  Several requests flatten to tiles = ceil(S C / 64) tiles per group: from
 // GRP_TILES_MIN tiles on the tile screen runs, below that the chunk-splitting screen over the flattened pool.
@@ -866,7 +851,8 @@ static bool grp_tile_screen(int64_t S, int64_t tiles) {
 static bool grp_floor_default(const ScoreFloor& F) { return F.f == HBX_PDF_FLOOR_DEFAULT; }
 
 // One screen launch: the bucket's instance (grp_model picked the bucket from D alone)
-template <bool TILES, bool MASK = false>
+// (LR: the log-ratio route has no floor, so only its <.., DEFF = true, ..> instances exist)
+template <bool TILES, bool MASK = false, bool LR = false>
 static void grp_launch_screen(GrpArgs& A, hipStream_t s) {
   const int nw = A.M.D <= 32 ? 4 : 2;  // waves of the bucket's instance
   A.slabs = (A.tiles + nw - 1) / nw;  // the tile screen: one tile per wave
@@ -874,15 +860,15 @@ static void grp_launch_screen(GrpArgs& A, hipStream_t s) {
 #define GRP_LAUNCH_F(DCP, DUP, NW, DT, DEFF)                                                                  \
   do {                                                                                                        \
     if (TILES)                                                                                                \
-      hipLaunchKernelGGL((groups_tiles_kernel<DCP, DUP, NW, DT, DEFF, MASK>), grid, dim3(64 * NW), 0, s, A);  \
-    else                                                                                                      \
-      hipLaunchKernelGGL((groups_screen_kernel<DCP, DUP, NW, DT, DEFF, MASK>), grid, dim3(64 * NW), 0, s, A); \
+      hipLaunchKernelGGL((groups_tiles_kernel<DCP, DUP, NW, DT, DEFF, MASK, LR>), grid, dim3(64 * NW), 0, s, A);  \
+    else                                                                                                          \
+      hipLaunchKernelGGL((groups_screen_kernel<DCP, DUP, NW, DT, DEFF, MASK, LR>), grid, dim3(64 * NW), 0, s, A); \
   } while (0)
-#define GRP_LAUNCH(DCP, DUP, NW, DT)       \
-  do {                                     \
-    if (grp_floor_default(A.F))            \
-      GRP_LAUNCH_F(DCP, DUP, NW, DT, true); \
-    else                                   \
+#define GRP_LAUNCH(DCP, DUP, NW, DT)         \
+  do {                                       \
+    if (LR || grp_floor_default(A.F))        \
+      GRP_LAUNCH_F(DCP, DUP, NW, DT, true);  \
+    else if constexpr (!LR)                  \
       GRP_LAUNCH_F(DCP, DUP, NW, DT, false); \
   } while (0)
   GRP_BUCKET_LAUNCH(A.M.D, GRP_LAUNCH);
@@ -920,7 +906,9 @@ static int grp_rules_floor(const char* who, const hbx_rules* rules, ScoreFloor* 
 
 // MASK: hbx_kde_acquire_groups_batch_m -- the same checks, the same choice of screen (from the dense S and tile count:
 // the host does not see the mask), the kernels' masked instances, the counters in the workspace's head zeroed first
-template <bool MASK = false>
+// LR: hbx_kde_acquire_groups_batch_lr -- MASK's checks and counters (eight of the head's words here), the screens'
+// <.., LR = true> instances under the same choice, and groups_select_lr_kernel (hbx_groups_lr.hip) as the select
+template <bool MASK = false, bool LR = false>
 static int grp_acquire(const char* who, const GrpModel& M, const hbx_rules* rules, const double* cand, int64_t S,
                        int64_t C, void* results, void* workspace, int64_t ws_bytes, void* stream,
                        const uint8_t* want = nullptr) {
@@ -938,7 +926,7 @@ static int grp_acquire(const char* who, const GrpModel& M, const hbx_rules* rule
   hipStream_t s = (hipStream_t)stream;
   if (C == 0) {  // nothing to score: every record is the empty one
     hipLaunchKernelGGL(groups_empty_kernel, dim3((unsigned)((B * S + 255) / 256)), dim3(256), 0, s, (AcqResult*)results,
-                       B * S, want);
+                       B * S, want, LR ? HBX_ACQ_LOG_RATIO : 0);
     HBX_LAUNCH_CHECK();
     return HBX_OK;
   }
@@ -952,15 +940,18 @@ static int grp_acquire(const char* who, const GrpModel& M, const hbx_rules* rule
   if constexpr (MASK) {
     A.want = want;
     A.stats = (unsigned long long*)workspace;
-    HBX_HIP(hipMemsetAsync(workspace, 0, 4 * sizeof(unsigned long long), s));
+    HBX_HIP(hipMemsetAsync(workspace, 0, (LR ? 8 : 4) * sizeof(unsigned long long), s));
   }
   if (grp_tile_screen(S, A.tiles))
-    grp_launch_screen<true, MASK>(A, s);
+    grp_launch_screen<true, MASK, LR>(A, s);
   else
-    grp_launch_screen<false, MASK>(A, s);
+    grp_launch_screen<false, MASK, LR>(A, s);
   HBX_LAUNCH_CHECK();
-  hipLaunchKernelGGL((grp_floor_default(F) ? groups_select_kernel<true, MASK> : groups_select_kernel<false, MASK>),
-                     dim3((unsigned)(B * S)), dim3(GRP_SEL_THREADS), 0, s, A);
+  if constexpr (LR)
+    grp_launch_select_lr(A, want != nullptr, s);
+  else
+    hipLaunchKernelGGL((grp_floor_default(F) ? groups_select_kernel<true, MASK> : groups_select_kernel<false, MASK>),
+                       dim3((unsigned)(B * S)), dim3(GRP_SEL_THREADS), 0, s, A);
   HBX_LAUNCH_CHECK();
   return HBX_OK;
 }
@@ -1056,6 +1047,18 @@ int hbx_kde_acquire_groups_batch_m(const double* X, int32_t D, const int64_t* se
                            grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good,
                                      nlev_bad),
                            rules, cand, S, C, results, workspace, ws_bytes, stream, want);
+}
+
+int hbx_kde_acquire_groups_batch_lr(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                    const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                    const double* bw_good, const double* bw_bad, const int32_t* nlev_good,
+                                    const int32_t* nlev_bad, const double* cand, int64_t S, int64_t C,
+                                    const uint8_t* want, void* results, void* workspace, int64_t ws_bytes,
+                                    void* stream) {
+  return grp_acquire<true, true>("hbx_kde_acquire_groups_batch_lr",
+                                 grp_model(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good,
+                                           nlev_bad),
+                                 nullptr, cand, S, C, results, workspace, ws_bytes, stream, want);
 }
 
 // the masked acquisition's counters (the workspace's head): synchronises the device

@@ -34,6 +34,9 @@
 // hbx_kde_random_requests_groups writes want and not (u_q < random_fraction), the requests a model has to answer: rule 1
 // comes before the rules that read the pool, so hbx_kde_propose_groups_m with HBX_PROPOSE_SKIP_RANDOM samples and
 // scores under that mask, finishes under `want`, and returns the rows and sources of the call without the flag.
+//
+// hbx_kde_propose_groups_lr is hbx_kde_propose_groups_m with hbx_kde_acquire_groups_batch_lr in the middle (the pick by
+// ln g - ln l, hbx_groups_lr.hip) and no rules: the two share cfg_propose_m.
 #include "hbx_common.h"
 #include "hbx_groups_impl.h"  // grp_counts_ok
 #include "hbx_philox.h"
@@ -277,14 +280,17 @@ int64_t hbx_kde_propose_groups_m_workspace_bytes(int64_t B, int64_t S, int64_t C
   return hbx_kde_propose_groups_m_ws_offsets(B, S, C, D, off) == HBX_OK ? off[4] : -1;
 }
 
-int hbx_kde_propose_groups_m(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
-                             const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype, const double* bw_good,
-                             const double* bw_bad, const int32_t* nlev_good, const int32_t* nlev_bad,
-                             const int32_t* levels, double bandwidth_factor, double random_fraction, uint64_t seed,
-                             uint64_t counter_base, uint32_t stream_id, int64_t S, int64_t C, const uint8_t* want,
-                             int32_t flags, double* rows_out, uint8_t* source_out, void* records_out, double* cands_out,
-                             void* workspace, int64_t workspace_bytes, void* stream, const hbx_rules* rules) {
-  const char* who = "hbx_kde_propose_groups_m";
+}  // extern "C"
+
+// hbx_kde_propose_groups_m and hbx_kde_propose_groups_lr: the masked composition, with the floored acquisition under
+// `rules` or (lr) the log-ratio one in the middle
+static int cfg_propose_m(const char* who, bool lr, const double* X, int32_t D, const int64_t* seg_off, int64_t B,
+                         const int64_t* order, const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                         const double* bw_good, const double* bw_bad, const int32_t* nlev_good, const int32_t* nlev_bad,
+                         const int32_t* levels, double bandwidth_factor, double random_fraction, uint64_t seed,
+                         uint64_t counter_base, uint32_t stream_id, int64_t S, int64_t C, const uint8_t* want,
+                         int32_t flags, double* rows_out, uint8_t* source_out, void* records_out, double* cands_out,
+                         void* workspace, int64_t workspace_bytes, void* stream, const hbx_rules* rules) {
   if (const int rrc = hbx_rules_check(who, rules)) return rrc;
   if (flags & ~HBX_PROPOSE_SKIP_RANDOM) return hbx_fail(HBX_ERR_ARG, "%s: flags=%d", who, flags);
   const int rc = cfg_check(who, D, B, S, C, random_fraction, levels, rows_out, source_out);
@@ -314,13 +320,43 @@ int hbx_kde_propose_groups_m(const double* X, int32_t D, const int64_t* seg_off,
   int r = hbx_kde_sample_groups_m(X, D, seg_off, B, order, n_good, bw_good, levels, bandwidth_factor, seed, counter_base,
                                   stream_id, S, C, eff, pool, err, stream);
   if (r != HBX_OK) return r;
-  r = hbx_kde_acquire_groups_batch_m(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good,
-                                     nlev_bad, pool, S, C, eff, rec, workspace, off[0], stream, rules);
+  r = lr ? hbx_kde_acquire_groups_batch_lr(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good,
+                                           nlev_bad, pool, S, C, eff, rec, workspace, off[0], stream)
+         : hbx_kde_acquire_groups_batch_m(X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad, nlev_good,
+                                          nlev_bad, pool, S, C, eff, rec, workspace, off[0], stream, rules);
   if (r != HBX_OK) return r;
   return want ? hbx_kde_finish_groups_m(rec, pool, err, levels, D, B, S, C, random_fraction, seed, counter_base,
                                         stream_id, want, rows_out, source_out, stream)
               : hbx_kde_finish_groups(rec, pool, err, levels, D, B, S, C, random_fraction, seed, counter_base,
                                       stream_id, rows_out, source_out, stream);
+}
+
+extern "C" {
+
+int hbx_kde_propose_groups_m(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                             const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype, const double* bw_good,
+                             const double* bw_bad, const int32_t* nlev_good, const int32_t* nlev_bad,
+                             const int32_t* levels, double bandwidth_factor, double random_fraction, uint64_t seed,
+                             uint64_t counter_base, uint32_t stream_id, int64_t S, int64_t C, const uint8_t* want,
+                             int32_t flags, double* rows_out, uint8_t* source_out, void* records_out, double* cands_out,
+                             void* workspace, int64_t workspace_bytes, void* stream, const hbx_rules* rules) {
+  return cfg_propose_m("hbx_kde_propose_groups_m", false, X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad,
+                       nlev_good, nlev_bad, levels, bandwidth_factor, random_fraction, seed, counter_base, stream_id, S, C,
+                       want, flags, rows_out, source_out, records_out, cands_out, workspace, workspace_bytes, stream,
+                       rules);
+}
+
+int hbx_kde_propose_groups_lr(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                              const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype, const double* bw_good,
+                              const double* bw_bad, const int32_t* nlev_good, const int32_t* nlev_bad,
+                              const int32_t* levels, double bandwidth_factor, double random_fraction, uint64_t seed,
+                              uint64_t counter_base, uint32_t stream_id, int64_t S, int64_t C, const uint8_t* want,
+                              int32_t flags, double* rows_out, uint8_t* source_out, void* records_out, double* cands_out,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+  return cfg_propose_m("hbx_kde_propose_groups_lr", true, X, D, seg_off, B, order, n_good, n_bad, vartype, bw_good, bw_bad,
+                       nlev_good, nlev_bad, levels, bandwidth_factor, random_fraction, seed, counter_base, stream_id, S, C,
+                       want, flags, rows_out, source_out, records_out, cands_out, workspace, workspace_bytes, stream,
+                       nullptr);
 }
 
 }  // extern "C"

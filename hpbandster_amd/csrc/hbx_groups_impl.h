@@ -12,6 +12,7 @@
 //   grp_pair_t                 the pair exponent t (and the parity of a signed term) for one staged row
 //   grp_pairs, GRP_PAIRS_DISPATCH   the screens' running log-sum-exp over a chunk; the dispatch over the piece counts
 //   grp_estimate, grp_emit, grp_uncertified   sums -> KdeEst with its bound -> GScreen
+//   grp_ln_interval, grp_emit_lr    the log-ratio route's record: the unfloored interval of ln g - ln l, GS_NAN
 //   GrpView, grp_view          the per-group parameter view of the exact functions
 //   grp_compact, grp_exact_both     a 256-candidate chunk's shortlist; both exact pdfs of one entry
 //   grp_counts_ok, grp_check_dim, grp_model_null, grp_model_misaligned    the host checks
@@ -603,6 +604,110 @@ __device__ __forceinline__ GScreen grp_emit(int D, int st, bool certified, const
                   1.000001);
   g.fl = (v.one ? GS_ONE : 0u) | (v.of ? GS_OF : 0u) | ((v.lnan || v.slo != v.slo || v.shi != v.shi) ? GS_FORCE : 0u);
   return g;
+}
+
+// ---- the log-ratio route's record ----------------------------------------------------------------------------
+#define GS_NAN 16u  // log-ratio route: l or g certainly negative, so s = ln g - ln l is NaN: never picked, not re-scored
+
+// fp64 -> fp32 rounded towards -inf / +inf: the cast rounds to nearest, so where it came out on the wrong side of v
+// it is moved one step along hbx_f2ord's order (monotonic over all floats, the sign change and the infinities included)
+__device__ __forceinline__ float grp_f32_down(double v) {
+  const float f = (float)v;
+  return (double)f > v ? hbx_ord2f(hbx_f2ord(f) - 1u) : f;
+}
+__device__ __forceinline__ float grp_f32_up(double v) {
+  const float f = (float)v;
+  return (double)f < v ? hbx_ord2f(hbx_f2ord(f) + 1u) : f;
+}
+
+// The interval of ln P, P = S+ - S- the signed sum of one KDE, from its estimate {lpos = ln S+, lneg = ln S-, e = err}
+// (both with the normaliser added, rounded to fp32).  The screens' bound says each true sum lies within a factor
+// (1 +- e) of the estimated one, so
+//     P in [S+ (1 - e) - S- (1 + e),  S+ (1 + e) - S- (1 - e)].
+// The estimate holds no linear-domain value (the running maximum is an integer exponent, the sums were turned into
+// logs), so both ends are formed in the log domain, in fp64, around the larger of the two logs, hi:
+//     r = exp(lo - hi) <= 1 (the smaller sum over the larger),
+//     ln |P|_hi = hi + log1p(+e - r_lo (1 - e)),      ln |P|_lo = hi + log1p(-e - r_hi (1 + e))   (argument > -1),
+// and the sign of P is that of the larger sum when the lower end exists, unknown otherwise.  Without negative terms
+// (lneg = -inf) r = 0: ln P in [lpos + log1p(-e), lpos + log1p(e)].
+// What the fp32 logs lost, put back outward:
+//   - lpos and lneg were rounded to fp32 once, each off by at most 2^-24 |value|.  r therefore carries a factor within
+//     exp(+-dd), dd = 2^-23 (|lpos| + |lneg|) + 2^-40 (twice the roundings: the fp64 subtraction and exp sit in the
+//     other half); r_lo = r (1 - dd) <= r exp(-dd) and r_hi = r (1 + 1.02 dd) >= r exp(dd) for dd <= 0.03 -- a
+//     candidate with a larger dd is not certified.
+//   - the base hi is off by the same rounding: sl = 2^-23 |hi| + 2^-20 is taken from the lower end and added to the
+//     upper one; the 2^-20 (1e-6) covers the fp64 evaluation of log1p and exp, the normaliser's fp64 roundings and the
+//     difference between the true pdf and the exact re-score's value (grp_exact_rel, 1e-13), with four decimal orders
+//     to spare.
+// `neg`: the KDE has a negative match factor.  Its exact value is ln of the linear fp64 pdf as it is, so a bound is
+// only worth something while that pdf is a normal number: below ln p = -700 the candidate is not certified.  (Without
+// a negative factor the re-score takes the log-space value there, which the bound does cover.)  Above +700 nothing is
+// certified either.
+// Returns sg: +1 P certainly positive, ln P in [lo, hi]; 0 the interval holds 0, ln max(P, 0) <= hi; -1 P certainly
+// negative and far from underflow; 2 not usable.
+struct GrpLnIv {
+  double lo, hi;
+  int sg;
+};
+__device__ __forceinline__ GrpLnIv grp_ln_interval(const KdeEst e, bool neg) {
+  GrpLnIv v;
+  v.lo = v.hi = NAN;
+  v.sg = 2;
+  const double lp = (double)e.lpos, ln = (double)e.lneg, er = (double)e.err;
+  if (!(lp == lp) || !(ln == ln) || !(er >= 0.0 && er < 0.9)) return v;
+  const double hi = fmax(lp, ln), lo = fmin(lp, ln);
+  if (!(hi > -INFINITY && hi < INFINITY)) return v;  // (no term at all, or an overflow)
+  const double dd = 0x1p-23 * (fabs(lp) + (ln > -INFINITY ? fabs(ln) : 0.0)) + 0x1p-40;
+  if (!(dd <= 0.03)) return v;
+  const double r = lo > -INFINITY ? exp(lo - hi) : 0.0;
+  const double sl = 0x1p-23 * fabs(hi) + 0x1p-20;
+  const double ahi = er - r * (1.0 - dd) * (1.0 - er), alo = -er - r * (1.0 + 1.02 * dd) * (1.0 + er);
+  const double mhi = hi + log1p(ahi) + sl;
+  const double mlo = alo > -1.0 + 0x1p-40 ? hi + log1p(alo) - sl : -INFINITY;
+  if (!(mhi < 700.0)) return v;
+  if (mlo == -INFINITY) {  // the sign is open: usable (as "may be 0") only where the positive sum is the larger one
+    if (lp < ln) return v;
+    v.sg = 0;
+    v.lo = -INFINITY;
+    v.hi = mhi;
+    return v;
+  }
+  if (lp < ln) {  // certainly negative -- NaN by definition, provided the exact pdf cannot underflow to -0
+    if (mlo > -700.0) v.sg = -1;
+    return v;
+  }
+  if (neg && !(mlo > -700.0)) return v;
+  v.sg = 1;
+  v.lo = mlo;
+  v.hi = mhi;
+  return v;
+}
+
+// Both estimates -> the interval of s = ln g - ln l with no floor -> the candidate's slot (the screens' <.., LR = true>
+// instances).  slo = ln g_lo - ln l_hi, shi = ln g_hi - ln l_lo in fp64 from grp_ln_interval's ends; the subtraction's
+// own rounding (2^-53 relative) is inside the ends' 2^-20, and the narrowing to fp32 is made outward (grp_f32_down /
+// grp_f32_up), so where both signs are certain [slo, shi] holds the re-score's s.  An l that may be 0 or is not usable:
+// GS_FORCE, always re-scored.  An l or g that is certainly negative: GS_NAN, never picked and not re-scored.  A g whose
+// interval holds 0 may as well be negative, and then s is NaN and the candidate cannot be picked: [slo, shi] =
+// [-inf, +inf] -- always listed (if g >= 0 it may win), and its upper end never lowers the select's U = min shi, which
+// would discard candidates on behalf of one that may have no score.  There is no floor on this route, hence no GS_ONE
+// and no GS_OF.
+__device__ __forceinline__ GScreen grp_emit_lr(int D, int st, bool certified, const KdeEst& est_l, const KdeEst& est_g) {
+  if (!certified) return grp_uncertified(D, st);
+  const GrpLnIv l = grp_ln_interval(est_l, st & GRP_NEG(0)), g = grp_ln_interval(est_g, st & GRP_NEG(1));
+  if (l.sg == 2 || g.sg == 2 || l.sg == 0) return grp_uncertified(D, st);
+  GScreen o;
+  o.rel = (float)((grp_exact_rel(D, st & GRP_NEG(0), &est_l) + grp_exact_rel(D, st & GRP_NEG(1), &est_g) + 0x1p-51) *
+                  1.000001);
+  if (l.sg < 0 || g.sg < 0) {
+    o.slo = o.shi = NAN;
+    o.fl = GS_NAN;
+    return o;
+  }
+  o.slo = g.sg == 0 ? -INFINITY : grp_f32_down(g.lo - l.hi);
+  o.shi = g.sg == 0 ? INFINITY : grp_f32_up(g.hi - l.lo);  // (g may be negative: s may be NaN, nothing bounds it above)
+  o.fl = 0u;
+  return o;
 }
 
 // ---- the exact re-score ------------------------------------------------------------------------------------

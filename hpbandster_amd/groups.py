@@ -180,6 +180,7 @@ class GroupTopK(object):
 SOURCE_MODEL, SOURCE_RANDOM_FRACTION, SOURCE_NO_MODEL, SOURCE_NO_SCORE, SOURCE_DOMAIN_ERR = 0, 1, 2, 3, 4  # HBX_CFG_*
 SOURCE_SKIPPED = 5           # HBX_CFG_SKIPPED: the request mask left the request out (its row is NaN)
 ACQ_SKIPPED = 64             # include/hbx.h HBX_ACQ_SKIPPED: the record of such a request
+ACQ_LOG_RATIO = 128          # include/hbx.h HBX_ACQ_LOG_RATIO: the record's score is ln g - ln l (score="log_ratio")
 PROPOSE_SKIP_RANDOM = 1      # include/hbx.h HBX_PROPOSE_SKIP_RANDOM
 
 
@@ -370,6 +371,12 @@ RANK_MAX_K = 1024  # include/hbx.h HBX_RANK_MAX_K
 RANK_HEAD_BYTES = 16
 RANK_REC = np.dtype([("index", "<i4"), ("pad", "<i4"), ("score", "<f8"), ("ln_l", "<f8"), ("ln_g", "<f8")])
 SCORES = ("ratio", "log_ratio")  # propose's rankings: the reference's floored ratio, or ln g - ln l with no floor
+
+
+def _check_score(score):
+    if score not in SCORES:
+        raise ValueError("score must be one of %r, got %r" % (SCORES, score))
+    return score
 
 
 def _rank_k(k, C):
@@ -648,10 +655,10 @@ class GroupModel(object):
             raise N.HbxError("workspace too small")
         return ws
 
-    def _acquire(self, cd, S, C, stream, workspace, sync, want=None):
+    def _acquire(self, cd, S, C, stream, workspace, sync, want=None, score="ratio"):
         """``acquire`` (``S`` None) and ``acquire_requests`` over the staged pool ``cd``, inside the caller's
         on_device context: the one-request entry point for ``S`` None under the default floor, the batched one
-        otherwise; records [B, 48] or [B, S, 48]."""
+        otherwise; records [B, 48] or [B, S, 48].  ``score="log_ratio"``: hbx_kde_acquire_groups_batch_lr."""
         torch = kde._torch()
         Sn = 1 if S is None else S
         sizes = "B * C = %d * %d" % (self.B, C) if S is None else "B * S * C = %d * %d * %d" % (self.B, S, C)
@@ -660,7 +667,9 @@ class GroupModel(object):
                           dtype=torch.uint8, device=self.device)
         model = self.model_args() + (N.ptr(cd),)
         tail = (N.ptr(res), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device))
-        if want is not None:
+        if score == "log_ratio":
+            N.check(N.lib().hbx_kde_acquire_groups_batch_lr(*(model + (Sn, C, N.ptr(want)) + tail)))
+        elif want is not None:
             N.check(N.lib().hbx_kde_acquire_groups_batch_m(*(model + (Sn, C, N.ptr(want)) + tail + (
                 None if self._rules is None else ctypes.addressof(self._rules),))))
         elif S is None and self._rules is None:
@@ -680,18 +689,23 @@ class GroupModel(object):
             cd = self._stage_cands(cands, (3,))
             return self._acquire(cd, None, int(cd.shape[1]), stream, workspace, sync)
 
-    def acquire_requests(self, cands, stream=None, workspace=None, sync=True, want=None):
+    def acquire_requests(self, cands, stream=None, workspace=None, sync=True, want=None, score="ratio"):
         """S get_config requests per group in one call (hbx_kde_acquire_groups_batch; HB_iteration.py:136-138 issues
         a stage's requests back to back against one model): request (b, s) is ``acquire`` for group b over its own
         pool ``cands[b, s]`` and sees no other request.  ``cands``: [B, S, C, D] float64, numpy or a device tensor.
         Returns GroupPicks with arrays of shape [B, S], or with ``sync=False`` the device tensor of the records
         (uint8 [B, S, 48]).  ``want`` (request_mask's forms): hbx_kde_acquire_groups_batch_m -- the wanted requests'
         records are the same bytes, the others get the empty record with ACQ_SKIPPED and their pools are not read;
-        ``request_stats(workspace)`` then says what was computed."""
+        ``request_stats(workspace)`` then says what was computed.
+        ``score="log_ratio"`` (hbx_kde_acquire_groups_batch_lr): the pick is the first index minimising
+        ``ln g - ln l`` with no floor -- what still orders the candidates where both densities lie under ``pdf_floor``
+        and the floored score is 1 for all of them.  The records keep their layout: ``score`` is that difference,
+        ``pdf_l`` / ``pdf_g`` the winner's exact pdfs, flags carry ACQ_LOG_RATIO; with or without ``want``."""
+        _check_score(score)
         with N.on_device(self.device, stream):
             cd = self._stage_cands(cands, (4,))
             wd = request_mask(want, self.B, int(cd.shape[1]), self.device)
-            return self._acquire(cd, int(cd.shape[1]), int(cd.shape[2]), stream, workspace, sync, wd)
+            return self._acquire(cd, int(cd.shape[1]), int(cd.shape[2]), stream, workspace, sync, wd, score)
 
     def request_stats(self, workspace):
         """The counters of the last masked acquisition that used ``workspace`` (``acquire_requests(want=...)``, or
@@ -811,8 +825,9 @@ class GroupModel(object):
         return int(N.lib().hbx_kde_propose_groups_workspace_bytes(self.B, int(requests), int(C), self.D))
 
     def _get_config_m(self, C, S, requests, seed, levels, rf, bandwidth_factor, counter_base, stream, stream_id,
-                      workspace, sync, keep_pools, records, want, skip_random):
-        """get_config under a request mask and / or skip_random: one hbx_kde_propose_groups_m call"""
+                      workspace, sync, keep_pools, records, want, skip_random, score="ratio"):
+        """get_config under a request mask and / or skip_random: one hbx_kde_propose_groups_m call; with
+        ``score="log_ratio"``, masked or not: one hbx_kde_propose_groups_lr call"""
         torch = kde._torch()
         with N.on_device(self.device, stream):
             wd = request_mask(want, self.B, S, self.device)
@@ -826,11 +841,14 @@ class GroupModel(object):
             # (the pools of unanswered requests are not written: NaN rather than what the allocation held)
             cands = torch.full((self.B, S, C, self.D), float("nan"), dtype=torch.float64, device=self.device) \
                 if keep_pools else None
-            N.check(N.lib().hbx_kde_propose_groups_m(*(
-                self.model_args() + (N.ptr(lvd), float(bandwidth_factor), rf) + _philox(seed, counter_base, stream_id) +
-                (S, C, N.ptr(wd), PROPOSE_SKIP_RANDOM if skip_random else 0, N.ptr(rows), N.ptr(source), N.ptr(rec),
-                 N.ptr(cands), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device),
-                 None if self._rules is None else ctypes.addressof(self._rules)))))
+            args = self.model_args() + (N.ptr(lvd), float(bandwidth_factor), rf) + _philox(seed, counter_base, stream_id) + (
+                S, C, N.ptr(wd), PROPOSE_SKIP_RANDOM if skip_random else 0, N.ptr(rows), N.ptr(source), N.ptr(rec),
+                N.ptr(cands), N.ptr(ws), ws.numel(), N.stream_handle(stream, self.device))
+            if score == "log_ratio":  # (no floor on this route: no rules)
+                N.check(N.lib().hbx_kde_propose_groups_lr(*args))
+            else:
+                N.check(N.lib().hbx_kde_propose_groups_m(*(
+                    args + (None if self._rules is None else ctypes.addressof(self._rules),))))
             err = None
             if keep_pools:
                 off = np.zeros(5, dtype=np.int64)
@@ -842,7 +860,7 @@ class GroupModel(object):
 
     def get_config(self, C, seed, levels, requests=None, random_fraction=1.0 / 3, bandwidth_factor=3, counter_base=0,
                    stream=None, stream_id=0, workspace=None, sync=True, keep_pools=False, records=True, want=None,
-                   skip_random=False):
+                   skip_random=False, score="ratio"):
         """The reference's get_config (bohb.py:104-169) for ``requests`` requests of every group in one call
         (hbx_kde_propose_groups: ``sample`` with pool size S * C, ``acquire_requests`` and ``finish`` on one stream):
         always a configuration -- the best of the request's C candidates, or a prior draw where the group has no
@@ -857,14 +875,20 @@ class GroupModel(object):
         the bytes of the call without a mask; the others come back as SOURCE_SKIPPED with a NaN row and an ACQ_SKIPPED
         record.  ``skip_random``: requests that the random fraction takes are not sampled and scored either -- rows
         and sources are unchanged, their records are skipped ones and their pools are not written (NaN with
-        ``keep_pools``).  ``request_stats(workspace)`` reports what was computed."""
+        ``keep_pools``).  ``request_stats(workspace)`` reports what was computed.
+
+        ``score="log_ratio"``: the best candidate is the first index minimising ``ln g - ln l`` with no floor
+        (``acquire_requests``' route of that name) instead of the floored ratio, which is 1 for nearly every candidate
+        once both densities lie under ``pdf_floor`` and then picks candidate 0.  One hbx_kde_propose_groups_lr call,
+        with or without a mask and ``skip_random``; the sampler, the fall-backs and the workspace
+        (``workspace_bytes_get_config(masked=True)``) are the masked call's."""
         torch = kde._torch()
         S = 1 if requests is None else int(requests)
         C = int(C)
         rf = _fraction(random_fraction)
-        if want is not None or skip_random:
+        if _check_score(score) == "log_ratio" or want is not None or skip_random:
             return self._get_config_m(C, S, requests, seed, levels, rf, bandwidth_factor, counter_base, stream,
-                                      stream_id, workspace, sync, keep_pools, records, want, bool(skip_random))
+                                      stream_id, workspace, sync, keep_pools, records, want, bool(skip_random), score)
         with N.on_device(self.device, stream):
             ws = self._workspace(workspace, self.workspace_bytes_get_config(C, S),
                                  "get_config: B=%d S=%d C=%d out of range (C >= 1, B * S * C within int32)" %
@@ -1136,6 +1160,9 @@ class GroupBOHB(object):
     that budget's device store; ``kde_models`` maps budget -> GroupModel.  ``var_type``: the KDE's kinds ('c' / 'u'
     per dim), ``levels``: D level counts (0: continuous).  ``bw_estimation``: every refit's bandwidth rule,
     "normal_reference" (the reference's) or "cv_ml" (fit_groups' ``bw``: searched on the device, at most 32 dims).
+    ``score``: what picks a request's best candidate, "ratio" (the reference's floored score) or "log_ratio"
+    (``ln g - ln l`` with no floor, GroupModel.get_config's route: it still tells candidates apart where both densities
+    lie under the floor and "ratio" returns the first one drawn).
 
     Conditional search spaces: with ``impute_seed`` the reported rows may hold NaN at inactive dims, and every refit
     imputes them (fit_groups) on a counter block of its own -- ``impute_counter``, which advances by the view's row
@@ -1146,8 +1173,9 @@ class GroupBOHB(object):
     def __init__(self, B, var_type, levels, min_points_in_model=None, top_n_percent=15, num_samples=64,
                  random_fraction=1.0 / 3, bandwidth_factor=3, seed=0, device=None, min_bandwidth=None,
                  pdf_floor=N.PDF_FLOOR_DEFAULT, impute_seed=None, conditions=None, skip_random=False,
-                 bw_estimation="normal_reference"):
+                 bw_estimation="normal_reference", score="ratio"):
         self.B, self.var_type, self.D = int(B), var_type, len(var_type)
+        self.score = _check_score(score)  # every get_configs' acquisition (GroupModel.get_config's ``score``)
         self.bw_estimation = _bw_rule(bw_estimation)  # every refit's bandwidth rule (fit_groups' ``bw``)
         if not isinstance(skip_random, (bool, np.bool_)):
             raise ValueError("skip_random must be a bool, got %r" % (skip_random,))
@@ -1266,7 +1294,7 @@ class GroupBOHB(object):
             gm = self.kde_models[max(self.kde_models.keys())]
             cfg = gm.get_config(self.num_samples, self.seed, self._levels(), requests=S,
                                 random_fraction=self.random_fraction, bandwidth_factor=self.bandwidth_factor,
-                                counter_base=counter_base, sync=dsync, want=want, skip_random=skip)
+                                counter_base=counter_base, sync=dsync, want=want, skip_random=skip, score=self.score)
         if self.conditions is None:
             return cfg
         if self._cond_dev is None:

@@ -602,6 +602,45 @@ int hbx_kde_propose_groups_m(const double* X, int32_t D, const int64_t* seg_off,
                              double* rows_out, uint8_t* source_out, void* records_out, double* cands_out,
                              void* workspace, int64_t workspace_bytes, void* stream, const hbx_rules* rules);
 
+/* ---- grouped acquisition by log ratio --------------------------------------------------------
+ * The floored score max(f, g) / max(l, f) is exactly 1 wherever both densities lie under the floor, and the strict
+ * argmin then returns candidate 0.  These two calls pick by s = ln g(x) - ln l(x) instead, with no floor: per request
+ * the first index minimising s.  They are acquisitions -- a screen, a shortlist, an exact re-score -- not ln-pdfs of
+ * every candidate followed by a ranking.
+ *
+ * hbx_kde_acquire_groups_batch_lr: hbx_kde_acquire_groups_batch_m's arguments and checks without `rules` (want may be
+ *   NULL; the same workspace, hbx_kde_groups_batch_workspace_bytes; the same choice of screen; the same four counters
+ *   for hbx_kde_groups_request_stats; C == 0: empty records).  Every shortlisted candidate gets both exact fp64 pdfs,
+ *   the reference's values bit for bit, and per KDE k
+ *       L_k = log(p_k)   p_k a positive normal number;    NaN   p_k negative or NaN;
+ *       L_k = ln p_k evaluated in fp64 log space          p_k zero or subnormal, no categorical bandwidth > 1 in KDE k
+ *             (within (D + 2) 2^-53 max|t| + (n_k + 256) 2^-52 of the true value, t the pairs' exponents);
+ *       L_k = log(p_k) as it is (-inf for 0)              p_k zero or subnormal otherwise.
+ *   s = L_g - L_l.  Order: hbx_kde_rank_groups' for k = 1 -- finite and -inf values by value (-0 as +0), then +inf, NaN
+ *   never picked, equal values to the lower index.  Record (48 bytes, hbx_kde_result_ptr's layout): index (-1 when every
+ *   s is NaN), score = s, pdf_l / pdf_g the winner's exact pdfs, shortlist, near (re-scored candidates whose s lies
+ *   within the values' error bounds of the winner's; HBX_ACQ_NEAR_TIE when > 1), rel, HBX_ACQ_OVERFLOW where the whole
+ *   pool was re-scored, HBX_ACQ_NO_MODEL / HBX_ACQ_UNSUPPORTED as there, and HBX_ACQ_LOG_RATIO on every record that is
+ *   not a skipped one (the empty records of C == 0 included).
+ * hbx_kde_propose_groups_lr: hbx_kde_propose_groups_m without `rules`, with this acquisition in the middle
+ *   (hbx_kde_sample_groups_m, hbx_kde_acquire_groups_batch_lr, hbx_kde_finish_groups(_m)); want, flags
+ *   (HBX_PROPOSE_SKIP_RANDOM), the workspace and its offsets are hbx_kde_propose_groups_m's. */
+#define HBX_ACQ_LOG_RATIO 128  /* the record was picked by ln g - ln l (the next free bit after HBX_ACQ_SKIPPED) */
+int hbx_kde_acquire_groups_batch_lr(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                                    const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                                    const double* bw_good, const double* bw_bad,
+                                    const int32_t* nlev_good, const int32_t* nlev_bad,
+                                    const double* cand, int64_t S, int64_t C, const uint8_t* want, void* results,
+                                    void* workspace, int64_t ws_bytes, void* stream);
+int hbx_kde_propose_groups_lr(const double* X, int32_t D, const int64_t* seg_off, int64_t B, const int64_t* order,
+                              const int64_t* n_good, const int64_t* n_bad, const int32_t* vartype,
+                              const double* bw_good, const double* bw_bad,
+                              const int32_t* nlev_good, const int32_t* nlev_bad, const int32_t* levels,
+                              double bandwidth_factor, double random_fraction, uint64_t seed, uint64_t counter_base,
+                              uint32_t stream_id, int64_t S, int64_t C, const uint8_t* want, int32_t flags,
+                              double* rows_out, uint8_t* source_out, void* records_out, double* cands_out,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- conditional search spaces ---------------------------------------------------------------
  * An observation of a conditional space holds NaN where a hyperparameter is inactive.  Released hpbandster imputes
  * such entries before the KDEs are fitted (impute_conditional_data, a rule added after the reference snapshot);

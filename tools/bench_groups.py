@@ -46,6 +46,12 @@ profiles/groups_logpdf_signed/bench_{logpdf,rank}_signed.json.
 times the grouped get_config (get_config_bench below): hbx_kde_propose_groups against its parts and against
 propose(requests=S) plus a host prior fill; writes profiles/groups_get_config/bench_groups_get_config.json.
 
+    python tools/bench_groups.py --get-config --score log_ratio [--out FILE]
+
+times the get_config that picks by ln g - ln l (get_config_lr_bench below): hbx_kde_propose_groups_lr at S = 1 and 4
+against the sampler plus hbx_kde_rank_logratio_groups (k = 1) under both signed routes, taking turns; writes
+profiles/groups_lr/bench_groups_lr.json.
+
     python tools/bench_groups.py --sh [--sh-max-budget 729] [--fills needed] [--out FILE]
 
 times the grouped successive-halving transition (sh_bench below): hbx_sh_advance_groups alone against the sync-free
@@ -391,6 +397,62 @@ def each_timed(fn, reps, warm=3):
     torch.cuda.synchronize()
     ms = [e0.elapsed_time(e1) for e0, e1 in ev]
     return {"ms_mean": float(np.mean(ms)), "ms_min": float(np.min(ms)), "ms_max": float(np.max(ms))}
+
+
+def get_config_lr_bench(a, gm, L, sh, lvd, levels):
+    """--get-config --score log_ratio: the grouped get_config picking by ln g - ln l (hbx_kde_propose_groups_lr: sampler,
+    log-ratio acquisition, finish) at S = 1 and S = 4 requests per bracket, taking turns in one session with the only
+    route the library had to the same picks: the sampler plus hbx_kde_rank_logratio_groups with k = 1 (what
+    propose(topk=1, score="log_ratio") runs, through GroupModel.sample / rank_logratio(sync=False), which allocate their
+    outputs per call), S = 1, signed="exact" and "logspace".
+    Two rounds of --reps warmed repetitions per run, each repetition between device events; the headline is the slowest
+    new run against the fastest parent run.  Also: the shortlists from the records, the forced candidates and the
+    log-space evaluations from the workspace head, and how many S = 1 picks equal the parent's rank-1 index."""
+    dev = gm.device
+    B, C, D, seed = gm.B, a.C, gm.D, S.SEED_CAND
+    a.out = a.out or os.path.join(ROOT, "profiles", "groups_lr", "bench_groups_lr.json")
+    model = gm.model_args()
+    new, buf = {}, {}
+    for R in (1, 4):
+        wsm = int(L.hbx_kde_propose_groups_m_workspace_bytes(B, R, C, D))
+        buf[R] = (torch.empty(wsm, dtype=torch.uint8, device=dev), torch.empty((B, R, D), dtype=torch.float64, device=dev),
+                  torch.empty((B, R), dtype=torch.uint8, device=dev),
+                  torch.empty((B, R, kde.RESULT_BYTES), dtype=torch.uint8, device=dev))
+
+        def call(R=R, wsm=wsm):
+            ws, rows, src, rec = buf[R]
+            N.check(L.hbx_kde_propose_groups_lr(*model, N.ptr(lvd), 3.0, 1.0 / 3, seed, 0, 0, R, C, None, 0, N.ptr(rows),
+                                                N.ptr(src), N.ptr(rec), None, N.ptr(ws), wsm, sh))
+        new["lr_s%d" % R] = call
+    parent = {"parent_rank_signed_%s" % sg: (lambda sg=sg: gm.rank_logratio(gm.sample(C, seed, lvd)[0], 1, sync=False,
+                                                                            signed=sg)) for sg in groups.SIGNED_ROUTES}
+    runs = {}
+    for rnd in range(2):
+        for name, fn in list(new.items()) + list(parent.items()):
+            runs["%s_round%d" % (name, rnd)] = each_timed(fn, a.reps)
+    slow_new = max(v["ms_mean"] for k, v in runs.items() if k.startswith("lr_"))
+    fast_parent = min(v["ms_mean"] for k, v in runs.items() if k.startswith("parent_"))
+    out = {"workload": "grouped_get_config_log_ratio_b%d_n%d_d32_24c8u_c%d" % (B, a.n, C),
+           "device": torch.cuda.get_device_name(0), "reps": a.reps, "runs": runs, "slowest_new_ms": slow_new,
+           "fastest_parent_ms": fast_parent, "parent_over_new": fast_parent / slow_new}
+    for R in (1, 4):
+        ws, rows, src, rec = buf[R]
+        picks = groups.GroupPicks.from_bytes(rec.cpu().numpy().tobytes(), B, R)
+        head = [int(v) for v in ws[:64].cpu().numpy().view(np.int64)]
+        out["s%d" % R] = {"mean_shortlist": float(picks.shortlist.mean()), "max_shortlist": int(picks.shortlist.max()),
+                          "rescored": head[3], "forced_share": head[5] / max(head[3], 1), "logspace_evals": head[4],
+                          "near_tie_requests": int(((picks.flags & 2) != 0).sum()),
+                          "index_not_0": int((picks.index > 0).sum()),
+                          "model_sourced": int((src.cpu().numpy() == groups.SOURCE_MODEL).sum())}
+        if R == 1:
+            top = groups.GroupRank.from_bytes(parent["parent_rank_signed_exact"]().cpu().numpy().tobytes(), B, 1)
+            out["s1"]["picks_equal_parent_rank1"] = int((top.index[:, 0] == picks.index[:, 0]).sum())
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+    return 0
 
 
 def get_config_bench(a, gm, L, sh, lvd, levels):
@@ -1008,6 +1070,8 @@ def main(argv=None):
     ap.add_argument("--logpdf", action="store_true", help="both KDEs' ln pdf of every pool (logpdf_bench)")
     ap.add_argument("--get-config", action="store_true",
                     help="a configuration per request with the reference's fall-backs (get_config_bench)")
+    ap.add_argument("--score", choices=groups.SCORES, default="ratio",
+                    help="--get-config: 'log_ratio' measures the pick by ln g - ln l (get_config_lr_bench)")
     ap.add_argument("--skip-random", action="store_true",
                     help="--get-config: also the masked call that does not sample and score random requests")
     ap.add_argument("--counts", type=int, default=0,
@@ -1045,6 +1109,8 @@ def main(argv=None):
     seg = np.arange(B + 1, dtype=np.int64) * n
     gm = groups.fit_groups(X, losses, seg, vts, device=dev)
     sh = N.stream_handle(None, dev)
+    if a.get_config and a.score == "log_ratio":
+        return get_config_lr_bench(a, gm, L, sh, torch.tensor(levels, dtype=torch.int32, device=dev), levels)
     if a.get_config:
         return get_config_bench(a, gm, L, sh, torch.tensor(levels, dtype=torch.int32, device=dev), levels)
     if a.topk:
