@@ -430,48 +430,22 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
   __shared__ int32_t slist[GRP_SEL_THREADS];
   __shared__ int32_t swc[GRP_SEL_THREADS / 64];
   __shared__ uint32_t s_U;
-  __shared__ int32_t s_st, s_of, s_first1, s_none, s_near;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ int32_t s_st, s_of, s_first1, s_none;
+  const int tid = threadIdx.x;
   const int64_t q = blockIdx.x, b = q / A.S;  // request q = b S + s of group b
   const int D = A.M.D;
   const int64_t C = A.C;
-  if (wv == 0) {
-    int dc, du;
-    const int st0 = grp_classify(A.M, b, &dc, &du);
-    if (lane == 0) s_st = st0;
-  }
   if (tid == 0) {
     s_U = hbx_f2ord(INFINITY);
     s_of = 0;
     s_first1 = INT32_MAX;
     s_none = 0;
-    s_near = 0;
   }
-  __syncthreads();
-  const int st = s_st;
-  if constexpr (MASK) {
-    if (A.want && A.want[q] == 0) {  // (uniform) the skipped record, with the group's bits as the dense call sets them
-      if (tid == 0) {
-        A.res[q] = grp_empty_record(HBX_ACQ_SKIPPED | ((st & GRP_NO_MODEL)      ? HBX_ACQ_NO_MODEL
-                                                       : (st & GRP_UNSUPPORTED) ? HBX_ACQ_UNSUPPORTED
-                                                                                : 0));
-        atomicAdd(A.stats + 1, 1ull);
-      }
-      return;
-    }
-  }
-  if (st & (GRP_NO_MODEL | GRP_UNSUPPORTED)) {
-    if (tid == 0) {
-      A.res[q] = grp_empty_record((st & GRP_NO_MODEL) ? HBX_ACQ_NO_MODEL : HBX_ACQ_UNSUPPORTED);
-      if constexpr (MASK) atomicAdd(A.stats + 0, 1ull);
-    }
-    return;
-  }
-  const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
-  const double* Xs = A.M.X + s0 * D;
-  const int64_t* rows_g = A.M.order + s0;
-  const int64_t* rows_b = A.M.order + s0 + (n - A.M.n_bad[b]);
-  if (tid < 2) vw[tid] = grp_view(A.M, b, tid);
+  int st;  // (the unmasked instances answer every request and keep no counters)
+  if (grp_select_prologue(A, q, b, MASK ? A.want : nullptr, MASK, 0, &s_st, &st)) return;
+  const double* Xs;
+  const int64_t *rows_g, *rows_b;
+  grp_rows(A.M, b, vw, &Xs, &rows_g, &rows_b);
   GScreen* scr = A.scr + q * C;
   const double* cand = A.cand + q * C * D;
   // pass 1: U = min shi over the certified candidates, the overflow rule, the first certain score 1
@@ -530,50 +504,15 @@ __global__ __launch_bounds__(GRP_SEL_THREADS) void groups_select_kernel(GrpArgs 
     }
     nshort += tot;
   }
-  // the near set: every re-scored candidate the winner cannot be told apart from by the bounds
-  __shared__ double s_best, s_rb;
-  __shared__ int64_t s_bidx;
-  if (tid == 0) {
-    s_best = best;
-    s_bidx = bidx;
-    s_rb = bidx >= 0 ? (double)scr[bidx].rel : 0.0;
-  }
-  __threadfence_block();
-  __syncthreads();  // (also: thread 0's stores to scr are visible to the block)
-  const double sb = s_best, rb = s_rb;
-  const int64_t wi = s_bidx;
-  if (wi >= 0) {
-    int cnt = 0;
-    for (int64_t i = tid; i < C; i += GRP_SEL_THREADS) {
-      const GScreen g = scr[i];
-      if (!(g.fl & GS_DONE)) continue;
-      const double s = g.score;
-      if (i == wi || near_best(s, (double)g.rel, sb, rb)) ++cnt;
-    }
-    if (cnt) atomicAdd(&s_near, cnt);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    AcqResult r = grp_empty_record(all ? HBX_ACQ_OVERFLOW : 0);
-    r.shortlist = nshort;
-    int near = s_near;
-    // the candidates left out as certain exact 1s tie with a winner whose score is 1
-    if (wi >= 0 && !all && sb == 1.0 && s_none > 1) near += s_none - 1;
-    r.near = near;
-    r.rel = (float)rb;
-    if (near > 1) r.flags |= HBX_ACQ_NEAR_TIE;
-    if (wi >= 0) {
-      r.index = wi;
-      r.score = sb;
-      r.pdf_l = bl;
-      r.pdf_g = bg;
-    }
-    A.res[q] = r;
-    if constexpr (MASK) {
+  // the candidates left out as certain exact 1s tie with a winner whose score is 1 (thread 0's best, bidx)
+  const int32_t more_near = (bidx >= 0 && !all && best == 1.0 && s_none > 1) ? s_none - 1 : 0;
+  auto near = [](double s, double rel, double sb, double rb) { return near_best(s, rel, sb, rb); };
+  grp_select_tail(A, q, scr, C, best, bidx, bl, bg, nshort, all ? HBX_ACQ_OVERFLOW : 0, more_near, near);
+  if constexpr (MASK)
+    if (tid == 0) {
       atomicAdd(A.stats + 0, 1ull);
       atomicAdd(A.stats + 3, (unsigned long long)nshort);
     }
-  }
 }
 
 // C == 0: every record is the empty one; want (nullable): the skipped record for the unwanted requests; flags: what an

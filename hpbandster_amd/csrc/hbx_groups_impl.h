@@ -16,6 +16,9 @@
 //   GrpView, grp_view          the per-group parameter view of the exact functions
 //   grp_compact, grp_exact_both     a 256-candidate chunk's shortlist; both exact pdfs of one entry
 //   grp_counts_ok, grp_check_dim, grp_model_null, grp_model_misaligned    the host checks
+// Shared one level up, by two files each: hbx_groups_acq.h -- the select kernels' frame (grp_select_prologue, grp_rows,
+// grp_select_tail) -- and hbx_groups_logpdf_impl.h -- the KDE row view and the fp64 tile passes' pieces (glp_kde,
+// glp_slots, glp_slot_consts, glp_load_cand64, glp_stage64, glp_pair_t64).
 //
 // The pair exponent, in log2 units (fp32, direct differences -- no expansion, so no cancellation):
 //     t_ij = t0 + sum_c -(a_ic - b_jc)^2 + sum_u m_iju delta_u,      a = fl(s_c (x_c - mu_c)), b = fl(s_c (X_jc - mu_c))

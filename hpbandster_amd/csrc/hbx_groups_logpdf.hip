@@ -156,22 +156,10 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
   if (st & (GLP_BAD | GLP_EXACT_BIT(kd) | GLP_SIGNED_BIT(kd))) return;  // uniform: the later kernels write these
   const int64_t i = (int64_t)tile * 64 + lane;
   const bool valid = i < A.C;
-  if (wave == 0) {
-    int dc, du;
-    grp_slots(A.M, lane, K.cdim, K.udim, &dc, &du);  // (dc <= DCP, du <= DUP: the status kernel checked the bucket)
-    if (lane == 0) {
-      s_i[0] = dc;
-      s_i[1] = du;
-    }
-  }
-  __syncthreads();
-  const int dc = s_i[0], du = s_i[1];
-  const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
-  const int64_t nk = kd ? A.M.n_bad[b] : A.M.n_good[b];
-  const double* Xs = A.M.X + s0 * D;
-  const int64_t* rows = A.M.order + s0 + (kd ? n - nk : 0);
-  const double* bw = (kd ? A.M.bw_bad : A.M.bw_good) + b * D;
-  const int32_t* nlev = (kd ? A.M.nlev_bad : A.M.nlev_good) + b * D;
+  int dc, du;
+  glp_slots(A.M, K.cdim, K.udim, s_i, &dc, &du);
+  const GlpKde V = glp_kde(A.M, b, kd);
+  const int64_t nk = V.nk;
   const GrpLayout lay = grp_layout<DCP, DUP>(D, dc, du);
   for (int e = tid; e < NT * lay.rs; e += NT) sobs[e] = 0.f;  // (the padding slots stay 0)
   for (int k = tid; k < DCP; k += NT) s_bmax[k] = 0u;
@@ -181,10 +169,10 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
   // are the fp32 chain's start and its bound, other quantities
   if (tid == 0) {
     double sl = 0.0, lbln = 0.0, sdp = 0.0, sad = 0.0;
-    for (int k = 0; k < dc; ++k) sl += log(bw[K.cdim[k]]);
+    for (int k = 0; k < dc; ++k) sl += log(V.bw[K.cdim[k]]);
     for (int u = 0; u < du; ++u) {
       const int d = K.udim[u];
-      lbln += log(bw[d] / (double)(nlev[d] - 1));
+      lbln += log(V.bw[d] / (double)(V.nlev[d] - 1));
       if (K.delta[0][u] > -1e29f) {
         sdp += fmax((double)K.delta[0][u], 0.0);
         sad += fabs((double)K.delta[0][u]);
@@ -207,7 +195,7 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
     __syncthreads();  // (the rows of the previous round are read)
     const int64_t j0 = c0 + (int64_t)wave * 64;
     const int jmax = (int)(nk - j0 < 64 ? (nk - j0 > 0 ? nk - j0 : 0) : 64);
-    if (jmax > 0) grp_stage<16>(Xs, D, rows, j0, jmax, wrows, lay.rs, lay.rpp, dc, K.doff, K.dsc[0], K.dmu, s_bmax, lane);
+    if (jmax > 0) grp_stage<16>(V.Xs, D, V.rows, j0, jmax, wrows, lay.rs, lay.rpp, dc, K.doff, K.dsc[0], K.dmu, s_bmax, lane);
     __syncthreads();
     if (jmax > 0) GRP_PAIRS_DISPATCH_UNSIGNED(DCP, lay, du == 0 ? 0 : 1, GLP_PAIRS_CALL);
   }
@@ -260,8 +248,7 @@ __global__ __launch_bounds__(64 * NW) void glp_dd_kernel(GlpArgs A) {
 // the fp64 log-space pass (header): tile `tile` of the (group, KDE)'s list -- or, fp64_only, of its pool
 template <int DCP, int DUP, int NW, bool EXP64>
 __global__ __launch_bounds__(64 * NW) void glp_f64_kernel(GlpArgs A) {
-  constexpr int NT = 64 * NW, OB = 32;  // observations per wave and round
-  constexpr int RB = DCP * 8 + DUP * 4;  // bytes per staged row: DCP scaled coordinates (f64), DUP codes (f32)
+  constexpr int NT = 64 * NW, OB = GLP_OB, RB = GLP_RB(DCP, DUP);
   __shared__ __align__(16) char srow[NW * OB * RB];
   __shared__ double s_sa[DCP], s_dl[DUP];
   __shared__ int32_t s_cdim[DCP], s_udim[DUP];
@@ -291,92 +278,26 @@ __global__ __launch_bounds__(64 * NW) void glp_f64_kernel(GlpArgs A) {
   if ((int64_t)tile * 64 >= cnt) return;  // uniform
   const bool valid = pi < cnt;
   const int64_t p = valid ? (A.fp64_only ? pi : (int64_t)A.list[(b * 2 + kd) * A.C + pi]) : 0;
-  if (wave == 0) {
-    int dc, du;
-    grp_slots(A.M, lane, s_cdim, s_udim, &dc, &du);
-    if (lane == 0) {
-      s_i[0] = dc;
-      s_i[1] = du;
-    }
-  }
-  __syncthreads();
-  const int dc = s_i[0], du = s_i[1];
-  const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
-  const int64_t nk = kd ? A.M.n_bad[b] : A.M.n_good[b];
-  const double* Xs = A.M.X + s0 * D;
-  const int64_t* rows = A.M.order + s0 + (kd ? n - nk : 0);
-  const double* bw = (kd ? A.M.bw_bad : A.M.bw_good) + b * D;
-  const int32_t* nlev = (kd ? A.M.nlev_bad : A.M.nlev_good) + b * D;
-  // per-slot constants: a_c = 1 / (h sqrt 2); categorical: ln(h / (c - 1)) + [match] (ln(1 - h) - ln(h / (c - 1))),
-  // the first part summed into the constant (kde_logpdf_tiled_kernel's)
-  for (int k = tid; k < DCP; k += NT) s_sa[k] = k < dc ? 1.0 / (bw[s_cdim[k]] * 1.4142135623730951) : 0.0;
-  for (int u = tid; u < DUP; u += NT) {
-    double v = 0.0;
-    if (u < du) {
-      const int d = s_udim[u];
-      v = log(1. - bw[d]) - log(bw[d] / (double)(nlev[d] - 1));
-    }
-    s_dl[u] = v;
-  }
-  if (tid == 0) {
-    double lc = -log((double)nk);
-    for (int k = 0; k < dc; ++k) lc -= log(bw[s_cdim[k]]) + 0.91893853320467274178;  // ln(h sqrt(2 pi))
-    for (int u = 0; u < du; ++u) {
-      const int d = s_udim[u];
-      lc += log(bw[d] / (double)(nlev[d] - 1));
-    }
-    s_lconst = lc;
-  }
-  __syncthreads();
+  int dc, du;
+  glp_slots(A.M, s_cdim, s_udim, s_i, &dc, &du);
+  const GlpKde V = glp_kde(A.M, b, kd);
+  const int64_t nk = V.nk;
+  glp_slot_consts<DCP, DUP, NT, false>(V, dc, du, s_cdim, s_udim, s_sa, s_dl, &s_lconst, nullptr, nullptr);
   const int dcq = (dc + 3) >> 2, duq = (du + 3) >> 2;
-  const double* x = A.cand + (b * A.C + p) * D;
   double xc[DCP];
   float xu[DUP];
-#pragma unroll
-  for (int k = 0; k < DCP; ++k) xc[k] = k < dc ? x[s_cdim[k]] * s_sa[k] : 0.0;
-#pragma unroll
-  for (int u = 0; u < DUP; ++u) xu[u] = u < du ? cand_code(x[s_udim[u]]) : 0.f;
   char* wrow = srow + (size_t)wave * OB * RB;
-  for (int e = lane; e < OB * RB / 4; e += 64) ((float*)wrow)[e] = 0.f;  // (the padding slots stay 0)
+  glp_load_cand64<DCP, DUP>(A.cand + (b * A.C + p) * D, dc, du, s_cdim, s_udim, s_sa, wrow, lane, xc, xu);
   double m = -INFINITY, S = 0.0;
   bool nan = false;
   for (int64_t c0 = 0; c0 < nk; c0 += (int64_t)NW * OB) {  // uniform trip count: the barriers are block-wide
     __syncthreads();  // (the rows of the previous round are read)
     const int64_t j0 = c0 + (int64_t)wave * OB;
     const int jmax = (int)(nk - j0 < OB ? (nk - j0 > 0 ? nk - j0 : 0) : OB);
-    for (int e = lane; e < jmax * D; e += 64) {  // a row's slots by consecutive lanes
-      const int r = e / D, k = e - r * D;
-      const double* xr = Xs + rows[j0 + r] * (int64_t)D;
-      if (k < dc)
-        ((double*)(wrow + r * RB))[k] = xr[s_cdim[k]] * s_sa[k];
-      else
-        ((float*)(wrow + r * RB + DCP * 8))[k - dc] = (float)xr[s_udim[k - dc]];  // (an integer in [0, 1024): exact)
-    }
+    glp_stage64<DCP, DUP>(V, D, dc, s_cdim, s_udim, s_sa, j0, jmax, wrow, lane);
     __syncthreads();
     for (int j = 0; j < jmax; ++j) {
-      const double2* rc = (const double2*)(wrow + j * RB);
-      const float4* ru = (const float4*)(wrow + j * RB + DCP * 8);
-      double t = 0.0;
-#pragma unroll
-      for (int q = 0; q < DCP / 4; ++q)
-        if (q < dcq) {  // uniform
-          const double2 v0 = rc[2 * q], v1 = rc[2 * q + 1];
-          const double d0 = xc[4 * q] - v0.x, d1 = xc[4 * q + 1] - v0.y, d2 = xc[4 * q + 2] - v1.x,
-                       d3 = xc[4 * q + 3] - v1.y;
-          t = fma(-d0, d0, t);
-          t = fma(-d1, d1, t);
-          t = fma(-d2, d2, t);
-          t = fma(-d3, d3, t);
-        }
-#pragma unroll
-      for (int q = 0; q < DUP / 4; ++q)
-        if (q < duq) {  // uniform
-          const float4 v = ru[q];
-          t += (xu[4 * q] == v.x) ? s_dl[4 * q] : 0.0;
-          t += (xu[4 * q + 1] == v.y) ? s_dl[4 * q + 1] : 0.0;
-          t += (xu[4 * q + 2] == v.z) ? s_dl[4 * q + 2] : 0.0;
-          t += (xu[4 * q + 3] == v.w) ? s_dl[4 * q + 3] : 0.0;
-        }
+      const double t = glp_pair_t64<DCP, DUP, false>(wrow + j * RB, dcq, duq, xc, xu, s_dl, nullptr);
       const double tl = t * 1.4426950408889634;  // log2 units
       if (tl > m) {
         S = (m > -INFINITY ? S * (EXP64 ? exp2(m - tl) : (double)__builtin_amdgcn_exp2f((float)(m - tl))) : 0.0) + 1.0;
@@ -424,17 +345,14 @@ __global__ __launch_bounds__(EXACT_THREADS) void glp_exact_kernel(GlpArgs A) {
   const int32_t* list = (st & GLP_SIGNED_BIT(kd)) ? A.list + (b * 2 + kd) * A.C : nullptr;
   const int64_t lim = list ? (int64_t)A.cnt[b * 2 + kd] : A.C;  // (cnt <= C: a candidate is listed once)
   if ((int64_t)tile * 64 >= lim) return;  // uniform
-  const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
-  const int64_t nk = kd ? A.M.n_bad[b] : A.M.n_good[b];
-  const double* Xs = A.M.X + s0 * D;
-  const int64_t* rows = A.M.order + s0 + (kd ? n - nk : 0);
+  const GlpKde V = glp_kde(A.M, b, kd);
   if (threadIdx.x == 0) vw = grp_view(A.M, b, kd);
   __syncthreads();
   const int64_t i0 = (int64_t)tile * 64, i1 = i0 + 64 < lim ? i0 + 64 : lim;
   for (int64_t e = i0; e < i1; ++e) {
     const int64_t i = list ? (int64_t)list[e] : e;
     exact_setup(&vw, D, A.cand + (b * A.C + i) * D, &sh);
-    const double v = exact_pdf(Xs, D, rows, &vw, &sh);
+    const double v = exact_pdf(V.Xs, D, V.rows, &vw, &sh);
     if (threadIdx.x == 0) A.out[kd][b * A.C + i] = log(v);
     __syncthreads();
   }

@@ -3,11 +3,9 @@
 // in log space, exact only where the sum cancels.  hbx_groups_logpdf.hip has the call, the other passes and the
 // contract; without the flag such a KDE goes through the exact pdf for every candidate and this file is not reached.
 //
-// glp_signed_kernel<DCP, DUP, NW, EXP64>: glp_f64_kernel's work split and staging.  A block is one 64-candidate tile
-// of one (group, KDE), lane = candidate, its scaled coordinates (fp64) and codes (fp32) in registers; the NW waves take
-// the KDE's rows in rounds of 32 per wave, each gathered through `order`, scaled and staged in the wave's LDS slice
-// (DCP doubles and DUP floats per row) and read back as broadcasts, one barrier pair per round.  Per pair, fp64,
-// direct differences:
+// glp_signed_kernel<DCP, DUP, NW, EXP64>: glp_f64_kernel's work split, staging and pair exponent, the shared pieces
+// of hbx_groups_logpdf_impl.h ("the fp64 tile passes": glp_slot_consts<.., SIGNED = true>, glp_load_cand64,
+// glp_stage64, glp_pair_t64<.., BITS = true>).  Per pair, fp64, direct differences:
 //     t = sum_c -((x_c - X_jc) / (h_c sqrt 2))^2 + sum_u [x_u == X_ju] delta_u,   delta_u = ln|1 - h_u| - ln(h_u / (c_u - 1))
 //   (delta_u = -inf where 1 - h_u == 0: a matching term is exactly 0, t = -inf and the pair adds nothing).  The
 //   term's sign is the parity of its matches in slots with h > 1: the pair's match bits form one 32-bit word (DUP <=
@@ -43,9 +41,7 @@
 
 template <int DCP, int DUP, int NW, bool EXP64>
 __global__ __launch_bounds__(64 * NW) void glp_signed_kernel(GlpArgs A) {
-  static_assert(DUP <= 32, "a pair's match bits are one 32-bit word");
-  constexpr int NT = 64 * NW, OB = 32;   // observations per wave and round
-  constexpr int RB = DCP * 8 + DUP * 4;  // bytes per staged row: DCP scaled coordinates (f64), DUP codes (f32)
+  constexpr int NT = 64 * NW, OB = GLP_OB, RB = GLP_RB(DCP, DUP);
   __shared__ __align__(16) char srow[NW * OB * RB];
   __shared__ double s_sa[DCP], s_dl[DUP];
   __shared__ int32_t s_cdim[DCP], s_udim[DUP];
@@ -63,104 +59,29 @@ __global__ __launch_bounds__(64 * NW) void glp_signed_kernel(GlpArgs A) {
   if ((st & GLP_BAD) || !(st & GLP_SIGNED_BIT(kd))) return;  // uniform
   const int64_t i = (int64_t)tile * 64 + lane;
   const bool valid = i < A.C;
-  if (wave == 0) {
-    int dc, du;
-    grp_slots(A.M, lane, s_cdim, s_udim, &dc, &du);  // (dc <= DCP, du <= DUP: the status kernel checked the bucket)
-    if (lane == 0) {
-      s_i[0] = dc;
-      s_i[1] = du;
-    }
-  }
-  __syncthreads();
-  const int dc = s_i[0], du = s_i[1];
-  const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
-  const int64_t nk = kd ? A.M.n_bad[b] : A.M.n_good[b];
-  const double* Xs = A.M.X + s0 * D;
-  const int64_t* rows = A.M.order + s0 + (kd ? n - nk : 0);
-  const double* bw = (kd ? A.M.bw_bad : A.M.bw_good) + b * D;
-  const int32_t* nlev = (kd ? A.M.nlev_bad : A.M.nlev_good) + b * D;
-  // per-slot constants: a_c = 1 / (h sqrt 2); delta_u (header), ln(h / (c - 1)) summed into the constant
-  for (int k = tid; k < DCP; k += NT) s_sa[k] = k < dc ? 1.0 / (bw[s_cdim[k]] * 1.4142135623730951) : 0.0;
-  for (int u = tid; u < DUP; u += NT) {
-    double v = 0.0;
-    if (u < du) {
-      const int d = s_udim[u];
-      const double a = 1.0 - bw[d];
-      v = a == 0.0 ? -INFINITY : log(fabs(a)) - log(bw[d] / (double)(nlev[d] - 1));
-    }
-    s_dl[u] = v;
-  }
-  __syncthreads();
-  if (tid == 0) {  // in slot order (deterministic)
-    double lc = -log((double)nk), sad = 0.0;
-    uint32_t neg = 0u;
-    for (int k = 0; k < dc; ++k) lc -= log(bw[s_cdim[k]]) + 0.91893853320467274178;  // ln(h sqrt(2 pi))
-    for (int u = 0; u < du; ++u) {
-      const int d = s_udim[u];
-      lc += log(bw[d] / (double)(nlev[d] - 1));
-      if (1.0 - bw[d] < 0.0) neg |= 1u << u;
-      if (s_dl[u] > -INFINITY) sad += fabs(s_dl[u]);
-    }
-    s_lconst = lc;
-    s_sad = sad;
-    s_neg = neg;
-  }
-  __syncthreads();
+  int dc, du;
+  glp_slots(A.M, s_cdim, s_udim, s_i, &dc, &du);
+  const GlpKde V = glp_kde(A.M, b, kd);
+  const int64_t nk = V.nk;
+  glp_slot_consts<DCP, DUP, NT, true>(V, dc, du, s_cdim, s_udim, s_sa, s_dl, &s_lconst, &s_sad, &s_neg);
   const uint32_t neg = __builtin_amdgcn_readfirstlane(s_neg);
   const int dcq = (dc + 3) >> 2, duq = (du + 3) >> 2;
-  const double* x = A.cand + (b * A.C + (valid ? i : (int64_t)tile * 64)) * D;
   double xc[DCP];
   float xu[DUP];
-#pragma unroll
-  for (int k = 0; k < DCP; ++k) xc[k] = k < dc ? x[s_cdim[k]] * s_sa[k] : 0.0;
-#pragma unroll
-  for (int u = 0; u < DUP; ++u) xu[u] = u < du ? cand_code(x[s_udim[u]]) : 0.f;
   char* wrow = srow + (size_t)wave * OB * RB;
-  for (int e = lane; e < OB * RB / 4; e += 64) ((float*)wrow)[e] = 0.f;  // (the padding slots stay 0: delta 0, mask 0)
+  glp_load_cand64<DCP, DUP>(A.cand + (b * A.C + (valid ? i : (int64_t)tile * 64)) * D, dc, du, s_cdim, s_udim, s_sa, wrow,
+                            lane, xc, xu);
   double m = -INFINITY, Sp = 0.0, Sn = 0.0;
   bool nan = false;
   for (int64_t c0 = 0; c0 < nk; c0 += (int64_t)NW * OB) {  // uniform trip count: the barriers are block-wide
     __syncthreads();  // (the rows of the previous round are read)
     const int64_t j0 = c0 + (int64_t)wave * OB;
     const int jmax = (int)(nk - j0 < OB ? (nk - j0 > 0 ? nk - j0 : 0) : OB);
-    for (int e = lane; e < jmax * D; e += 64) {  // a row's slots by consecutive lanes
-      const int r = e / D, k = e - r * D;
-      const double* xr = Xs + rows[j0 + r] * (int64_t)D;
-      if (k < dc)
-        ((double*)(wrow + r * RB))[k] = xr[s_cdim[k]] * s_sa[k];
-      else
-        ((float*)(wrow + r * RB + DCP * 8))[k - dc] = (float)xr[s_udim[k - dc]];  // (an integer in [0, 1024): exact)
-    }
+    glp_stage64<DCP, DUP>(V, D, dc, s_cdim, s_udim, s_sa, j0, jmax, wrow, lane);
     __syncthreads();
     for (int j = 0; j < jmax; ++j) {
-      const double2* rc = (const double2*)(wrow + j * RB);
-      const float4* ru = (const float4*)(wrow + j * RB + DCP * 8);
-      double t = 0.0;
-      uint32_t mb = 0u;  // the pair's match bits, slot u at bit u
-#pragma unroll
-      for (int q = 0; q < DCP / 4; ++q)
-        if (q < dcq) {  // uniform
-          const double2 v0 = rc[2 * q], v1 = rc[2 * q + 1];
-          const double d0 = xc[4 * q] - v0.x, d1 = xc[4 * q + 1] - v0.y, d2 = xc[4 * q + 2] - v1.x,
-                       d3 = xc[4 * q + 3] - v1.y;
-          t = fma(-d0, d0, t);
-          t = fma(-d1, d1, t);
-          t = fma(-d2, d2, t);
-          t = fma(-d3, d3, t);
-        }
-#pragma unroll
-      for (int q = 0; q < DUP / 4; ++q)
-        if (q < duq) {  // uniform
-          const float4 v = ru[q];
-          const bool e0 = xu[4 * q] == v.x, e1 = xu[4 * q + 1] == v.y, e2 = xu[4 * q + 2] == v.z,
-                     e3 = xu[4 * q + 3] == v.w;
-          t += e0 ? s_dl[4 * q] : 0.0;
-          t += e1 ? s_dl[4 * q + 1] : 0.0;
-          t += e2 ? s_dl[4 * q + 2] : 0.0;
-          t += e3 ? s_dl[4 * q + 3] : 0.0;
-          mb |= (e0 ? 1u : 0u) << (4 * q) | (e1 ? 2u : 0u) << (4 * q) | (e2 ? 4u : 0u) << (4 * q) |
-                (e3 ? 8u : 0u) << (4 * q);
-        }
+      uint32_t mb;  // the pair's match bits, slot u at bit u
+      const double t = glp_pair_t64<DCP, DUP, true>(wrow + j * RB, dcq, duq, xc, xu, s_dl, &mb);
       const double tl = t * 1.4426950408889634;  // log2 units
       const bool odd = __popc(mb & neg) & 1;
       double e = 0.0;

@@ -142,46 +142,21 @@ __global__ __launch_bounds__(LR_T) void groups_select_lr_kernel(GrpArgs A) {
   __shared__ double s_m[LR_T], s_s[LR_T];
   __shared__ unsigned long long s_tmax;
   __shared__ uint32_t s_U;
-  __shared__ int32_t s_st, s_near, s_need, s_nforce;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ int32_t s_st, s_need, s_nforce;
+  const int tid = threadIdx.x;
   const int64_t q = blockIdx.x, b = q / A.S;  // request q = b S + s of group b
   const int D = A.M.D;
   const int64_t C = A.C;
-  if (wv == 0) {
-    int dc, du;
-    const int st0 = grp_classify(A.M, b, &dc, &du);
-    if (lane == 0) s_st = st0;
-  }
   if (tid == 0) {
     s_U = hbx_f2ord(INFINITY);
-    s_near = 0;
     s_need = 0;
     s_nforce = 0;
   }
-  __syncthreads();
-  const int st = s_st;
-  const int32_t gbits = (st & GRP_NO_MODEL) ? HBX_ACQ_NO_MODEL : (st & GRP_UNSUPPORTED) ? HBX_ACQ_UNSUPPORTED : 0;
-  if constexpr (MASK) {
-    if (A.want[q] == 0) {  // (uniform) the skipped record, with the group's bits as the dense call sets them
-      if (tid == 0) {
-        A.res[q] = grp_empty_record(HBX_ACQ_SKIPPED | gbits);
-        atomicAdd(A.stats + 1, 1ull);
-      }
-      return;
-    }
-  }
-  if (gbits) {
-    if (tid == 0) {
-      A.res[q] = grp_empty_record(HBX_ACQ_LOG_RATIO | gbits);
-      atomicAdd(A.stats + 0, 1ull);
-    }
-    return;
-  }
-  const int64_t s0 = A.M.seg_off[b], n = A.M.seg_off[b + 1] - s0;
-  const double* Xs = A.M.X + s0 * D;
-  const int64_t* rows_g = A.M.order + s0;
-  const int64_t* rows_b = A.M.order + s0 + (n - A.M.n_bad[b]);
-  if (tid < 2) vw[tid] = grp_view(A.M, b, tid);
+  int st;
+  if (grp_select_prologue(A, q, b, MASK ? A.want : nullptr, true, HBX_ACQ_LOG_RATIO, &s_st, &st)) return;
+  const double* Xs;
+  const int64_t *rows_g, *rows_b;
+  grp_rows(A.M, b, vw, &Xs, &rows_g, &rows_b);
   GScreen* scr = A.scr + q * C;
   const double* cand = A.cand + q * C * D;
   const bool all = (st & GRP_EXACT_ONLY) != 0;
@@ -245,42 +220,13 @@ __global__ __launch_bounds__(LR_T) void groups_select_lr_kernel(GrpArgs A) {
     nshort += tot;
   }
   if (nforce) atomicAdd(&s_nforce, nforce);
-  // the near set: every re-scored candidate the winner cannot be told apart from by the bounds
-  __shared__ double s_best, s_rb;
-  __shared__ int64_t s_bidx;
+  // near: s <= s_best + 1.0001 (rel + rel_best); w = +inf: no bound, near whatever s is
+  auto near = [](double s, double rel, double sb, double rb) {
+    const double w = 1.0001 * (rel + rb);
+    return s < INFINITY && (w == INFINITY || s <= sb + w);
+  };
+  grp_select_tail(A, q, scr, C, best, bidx, bl, bg, nshort, HBX_ACQ_LOG_RATIO | (all ? HBX_ACQ_OVERFLOW : 0), 0, near);
   if (tid == 0) {
-    s_best = best;
-    s_bidx = bidx;
-    s_rb = bidx >= 0 ? (double)scr[bidx].rel : 0.0;
-  }
-  __threadfence_block();
-  __syncthreads();  // (also: thread 0's stores to scr are visible to the block)
-  const double sb = s_best, rb = s_rb;
-  const int64_t wi = s_bidx;
-  if (wi >= 0) {
-    int cnt = 0;
-    for (int64_t i = tid; i < C; i += LR_T) {
-      const GScreen g = scr[i];
-      if (!(g.fl & GS_DONE)) continue;
-      const double s = g.score, w = 1.0001 * ((double)g.rel + rb);  // (w = +inf: no bound, near whatever s is)
-      if (i == wi || (s < INFINITY && (w == INFINITY || s <= sb + w))) ++cnt;
-    }
-    if (cnt) atomicAdd(&s_near, cnt);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    AcqResult r = grp_empty_record(HBX_ACQ_LOG_RATIO | (all ? HBX_ACQ_OVERFLOW : 0));
-    r.shortlist = nshort;
-    r.near = s_near;
-    r.rel = (float)rb;
-    if (r.near > 1) r.flags |= HBX_ACQ_NEAR_TIE;
-    if (wi >= 0) {
-      r.index = wi;
-      r.score = sb;
-      r.pdf_l = bl;
-      r.pdf_g = bg;
-    }
-    A.res[q] = r;
     atomicAdd(A.stats + 0, 1ull);
     atomicAdd(A.stats + 3, (unsigned long long)nshort);
     if (nls) atomicAdd(A.stats + 4, (unsigned long long)nls);

@@ -188,6 +188,32 @@ def test_unsigned_categorical_buckets(device, dc, du, lev):
     assert runs[1].stats[0] == 0
 
 
+@pytest.mark.parametrize("signed", ["exact", "logspace"])
+@pytest.mark.parametrize("fp64_only", [False, True])
+def test_categorical_bandwidth_of_exactly_one(device, fp64_only, signed):
+    """h == 1 in the good KDE's categorical dim: 1 - h == 0, delta = -inf, a matching pair contributes nothing (the
+    factor is not negative, so the KDE stays on the fp32 / fp64 passes on both routes).  B = 2, three rows each (the
+    smallest group with a model at D = 2), codes (0, 0, 1) and (0, 1, 2); per pool: code 0 (matches two rows / one),
+    code 1, codes 2 and 7 (7, and in group 0 also 2, match no row).  No code can match every row: a KDE with one
+    observed level goes through the exact pdf, not these passes."""
+    from hpbandster_amd import groups
+    X = np.array([[0.2, 0], [0.5, 0], [0.9, 1], [0.1, 0], [0.4, 1], [0.8, 2]], dtype=np.float64)
+    seg, vt, C = np.array([0, 3, 6]), "cu", 4
+    gm = groups.fit_groups(X, np.array([0.3, 0.1, 0.2, 0.6, 0.4, 0.5]), seg, vt, device=device)
+    assert np.all(gm.has_model) and np.all(gm.nlev_good.cpu().numpy()[:, 1] >= 2)
+    gm.bw_good[:, 1] = 1.0
+    cands = np.array([[[0.3, 0], [0.6, 1], [0.45, 2], [0.7, 7]], [[0.2, 0], [0.5, 1], [0.75, 2], [0.3, 7]]], dtype=np.float64)
+    r = gm.logpdf(cands, fp64_only=fp64_only, signed=signed)
+    assert np.all(r.status == 0) and sum(r.stats) == 2 * 2 * C and r.stats[2] == 0 and r.stats[3] == 0
+    bws, nls = gm.bandwidths(), (gm.nlev_good.cpu().numpy(), gm.nlev_bad.cpu().numpy())
+    assert np.all(bws[0][:, 1] == 1.0)
+    for b in range(2):
+        for kd, rows in enumerate(gm.rows_of(b)):
+            ref = O.log_pdf_many(X[seg[b]:seg[b + 1]][rows], bws[kd][b], vt, cands[b], nls[kd][b])
+            assert np.all(np.isfinite(ref))  # (no pool's code matches every row)
+            _check_positive((r.ln_g if kd else r.ln_l)[b], ref, 1e-5, ("h = 1", fp64_only, signed, b, kd))
+
+
 def test_plumbing(device):
     import torch
     from hpbandster_amd import groups
