@@ -55,6 +55,9 @@ SIGNATURES = {
     "hbx_kde_pair_bind": (c_vp, [c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                  c_i64]),
     "hbx_kde_acquire_bound": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hbx_kde_lr_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "hbx_kde_acquire_lr": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "hbx_kde_acquire_bound_lr": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "hbx_kde_pair_free": (None, [c_vp]),
     "hbx_kde_pair_set_rules": (c_i32, [c_vp, c_vp]),
     "hbx_kde_batch_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),

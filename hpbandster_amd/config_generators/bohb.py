@@ -24,7 +24,7 @@ import numpy as np
 from .. import _native
 # the host draws (the benchmark reads _HostModel, _draw_rvs, _global_mt, host_draw_ok and _HOSTDRAW from this module)
 from ..host_draw import _HOSTDRAW, _MT, _HostModel, _draw_fast, _draw_rvs, _global_mt, host_draw_ok  # noqa: F401
-from ..kde import ACQ_DOMAIN_ERR, ObservationStore, mapped_candidates
+from ..kde import ACQ_DOMAIN_ERR, ACQ_SCORES, ObservationStore, mapped_candidates
 from .base import base_config_generator
 from ._cs import ConfigSpace
 
@@ -76,8 +76,16 @@ class BOHB(base_config_generator):
     def __init__(self, configspace, min_points_in_model=None, top_n_percent=15, num_samples=64,
                  random_fraction=1 / 3, bandwidth_factor=3, device=None, sampler="host", sampler_seed=None,
                  speculative="auto", min_bandwidth=None, pdf_floor=_native.PDF_FLOOR_DEFAULT, impute_seed=0,
-                 **kwargs):
+                 score="floored", **kwargs):
         super().__init__(**kwargs)
+        # score: how get_config picks among its num_samples candidates -- "floored", the reference's
+        # max(f, g) / max(l, f) (exactly 1 wherever both densities lie under f, where the first candidate then wins),
+        # or "log_ratio", s = ln g - ln l with no floor (KDEPair.acquire's score="log_ratio"; GroupBOHB's of the same
+        # name).  The draws, the random fraction and the fall-backs do not depend on it.  Under "log_ratio" the calls
+        # are single ones: no speculative batches, no get_config_batch, no get_config_topk.
+        if score not in ACQ_SCORES:
+            raise ValueError("score must be 'floored' or 'log_ratio', got %r" % (score,))
+        self.score = score
         # conditional search spaces (the configspace reports conditions): an observation holds NaN where a
         # hyperparameter is inactive.  Its store accepts such rows, a refit over rows with a NaN imputes them on the
         # device first (the releases' impute_conditional_data; include/hbx.h hbx_kde_impute_groups) under
@@ -199,7 +207,7 @@ class BOHB(base_config_generator):
                 else:  # drawn into mapped host memory, which the acquisition's kernels read in place
                     cands = self.sample_candidates(pair['good'], self.num_samples,
                                                    out=mapped_candidates(self.num_samples, len(self.vartypes)))
-                    res = pair.acquire_mapped(cands)
+                    res = pair.acquire_mapped(cands, self.score)
                     best_vector = cands[res.index].copy() if res.index >= 0 else None
                 if res.index < 0:
                     self.logger.debug(self._failed("no score"))
@@ -252,7 +260,7 @@ class BOHB(base_config_generator):
         n, D = self.num_samples, len(self.vartypes)
         t = self._pick_tls
         keep = getattr(t, "keep", None)
-        wsb = pair.workspace_bytes(n)
+        wsb = pair.workspace_bytes(n, self.score)
         if keep is None or keep[3].numel() < wsb or keep[0].device != dev:
             keep = t.keep = (torch.empty((n, D), dtype=torch.float64, device=dev),
                              torch.empty(n, dtype=torch.int64, device=dev),
@@ -260,7 +268,7 @@ class BOHB(base_config_generator):
                              torch.empty(wsb, dtype=torch.uint8, device=dev), np.empty(D))
         cands, _, err, ws, row = keep
         pair.good.sample(self.vartypes, self.bw_factor, n, self.sampler_seed, counter, out=keep[:3])
-        res = pair.acquire_pick(cands, err, ws, row)
+        res = pair.acquire_pick(cands, err, ws, row, score=self.score)
         return res, (row.copy() if res.index >= 0 else None)
 
     # -- the k best candidates of one pool --------------------------------------------------------
@@ -277,6 +285,7 @@ class BOHB(base_config_generator):
         k = int(k)
         if k < 1 or k > 1024:
             raise ValueError("k must be in [1, 1024], got %d" % k)
+        self._floored_only("get_config_topk")
         if len(self.kde_models.keys()) == 0:
             return []
         np.random.rand()  # get_config's random_fraction draw
@@ -303,7 +312,13 @@ class BOHB(base_config_generator):
                 for j in range(top.count)]
 
     # -- several get_config calls in one GPU pass ----------------------------
+    def _floored_only(self, what):
+        if self.score != "floored":
+            raise ValueError("%s is not offered under score=%r (single get_config calls only)" % (what, self.score))
+
     def speculation_enabled(self):
+        if self.score != "floored":  # the batched acquisition ranks by the floored score
+            return False
         return self.speculative == "always" or (self.speculative == "auto" and self.sampler == "gpu")
 
     def spec_fingerprint(self):
@@ -344,6 +359,7 @@ class BOHB(base_config_generator):
         same order as k sequential calls (the draws of a call do not depend on earlier calls' scores)
         and the configspace RNG in call order, so the returned list is identical to the sequential one.
         """
+        self._floored_only("get_config_batch")
         return [self._serve(e) for e in self._batch_entries(k, np.random.mtrand._rand)]
 
     def _batch_entries(self, k, R, states=None, counters=None, mt=None):

@@ -175,6 +175,51 @@ __device__ __forceinline__ double score_rel(const KdeParams* __restrict__ Pg, co
   return exact_rel(Pg, el[i]) + exact_rel(Pb, eg[i]) + 0x1p-51;
 }
 
+// A get_config pick published to device-mapped host memory by a final argmin (hbx_kde_acquire_bound and
+// hbx_kde_acquire_bound_lr with err / row_out): the record, whether any of the call's candidates hit a sampler domain
+// error, the winning row (as tagged 8-byte words: acq_publish)
+struct PickOut {
+  const double* cand;
+  const uint8_t* err;  // nullable
+  int64_t Nc;
+  int32_t D;
+  char* out;  // null: no pick
+};
+
+// whether any domain-error flag of a pick is set (whole block of 256; 0 without a pick or without flags)
+__device__ __forceinline__ int acq_pick_err_any(const PickOut& pick) {
+  int err_any = 0;
+  if (pick.out && pick.err) {  // uniform
+    bool e = false;
+    for (int64_t i = threadIdx.x; i < pick.Nc; i += 256) e = e || pick.err[i] != 0;
+    err_any = __syncthreads_or(e);
+  }
+  return err_any;
+}
+
+// The tail of a single acquisition's final kernel (whole block of 256; rec: the record in LDS, written by thread 0
+// before the call): the record, and a pick's flag and winning row, to mapped host memory.
+// Every 32-bit word goes out as one 8-byte system-scope store tagged with the call's sequence number (seq << 32 |
+// word): the host takes each word only once its tag is the call's, so there is no acknowledgement wait and no
+// completion word (wait_tagged)
+__device__ __forceinline__ void acq_publish(const AcqResult* rec, AcqResult* host_res, int32_t seq, const PickOut& pick,
+                                            int64_t index_base, int err_any) {
+  if (!(host_res || pick.out)) return;  // uniform
+  static_assert(sizeof(AcqResult) % 4 == 0, "record of whole words");
+  __syncthreads();
+  uint64_t* out = (uint64_t*)(pick.out ? pick.out : (char*)host_res);
+  const uint64_t tag = (uint64_t)(uint32_t)seq << 32;
+  constexpr int RW = (int)(sizeof(AcqResult) / 4);
+  if (threadIdx.x < RW) hbx_publish_store64(out + threadIdx.x, tag | ((const uint32_t*)rec)[threadIdx.x]);
+  if (pick.out) {  // a pick: + the domain-error flag (word RW) and the winning row (words RW + 1 ..)
+    if (threadIdx.x == 0) hbx_publish_store64(out + RW, tag | (err_any ? 1u : 0u));
+    const int64_t idx = rec->index - index_base;
+    if (rec->index >= 0 && idx < pick.Nc)
+      for (int w = threadIdx.x; w < 2 * pick.D; w += 256)
+        hbx_publish_store64(out + RW + 1 + w, tag | ((const uint32_t*)(pick.cand + idx * pick.D))[w]);
+  }
+}
+
 // p may beat the winner in numpy's arithmetic only if s_p (1 - R_p) <= s_best (1 + R_best)
 __device__ __forceinline__ bool near_best(double s, double rp, double best, double rb) {
   return s < INFINITY && s <= best * (1.0 + 1.0001 * (rp + rb));

@@ -36,9 +36,13 @@ struct WsLayout {
   // coarse pair kernel covers 256 or 512)
   size_t stage, seeds, surv, lpart, bmax;
   int32_t list_cap;
+  // the log-ratio acquisition (hbx_acquire_lr.hip), appended under ws_layout's lr flag (without it: all = total, no
+  // bytes): L_l, L_g per shortlist entry ([2 p], [2 p + 1]), their log-space bounds likewise, two counters (log-space
+  // evaluations, forced candidates re-scored)
+  size_t lr_L, lr_bnd, lr_stat;
 };
 #define STAGED_LIST_CAP 4096  // seeds at most, and listed candidates at most of a split list launch
-WsLayout ws_layout(int64_t Nc, int64_t nmax, int64_t B = 1);
+WsLayout ws_layout(int64_t Nc, int64_t nmax, int64_t B = 1, bool lr = false);
 
 // the workspace's arrays as typed pointers
 struct AcqWs {
@@ -56,6 +60,8 @@ struct AcqWs {
   KdeEst* lpart;
   float* bmax;
   int32_t list_cap;
+  double *lr_L, *lr_bnd;
+  int32_t* lr_stat;
   AcqWs(void* workspace, const WsLayout& w) {
     char* ws = (char*)workspace;
     res = (AcqResult*)(ws + w.res);
@@ -82,6 +88,9 @@ struct AcqWs {
     lpart = (KdeEst*)(ws + w.lpart);
     bmax = (float*)(ws + w.bmax);
     list_cap = w.list_cap;
+    lr_L = (double*)(ws + w.lr_L);
+    lr_bnd = (double*)(ws + w.lr_bnd);
+    lr_stat = (int32_t*)(ws + w.lr_stat);
   }
   // a single acquisition's state, for the launch that initialises it
   KdePairArgs::AcqInitPtrs init() const { return {U, count, flags, first1, res}; }
@@ -95,7 +104,7 @@ struct AcqPlan {
 };
 const KdePairRef* acq_pair(const char* who, const void* pair);  // an entry point's handle; NULL: HBX_ERR_ARG is set
 int acq_check(const char* who, const KdePairRef& p, const double* cand, int64_t Nc, const void* workspace);
-int acq_plan(const KdePairRef& p, bool fast, AcqPlan* plan);
+int acq_plan(const KdePairRef& p, bool fast, AcqPlan* plan, bool coarse_ok = true);  // (coarse_ok: pick_logpdf's)
 // (2) the scoring launch (first: it touches none of the per-acquisition state, so the GPU starts on it while
 // the host enqueues the rest; launch_score2, hbx_score.h, which also documents rq and out), then the state's
 // initialisation where the launch did not do it (batch_B > 0: the B segments' state instead, rq.init empty), then
@@ -148,6 +157,17 @@ int staged_score_survivors(const AcqPlan& plan, const KdePairRef& p, const doubl
                            hipStream_t s, bool lonly);
 // exact-only acquisitions instead of a combine / bounds pass: every candidate joins the re-score
 int acq_exact_only_init(int64_t Nc, uint32_t seg, const AcqWs& a, hipStream_t s);
+// 256-candidate sub-blocks per block of the combine kernels (kde_combine_kernel, kde_combine_lr_kernel)
+#ifndef COMBINE_SUB
+#define COMBINE_SUB 2  // (2: 13-15 us at 1e6, 4: 15-17, 8: 19)
+#endif
+// a single acquisition's shortlist launch (kde_shortlist_kernel: every candidate whose a.lo is not NaN and <= a.U, the
+// whole pool under the overflow flag), for an acquisition outside hbx_kde.hip
+int acq_shortlist(int64_t Nc, const AcqWs& a, hipStream_t s);
+// a bound call's wait for its final kernel's tagged words at pub (hbx_kde_acquire_bound): the record to rec_out, a
+// pick's domain-error flag into its flags and the winning row to row_out
+int acq_bound_wait(const char* who, const char* pub, int32_t seq, bool pick, int32_t D, int64_t Nc, int64_t index_base,
+                   hipStream_t s, void* rec_out, double* row_out);
 // (3) the exact fp64 re-score of the shortlist a.list / a.count (scan, a single acquisition of at most
 // EXACT_SCAN_MAX candidates: the blocks shortlist for themselves), then -- combine -- its unit sums into
 // a.exact_l / a.exact_g; wide: behind the staged acquisition's short tail (short shortlists: the re-score's wide

@@ -51,6 +51,7 @@
 
 #include "hbx_acq_impl.h"
 #include "hbx_exact_impl.h"
+#include "hbx_lr_interval.h"
 
 // ---- the model --------------------------------------------------------------------------------------------
 // Inputs are hbx_kde_fit's, as they lie on the device: group b's rows are X[seg_off[b] + order[seg_off[b] + j]], good
@@ -612,79 +613,8 @@ __device__ __forceinline__ GScreen grp_emit(int D, int st, bool certified, const
 // ---- the log-ratio route's record ----------------------------------------------------------------------------
 #define GS_NAN 16u  // log-ratio route: l or g certainly negative, so s = ln g - ln l is NaN: never picked, not re-scored
 
-// fp64 -> fp32 rounded towards -inf / +inf: the cast rounds to nearest, so where it came out on the wrong side of v
-// it is moved one step along hbx_f2ord's order (monotonic over all floats, the sign change and the infinities included)
-__device__ __forceinline__ float grp_f32_down(double v) {
-  const float f = (float)v;
-  return (double)f > v ? hbx_ord2f(hbx_f2ord(f) - 1u) : f;
-}
-__device__ __forceinline__ float grp_f32_up(double v) {
-  const float f = (float)v;
-  return (double)f < v ? hbx_ord2f(hbx_f2ord(f) + 1u) : f;
-}
-
-// The interval of ln P, P = S+ - S- the signed sum of one KDE, from its estimate {lpos = ln S+, lneg = ln S-, e = err}
-// (both with the normaliser added, rounded to fp32).  The screens' bound says each true sum lies within a factor
-// (1 +- e) of the estimated one, so
-//     P in [S+ (1 - e) - S- (1 + e),  S+ (1 + e) - S- (1 - e)].
-// The estimate holds no linear-domain value (the running maximum is an integer exponent, the sums were turned into
-// logs), so both ends are formed in the log domain, in fp64, around the larger of the two logs, hi:
-//     r = exp(lo - hi) <= 1 (the smaller sum over the larger),
-//     ln |P|_hi = hi + log1p(+e - r_lo (1 - e)),      ln |P|_lo = hi + log1p(-e - r_hi (1 + e))   (argument > -1),
-// and the sign of P is that of the larger sum when the lower end exists, unknown otherwise.  Without negative terms
-// (lneg = -inf) r = 0: ln P in [lpos + log1p(-e), lpos + log1p(e)].
-// What the fp32 logs lost, put back outward:
-//   - lpos and lneg were rounded to fp32 once, each off by at most 2^-24 |value|.  r therefore carries a factor within
-//     exp(+-dd), dd = 2^-23 (|lpos| + |lneg|) + 2^-40 (twice the roundings: the fp64 subtraction and exp sit in the
-//     other half); r_lo = r (1 - dd) <= r exp(-dd) and r_hi = r (1 + 1.02 dd) >= r exp(dd) for dd <= 0.03 -- a
-//     candidate with a larger dd is not certified.
-//   - the base hi is off by the same rounding: sl = 2^-23 |hi| + 2^-20 is taken from the lower end and added to the
-//     upper one; the 2^-20 (1e-6) covers the fp64 evaluation of log1p and exp, the normaliser's fp64 roundings and the
-//     difference between the true pdf and the exact re-score's value (grp_exact_rel, 1e-13), with four decimal orders
-//     to spare.
-// `neg`: the KDE has a negative match factor.  Its exact value is ln of the linear fp64 pdf as it is, so a bound is
-// only worth something while that pdf is a normal number: below ln p = -700 the candidate is not certified.  (Without
-// a negative factor the re-score takes the log-space value there, which the bound does cover.)  Above +700 nothing is
-// certified either.
-// Returns sg: +1 P certainly positive, ln P in [lo, hi]; 0 the interval holds 0, ln max(P, 0) <= hi; -1 P certainly
-// negative and far from underflow; 2 not usable.
-struct GrpLnIv {
-  double lo, hi;
-  int sg;
-};
-__device__ __forceinline__ GrpLnIv grp_ln_interval(const KdeEst e, bool neg) {
-  GrpLnIv v;
-  v.lo = v.hi = NAN;
-  v.sg = 2;
-  const double lp = (double)e.lpos, ln = (double)e.lneg, er = (double)e.err;
-  if (!(lp == lp) || !(ln == ln) || !(er >= 0.0 && er < 0.9)) return v;
-  const double hi = fmax(lp, ln), lo = fmin(lp, ln);
-  if (!(hi > -INFINITY && hi < INFINITY)) return v;  // (no term at all, or an overflow)
-  const double dd = 0x1p-23 * (fabs(lp) + (ln > -INFINITY ? fabs(ln) : 0.0)) + 0x1p-40;
-  if (!(dd <= 0.03)) return v;
-  const double r = lo > -INFINITY ? exp(lo - hi) : 0.0;
-  const double sl = 0x1p-23 * fabs(hi) + 0x1p-20;
-  const double ahi = er - r * (1.0 - dd) * (1.0 - er), alo = -er - r * (1.0 + 1.02 * dd) * (1.0 + er);
-  const double mhi = hi + log1p(ahi) + sl;
-  const double mlo = alo > -1.0 + 0x1p-40 ? hi + log1p(alo) - sl : -INFINITY;
-  if (!(mhi < 700.0)) return v;
-  if (mlo == -INFINITY) {  // the sign is open: usable (as "may be 0") only where the positive sum is the larger one
-    if (lp < ln) return v;
-    v.sg = 0;
-    v.lo = -INFINITY;
-    v.hi = mhi;
-    return v;
-  }
-  if (lp < ln) {  // certainly negative -- NaN by definition, provided the exact pdf cannot underflow to -0
-    if (mlo > -700.0) v.sg = -1;
-    return v;
-  }
-  if (neg && !(mlo > -700.0)) return v;
-  v.sg = 1;
-  v.lo = mlo;
-  v.hi = mhi;
-  return v;
-}
+// (grp_f32_down / grp_f32_up, grp_ln_interval and the interval of s, lr_s_interval: hbx_lr_interval.h, shared with the
+// single-pool log-ratio acquisition, hbx_acquire_lr.hip)
 
 // Both estimates -> the interval of s = ln g - ln l with no floor -> the candidate's slot (the screens' <.., LR = true>
 // instances).  slo = ln g_lo - ln l_hi, shi = ln g_hi - ln l_lo in fp64 from grp_ln_interval's ends; the subtraction's
@@ -697,19 +627,14 @@ __device__ __forceinline__ GrpLnIv grp_ln_interval(const KdeEst e, bool neg) {
 // and no GS_OF.
 __device__ __forceinline__ GScreen grp_emit_lr(int D, int st, bool certified, const KdeEst& est_l, const KdeEst& est_g) {
   if (!certified) return grp_uncertified(D, st);
-  const GrpLnIv l = grp_ln_interval(est_l, st & GRP_NEG(0)), g = grp_ln_interval(est_g, st & GRP_NEG(1));
-  if (l.sg == 2 || g.sg == 2 || l.sg == 0) return grp_uncertified(D, st);
+  const LrIv v = lr_s_interval(grp_ln_interval(est_l, st & GRP_NEG(0)), grp_ln_interval(est_g, st & GRP_NEG(1)));
+  if (v.kind == LR_IV_FORCE) return grp_uncertified(D, st);
   GScreen o;
   o.rel = (float)((grp_exact_rel(D, st & GRP_NEG(0), &est_l) + grp_exact_rel(D, st & GRP_NEG(1), &est_g) + 0x1p-51) *
                   1.000001);
-  if (l.sg < 0 || g.sg < 0) {
-    o.slo = o.shi = NAN;
-    o.fl = GS_NAN;
-    return o;
-  }
-  o.slo = g.sg == 0 ? -INFINITY : grp_f32_down(g.lo - l.hi);
-  o.shi = g.sg == 0 ? INFINITY : grp_f32_up(g.hi - l.lo);  // (g may be negative: s may be NaN, nothing bounds it above)
-  o.fl = 0u;
+  o.slo = v.slo;
+  o.shi = v.shi;
+  o.fl = v.kind == LR_IV_NAN ? GS_NAN : 0u;
   return o;
 }
 

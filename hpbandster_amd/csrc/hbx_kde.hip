@@ -79,9 +79,7 @@ __global__ __launch_bounds__(256) void kde_merge_splits_kernel(KdeEst* __restric
   if (ns > 1) (g ? eg : el)[i] = merge_splits(g ? eg : el, Nc, i, ns);
 }
 
-#ifndef COMBINE_SUB
-#define COMBINE_SUB 2  // 256-candidate sub-blocks per block of kde_combine_kernel (2: 13-15 us at 1e6, 4: 15-17, 8: 19)
-#endif
+// (COMBINE_SUB, the 256-candidate sub-blocks per block: hbx_acquire.h)
 // RESCUE: the rescue pass done here (a single acquisition scored by a 32x32 pair launch without splits):
 // with the scoring launch's marker count non-zero, a thread re-scores its own marked candidates before
 // combining them (kde_rescue_one, the rescue kernel's arithmetic) and stores them for the later steps --
@@ -245,16 +243,8 @@ __global__ __launch_bounds__(256) void kde_shortlist_kernel(const float* __restr
   }
 }
 
-// A get_config pick published to device-mapped host memory by the final argmin (hbx_kde_acquire_bound with err /
-// row_out): the record, whether any of the call's candidates hit a sampler domain error, the winning row (as
-// tagged 8-byte words: kde_final_kernel)
-struct PickOut {
-  const double* cand;
-  const uint8_t* err;  // nullable
-  int64_t Nc;
-  int32_t D;
-  char* out;  // null: no pick
-};
+// (PickOut, a get_config pick published to device-mapped host memory, and the publishing tail acq_publish:
+// hbx_acq_impl.h, shared with the log-ratio acquisition's final kernel)
 
 // the final argmin of one acquisition (256 threads): the split re-score's unit sums -> pdfs, strict '<'
 // first-index argmin over the shortlist, the near set, the result record
@@ -277,12 +267,7 @@ __global__ __launch_bounds__(256) void kde_final_kernel(const int32_t* __restric
   __shared__ double rb_sh;
   __shared__ int32_t nnear;
   const int cnt = *count;
-  int err_any = 0;
-  if (pick.out && pick.err) {  // uniform
-    bool e = false;
-    for (int64_t i = threadIdx.x; i < pick.Nc; i += 256) e = e || pick.err[i] != 0;
-    err_any = __syncthreads_or(e);
-  }
+  const int err_any = acq_pick_err_any(pick);
   // shortlists of <= 256 (the common case): thread p owns candidate p -- its index and bound are loaded
   // first, beside the unit sums' combination, and its pdfs come back through LDS
   const bool small = cnt <= 256;
@@ -380,24 +365,7 @@ __global__ __launch_bounds__(256) void kde_final_kernel(const int32_t* __restric
     *res = r;
     rec_sh = r;
   }
-  if (host_res || pick.out) {  // uniform: the record (and a pick's flag and row) to mapped host memory
-    static_assert(sizeof(AcqResult) % 4 == 0, "record of whole words");
-    __syncthreads();
-    // every 32-bit word as one 8-byte system-scope store tagged with the call's sequence number (seq << 32 |
-    // word): the host takes each word only once its tag is the call's, so there is no acknowledgement wait
-    // and no completion word (wait_tagged)
-    uint64_t* out = (uint64_t*)(pick.out ? pick.out : (char*)host_res);
-    const uint64_t tag = (uint64_t)(uint32_t)seq << 32;
-    constexpr int RW = (int)(sizeof(AcqResult) / 4);
-    if (threadIdx.x < RW) hbx_publish_store64(out + threadIdx.x, tag | ((const uint32_t*)&rec_sh)[threadIdx.x]);
-    if (pick.out) {  // a pick: + the domain-error flag (word RW) and the winning row (words RW + 1 ..)
-      if (threadIdx.x == 0) hbx_publish_store64(out + RW, tag | (err_any ? 1u : 0u));
-      const int64_t idx = rec_sh.index - index_base;
-      if (rec_sh.index >= 0 && idx < pick.Nc)
-        for (int w = threadIdx.x; w < 2 * pick.D; w += 256)
-          hbx_publish_store64(out + RW + 1 + w, tag | ((const uint32_t*)(pick.cand + idx * pick.D))[w]);
-    }
-  }
+  acq_publish(&rec_sh, host_res, seq, pick, index_base, err_any);  // the record (and a pick's flag and row)
 }
 
 // Batched argmin, three passes over the shortlist: (1) per-segment minimum of the exact score,
@@ -528,7 +496,7 @@ __global__ __launch_bounds__(256) void kde_exact_logs_kernel(const int32_t* __re
 // ------------------------------------------------------------------------------------------
 // launch side
 
-WsLayout ws_layout(int64_t Nc, int64_t nmax, int64_t B) {
+WsLayout ws_layout(int64_t Nc, int64_t nmax, int64_t B, bool lr) {
   WsLayout w;
   size_t o = 0;
   auto take = [&](size_t bytes) {
@@ -573,6 +541,14 @@ WsLayout ws_layout(int64_t Nc, int64_t nmax, int64_t B) {
   // of the split partials -- no block count at which the fold would have to be off, nothing to reason about when
   // another launch starts to use that area
   w.bmax = take(4 * (size_t)((Nc + 255) / 256));
+  // the log-ratio acquisition (hbx_acquire_lr.hip), behind everything else and only under its flag, so every other
+  // call's layout and size stay what they are: per shortlist entry L_l, L_g and their log-space bounds, two counters
+  w.lr_L = w.lr_bnd = w.lr_stat = o;
+  if (lr) {
+    w.lr_L = take(8 * (size_t)2 * Nc);
+    w.lr_bnd = take(8 * (size_t)2 * Nc);
+    w.lr_stat = take(8);
+  }
   w.total = o;
   return w;
 }
@@ -590,10 +566,10 @@ const KdePairRef* acq_pair(const char* who, const void* pair) {
   return (const KdePairRef*)pair;
 }
 
-int acq_plan(const KdePairRef& p, bool fast, AcqPlan* plan) {
+int acq_plan(const KdePairRef& p, bool fast, AcqPlan* plan, bool coarse_ok) {
   plan->exact_only = KdeVariant::decode(p.variant_good).exact_only || KdeVariant::decode(p.variant_bad).exact_only;
-  plan->fg = pick_logpdf(p.dc_pad, p.du_pad, p.variant_good, fast);
-  plan->fb = pick_logpdf(p.dc_pad, p.du_pad, p.variant_bad, fast);
+  plan->fg = pick_logpdf(p.dc_pad, p.du_pad, p.variant_good, fast, coarse_ok);
+  plan->fb = pick_logpdf(p.dc_pad, p.du_pad, p.variant_bad, fast, coarse_ok);
   if (!plan->exact_only && (!plan->fg.main || !plan->fb.main))
     return hbx_fail(HBX_ERR_UNSUPPORTED, "no kernel for dc_pad=%d du_pad=%d", p.dc_pad, p.du_pad);
   return HBX_OK;
@@ -629,6 +605,38 @@ int acq_exact_only_init(int64_t Nc, uint32_t seg, const AcqWs& a, hipStream_t s)
   hipLaunchKernelGGL(kde_exact_only_init_kernel, dim3((unsigned)((Nc + 255) / 256)), dim3(256), 0, s, Nc, seg, a.el,
                      a.eg, a.lo, a.flags);
   HBX_LAUNCH_CHECK();
+  return HBX_OK;
+}
+
+int acq_shortlist(int64_t Nc, const AcqWs& a, hipStream_t s) {
+  hipLaunchKernelGGL(kde_shortlist_kernel, dim3((unsigned)((Nc + 255) / 256)), dim3(256), 0, s, a.lo, Nc,
+                     (uint32_t)(Nc > 0 ? Nc : 1), a.U, a.flags, a.list, a.count, (int32_t*)nullptr, a.first1, a.rescue);
+  HBX_LAUNCH_CHECK();
+  return HBX_OK;
+}
+
+int acq_bound_wait(const char* who, const char* pub, int32_t seq, bool pick, int32_t D, int64_t Nc, int64_t index_base,
+                   hipStream_t s, void* rec_out, double* row_out) {
+  // the final kernel's tagged words: the record, then (a pick) the flag, then the row when there is a winner
+  constexpr int RW = (int)(sizeof(AcqResult) / 4);
+  constexpr int64_t SPIN = 20000000;  // ~0.1 s
+  const volatile uint64_t* w = (const volatile uint64_t*)pub;
+  uint32_t words[RW];
+  int rc = wait_tagged(w, RW, seq, words, s, SPIN, who);
+  if (rc) return rc;
+  AcqResult r;
+  memcpy(&r, words, sizeof(AcqResult));
+  if (pick) {
+    uint32_t e = 0;
+    rc = wait_tagged(w + RW, 1, seq, &e, s, SPIN, who);
+    if (rc) return rc;
+    if (e) r.flags |= HBX_ACQ_DOMAIN_ERR;
+    if (row_out && r.index >= 0 && r.index - index_base < Nc) {
+      rc = wait_tagged(w + RW + 1, 2 * D, seq, (uint32_t*)row_out, s, SPIN, who);
+      if (rc) return rc;
+    }
+  }
+  memcpy(rec_out, &r, sizeof(AcqResult));
   return HBX_OK;
 }
 
@@ -846,27 +854,7 @@ int hbx_kde_acquire_bound(const void* pair, const double* cand, int64_t Nc, int6
                            events, stream, pick ? nullptr : (AcqResult*)pub, seq,
                            pick ? PickOut{cand, err, Nc, b.D, pub} : PickOut{}});
   if (rc) return rc;
-  // the final kernel's tagged words: the record, then (a pick) the flag, then the row when there is a winner
-  constexpr int RW = (int)(sizeof(AcqResult) / 4);
-  constexpr int64_t SPIN = 20000000;  // ~0.1 s
-  const volatile uint64_t* w = (const volatile uint64_t*)pub;
-  uint32_t words[RW];
-  rc = wait_tagged(w, RW, seq, words, s, SPIN, who);
-  if (rc) return rc;
-  AcqResult r;
-  memcpy(&r, words, sizeof(AcqResult));
-  if (pick) {
-    uint32_t e = 0;
-    rc = wait_tagged(w + RW, 1, seq, &e, s, SPIN, who);
-    if (rc) return rc;
-    if (e) r.flags |= HBX_ACQ_DOMAIN_ERR;
-    if (row_out && r.index >= 0 && r.index - index_base < Nc) {
-      rc = wait_tagged(w + RW + 1, 2 * b.D, seq, (uint32_t*)row_out, s, SPIN, who);
-      if (rc) return rc;
-    }
-  }
-  memcpy(rec_out, &r, sizeof(AcqResult));
-  return HBX_OK;
+  return acq_bound_wait(who, pub, seq, pick, b.D, Nc, index_base, s, rec_out, row_out);
 }
 
 // Byte offsets inside an acquisition workspace of (Nc, seg, nmax) -- hbx_kde_acquire: seg = Nc -- of

@@ -22,7 +22,9 @@ struct ScoreFns {
 // variant: a prepared KDE's code (KdeVariant, hbx_kde_impl.h)
 // fast: the acquisition's instance where one exists (the 32x32 kernel without the one-hot lo steps,
 // their bound added) -- its ln-pdf estimates are looser than 1e-5, so calls that report them do not use it
-ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast);
+// coarse_ok = false: fast without the coarse 32x32 pre-screen instance, whose bound suits the floored score's screen
+// but can exceed what the log-ratio interval certifies (hbx_lr_interval.h: err < 0.9)
+ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast, bool coarse_ok = true);
 
 // Observation splits of a pair launch with `tiles` candidate tiles per KDE over <= nmax observations
 // (HBX_OBS_SPLIT=0: none; ws_sizing: the workspace's bound, no switch) ...

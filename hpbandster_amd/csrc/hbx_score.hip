@@ -107,7 +107,7 @@ static const ScoreFns NO_SCORE_FNS{nullptr, nullptr, 0, 0, nullptr, nullptr};  /
 // (the variant code and `fast`: hbx_score.h)  The family's file picks the instance and says what block it is
 // compiled for; here: which family a variant runs, the rescue kernels of its bucket, and what the coarse
 // instances need around them.
-ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast) {
+ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast, bool coarse_ok) {
   const KdeVariant v = KdeVariant::decode(variant);
   const bool sg = v.has_neg;
   const int kc = du_pad == 0 ? 0 : v.kc;  // no categorical dims: kc irrelevant
@@ -127,7 +127,7 @@ ScoreFns pick_logpdf(int dc_pad, int du_pad, int variant, bool fast) {
   if (v.hmode && dc_pad < 8) return NO_SCORE_FNS;
   if (v.hmode && v.h32) {
     const int kp = h32_kp(kc);
-    const bool co = fast && !sg && v.coarse;  // the acquisition's coarse pre-screen instance
+    const bool co = fast && !sg && v.coarse && coarse_ok;  // the acquisition's coarse pre-screen instance
     const H32Inst h = hbx_pick_h32(nsc_of(dc_pad), kp, sg, fast && kp > 0, co);
     ScoreFns f{h.main, r.one, h.cands_per_block, h.threads, h.pair, r.pair, true};
     if (co && H32C_CT > 1) f.pair1 = h.pair1;

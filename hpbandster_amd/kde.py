@@ -25,6 +25,15 @@ from . import _native as N
 RESULT_FMT = "<qdfiiidd"  # AcqResult: index, score, rel, flags, shortlist, near, pdf_l, pdf_g
 RESULT_BYTES = struct.calcsize(RESULT_FMT)
 ACQ_OVERFLOW, ACQ_NEAR_TIE, ACQ_RESOLVED, ACQ_DOMAIN_ERR = 1, 2, 4, 8  # include/hbx.h HBX_ACQ_*
+ACQ_LOG_RATIO = 128  # HBX_ACQ_LOG_RATIO: the record was picked by ln g - ln l (score="log_ratio")
+# a single pool's selection rules: the reference's floored max(f, g)/max(l, f), or s = ln g - ln l with no floor
+ACQ_SCORES = ("floored", "log_ratio")
+
+
+def _check_score(score):
+    if score not in ACQ_SCORES:
+        raise ValueError("score must be 'floored' or 'log_ratio', got %r" % (score,))
+    return score == "log_ratio"
 
 
 def _torch():
@@ -441,6 +450,7 @@ class KDEPair(object):
         # codes): every acquisition takes the handle
         self._bound = None
         self._bound_fn = L.hbx_kde_acquire_bound
+        self._bound_lr_fn = getattr(L, "hbx_kde_acquire_bound_lr", None)  # (absent from an older build under A/B)
         self._free_fn = L.hbx_kde_pair_free
         self._bound = L.hbx_kde_pair_bind(
             good.k_vars, good.params.data_ptr(), good.table.data_ptr(), good.X_dev.data_ptr(),
@@ -479,34 +489,40 @@ class KDEPair(object):
             self._roff = int(N.lib().hbx_kde_result_ptr(4096)) - 4096
         return self._roff
 
-    def workspace_bytes(self, Nc):
-        wsb = self._wsb.get(Nc)
+    def workspace_bytes(self, Nc, score="floored"):
+        """Bytes of an acquisition workspace for ``Nc`` candidates; ``score="log_ratio"``: of that route's (never
+        smaller: the floored layout with its arrays appended)."""
+        lr = _check_score(score)
+        wsb = self._wsb.get((Nc, lr))
         if wsb is None:
-            wsb = self._wsb[Nc] = int(N.lib().hbx_kde_workspace_bytes(int(Nc), self.nmax))
+            fn = N.lib().hbx_kde_lr_workspace_bytes if lr else N.lib().hbx_kde_workspace_bytes
+            wsb = self._wsb[(Nc, lr)] = int(fn(int(Nc), self.nmax))
         return wsb
 
-    def _thread_workspace(self, Nc):
+    def _thread_workspace(self, Nc, lr=False):
         """This thread's workspace for synchronous calls over ``Nc`` candidates made without one: allocated on
-        first use (workspace_bytes), kept for the pair's lifetime."""
+        first use (workspace_bytes; the log-ratio route's serves both), kept for the pair's lifetime."""
         key = (threading.get_ident(), Nc)
         ws = self._ws_cache.get(key)
-        if ws is None:
-            ws = self._ws_cache[key] = _torch().empty(self.workspace_bytes(Nc), dtype=_torch().uint8,
-                                                      device=self.good.device)
+        if ws is None or (lr and ws.numel() < self.workspace_bytes(Nc, "log_ratio")):
+            ws = self._ws_cache[key] = _torch().empty(self.workspace_bytes(Nc, "log_ratio" if lr else "floored"),
+                                                      dtype=_torch().uint8, device=self.good.device)
         return ws
 
-    def _acquire_bound(self, cand_ptr, Nc, index_base, ws, sh, err=None, events=None, row=None):
-        """THE synchronous acquisition (hbx_kde_acquire_bound): ``Nc`` candidates at address ``cand_ptr`` scored
+    def _acquire_bound(self, cand_ptr, Nc, index_base, ws, sh, err=None, events=None, row=None, lr=False):
+        """THE synchronous acquisition (hbx_kde_acquire_bound; ``lr``: hbx_kde_acquire_bound_lr): ``Nc`` candidates at
+        address ``cand_ptr`` scored
         on stream handle ``sh`` (ordered after the model's preparation first) with workspace ``ws``, the record
         published to this thread's host buffer when the call returns -> AcqResult.  ``err`` (device u8 [Nc]):
         any set flag comes back as ACQ_DOMAIN_ERR; ``row`` (host f64 [D]): receives the winning row."""
         if sh != self._home:
             self._order(sh)
         rec = _record_buffer()
-        N.check(self._bound_fn(self._bound, cand_ptr, Nc, int(index_base), ws.data_ptr(), ws.numel(),
-                               err.data_ptr() if err is not None else None,
-                               events.address if events is not None else None, sh, rec,
-                               row.ctypes.data if row is not None else None))
+        fn = self._bound_lr_fn if lr else self._bound_fn
+        N.check(fn(self._bound, cand_ptr, Nc, int(index_base), ws.data_ptr(), ws.numel(),
+                   err.data_ptr() if err is not None else None,
+                   events.address if events is not None else None, sh, rec,
+                   row.ctypes.data if row is not None else None))
         return AcqResult.from_bytes(rec.raw[:RESULT_BYTES])
 
     def acquire_stats(self, workspace, Nc):
@@ -531,8 +547,15 @@ class KDEPair(object):
         return {"lhi_epilogue": bool(out[0]), "lmax_bits": int(out[1])}
 
     def acquire(self, cands, index_base=0, logs=False, stream=None, workspace=None, sync=True, events=None,
-                ties="pinned"):
+                ties="pinned", score="floored"):
         """Select the first index minimising max(f, g)/max(l, f) over the candidates (f: the pair's ``pdf_floor``).
+
+        ``score="log_ratio"``: the first index minimising s = ln g - ln l instead, with no floor
+        (hbx_kde_acquire_lr) -- where both densities lie under the floor the floored score is exactly 1 and its
+        argmin returns candidate 0; s still orders those candidates.  Ordered by (s, index), +inf last, NaN never
+        picked (index -1 when no candidate has a score).  The record's ``score`` is s, ``pdf_l`` / ``pdf_g`` the
+        winner's exact pdfs, ``flags`` carries ACQ_LOG_RATIO.  Unstaged; no ``logs`` (the call forms no ln-pdfs of
+        every candidate) and no ``ties='process'`` (the host re-resolution forms the floored score): ValueError.
 
         ``cands``: [Nc, D] float64 (numpy or a device tensor).  Returns AcqResult (index -1 when no
         candidate has a finite score: the reference then falls back to a random configuration).
@@ -559,9 +582,14 @@ class KDEPair(object):
         """
         if ties not in ("pinned", "process"):
             raise ValueError("ties must be 'pinned' or 'process'")
+        lr = _check_score(score)
+        if lr and logs:
+            raise ValueError("score='log_ratio' returns no ln-pdf estimates (logs=True)")
+        if lr and ties == "process":
+            raise ValueError("score='log_ratio' offers ties='pinned' only")
         sh = N.home_stream(self._dev_index) if sync and not logs and stream is None else None
         if sh is not None:
-            r = self._acquire_sync(cands, index_base, workspace, events, sh)
+            r = self._acquire_sync(cands, index_base, workspace, events, sh, lr)
             if r is not None:
                 if ties == "process" and r.flags & ACQ_NEAR_TIE:
                     with N.on_device(self.good.device):
@@ -569,9 +597,9 @@ class KDEPair(object):
                         self._resolve(r, ws, len(cands), len(cands), cands, int(index_base))
                 return r
         with N.on_device(self.good.device, stream):
-            return self._acquire(cands, index_base, logs, stream, workspace, sync, events, ties)
+            return self._acquire(cands, index_base, logs, stream, workspace, sync, events, ties, lr)
 
-    def _acquire_sync(self, cands, index_base, workspace, events, sh):
+    def _acquire_sync(self, cands, index_base, workspace, events, sh, lr=False):
         """The drop-in's common call -- synchronous, the winner only, on the model's device and its current
         stream ``sh``, which is this thread's current device (no device switch): the bound call with the fewest
         host steps around it; a workspace is kept per thread and candidate count when none is given.  None when
@@ -585,10 +613,10 @@ class KDEPair(object):
             return None
         Nc = cands.shape[0]
         if workspace is None:
-            workspace = self._thread_workspace(Nc)
-        elif workspace.numel() < self.workspace_bytes(Nc):
+            workspace = self._thread_workspace(Nc, lr)
+        elif workspace.numel() < self.workspace_bytes(Nc, "log_ratio" if lr else "floored"):
             raise N.HbxError("workspace too small")
-        return self._acquire_bound(cands.data_ptr(), Nc, index_base, workspace, sh, None, events)
+        return self._acquire_bound(cands.data_ptr(), Nc, index_base, workspace, sh, None, events, lr=lr)
 
     def _stage_cands(self, cands):
         """The general paths' candidates on the model's device, checked: (device tensor, Nc)."""
@@ -618,22 +646,27 @@ class KDEPair(object):
         if ties == "process" and res.flags & ACQ_NEAR_TIE:
             self._resolve(res, ws, Nc, Nc, cands if isinstance(cands, np.ndarray) else c_dev, int(index_base))
 
-    def _acquire(self, cands, index_base, logs, stream, workspace, sync, events, ties):
+    def _acquire(self, cands, index_base, logs, stream, workspace, sync, events, ties, lr=False):
         torch = _torch()
         L = N.lib()
         dev = self.good.device
         c_dev, Nc = self._stage_cands(cands)
-        ws = self._workspace(workspace, self.workspace_bytes(Nc))
+        ws = self._workspace(workspace, self.workspace_bytes(Nc, "log_ratio" if lr else "floored"))
         logl = torch.empty(Nc, dtype=torch.float32, device=dev) if logs else None
         logg = torch.empty(Nc, dtype=torch.float32, device=dev) if logs else None
         sh = N.stream_handle(stream, dev)
         if sync and not logs:  # one native call: the acquisition and its record on the host
-            res = self._acquire_bound(c_dev.data_ptr(), Nc, index_base, ws, sh, None, events)
+            res = self._acquire_bound(c_dev.data_ptr(), Nc, index_base, ws, sh, None, events, lr=lr)
             self._resolve_if_near(ties, res, ws, Nc, cands, c_dev, index_base)
             return res
         self._order(sh)
-        N.check(L.hbx_kde_acquire(c_dev.data_ptr(), Nc, int(index_base), self._bound, N.ptr(logl), N.ptr(logg),
-                                  ws.data_ptr(), ws.numel(), events.address if events is not None else None, sh))
+        ev = events.address if events is not None else None
+        if lr:
+            N.check(L.hbx_kde_acquire_lr(c_dev.data_ptr(), Nc, int(index_base), self._bound, ws.data_ptr(),
+                                         ws.numel(), ev, sh))
+        else:
+            N.check(L.hbx_kde_acquire(c_dev.data_ptr(), Nc, int(index_base), self._bound, N.ptr(logl), N.ptr(logg),
+                                      ws.data_ptr(), ws.numel(), ev, sh))
         off = self.result_offset()
         rview = ws[off:off + RESULT_BYTES]
         if not sync:
@@ -716,29 +749,32 @@ class KDEPair(object):
             if r.flags & ACQ_NEAR_TIE:
                 self._repick(r, cands, np.sort(lst[(flg != 0) & (lst // seg == b)]), -b * seg)
 
-    def acquire_mapped(self, cands):
+    def acquire_mapped(self, cands, score="floored"):
         """acquire(cands) for a host array from mapped_candidates(): the kernels read the candidates in host
-        memory (zero copy), the pick comes back in the same synchronous call (hbx_kde_acquire_bound).  Falls
-        back to acquire() off the fast path's conditions (another current device)."""
+        memory (zero copy), the pick comes back in the same synchronous call (hbx_kde_acquire_bound; ``score``:
+        acquire()'s).  Falls back to acquire() off the fast path's conditions (another current device)."""
+        lr = _check_score(score)
         sh = N.home_stream(self._dev_index)
         if sh is None:
-            return self.acquire(np.array(cands))
+            return self.acquire(np.array(cands), score=score)
         Nc = cands.shape[0]
-        return self._acquire_bound(cands.ctypes.data, Nc, 0, self._thread_workspace(Nc), sh)
+        return self._acquire_bound(cands.ctypes.data, Nc, 0, self._thread_workspace(Nc, lr), sh, lr=lr)
 
-    def acquire_pick(self, cands, err, workspace, row, sh=None):
+    def acquire_pick(self, cands, err, workspace, row, sh=None, score="floored"):
         """One synchronous acquisition of ``cands`` (a device [Nc, D] f64 tensor on the model's device) with its
         whole pick on the host after ONE wait (hbx_kde_acquire_bound with err and row_out): the record, whether
         any ``err`` flag (the GPU sampler's per-candidate domain errors, a device u8 tensor or None) is set
         (ACQ_DOMAIN_ERR in ``flags``), and the winning row written into ``row`` (a host f64 array of D).
         ``sh``: the stream handle (default: the device's current stream; a thread on another device makes the
-        call with the model's device current).  Returns the AcqResult."""
+        call with the model's device current).  ``score``: acquire()'s ("log_ratio": ``workspace`` of
+        ``workspace_bytes(Nc, "log_ratio")``).  Returns the AcqResult."""
+        lr = _check_score(score)
         if sh is None:
             sh = N.home_stream(self._dev_index)
             if sh is None:
                 with N.on_device(self.good.device):
-                    return self.acquire_pick(cands, err, workspace, row, N.stream_handle(None, self.good.device))
-        return self._acquire_bound(cands.data_ptr(), int(cands.shape[0]), 0, workspace, sh, err, None, row)
+                    return self.acquire_pick(cands, err, workspace, row, N.stream_handle(None, self.good.device), score)
+        return self._acquire_bound(cands.data_ptr(), int(cands.shape[0]), 0, workspace, sh, err, None, row, lr=lr)
 
     def batch_workspace_bytes(self, Nc, seg):
         return int(N.lib().hbx_kde_batch_workspace_bytes(int(Nc), int(seg), self.nmax))

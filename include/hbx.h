@@ -263,6 +263,35 @@ int hbx_kde_acquire_bound(const void* pair, const double* cand, int64_t Nc, int6
                           double* row_out);
 void hbx_kde_pair_free(void* pair);
 
+/* Acquisition of ONE pool by log ratio: the first index minimising s = ln g - ln l, with no floor -- what
+ * hbx_kde_acquire_groups_batch_lr is to the grouped engine, for hbx_kde_acquire's and hbx_kde_acquire_bound's callers.
+ * (The floored score is exactly 1 wherever both densities lie under the floor, and its argmin then returns candidate
+ * 0; s still orders those candidates.)  The order is hbx_kde_rank_groups' for k = 1: the key of a candidate is s --
+ * finite values and -inf by value, +inf behind them, NaN never picked -- and the lower index among equal keys; index -1
+ * when no candidate has a score.  Per KDE, L = ln of the exact fp64 pdf p where p is a positive normal number, NaN
+ * where p is negative or NaN, and for a zero or subnormal p the fp64 log-space value of ln p (a KDE without a
+ * negative categorical match factor; its bound: hbx_acquire_lr.hip) or log(p) as it is (a KDE with one); s = L_g - L_l.
+ * The call screens by intervals of s from the fp32 scoring (unstaged; the coarse 32x32 instance where the pair has one,
+ * HBX_LR_COARSE=0: the fast instance without it),
+ * re-scores the candidates that can still be the minimum exactly, and does not form ln-pdfs of every candidate: there
+ * are no logl / logg outputs.  The pair's pdf_floor plays no part.
+ * The record (hbx_kde_result_ptr, or rec_out) on this route: index as above (+ index_base); score = s; pdf_l, pdf_g
+ * the winner's exact pdfs (the reference's values bit for bit); shortlist the candidates re-scored; near the re-scored
+ * candidates with s <= s_best + 1.0001 (rel + rel_best), rel the winner's absolute bound of s (both pdfs' relative
+ * bounds and the log-space bounds), HBX_ACQ_NEAR_TIE when near > 1; HBX_ACQ_OVERFLOW for exact-only pairs (the whole
+ * pool re-scored); HBX_ACQ_LOG_RATIO always, the empty record of Nc == 0 included.
+ * hbx_kde_acquire_bound_lr: hbx_kde_acquire_bound's arguments and publish (err, row_out, one wait).
+ * Workspace: hbx_kde_lr_workspace_bytes(Nc, nmax) -- hbx_kde_acquire's layout with this route's arrays appended, so
+ * hbx_kde_result_ptr and hbx_kde_ws_offsets hold for it.  Its last 256-byte slot begins with two int32 counters of
+ * the last call: log-space evaluations, forced (uncertified) candidates re-scored.
+ * Not offered by log ratio: the batched call, top-k, the staged form, the multi-GPU reduction. */
+int64_t hbx_kde_lr_workspace_bytes(int64_t Nc, int64_t nmax);
+int hbx_kde_acquire_lr(const double* cand, int64_t Nc, int64_t index_base, const void* pair, void* workspace,
+                       int64_t ws_bytes, void* events, void* stream);
+int hbx_kde_acquire_bound_lr(const void* pair, const double* cand, int64_t Nc, int64_t index_base, void* workspace,
+                             int64_t ws_bytes, const uint8_t* err, void* events, void* stream, void* rec_out,
+                             double* row_out);
+
 /* Batched acquisition: B = ceil(Nc / seg) independent get_config calls against the same model in one
  * pass (replaces B sequential runs of the bohb.py:124-169 loop, as an SH stage issues
  * them back to back, HB_iteration.py:136-138).  Candidates [b*seg, min((b+1)*seg, Nc)) belong to call b;
