@@ -65,6 +65,8 @@ SIGNATURES = {
     "hbx_kde_topk_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64]),
     "hbx_kde_topk_result_bytes": (c_i64, [c_i32]),
     "hbx_kde_acquire_topk": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "hbx_kde_topk_lr_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64]),
+    "hbx_kde_acquire_topk_lr": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "hbx_kde_groups_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
     "hbx_kde_acquire_groups": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),

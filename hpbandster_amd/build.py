@@ -53,7 +53,9 @@ EXTRA_FLAGS = {"hbx_score_h.hip": ["-fno-slp-vectorize"], "hbx_score_h32.hip": [
                # fp64 logs, sums and keys; fp32 only in the screen slots it reads
                "hbx_groups_lr.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # the single-pool log-ratio acquisition: fp64 log-space sums; fp32 only in the interval ends
-               "hbx_acquire_lr.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "hbx_acquire_lr.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               # its top-k: fp64 differences and integer keys; fp32 only in the interval ends
+               "hbx_topk_lr.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def sources():

@@ -175,3 +175,28 @@ int acq_bound_wait(const char* who, const char* pub, int32_t seq, bool pick, int
 #define EXACT_SCAN_MAX 1024
 int acq_exact(const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a, bool scan, bool combine,
               hipStream_t s, bool wide = false);
+
+// The top-k's selection steps (hbx_topk.hip), shared with the top-k by log ratio (hbx_topk_lr.hip).
+#define TOPK_KEY_INF 0xFF800000u   // hbx_f2ord(+inf): keys below it are finite upper bounds
+#define TOPK_HIST_WORDS (4 * 256)  // workspace of the k-th bound's radix select: 4 histograms of 256 bins
+#define TOPK_T 512                 // threads of the final ranking block
+#define TOPK_CAP 2048              // entries of its LDS array: <= k + 1 kept + pending ones
+// The evaluated list of a staged call (hbx_staged.hip; all null / 0: the unstaged call, every candidate)
+struct TopkEval {
+  const uint32_t* stage;
+  const int32_t* seeds;
+  const int32_t* surv;
+  int32_t cap;
+};
+// U[0] = the k-th smallest finite hi (+inf with fewer than k), then the shortlist {i: lo[i] == lo[i] &&
+// (flags[0] & 1 || lo[i] <= U[0])} into list / count; zeroes the scoring launch's marker count.  hik null: no keys
+// (an exact-only acquisition, its histograms zero, U_k = +inf)
+int hbx_topk_shortlist(const float* lo, const uint32_t* hik, int64_t Nc, int32_t k, uint32_t* hist, uint32_t* U,
+                       const int32_t* flags, int32_t* list, int32_t* count, int32_t* rescue_cnt, const TopkEval& ev,
+                       hipStream_t s);
+
+// The log-ratio acquisitions (hbx_acquire_lr.hip), shared with the top-k by log ratio.
+bool acq_lr_coarse();  // HBX_LR_COARSE: whether the scoring may take the coarse 32x32 instance (acq_plan's coarse_ok)
+// The log-space step over the re-scored shortlist a.list / a.count (kde_lr_ln_kernel, one block per (entry, KDE)): per
+// (entry p, KDE) L into a.lr_L[2 p + kd] and its log-space bound (0: none was due) into a.lr_bnd
+int acq_lr_ln(const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a, hipStream_t s);

@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void kde_final_lr_kernel(const int32_t* __rest
 // the pair has one: measured at config #3 it certifies every candidate as well and the call is 1.2 - 1.7 ms against
 // 1.9 - 2.1 (profiles/acquire_lr/README.md).  HBX_LR_SCAN=0: a shortlist launch of its own even for pools of
 // <= EXACT_SCAN_MAX candidates (measured slower at 64).  Both read per call.
-static bool lr_coarse() { return hbx_switch_on("HBX_LR_COARSE"); }
+bool acq_lr_coarse() { return hbx_switch_on("HBX_LR_COARSE"); }
 
 // CUs of the current device (asked once per device)
 static int lr_cu_count() {
@@ -358,6 +358,15 @@ static int lr_cu_count() {
     cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
   }
   return cus[dev];
+}
+
+int acq_lr_ln(const KdePairRef& p, const double* cand, int64_t Nc, const AcqWs& a, hipStream_t s) {
+  const LrLnArgs la{cand, p.D, {p.Pg(), p.Pb()}, {p.X_good, p.X_bad}, {p.rows_good, p.rows_bad}, a.list, a.count,
+                    {a.exact_l, a.exact_g}, a.lr_L, a.lr_bnd};
+  const int64_t cap = 2 * (int64_t)lr_cu_count();  // two blocks per CU
+  hipLaunchKernelGGL(kde_lr_ln_kernel, dim3((unsigned)(2 * Nc < cap ? 2 * Nc : cap)), dim3(LRL_T), 0, s, la);
+  HBX_LAUNCH_CHECK();
+  return HBX_OK;
 }
 
 struct AcqLrCall {
@@ -383,7 +392,7 @@ static int acquire_lr_impl(const void* pair, const AcqLrCall& c) {
   if ((size_t)c.ws_bytes < w.total)
     return hbx_fail(HBX_ERR_ARG, "workspace too small: %lld < %lld bytes", (long long)c.ws_bytes, (long long)w.total);
   AcqPlan plan;
-  rc = acq_plan(p, true, &plan, lr_coarse());
+  rc = acq_plan(p, true, &plan, acq_lr_coarse());
   if (rc) return rc;
   const AcqWs a(c.workspace, w);
   const hipStream_t s = (hipStream_t)c.stream;
@@ -409,11 +418,8 @@ static int acquire_lr_impl(const void* pair, const AcqLrCall& c) {
     }
     rc = acq_exact(p, c.cand, Nc, a, scan, true, s);
     if (rc) return rc;
-    const LrLnArgs la{c.cand, p.D, {p.Pg(), p.Pb()}, {p.X_good, p.X_bad}, {p.rows_good, p.rows_bad}, a.list, a.count,
-                      {a.exact_l, a.exact_g}, a.lr_L, a.lr_bnd};
-    const int64_t cap = 2 * (int64_t)lr_cu_count();  // two blocks per CU
-    hipLaunchKernelGGL(kde_lr_ln_kernel, dim3((unsigned)(2 * Nc < cap ? 2 * Nc : cap)), dim3(LRL_T), 0, s, la);
-    HBX_LAUNCH_CHECK();
+    rc = acq_lr_ln(p, c.cand, Nc, a, s);
+    if (rc) return rc;
   }
   hipLaunchKernelGGL(kde_final_lr_kernel, dim3(1), dim3(256), 0, s, a.list, a.count, a.exact_l, a.exact_g, a.lr_L,
                      a.lr_bnd, a.lo, a.flags, c.index_base, p.Pg(), p.Pb(), a.el, a.eg, a.near, a.res, a.lr_stat,

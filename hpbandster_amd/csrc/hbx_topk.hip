@@ -76,9 +76,6 @@
 #include "hbx_rescue_impl.h"
 #include "hbx_topk_rank.h"
 
-#define TOPK_KEY_INF 0xFF800000u  // hbx_f2ord(+inf): keys below it are finite upper bounds
-#define TOPK_HIST_WORDS (4 * 256)  // workspace of the k-th bound's radix select: 4 histograms of 256 bins
-
 __global__ __launch_bounds__(256) void topk_bounds_kernel(const KdeEst* __restrict__ el,
                                                           const KdeEst* __restrict__ eg, int64_t Nc,
                                                           float* __restrict__ lo, uint32_t* __restrict__ hik,
@@ -170,13 +167,7 @@ __global__ __launch_bounds__(256) void topk_hist_kernel(const uint32_t* __restri
 }
 
 #define TOPK_SHORT_PER_BLOCK 1024
-// The evaluated list of a staged call (hbx_staged.hip; all null / 0: the unstaged call, every candidate)
-struct TopkEval {
-  const uint32_t* stage;
-  const int32_t* seeds;
-  const int32_t* surv;
-  int32_t cap;
-};
+// (TopkEval, hbx_acquire.h: the evaluated list of a staged call; all null / 0: the unstaged call, every candidate)
 __device__ __forceinline__ int32_t topk_entry(const TopkEval& ev, int64_t e) {
   const int64_t ns = (int64_t)ev.stage[HBX_ST_NSEED] < ev.cap ? (int64_t)ev.stage[HBX_ST_NSEED] : ev.cap;
   return e < ns ? ev.seeds[e] : ev.surv[e - ns];
@@ -376,8 +367,7 @@ __global__ __launch_bounds__(256) void topk_staged_bounds_kernel(TopkStagedArgs 
 // ------------------------------------------------------------------------------------------
 // the final ranking
 
-#define TOPK_T 512        // threads of the final block
-#define TOPK_CAP 2048     // entries of its LDS array: <= k + 1 kept + pending ones
+// (TOPK_T threads, TOPK_CAP entries of the LDS array: hbx_acquire.h)
 static_assert(HBX_TOPK_MAX_K + 1 + TOPK_T <= TOPK_CAP, "a chunk fits behind the kept entries after a merge");
 
 __global__ __launch_bounds__(TOPK_T) void topk_final_kernel(
@@ -456,10 +446,9 @@ static int hbx_topk_bounds(const KdeEst* el, const KdeEst* eg, int64_t Nc, float
   return HBX_OK;
 }
 
-// U[0] = the k-th smallest finite hi (+inf with fewer than k), then the shortlist {i: lo[i] == lo[i] &&
-// (flags[0] & 1 || lo[i] <= U[0])} into list / count; zeroes the scoring launch's marker count
+// the select and the shortlist (hbx_acquire.h)
 // ev (a staged call): hik holds one key per entry of the evaluated list, and the shortlist comes from that list
-static int hbx_topk_shortlist(const float* lo, const uint32_t* hik, int64_t Nc, int32_t k, uint32_t* hist, uint32_t* U,
+int hbx_topk_shortlist(const float* lo, const uint32_t* hik, int64_t Nc, int32_t k, uint32_t* hist, uint32_t* U,
                        const int32_t* flags, int32_t* list, int32_t* count, int32_t* rescue_cnt, const TopkEval& ev,
                        hipStream_t s) {
   if (hik) {  // the radix select (no keys: an exact-only acquisition, its histograms zero, U_k = +inf)

@@ -64,7 +64,8 @@ def merge_topk(parts, k):
     shard with its ``index_base``, so the indices are global; every shard's pair under the same rules): the first k entries by (score, index) over all
     parts -- what acquire_topk(k) over the whole pool returns, since every shard returns its own k best and
     each entry of the global top-k is among its shard's.  Pure host code, no collective: any transport may
-    gather the blocks.  ``count`` can be below k (parts with few or no rankable candidates); ``shortlist`` adds
+    gather the blocks.  Shards ranked with ``score="log_ratio"`` merge the same way: s is a property of the candidate
+    alone, and -inf / +inf sort by value.  ``count`` can be below k (parts with few or no rankable candidates); ``shortlist`` adds
     up, ``flags`` are or-ed."""
     from .kde import TopK, TOPK_MAX_K
     k = int(k)

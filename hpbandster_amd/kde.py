@@ -677,10 +677,12 @@ class KDEPair(object):
             return res, logl.cpu().numpy(), logg.cpu().numpy()
         return res
 
-    def topk_workspace_bytes(self, Nc, k):
-        return int(N.lib().hbx_kde_topk_workspace_bytes(int(Nc), int(k), self.nmax))
+    def topk_workspace_bytes(self, Nc, k, score="floored"):
+        L = N.lib()
+        fn = L.hbx_kde_topk_lr_workspace_bytes if _check_score(score) else L.hbx_kde_topk_workspace_bytes
+        return int(fn(int(Nc), int(k), self.nmax))
 
-    def acquire_topk(self, cands, k, index_base=0, stream=None, workspace=None, ties="pinned"):
+    def acquire_topk(self, cands, k, index_base=0, stream=None, workspace=None, ties="pinned", score="floored"):
         """The k best candidates of ONE pool: the first min(k, F) entries of the stable ascending order of
         max(f, g)/max(l, f) (f: the pair's ``pdf_floor``) over the F
         candidates whose score is not NaN -- ordered by (score, index), so
@@ -688,6 +690,12 @@ class KDEPair(object):
         (k > Nc is legal).  Returns a TopK (empty when no candidate has a score: the drop-in then falls back to
         random configurations, as for acquire()'s index -1).  Only ties='pinned' is offered: the GPU's re-score
         is the reference's arithmetic on the pinned numpy bit for bit.
+
+        ``score="log_ratio"``: the k best by s = ln g - ln l instead, with no floor (hbx_kde_acquire_topk_lr) -- where
+        both densities lie under the floor the floored score is exactly 1 and the floored ranking is the lowest
+        indices; s still orders those candidates.  Ordered by (s, index), +inf last, NaN never returned; entry 0 is
+        ``acquire(score="log_ratio")``'s pick.  ``score`` holds s, ``pdf_l`` / ``pdf_g`` the exact pdfs, ``rel`` the
+        absolute bound of s, ``flags`` carries ACQ_LOG_RATIO.  Unstaged.
 
         Large calls whose KDEs both run the coarse 32x32 kernel are scored in stages like ``acquire``'s (the
         same ``HBX_STAGED`` switch; unset, from 4e9 candidates x observations): the good KDE for every candidate, the bad KDE only for
@@ -698,23 +706,24 @@ class KDEPair(object):
         splits).  ``acquire_stats(workspace, Nc)`` on the call's workspace reports what it did."""
         if ties != "pinned":
             raise ValueError("acquire_topk offers ties='pinned' only")
+        lr = _check_score(score)
         k = int(k)
         if k < 1 or k > TOPK_MAX_K:
             raise ValueError("k must be in [1, %d], got %d" % (TOPK_MAX_K, k))
         with N.on_device(self.good.device, stream):
-            return self._acquire_topk(cands, k, index_base, stream, workspace)
+            return self._acquire_topk(cands, k, index_base, stream, workspace, lr)
 
-    def _acquire_topk(self, cands, k, index_base, stream, workspace):
+    def _acquire_topk(self, cands, k, index_base, stream, workspace, lr=False):
         torch = _torch()
         L = N.lib()
         dev = self.good.device
         c_dev, Nc = self._stage_cands(cands)
-        ws = self._workspace(workspace, self.topk_workspace_bytes(Nc, k))
+        ws = self._workspace(workspace, self.topk_workspace_bytes(Nc, k, "log_ratio" if lr else "floored"))
         out = torch.empty(int(L.hbx_kde_topk_result_bytes(k)), dtype=torch.uint8, device=dev)
         sh = N.stream_handle(stream, dev)
         self._order(sh)
-        N.check(L.hbx_kde_acquire_topk(c_dev.data_ptr(), Nc, k, int(index_base), self._bound, N.ptr(out),
-                                       ws.data_ptr(), ws.numel(), sh))
+        fn = L.hbx_kde_acquire_topk_lr if lr else L.hbx_kde_acquire_topk
+        N.check(fn(c_dev.data_ptr(), Nc, k, int(index_base), self._bound, N.ptr(out), ws.data_ptr(), ws.numel(), sh))
         return TopK.from_bytes(fetch_bytes(out, stream))  # one device-to-host copy: the whole result block
 
     def _ws_offsets(self, Nc, seg):

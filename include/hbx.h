@@ -284,7 +284,8 @@ void hbx_kde_pair_free(void* pair);
  * Workspace: hbx_kde_lr_workspace_bytes(Nc, nmax) -- hbx_kde_acquire's layout with this route's arrays appended, so
  * hbx_kde_result_ptr and hbx_kde_ws_offsets hold for it.  Its last 256-byte slot begins with two int32 counters of
  * the last call: log-space evaluations, forced (uncertified) candidates re-scored.
- * Not offered by log ratio: the batched call, top-k, the staged form, the multi-GPU reduction. */
+ * Not offered by log ratio: the batched call, the staged form, the multi-GPU reduction.  (The top-k:
+ * hbx_kde_acquire_topk_lr, below.) */
 int64_t hbx_kde_lr_workspace_bytes(int64_t Nc, int64_t nmax);
 int hbx_kde_acquire_lr(const double* cand, int64_t Nc, int64_t index_base, const void* pair, void* workspace,
                        int64_t ws_bytes, void* events, void* stream);
@@ -333,6 +334,26 @@ int64_t hbx_kde_topk_workspace_bytes(int64_t Nc, int32_t k, int64_t nmax);
 int64_t hbx_kde_topk_result_bytes(int32_t k);
 int hbx_kde_acquire_topk(const double* cand, int64_t Nc, int32_t k, int64_t index_base, const void* pair,
                          void* results, void* workspace, int64_t ws_bytes, void* stream);
+
+/* Top-k acquisition by log ratio: the k best candidates of ONE pool by s = ln g - ln l, with no floor -- what
+ * hbx_kde_acquire_topk is to hbx_kde_acquire, for hbx_kde_acquire_lr.  (Where both densities lie under the floor the
+ * floored score is exactly 1 and the floored top-k returns the lowest indices; s still orders those candidates.)
+ * results: hbx_kde_acquire_topk's block, hbx_kde_topk_result_bytes(k) bytes.  Entries ascend by (key of s, index), the
+ * key hbx_kde_acquire_lr's: finite values and -inf by value, +inf behind them, NaN never returned; count = min(k, F),
+ * F the candidates whose s is not NaN; entry 0 is hbx_kde_acquire_lr's pick.  Per record: score = s (L_g - L_l as
+ * defined at hbx_kde_acquire_lr), pdf_l and pdf_g the reference's fp64 pdfs bit for bit, rel the absolute bound of s
+ * (both pdfs' relative bounds and the log-space bounds).  Header: shortlist the candidates re-scored; flags
+ * HBX_ACQ_LOG_RATIO always (the zeroed header of Nc == 0 excepted: nothing is launched), HBX_ACQ_OVERFLOW for
+ * exact-only pairs (the whole pool re-scored), HBX_ACQ_NEAR_TIE when an entry and its successor -- the last returned
+ * one's successor is the best re-scored entry left out -- satisfy s_next <= s + 1.0001 (rel + rel_next) or the bound is
+ * infinite.  1 <= k <= HBX_TOPK_MAX_K; k > Nc is legal.  The scoring is unstaged (staging prunes by the floor), its
+ * instance chosen as hbx_kde_acquire_lr chooses it (HBX_LR_COARSE); the pair's pdf_floor plays no part.
+ * Workspace: hbx_kde_topk_lr_workspace_bytes(Nc, k, nmax) (-1 for k out of range) -- it begins with
+ * hbx_kde_lr_workspace_bytes' layout, the two counters of the last call included.  With these two the library has 120
+ * exports. */
+int64_t hbx_kde_topk_lr_workspace_bytes(int64_t Nc, int32_t k, int64_t nmax);
+int hbx_kde_acquire_topk_lr(const double* cand, int64_t Nc, int32_t k, int64_t index_base, const void* pair,
+                            void* results, void* workspace, int64_t ws_bytes, void* stream);
 
 /* Grouped acquisition: ONE exact pick per KDE pair for B independent brackets -- what follows the batched refit
  * (hbx_seg_argsort_ex + hbx_kde_fit) when every bracket proposes a configuration (bohb.py:124-169 per bracket).

@@ -1,6 +1,6 @@
 """Single-pool acquisition by log ratio, measured (profiles/acquire_lr/README.md):
 
-    python tools/bench_acquire_lr.py [--reps 20] [--nc 1000000] [--nobs 10000] [--out FILE.json]
+    python tools/bench_acquire_lr.py [--reps 20] [--nc 1000000] [--nobs 10000] [--out FILE.json] [--topk K]
 
 1. config #3 (nc x nobs x 24c + 8u): KDEPair.acquire(score="log_ratio") with the fast scoring instance without the
    coarse one (the default) and with the coarse one (HBX_LR_COARSE=1), the floored acquire for context, and the only
@@ -8,6 +8,9 @@
 2. the generator's own call: 64 candidates against 400 and nobs observations, the bound form (acquire_pick), by log
    ratio (with and without the re-score's scan form, HBX_LR_SCAN) against the floored call.
 3. a converged model (bandwidths about 1e-3) with a far pool: the log-space evaluations and the call's time over them.
+--topk K: instead of the three sections, config #3's k best (profiles/topk_lr/README.md): acquire_topk(score="log_ratio"),
+the only other route to that ranking -- hbx_kde_logpdf_rtol for both KDEs plus torch.topk of ln l - ln g -- and the
+floored acquire_topk for context.
 The routes take turns within one session; device events around every call, warmed shapes; min / median / max."""
 import argparse
 import json
@@ -55,6 +58,7 @@ def main():
     ap.add_argument("--nc", type=int, default=1000000)
     ap.add_argument("--nobs", type=int, default=10000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--topk", type=int, default=0)
     a = ap.parse_args()
     import torch
     from hpbandster_amd import _native as N
@@ -82,6 +86,32 @@ def main():
         s = lg[1] - lg[0]
         return int(torch.argmin(torch.where(torch.isnan(s), torch.full_like(s, float("inf")), s)).item())
 
+    if a.topk:
+        K = a.topk
+        wk = torch.empty(pair.topk_workspace_bytes(a.nc, K, "log_ratio"), dtype=torch.uint8, device=dev)
+
+        def lnpdf_topk():
+            lnpdf_argmin()
+            d = lg[0] - lg[1]  # the K largest ln l - ln g are the K smallest s; NaN never
+            return torch.topk(torch.where(torch.isnan(d), torch.full_like(d, -float("inf")), d), K).indices.cpu().numpy()
+
+        routes = {"topk_log_ratio": ({}, lambda: pair.acquire_topk(cands, K, workspace=wk, score="log_ratio")),
+                  "lnpdf_topk": ({}, lnpdf_topk),
+                  "topk_floored": ({}, lambda: pair.acquire_topk(cands, K, workspace=wk))}
+        t, out = timed(torch, routes, a.reps)
+        top = pair.acquire_topk(cands, K, workspace=wk, score="log_ratio")
+        ls, forced = lr_counters(pair, wk, a.nc)
+        other = out["lnpdf_topk"]
+        t["topk_log_ratio"].update(shortlist=top.shortlist, flags=top.flags, logspace=ls, forced=forced,
+                                   first=[int(i) for i in top.index[:4]], rel_max=float(np.max(top.rel)),
+                                   same_set_as_lnpdf_topk=bool(set(top.index.tolist()) == set(other.tolist())))
+        t["topk_floored"].update(shortlist=out["topk_floored"].shortlist, first=[int(i) for i in out["topk_floored"].index[:4]])
+        res["config3_topk_%d" % K] = t
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     routes = {"log_ratio": (LRD, lambda: pair.acquire(cands, workspace=ws, score="log_ratio")),
               "log_ratio_coarse": (LRC, lambda: pair.acquire(cands, workspace=ws, score="log_ratio")),
               "floored": ({}, lambda: pair.acquire(cands, workspace=ws)),
